@@ -33,6 +33,10 @@ Objects on the JSON line:
   reference_gpu_benchmark_shapes   the shapes of the reference's benchmark/gpu_benchmark.jl through the allocating calls
 
 Other workloads (parity-test configs, not the headline): --workload c1|c2|c4|c5.
+
+--dump-outputs DIR   after the timed steps, the output of the last timed step as DIR/*.npy (dump_outputs: the whole array, or its
+                     leading block and a fixed seeded sample when it is larger); the inputs are seeded, so two builds given the
+                     same arguments can be compared file for file.
 """
 import argparse
 import gc
@@ -71,7 +75,12 @@ def parse():
     ap.add_argument("--no-depths", action="store_true", help="skip the by_depth object")
     ap.add_argument("--c5-signals", type=int, default=65536, help="total signals of the C5 batch (BASELINE: 65536)")
     ap.add_argument("--stub-backend", default=None, help=argparse.SUPPRESS)   # tests only: 'gloo' = CPU ranks, stub transform
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port():
@@ -317,6 +326,44 @@ def _timed_steps(step, backend, dist, sharding, device, steps, warmup, precondit
     return sharding.max_over_ranks(dt, dist, device)
 
 
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: at most this many bytes of array data in all (shared by the ranks)
+DUMP_SAMPLE = 1 << 22          # elements of the seeded sample of an output too large to write whole
+DUMP_HEAD = 1 << 20            # elements of its leading block
+
+
+def dump_outputs(outdir, arrays, rank=0, world=1):
+    """--dump-outputs: the arrays the timed path handed its caller in the last timed step, as outdir/<name>.npy in their own
+    dtype (float32 / float64) and logical shape, so that two builds can be compared output for output.  An array of at most half
+    the budget is written whole; a larger one as <name>_head, the leading block in logical index order (the coarse levels of
+    a dwt), and <name>_sample, the values at DUMP_SAMPLE logical flat indices drawn with a fixed seed (sorted; the same for every
+    run of the same shape).  With several ranks every rank writes its own files (<name>_rank<r>) within 1 / world of the budget.
+    manifest.json says what each file holds."""
+    os.makedirs(outdir, exist_ok=True)
+    budget = DUMP_BYTES // world
+    manifest = {}
+    for name, t in arrays.items():
+        if world > 1:
+            name = f"{name}_rank{rank}"
+        shape = tuple(t.shape)
+        if t.numel() * t.element_size() <= budget // 2:
+            parts = {name: (t, "the whole array")}
+        else:
+            side = max(1, int(round((DUMP_HEAD // world) ** (1.0 / t.dim()))))
+            head = t[tuple(slice(0, min(n, side)) for n in shape)]
+            m = min(DUMP_SAMPLE // world, t.numel())
+            idx = np.sort(np.random.default_rng(20241015).choice(t.numel(), size=m, replace=False))
+            sub = tuple(torch.from_numpy(np.ascontiguousarray(i)).to(t.device) for i in np.unravel_index(idx, shape))
+            parts = {name + "_head": (head, f"leading block {list(head.shape)} in logical index order"),
+                     name + "_sample": (t[sub], f"{m} sorted logical flat (C-order) indices, numpy default_rng(20241015).choice")}
+        for fname, (a, what) in parts.items():
+            arr = a.detach().cpu().numpy()
+            np.save(os.path.join(outdir, fname + ".npy"), arr)
+            manifest[fname] = {"of": list(shape), "dtype": str(arr.dtype), "shape": list(arr.shape), "holds": what}
+    mname = "manifest.json" if world == 1 else f"manifest_rank{rank}.json"
+    with open(os.path.join(outdir, mname), "w") as f:
+        json.dump(manifest, f, indent=1, sort_keys=True)
+
+
 def rccl_info(dist, device, backend_name):
     """What the collective library itself reports: its version, and the number of ranks as counted by an all-reduce of ones
     (not torch's bookkeeping)."""
@@ -371,11 +418,11 @@ def c5_roofline(backend, x, y, ncol, rank, dist, sharding, device):
     return out
 
 
-def multi_gpu_line(args, rank, world, dist, sharding, device, backend, steps=None, warm=None, nested=True):
+def multi_gpu_line(args, rank, world, dist, sharding, device, backend, steps=None, warm=None, nested=True, dump=None):
     """The sharded C5 batch as the top-level metric: `--gpus N > 1`, `--gpus 1 --workload c5`, and (with few steps) the
     `c5_batched` object of the one-GPU C3 line -- the same keys everywhere, so the N = 1 point and the N > 1 points of the
     scaling curve compare like for like.  nested: also report the C3 weak-scaling figure (every rank its own image) and, for
-    N > 1, the whole batch on rank 0 alone measured in the SAME job."""
+    N > 1, the whole batch on rank 0 alone measured in the SAME job.  dump: --dump-outputs DIR of the timed path (top level only)."""
     n = 1 << 16
     steps = args.steps if steps is None else steps
     lo, hi = sharding.shard_range(args.c5_signals, rank, world)
@@ -383,6 +430,8 @@ def multi_gpu_line(args, rank, world, dist, sharding, device, backend, steps=Non
     x, y = backend.make_shard(ncol, 4242 + 1000 * rank)
     warm = min(args.warmup, 20) if warm is None else warm   # a 16 GiB / N shard per step: a handful of warm-up steps reach steady clocks
     dt = timed_steps(lambda i: backend.dwtc(y, x), backend, dist, sharding, device, steps, warm)
+    if dump:
+        dump_outputs(dump, {"y": y}, rank, world)
     kernel = backend.kernel()
     checksum = sharding.sum_over_ranks(float(y.double().sum().item()), dist, device)
     cols = sharding.sum_over_ranks(float(ncol), dist, device)
@@ -465,7 +514,7 @@ def main():
         from wavelets_jl_amd import sharding
         dist.init_process_group(backend=args.stub_backend)
         device = torch.device("cpu")
-        out = multi_gpu_line(args, rank, world, dist, sharding, device, StubBackend(device, rank))
+        out = multi_gpu_line(args, rank, world, dist, sharding, device, StubBackend(device, rank), dump=args.dump_outputs)
         if rank == 0:
             out["cpu_baseline"] = {"value": 0.0, "unit": "Msamples/s", "cores": 1, "kind": "port", "sample": "stub run: not measured"}
             print(json.dumps(out), flush=True)
@@ -502,7 +551,7 @@ def main():
     if (world > 1 and args.workload is None) or args.workload == "c5":
         # the sharded C5 batch: the metric of every N > 1 line, and of `--gpus 1 --workload c5` (the like-for-like N = 1 point)
         out = multi_gpu_line(args, rank, world, dist, sharding, device, HipBackend(W, sharding, dist, device),
-                             steps=(args.steps if world > 1 else min(args.steps, 60)), nested=(args.workload is None))
+                             nested=(args.workload is None), dump=args.dump_outputs)
         if rank == 0 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline_leg(W, "c5", W.wavelet(W.WT.db4), 16)
         if affinity is not None:
@@ -549,6 +598,8 @@ def main():
     # load to ramp before the steady-state throughput this line reports
     precondition = max(0, 300 - args.warmup)
     dt = timed_steps(lambda i: fn(xs[i % len(xs)]), _B, dist, sharding, device, args.steps, args.warmup, precondition)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": yout}, rank, world)       # before the legs below overwrite yout
     kernel = W.last_kernel()
     ms_per_step = dt / args.steps * 1e3
     value = world * nsamples / (dt / args.steps) / 1e6          # whole-job Msamples/s

@@ -92,3 +92,22 @@ def test_rank_pinning_reads_the_gpu_local_cpulist(tmp_path):
         fh.write(",".join(str(c) for c in allowed) + "\n")
     same = bench.pin_rank_to_gpu_cores((0, 0x1b, 0), sysfs=str(tmp_path), apply=False)
     assert same["pinned"] is False
+
+
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: every rank writes the output of its last timed step (the stub's y is a copy of rank r's shard, r + 1)
+    as DIR/y_rank<r>.npy, with a manifest; --steps below 1 is refused."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+                        "--stub-backend", "gloo", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300,
+                       env=env, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert json.loads([l for l in p.stdout.strip().splitlines() if l.startswith("{")][-1])["steps"] == 2
+    for r in range(2):
+        y = np.load(tmp_path / f"y_rank{r}.npy")
+        assert y.dtype == np.float32 and y.shape == (64, 8) and (y == r + 1).all()
+        assert json.load(open(tmp_path / f"manifest_rank{r}.json"))[f"y_rank{r}"]["holds"] == "the whole array"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120,
+                       env=env, cwd=ROOT)
+    assert p.returncode != 0 and "--steps must be at least 1" in p.stderr

@@ -5,7 +5,7 @@ Bounds (reference = the Float64 oracle on the same inputs; L = levels):
     Float32:  ||y - ref||_2 / ||ref||_2 <= 1e-6 * sqrt(L)   and   max|y - ref| <= 1e-5 * max(1, ||ref||_inf)
     Float64:  ||y - ref||_2 / ||ref||_2 <= 1e-13 * sqrt(L)
     round trip idwt(dwt(x)) vs x: 1e-5 (Float32), 1e-12 (Float64)
-    golden vectors (the reference's own files, /root/reference/test/transforms.jl:15-16): ||y - golden||_2 <= 1e-9 * sqrt(len)
+    golden vectors (the reference's own files, Wavelets.jl test/transforms.jl:15-16): ||y - golden||_2 <= 1e-9 * sqrt(len)
 The fused build compiles the same kernels with -ffp-contract=fast: same summation order, a*b+c may round once.
 """
 import math

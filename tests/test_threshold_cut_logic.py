@@ -7,7 +7,7 @@ pins against the oracle): the reference compares / subtracts in Float64 (t = sig
   Stein:           1 - t^2 / x^2 < 0  <==  |x| <= the largest Float32 <= 0.999 t     (sufficient, not necessary)
 
 for every Float32 x, checked here on the Float32 neighbourhood of t (where a cut could go wrong) and on random values.
-Reference: /root/reference/src/Threshold/threshold_main.jl:37-122 (restated in oracle/wl_oracle_ext.c)."""
+Reference: Wavelets.jl src/Threshold/threshold_main.jl:37-122 (restated in oracle/wl_oracle_ext.c)."""
 import numpy as np
 
 

@@ -1,18 +1,19 @@
 """Extract the method signatures of the reference's dispatch seam into tests/golden/reference_seam_signatures.json.
 
-Runs in the build container only (reads /root/reference, which does not travel).  The output is DATA -- for every function
-the Julia glue adds methods to, the list of the reference's own methods as (positional parameter types, where-bounds, file:line)
+Needs a checkout of the reference (JuliaDSP/Wavelets.jl v0.10.1), which is not part of this repository.  The output is
+DATA -- for every function the Julia glue adds methods to, the list of the reference's own methods as (positional parameter types, where-bounds, file:line)
 -- used by tests/test_julia_glue.py to prove statically that each glue method is element-wise `<:` a reference method (so Julia's
 dispatch picks it without ambiguity).  Loops of the form `for (a, b, ...) in ((:x, :y, ...), ...) @eval ... end` are expanded.
 
-    python tools/gen_seam_signatures.py            # rewrites the fixture
+    python tools/gen_seam_signatures.py WAVELETS_JL_DIR            # rewrites the fixture
+    python tools/gen_seam_signatures.py WAVELETS_JL_DIR --check    # exit status 1 when the committed fixture differs
 """
 import json
 import os
 import re
 import sys
 
-REF = "/root/reference"
+REF = None          # the reference checkout (first argument)
 FILES = [
     "src/Transforms/transforms_main.jl", "src/Transforms/transforms_filter.jl", "src/Transforms/transforms_lifting.jl",
     "src/Transforms/transforms_maximal_overlap.jl", "src/Threshold/threshold_main.jl", "src/Threshold/denoising.jl",
@@ -131,13 +132,27 @@ def methods_of(path):
     return out
 
 
-def main():
+def extract():
     sigs = {}
     for f in FILES:
         for me in methods_of(f):
             sigs.setdefault(me["name"], [])
             if me not in sigs[me["name"]]:
                 sigs[me["name"]].append(me)
+    return sigs
+
+
+def main(argv):
+    global REF
+    if len(argv) not in (1, 2) or argv[1:] not in ([], ["--check"]):
+        print(__doc__, file=sys.stderr)
+        return 2
+    REF = argv[0]
+    sigs = extract()
+    if argv[1:] == ["--check"]:
+        same = sigs == json.load(open(OUT))["methods"]
+        print("fixture is current" if same else "fixture differs from a fresh extraction: rerun without --check")
+        return 0 if same else 1
     consts = {"DWTArray": "AbstractArray", "WPTArray": "AbstractVector", "ValueType": "Union{AbstractFloat, Complex}"}   # transforms_main.jl:5-7
     json.dump({"generated_by": "tools/gen_seam_signatures.py", "reference": "JuliaDSP/Wavelets.jl v0.10.1", "aliases": consts,
                "methods": sigs}, open(OUT, "w"), indent=1, sort_keys=True)
@@ -147,4 +162,4 @@ def main():
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(main(sys.argv[1:]))
