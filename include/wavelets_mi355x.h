@@ -117,6 +117,11 @@ WL_API size_t wl_workspace_bytes(int dtype, int ndims, const int64_t *dims, int 
  * (6.5 * prod(nspin) + nspin[0]) N elements (capped, see WL_TI_WS_CAP_MB) -- a plain one-spin denoise about 5.5 N -- and grows
  * the workspace (synchronising) on its first call like any other path; wl_modwt / wl_imodwt allocate nothing here.      */
 WL_API size_t wl_workspace_bytes_full(int dtype, int ndims, const int64_t *dims, int L);
+/* wl_bestbasistree_filter of an n-sample vector holds more than that bound: the packet region of wl_workspace_bytes_full(dtype, 1,
+ * {n}, L), rounded up to 256 bytes, then two packet buffers of n elements (each rounded up to 256 bytes), the node entropies
+ * (ntree + 2^(Lmax-1) doubles, unless the caller passes node_entropy), the best-subtree values (ntree doubles), the reduction
+ * partials (n / 1024 + 64 doubles), the norm (256 bytes) and three node byte vectors (3 ntree bytes, each rounded up to 256):
+ * about (ws_elems + 2) n elements + 2.1 n doubles + 3 n bytes.  wl_coefentropy holds (n / 1024 + 72) doubles.           */
 WL_API int wl_ctx_reserve(wl_ctx *ctx, size_t bytes);
 WL_API size_t wl_ctx_workspace_held(const wl_ctx *ctx);
 /* hipStreamSynchronize for hosts without their own HIP binding.                        */
@@ -284,6 +289,34 @@ WL_API int wl_denoise_ti_lifting(wl_ctx *ctx, int dtype, void *y, const void *x,
                           int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
                           const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2,
                           int L, int th, double t_unit, const int64_t *nspin, double sigma_host, void *stream);
+
+/* ---- best-basis search of packet trees (src/Threshold/entropy.jl) ----------------------- */
+/* Entropy measures: ShannonEntropy (-s log s) and LogEnergyEntropy (-log s) of s = (x / nrm)^2; s == 0 contributes -0.0.    */
+enum wl_entropy { WL_ENTROPY_SHANNON = 0, WL_ENTROPY_LOGENERGY = 1 };
+/* Accuracy contract (the one exception to "bit-identical"): the reference's log is Julia's, its norm BLAS
+ * nrm2 and its sums sequential in T, which no parallel reduction reproduces.  Here nrm = T(sqrt(Float64 sum of squares)) (about
+ * 1 ulp of T from the reference's), s is computed exactly as the reference does (in T, IEEE division, no contraction), the log and
+ * every sum are Float64 in a fixed order -- deterministic, the same bits call after call.  Against the exact entropy of the same T
+ * coefficients: <= 1e-12 sum|term| (Float64), <= 4e-7 sum|term| (Float32).  nrm == 0 gives exactly 0; an all-zero node gives
+ * exactly 0, so exact ties do not split.                                                                                   */
+/* *result = coefentropy(x, et, nrm) (have_nrm != 0) or coefentropy(x, et) with nrm = norm(x) (entropy.jl:31-40), rounded to the
+ * element type and widened to double.  nrm < 0 (or NaN) -> WL_EINVAL_ARG (the reference's @assert nrm >= 0); n == 0 gives 0.
+ * Synchronises `stream` (the result is a host scalar), like wl_median.                                                    */
+WL_API int wl_coefentropy(wl_ctx *ctx, int dtype, const void *x, int64_t n, int et, int have_nrm, double nrm, double *result,
+                          void *stream);
+/* tree_out = bestbasistree(x, OrthoFilter(qmf), tree, et) (entropy.jl:47-111): the best subtree of `tree` (one byte per node,
+ * ntree = 2^maxtransformlevels(n) - 1 nodes, HOST pointers for tree and tree_out).  Every depth 0 .. Lmax of the full packet
+ * decomposition comes from the packet transform (bit-identical to wl_wpt_filter), whatever `tree` is; node k's entropy entr_bf[k]
+ * is taken over its segment before it splits, entr_af[j] over the two children of bottom node j together.  Then
+ * best(k) = min(entr_bf[k], best(left) + best(right)) over the full tree (Julia's min: NaN propagates) and node k is split iff
+ * tree[k], its parent is split and !(entr_bf[k] <= best(k)): exact ties do not split, a NaN splits every node of `tree` under
+ * split parents.  node_entropy: optional DEVICE array (NULL allowed) of ntree + 2^(Lmax-1) doubles that receives
+ * [entr_bf ; entr_af].  Errors: WL_EINVAL_SIZE when maxtransformlevels(n) == 0 (odd n), WL_EINVAL_TREE for an invalid tree.
+ * Synchronises `stream` once to return the tree: not capturable in a hipGraph.  The workspace grows as noted at
+ * wl_workspace_bytes_full.                                                                                                 */
+WL_API int wl_bestbasistree_filter(wl_ctx *ctx, int dtype, const void *x, int64_t n, const double *qmf, int flen,
+                                   const uint8_t *tree, int64_t ntree, int et, uint8_t *tree_out, double *node_entropy,
+                                   void *stream);
 
 /* ---- introspection (tests / bench) ---------------------------------------------------- */
 /* Select the kernel family: 0 = auto (fast paths where they apply), 1 = generic kernels

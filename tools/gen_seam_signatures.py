@@ -7,6 +7,14 @@ dispatch picks it without ambiguity).  Loops of the form `for (a, b, ...) in ((:
 
     python tools/gen_seam_signatures.py WAVELETS_JL_DIR            # rewrites the fixture
     python tools/gen_seam_signatures.py WAVELETS_JL_DIR --check    # exit status 1 when the committed fixture differs
+
+Options for another fixture (defaults: the seam above):
+    --out PATH          the JSON file to write / check
+    --names a,b,...     the functions to extract
+    --files f1,f2,...   the reference files to read (relative to WAVELETS_JL_DIR)
+e.g. tests/golden/reference_bestbasis_signatures.json (the best-basis glue, tests/test_julia_glue_bestbasis.py):
+    python tools/gen_seam_signatures.py WAVELETS_JL_DIR --out tests/golden/reference_bestbasis_signatures.json \
+        --names bestbasistree,coefentropy --files src/Threshold/entropy.jl
 """
 import json
 import os
@@ -143,13 +151,29 @@ def extract():
 
 
 def main(argv):
-    global REF
-    if len(argv) not in (1, 2) or argv[1:] not in ([], ["--check"]):
+    global REF, FILES, NAMES, OUT
+    opts, check, rest = {}, False, argv[1:]
+    while rest:
+        a = rest.pop(0)
+        if a == "--check":
+            check = True
+        elif a in ("--out", "--names", "--files") and rest:
+            opts[a] = rest.pop(0)
+        else:
+            rest = None
+            break
+    if not argv or rest is None:
         print(__doc__, file=sys.stderr)
         return 2
     REF = argv[0]
+    if "--out" in opts:
+        OUT = os.path.abspath(opts["--out"])
+    if "--names" in opts:
+        NAMES = set(opts["--names"].split(","))
+    if "--files" in opts:
+        FILES = opts["--files"].split(",")
     sigs = extract()
-    if argv[1:] == ["--check"]:
+    if check:
         same = sigs == json.load(open(OUT))["methods"]
         print("fixture is current" if same else "fixture differs from a fresh extraction: rerun without --check")
         return 0 if same else 1

@@ -23,6 +23,7 @@ from .transforms import (dwt, idwt, dwt_, idwt_, dwt_oop_, idwt_oop_, dwtc, idwt
 from .modwt import modwt, imodwt, maxmodwttransformlevels
 from .threshold import (THType, HardTH, SoftTH, SemiSoftTH, SteinTH, BiggestTH, PosTH, NegTH, DEFAULT_TH, threshold, threshold_,
                         DNFT, VisuShrink, denoise, noisest, mad_, median, nspin2circ, circshift, DEFAULT_WAVELET)
+from .entropy import Entropy, ShannonEntropy, LogEnergyEntropy, coefentropy, bestbasistree
 from . import _lib
 
 __all__ = [
@@ -38,4 +39,5 @@ __all__ = [
     "modwt", "imodwt", "maxmodwttransformlevels",
     "THType", "HardTH", "SoftTH", "SemiSoftTH", "SteinTH", "BiggestTH", "PosTH", "NegTH", "DEFAULT_TH", "threshold", "threshold_",
     "DNFT", "VisuShrink", "denoise", "noisest", "mad_", "median", "nspin2circ", "circshift", "DEFAULT_WAVELET",
+    "Entropy", "ShannonEntropy", "LogEnergyEntropy", "coefentropy", "bestbasistree",
 ]

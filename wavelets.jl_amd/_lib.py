@@ -88,6 +88,8 @@ SIGNATURES = {
     "wl_circshift": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i64p, _i64p, _vp]),
     "wl_arrayadd": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, _vp]),
     "wl_rmul": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_double, _vp]),
+    "wl_coefentropy": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, _f64p, _vp]),
+    "wl_bestbasistree_filter": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _f64p, C.c_int, _u8p, C.c_int64, C.c_int, _u8p, _f64p, _vp]),
 }
 
 

@@ -667,9 +667,10 @@ static bool isvalidtree(int64_t n, const uint8_t *b, int64_t nb, int64_t *last_s
 template <typename T>
 static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
                     const Taps<T> *taps, const LiftScheme<T> *sc,
-                    const uint8_t *tree, int64_t ntree, int64_t last_set, int fw, int full_depth = -1)
+                    const uint8_t *tree, int64_t ntree, int64_t last_set, int fw, int full_depth = -1, int first_depth = 0)
 {
-    // full_depth >= 0: the full tree of that depth, no tree vector (tree == nullptr)
+    // full_depth >= 0: the full tree of that depth, no tree vector (tree == nullptr); only its depths >= first_depth are applied
+    // (x already holds the depth-first_depth content: the best-basis search steps one depth at a time)
     const bool lifting = (sc != nullptr);
     Extent3 full = {{n, 1, 1}};
     Strides3 fst = {{1, n, n}};
@@ -685,7 +686,7 @@ static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
     for (int L = Lmax; L > 0; --L) {
         int d = fw ? Lmax - L : L - 1;
         if (full_depth >= 0) {
-            if (d < full_depth) { depths.push_back(d); kind.push_back(2); }
+            if (d >= first_depth && d < full_depth) { depths.push_back(d); kind.push_back(2); }
             continue;
         }
         int64_t first = ((int64_t)1 << d) - 1, cnt = (int64_t)1 << d;
@@ -844,7 +845,79 @@ static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
     return WL_OK;
 }
 
+// ---- best-basis search (bestbasistree, entropy.jl:47-111) -----------------------------------------------------------------------
+// The reference decomposes the signal to the full depth Lmax one dwt! level per node and takes each node's entropy before its split.
+// Here depth d + 1 comes from depth d by one full-depth packet step (wpt_impl, first_depth = d: the packet kernels, bit-identical to
+// wpt), ping-ponging between two buffers, and every depth is reduced to its node entropies by the segmented kernel (wl_entropy.hip);
+// depth Lmax is reduced over the pairs of siblings only (entr_af).  The decision runs on the device; the tree comes back in one copy.
+template <typename T>
+static int bestbasis_impl(wl_ctx *ctx, hipStream_t st, const T *x, int64_t n, const Taps<T> &taps, const uint8_t *tree, int64_t ntree,
+                          int et, uint8_t *tree_out, double *node_entropy)
+{
+    const int Lmax = wl_maxtransformlevels(n);
+    const int64_t naf = (int64_t)1 << (Lmax - 1);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    // layout (bytes): [wpt_impl's region | A | B | entropies | best | partials | nrm | split | tree | tree_out]
+    size_t off = up(ws_elems(n) * sizeof(T) + 256);
+    const size_t oA = off; off += up((size_t)n * sizeof(T));
+    const size_t oB = off; off += up((size_t)n * sizeof(T));
+    const size_t oE = off; off += node_entropy ? 0 : up((size_t)(ntree + naf) * sizeof(double));
+    const size_t oBest = off; off += up((size_t)ntree * sizeof(double));
+    const size_t oP = off; off += up(entropy_partials(n) * sizeof(double));
+    const size_t oN = off; off += 256;
+    const size_t oS = off; off += up((size_t)ntree);
+    const size_t oT = off; off += up((size_t)ntree);
+    const size_t oO = off; off += up((size_t)ntree);
+    int rc = ensure_ws(ctx, off, st);
+    if (rc) return rc;
+    char *ws = (char *)ctx->ws;
+    T *A = (T *)(ws + oA), *B = (T *)(ws + oB);
+    double *ent = node_entropy ? node_entropy : (double *)(ws + oE);
+    double *best = (double *)(ws + oBest), *part = (double *)(ws + oP), *nrm = (double *)(ws + oN);
+    uint8_t *split = (uint8_t *)(ws + oS), *dtree = (uint8_t *)(ws + oT), *dout = (uint8_t *)(ws + oO);
+    rc = wl_stage_to_device(ctx, dtree, tree, (size_t)ntree, st);
+    if (rc) return rc;
+    WL_HIP(ctx, entropy_norm<T>(st, x, n, part, nrm));
+    const T *cur = x;
+    for (int d = 0; d <= Lmax; ++d) {
+        if (d > 0) {
+            T *out = (cur == A) ? B : A;
+            rc = wpt_impl<T>(ctx, st, out, cur, n, &taps, nullptr, nullptr, 0, -1, 1, d, d - 1);
+            if (rc) return rc;
+            cur = out;
+        }
+        if (d < Lmax) WL_HIP(ctx, entropy_segments<T>(st, et, cur, n >> d, (int64_t)1 << d, nrm, 0.0, part, ent + ((int64_t)1 << d) - 1));
+        else WL_HIP(ctx, entropy_segments<T>(st, et, cur, n >> (Lmax - 1), naf, nrm, 0.0, part, ent + ntree));
+    }
+    WL_HIP(ctx, bestbasis_decide(st, ent, ntree, Lmax, best, split, dtree, dout));
+    WL_HIP(ctx, hipMemcpyAsync(tree_out, dout, (size_t)ntree, hipMemcpyDeviceToHost, st));
+    WL_HIP(ctx, hipStreamSynchronize(st));
+    ctx->last_kernel = "k_entropy_seg";
+    return WL_OK;
+}
+
 extern "C" {
+
+int wl_bestbasistree_filter(wl_ctx *ctx, int dtype, const void *x, int64_t n, const double *qmf, int flen, const uint8_t *tree,
+                            int64_t ntree, int et, uint8_t *tree_out, double *node_entropy, void *stream)
+{
+    if (!ctx || !x || !qmf || !tree || !tree_out) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (et != WL_ENTROPY_SHANNON && et != WL_ENTROPY_LOGENERGY) return WL_EINVAL_ARG;
+    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
+    if (n < 1) return WL_EDIMS;
+    if (wl_maxtransformlevels(n) == 0) return WL_EINVAL_SIZE;        // the reference fails on 2^(Lmax - 1) (entropy.jl:85)
+    int64_t last_set = -1;
+    if (!isvalidtree(n, tree, ntree, &last_set)) return WL_EINVAL_TREE;
+    WL_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == WL_F32) {
+        Taps<float> t; make_taps<float>(qmf, flen, t);
+        return bestbasis_impl<float>(ctx, st, (const float *)x, n, t, tree, ntree, et, tree_out, node_entropy);
+    }
+    Taps<double> t; make_taps<double>(qmf, flen, t);
+    return bestbasis_impl<double>(ctx, st, (const double *)x, n, t, tree, ntree, et, tree_out, node_entropy);
+}
 
 int wl_wpt_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, const double *qmf, int flen,
                   const uint8_t *tree, int64_t ntree, int fw, void *stream)

@@ -174,6 +174,22 @@ inline Extent3 low_corner(const BoxSpec &b, const int64_t n[3])
     return lo;
 }
 
+// ---- best-basis search (wl_entropy.hip) ----
+// doubles of scratch a reduction over a vector of n samples needs (entropy_segments / entropy_norm)
+size_t entropy_partials(int64_t n);
+// out[s] = coefentropy(x[s * nj : (s + 1) * nj], et, nrm) for s < nseg, in Float64 (accuracy contract: wl_entropy.hip); the norm is
+// *nrmp (a T value held as a double) or, when nrmp == nullptr, nrm_val
+template <typename T>
+hipError_t entropy_segments(hipStream_t st, int et, const T *x, int64_t nj, int64_t nseg, const double *nrmp, double nrm_val, double *part,
+                            double *out);
+// *nrm_out = T(sqrt(Float64 sum of x^2)), held as a double
+template <typename T>
+hipError_t entropy_norm(hipStream_t st, const T *x, int64_t n, double *part, double *nrm_out);
+// bestbasistree's decision from ent = [entr_bf (ntree) ; entr_af (2^(Lmax - 1))]: best (ntree doubles) and split (ntree bytes) are
+// scratch, tree / tree_out device byte vectors of ntree nodes
+hipError_t bestbasis_decide(hipStream_t st, const double *ent, int64_t ntree, int Lmax, double *best, uint8_t *split, const uint8_t *tree,
+                            uint8_t *tree_out);
+
 __device__ __forceinline__ int64_t pmod(int64_t a, int64_t n)
 {
     int64_t r = a % n;

@@ -5,7 +5,8 @@
 # [weakdeps]/[extensions] of Project.toml with AMDGPU as the trigger).  It only adds methods to the
 # reference's internal seam -- `Transforms._dwt!` / `_wpt!` (src/Transforms/transforms_main.jl:105-176
 # end there) -- for `ROCArray`s, so `dwt / idwt / dwt! / idwt! / wpt / iwpt` and every caller of them
-# (denoise, bestbasistree, ...) pick the MI355X backend by array-type dispatch.  A `ROCVector` method
+# (denoise, ...) pick the MI355X backend by array-type dispatch.  bestbasistree / coefentropy do not (their reference methods index
+# host scratch element by element): WaveletsMI355X_bestbasis.jl adds device methods for them.  A `ROCVector` method
 # is more specific than the extension's `AbstractGPUVector` method, so it wins without touching it.
 module WaveletsMI355X
 
@@ -394,5 +395,7 @@ function Threshold.denoise(x::ROCArray{T,N}, wt::GLS;
                 L, THCODE[typeof(dnt.th)], Float64(dnt.t), nsp, sigma, stream()))
     return y
 end
+
+include("WaveletsMI355X_bestbasis.jl")
 
 end # module
