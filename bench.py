@@ -7,26 +7,38 @@ data already resident in HBM; output array and workspace are allocated once, out
   --gpus 1 (default)   workload C3 = BASELINE.json configs[2], the configuration the metric is quoted on:
                        2-D dwt, WT.db4 filter bank, 8192 x 8192 Float32, L = 13 (API default).  The K timed steps rotate over
                        THREE distinct input arrays (768 MiB together, beyond the 256 MiB Infinity Cache), so no step finds its
-                       input cached by the previous one.  `by_depth` repeats the measurement at L = 1, 4, 13.
+                       input cached by the previous one.
   --gpus N > 1         workload C5 = configs[4]: batched column-wise dwt, WT.db4, 65536 signals x 2^16 Float32, L = 16, the
                        batch block-partitioned over the N ranks (one process per GPU, sharding.shard_range; rank 0's taps reach
                        the other ranks by one RCCL broadcast; no signal data crosses GPUs).  value = whole batch / max-over-ranks
-                       time ("scaling": "strong").  Nested: `c3_weak_scaling` (every rank its own 8192 x 8192 image) and
+                       time ("scaling": "strong").  Nested (--full): `c3_weak_scaling` (every rank its own 8192 x 8192 image) and
                        `single_gpu_same_batch` (the whole batch on rank 0 alone, measured in the same job: the N = 1 point).
-  --gpus 1 --workload c5   the same line for N = 1 (the object `c5_batched` of the default line has the same keys).
+  --gpus 1 --workload c5   the same line for N = 1 (the object `c5_batched` of the --full C3 line has the same keys).
                        Started plainly (`python bench.py --gpus N`) the script re-launches ITSELF through torch.distributed.run
                        with N ranks; under a launcher it reads RANK / LOCAL_RANK / WORLD_SIZE.
 
-Objects on the JSON line:
+A plain run does only what the headline needs: set-up, the untimed conditioning and warm-up steps, the K timed steps,
+--dump-outputs if given, and ONE JSON line: the contract keys, the run's configuration and kernel, and the checksum of the last
+timed step's output.
+
+--full               also measure everything else, around the same timed steps: the objects below.  The complete
+                     line is then printed before a short final one (slim_line) and written to bench_full.json; the --no-*
+                     options skip single objects.
+
+Objects on the --full JSON line:
+  isolated_call_ms   whole calls issued into an idle device, before the timed steps (C3)
+  device_ms_per_step   device time per step, HIP events on the launch stream
   roofline       the dominant kernel = the launch that consumes the full-size input (C3: k_fwd2d_pair, levels 1-2 fused; C5: every
                  rank's first k_fwd1d_multi pass, levels 1-4): algorithmic bytes / average launch duration, HIP events on the launch
                  stream around a train of such launches; `rocprof` = the same figure from the committed rocprofv3 summary under
                  profiles/; `traffic` = HBM bytes per launch from the PMC counters, MEASURED IN THIS RUN for C3 when rocprofv3 is
                  present (two separate --pmc passes of tools/wlbench.bin), else the committed collection
-  by_depth       ms per transform and fraction of the 8 TB/s roofline at L = 1, 4, 13
+  by_depth       ms per transform and fraction of the 8 TB/s roofline at L = 1, 4, 13 (BASELINE.md 2)
   cpu_baseline   the oracle's sources (literal C restatement of the reference's single-threaded loops) built -O3 -march=native
                  on THIS host and timed on a bounded sample: 1 warm-up + 3 repetitions, median; 1 core (the reference has no
                  threading) and, beside it, the OpenMP-over-lines variant on all host cores
+  fused_mode, pipelined   the opt-in fused library on the headline workload; the same steps on 4 streams
+  c5_batched     the C5 batch on this one GPU (C3 line)
   secondary_configs   the other BASELINE configs and section-8(f) rows, cache-cold (5 inputs in rotation for the 64 MiB 1-D configs,
                  3 for the 256 MiB 2-D ones): >= 20 repetitions, one HIP event pair per repetition, median and minimum; C2 and C4
                  carry their own `roofline` object
@@ -67,12 +79,14 @@ def parse():
     ap.add_argument("--workload", default=None, choices=["c1", "c2", "c3", "c4", "c5"],
                     help="default: c3 on one GPU, the sharded c5 batch on several")
     ap.add_argument("--levels", type=int, default=None, help="override L (default: maxtransformlevels)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (roofline, by_depth, CPU baseline, other configs, ...)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--path", type=int, default=0, help="0 fast kernels, 1 generic kernels only")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short runs of the other BASELINE configs")
-    ap.add_argument("--no-c5", action="store_true", help="skip the C5 batch object of the one-GPU line")
-    ap.add_argument("--no-pipelined", action="store_true", help="skip the 4-stream leg (profiling runs: overlapping launches skew per-kernel statistics)")
-    ap.add_argument("--no-depths", action="store_true", help="skip the by_depth object")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the short runs of the other BASELINE configs")
+    ap.add_argument("--no-c5", action="store_true", help="--full: skip the C5 batch object of the one-GPU line")
+    ap.add_argument("--no-pipelined", action="store_true", help="--full: skip the 4-stream leg (profiling runs: overlapping launches skew per-kernel statistics)")
+    ap.add_argument("--no-depths", action="store_true", help="--full: skip the by_depth object")
     ap.add_argument("--c5-signals", type=int, default=65536, help="total signals of the C5 batch (BASELINE: 65536)")
     ap.add_argument("--stub-backend", default=None, help=argparse.SUPPRESS)   # tests only: 'gloo' = CPU ranks, stub transform
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -438,7 +452,7 @@ def multi_gpu_line(args, rank, world, dist, sharding, device, backend, steps=Non
     total = args.c5_signals * n
     ms = dt / steps * 1e3
     value = total / (dt / steps) / 1e6
-    roof = c5_roofline(backend, x, y, ncol, rank, dist, sharding, device)
+    roof = c5_roofline(backend, x, y, ncol, rank, dist, sharding, device) if args.full else None
     del x, y
     if backend.name == "hip":
         backend.W.destroy_contexts()
@@ -457,9 +471,10 @@ def multi_gpu_line(args, rank, world, dist, sharding, device, backend, steps=Non
         "achieved_hbm_GBps_algorithmic": round(8.0 * total / (dt / steps) / 1e9, 1),
         "hbm_frac_whole_transform_per_gpu": round(8.0 * total / (dt / steps) / 1e9 / world / HBM_PEAK_GBPS, 4),
         "checksum_all_ranks": checksum, "c5_signals_covered": cols,
-        "roofline": roof,
         "rccl": rccl_info(dist, device, backend.name),
     }
+    if roof is not None:
+        out["roofline"] = roof
     if nested and world > 1 and backend.name == "hip":
         # the N = 1 point of the same curve, measured in this job: rank 0 alone transforms the WHOLE batch (16 GiB in, 16 GiB out,
         # 16 GiB workspace) while the other ranks wait at the barrier
@@ -514,9 +529,11 @@ def main():
         from wavelets_jl_amd import sharding
         dist.init_process_group(backend=args.stub_backend)
         device = torch.device("cpu")
-        out = multi_gpu_line(args, rank, world, dist, sharding, device, StubBackend(device, rank), dump=args.dump_outputs)
+        out = multi_gpu_line(args, rank, world, dist, sharding, device, StubBackend(device, rank), nested=args.full,
+                             dump=args.dump_outputs)
         if rank == 0:
-            out["cpu_baseline"] = {"value": 0.0, "unit": "Msamples/s", "cores": 1, "kind": "port", "sample": "stub run: not measured"}
+            if args.full:
+                out["cpu_baseline"] = {"value": 0.0, "unit": "Msamples/s", "cores": 1, "kind": "port", "sample": "stub run: not measured"}
             print(json.dumps(out), flush=True)
         dist.destroy_process_group()
         return
@@ -551,12 +568,12 @@ def main():
     if (world > 1 and args.workload is None) or args.workload == "c5":
         # the sharded C5 batch: the metric of every N > 1 line, and of `--gpus 1 --workload c5` (the like-for-like N = 1 point)
         out = multi_gpu_line(args, rank, world, dist, sharding, device, HipBackend(W, sharding, dist, device),
-                             nested=(args.workload is None), dump=args.dump_outputs)
-        if rank == 0 and not args.no_cpu:
+                             nested=(args.workload is None and args.full), dump=args.dump_outputs)
+        if rank == 0 and args.full and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline_leg(W, "c5", W.wavelet(W.WT.db4), 16)
         if affinity is not None:
             out["rank0_cpu_affinity"] = affinity
-        finish(out, rank, dist)
+        finish(out, rank, dist, full=args.full)
         return
 
     workload = args.workload or "c3"
@@ -592,7 +609,7 @@ def main():
     # (code-object load, first-touch of the workspace), then single calls each after 50 ms of idleness (clocks down, caches
     # cold), one HIP event pair per call, no conditioning of any kind.
     isolated = None
-    if rank == 0 and workload == "c3":
+    if args.full and rank == 0 and workload == "c3":
         isolated = isolated_call_leg(fn, xs)
     # device conditioning before the W warm-up steps (untimed, reported in the JSON line): clocks need about a millisecond of
     # load to ramp before the steady-state throughput this line reports
@@ -605,10 +622,8 @@ def main():
     value = world * nsamples / (dt / args.steps) / 1e6          # whole-job Msamples/s
     gbps = 2 * esize * value * 1e6 / 1e9                        # algorithmic bytes: 2*N*sizeof(T) per call
 
-    # device-only time of one step (HIP events on the launch stream), for reference
-    dev_ms_per_step = _event_train_ms([(lambda t=t: fn(t)) for t in xs], min(args.steps, 200))
-
-    # cross-rank correctness token: sum over all ranks of each rank's coefficient sum, one 8-byte all-reduce
+    # cross-rank correctness token: sum over all ranks of each rank's coefficient sum (the last timed step's output),
+    # one 8-byte all-reduce
     checksum = sharding.sum_over_ranks(float(yout.sum(dtype=torch.float64).item()), dist, device)
 
     out = {
@@ -622,9 +637,13 @@ def main():
         "gpus_requested": args.gpus,
         "achieved_hbm_GBps_algorithmic": round(gbps, 1), "hbm_frac_whole_transform": round(gbps / HBM_PEAK_GBPS, 4),
         "precondition_steps": precondition, "untimed_steps_before_timing": args.warmup + precondition, "checksum_all_ranks": checksum,
-        "device_ms_per_step": round(dev_ms_per_step, 5),
         "rccl": rccl_info(dist, device, "hip"),
     }
+    if not args.full:
+        finish(out, rank, dist, full=False)
+        return
+    # device-only time of one step (HIP events on the launch stream), for reference
+    out["device_ms_per_step"] = round(_event_train_ms([(lambda t=t: fn(t)) for t in xs], min(args.steps, 200)), 5)
     if isolated is not None:
         out["isolated_call_ms"] = isolated
     if rank == 0 and workload == "c3" and not args.no_depths:
@@ -650,7 +669,7 @@ def main():
         out["reference_gpu_benchmark_shapes"] = reference_shapes_leg(W, device)
     if rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline_leg(W, workload, wt, L)
-    finish(out, rank, dist)
+    finish(out, rank, dist, full=True)
 
 
 def _pick(d, keys):
@@ -717,7 +736,9 @@ def slim_line(out, limit=6000):
     return text
 
 
-def finish(out, rank, dist):
+def finish(out, rank, dist, full):
+    """Prints the JSON line as the last line on stdout (rank 0).  full: the complete line, then slim_line(out) after it, and the
+    complete line in bench_full.json."""
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -730,14 +751,16 @@ def finish(out, rank, dist):
         except OSError:
             pass
         sys.stdout.flush()
-        full = json.dumps(out)
-        try:
-            with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "bench_full.json"), "w") as f:
-                f.write(full + "\n")
-        except OSError:
-            pass
-        print(full, flush=True)
-        print(slim_line(out), flush=True)
+        line = json.dumps(out)
+        if full:
+            try:
+                with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "bench_full.json"), "w") as f:
+                    f.write(line + "\n")
+            except OSError:
+                pass
+        print(line, flush=True)
+        if full:
+            print(slim_line(out), flush=True)
 
 
 def isolated_call_leg(fn, xs, n=7, idle_s=0.05):

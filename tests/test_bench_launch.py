@@ -31,7 +31,7 @@ def test_respawn_command_line():
 def test_gpus_flag_spawns_that_many_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--stub-backend", "gloo"], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+                        "--stub-backend", "gloo", "--full"], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.strip().splitlines() if l.startswith("{")][-1]
     out = json.loads(line)
@@ -47,6 +47,23 @@ def test_gpus_flag_spawns_that_many_ranks():
     assert "cpu_baseline" in out
 
 
+def test_plain_run_measures_only_the_headline():
+    """Without --full the run times its steps and prints one line: the headline keys and the checksum of the last timed step,
+    none of the objects --full adds (the nested weak-scaling run, the roofline train, the CPU baseline)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+                        "--stub-backend", "gloo"], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["checksum_all_ranks"] == 64 * 8 * (1 + 2)
+    for k in ("c3_weak_scaling", "single_gpu_same_batch", "roofline", "cpu_baseline"):
+        assert k not in out, k
+
+
 def test_eight_ranks_partition_and_reduce():
     """The N = 8 line of the scaling curve, as far as a host without eight GPUs can run it: eight gloo ranks with the transform
     stubbed out -- 65536 / 8 = 8192 signals per rank, the rank count comes from an all-reduce, the strong-scaling top level and the
@@ -54,7 +71,7 @@ def test_eight_ranks_partition_and_reduce():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-                        "--stub-backend", "gloo"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--stub-backend", "gloo", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([l for l in p.stdout.strip().splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 8 and out["gpus_requested"] == 8 and out["stub"] is True

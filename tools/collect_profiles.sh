@@ -11,11 +11,11 @@ export LD_LIBRARY_PATH=$REPO/wavelets.jl_amd:$LD_LIBRARY_PATH
 B=$REPO/tools/wlbench.bin
 for c in c3 c1 c2 c4 c5; do
   extra="--no-secondary --no-c5"; [ $c = c3 ] && extra=""
-  timeout 400 python $REPO/bench.py --workload $c $extra > $O/bench_$c.json 2> $O/bench_$c.err
+  timeout 400 python $REPO/bench.py --full --workload $c $extra > $O/bench_$c.json 2> $O/bench_$c.err
 done
 # rocprofv3 --kernel-trace --stats of the bench command itself (short: the statistics need a few hundred launches, not more)
 for c in c3 c2 c4 c5; do
-  $REPO/tools/rp.sh $O/stats_$c $R "--kernel-trace --stats" python $REPO/bench.py --workload $c --no-cpu --no-secondary --no-c5 --no-pipelined --steps 50 --warmup 3
+  $REPO/tools/rp.sh $O/stats_$c $R "--kernel-trace --stats" python $REPO/bench.py --full --workload $c --no-cpu --no-secondary --no-c5 --no-pipelined --steps 50 --warmup 3
 done
 for k in idwt2d idwt2d_sym8 idwt2d_sym5 idwt2d_f64 lift2d lift2d_inv lift3d dwt3d modwt denoise dwt2d_f64 dwt2d_db8 wpt batch2d; do
   $REPO/tools/rp.sh $O/stats_$k $R "--kernel-trace --stats" python $REPO/tools/run_case.py $k 20
