@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import onepass3d_cases as CASES_3D
 from conftest import golden, golden_cases, make_filter, rng_array
 
 pytestmark = pytest.mark.gpu
@@ -410,6 +411,37 @@ def test_fused_pair_tile_launch(gpu, W, oracle, tj):
         torch.cuda.synchronize()
         assert np.array_equal(W.to_host(yg), oracle.dwt_filter(xin[k], wt.qmf, 8)), k
     del graph
+
+
+def test_fused_pair_tile_launch_after_a_pair(gpu, W, oracle):
+    """WL_FUSE4 = 1 where level 1 cannot fuse four levels (its tiles would be larger than WL_TILEB_MAX) but level 3 can: the fused
+    launch then starts from the ping-pong buffer that the non-fused pair of levels 1 - 2 wrote, and must not put the level-6
+    approximation into that same buffer while its pair workgroups still read it.  Level-3 blocks of one, two and four strips of
+    512 rows and 512 columns (the fused launch needs level-5 tiles of >= 128 columns), depths that end with the fused launch
+    (L = 6) and go on behind it, every chunk length, every call twice -- bit for bit against the oracle."""
+    W.set_option("WL_FUSE4", 1)
+    W.set_option("WL_LDS_PAIR_MIN", 0)
+    W.set_option("WL_TILEB_MIN", 0)
+    W.set_option("WL_PAIR_WG_PER_CU", 0)
+    W.set_option("WL_TILE", 0)
+    W.set_option("WL_M2D_MAX", 64)
+    for shape in ((2048, 2048), (4096, 2048), (8192, 2048)):
+        W.set_option("WL_TILEB_MAX", max(shape) // 16)
+        x = rng_array(shape, np.float32, sum(shape) + 3)
+        xd = dev(W, x)
+        for fname in ("db4", "haar", "db2", "db3", "sym5"):
+            wt = W.wavelet(getattr(W.WT, fname))
+            for L in (6, 7, 9):
+                ye = oracle.dwt_filter(x, wt.qmf, L)
+                for tj in (32, 64, 128):
+                    W.set_option("WL_TJ2", tj)
+                    for rep in range(2):
+                        y = host(W, W.dwt(xd, wt, L))
+                        assert W.last_kernel() == "k_fwd2d_pair", (shape, L, W.last_kernel())      # (level 1: the two-level pair)
+                        if not np.array_equal(y, ye):
+                            bad = np.argwhere(y != ye)
+                            raise AssertionError((shape, fname, L, tj, rep, len(bad), bad.min(axis=0).tolist(), bad.max(axis=0).tolist(),
+                                                  float(np.abs(y - ye).max())))
 
 
 @pytest.mark.parametrize("tj", [16, 50, 128])
@@ -1978,27 +2010,27 @@ def test_3d_forward_level_in_slabs(gpu, W, oracle, dtype):
 def test_3d_one_pass_level(gpu, W, oracle, dtype):
     """Round 6: one forward 3-D level in ONE pass over HBM (k_fwd3d_one, wl_fwd3d.hip: whole dim-1 lines per workgroup, tiles of 4 raw
     planes along dim 3, a march along dim 2) instead of the axis-3 pass + the plane kernel.  Bit for bit against the oracle and
-    against the two-pass tier: both element types, every filter length it takes (2 .. 8 taps), every line length (32 .. 1024 rows in multiples
+    against the two-pass tier: both element types, every filter length it takes (2 .. 8 taps, 10 taps in Float32), every line length (32 .. 1024 rows in multiples
     of 8 / 4: 1 .. 8 waves per workgroup, 16- and 8-byte lanes, partly filled last waves), the tile whose raw planes wrap around the end of dim 3, segments of 8 .. 64 columns,
     with and without a deeper level behind it (approximation corner to the ping-pong buffer or into y)
-    (transforms_filter.jl:246-263)."""
-    for shape, L in (((256, 16, 16), 1), ((128, 32, 16), 1), ((256, 32, 48), 2), ((512, 16, 20), 1), ((1024, 16, 16), 2), ((256, 64, 32), 3),
-                     ((512, 64, 16), 1), ((128, 64, 64), 2), ((200, 24, 20), 1), ((240, 40, 16), 2), ((320, 16, 16), 1), ((72, 16, 16), 1),
-                     ((1000, 16, 16), 1), ((136, 48, 24), 1), ((300, 16, 16), 1), ((180, 24, 20), 1), ((900, 16, 16), 1),
-                     ((256, 20, 18), 1), ((200, 30, 22), 1), ((304, 36, 28), 2), ((128, 70, 26), 1)):         # (from 200 x 24 x 20 on: lines that do not fill the last wave, 8-byte lanes on two to eight waves, dim-2 / dim-3 extents
-                                                                       #  that are not multiples of 8 / 4: the last segment / tile overlaps its neighbour)
+    (transforms_filter.jl:246-263).  The rows and the kernel instance each of them reaches: tests/onepass3d_cases.py (every instance
+    in the library has a row: test_onepass3d_coverage.py)."""
+    tname = "float" if dtype == np.float32 else "double"
+    for shape, L in CASES_3D.FWD_CASES:
         x = rng_array(shape, dtype, shape[1] + shape[2])
         xd = dev(W, x)
-        for fname in ("db4", "haar", "db2", "db3", "db5"):
+        for fname in CASES_3D.FWD_FILTERS:
             wt = W.wavelet(getattr(W.WT, fname))
+            one = CASES_3D.fwd_instance(tname, len(wt.qmf), shape[0]) is not None
             W.set_option("WL_3D_ONE", 0)
             y0 = host(W, W.dwt(xd, wt, L))
             k0 = W.last_kernel()
             assert k0 != "k_fwd3d_one", k0
             W.clear_options()
-            if fname == "db4":
-                assert np.array_equal(y0, oracle.dwt_filter(x, wt.qmf, L)), (shape, fname)
-            for tj in (64, 8, 16, 32):
+            ye = oracle.dwt_filter(x, wt.qmf, L)
+            if not np.array_equal(y0, ye):
+                raise AssertionError(("two-pass tier", shape, L, fname, int((y0 != ye).sum()), float(np.abs(y0 - ye).max())))
+            for tj in CASES_3D.FWD_TJ:
                 W.set_option("WL_3D_ONE_MIN", 0)
                 W.set_option("WL_3D_ONE_WAVES", 0)                      # (keep the requested segment length on these small boxes)
                 W.set_option("WL_3D_ONE_TJ", tj)
@@ -2006,7 +2038,10 @@ def test_3d_one_pass_level(gpu, W, oracle, dtype):
                 k = W.last_kernel()
                 W.clear_options()
                 assert k == ("k_fwd3d_one" if (len(wt.qmf) <= 8 or dtype == np.float32) else k0), (shape, fname, k)     # (10 taps: Float32, 8-byte lanes)
+                assert (k == "k_fwd3d_one") == one, (shape, fname, k)
                 assert np.array_equal(y0, y1), (shape, L, fname, tj, int((y0 != y1).sum()))
+                if not np.array_equal(y1, ye):
+                    raise AssertionError(("one-pass", shape, L, fname, tj, int((y1 != ye).sum()), float(np.abs(y1 - ye).max())))
     # the default gate: 128^3 and up take it without options
     for n in (128, 256):
         x = rng_array((n, n, n), dtype, 77)
@@ -2018,6 +2053,21 @@ def test_3d_one_pass_level(gpu, W, oracle, dtype):
         y0 = host(W, W.dwt(xd, wt, 2))
         W.clear_options()
         assert np.array_equal(y0, y1), (n, int((y0 != y1).sum()))
+        assert np.array_equal(y1, oracle.dwt_filter(x, wt.qmf, 2)), n
+    if dtype == np.float32:
+        # ... and the reference's default wavelet (sym5, 10 taps) on lines of four waves, segments of 30 columns (three groups of five
+        # steps) at level 1: back-to-back calls, every one bit for bit against the oracle
+        x = rng_array((512, 512, 128), dtype, 79)
+        xd = dev(W, x)
+        wt = W.wavelet(W.WT.sym5)
+        ye = oracle.dwt_filter(x, wt.qmf, 2)
+        ys = []
+        for rep in range(4):
+            ys.append(W.dwt(xd, wt, 2))
+            assert W.last_kernel() == "k_fwd3d_one", W.last_kernel()
+        for rep, y in enumerate(ys):
+            y = host(W, y)
+            assert np.array_equal(y, ye), (rep, int((y != ye).sum()), float(np.abs(y - ye).max()))
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -2027,23 +2077,24 @@ def test_3d_inverse_one_pass_level(gpu, W, oracle, dtype):
     pass.  Bit for bit against the oracle and the two-pass tier: both element types, 2 .. 8 taps, lines of 32 .. 1024 rows (16- and
     8-byte lanes, partly filled waves), dim-2 / dim-3 extents that are not multiples of 4 / of the segment, segments of every
     length, with the approximation octant in the coefficient array (L = 1) and in the ping-pong buffer (L > 1)
-    (transforms_filter.jl:264-287)."""
-    for shape, L in (((256, 16, 16), 1), ((128, 32, 16), 1), ((256, 32, 48), 2), ((512, 16, 20), 1), ((1024, 16, 16), 2), ((256, 64, 32), 3),
-                     ((512, 64, 16), 1), ((128, 64, 64), 2), ((200, 24, 20), 1), ((240, 40, 16), 2), ((72, 16, 16), 1), ((1000, 16, 16), 1),
-                     ((300, 16, 16), 1), ((256, 20, 18), 1), ((200, 30, 22), 1), ((128, 70, 26), 1)):
+    (transforms_filter.jl:264-287).  The rows and the kernel instance each of them reaches: tests/onepass3d_cases.py."""
+    tname = "float" if dtype == np.float32 else "double"
+    for shape, L in CASES_3D.INV_CASES:
         if dtype == np.float64 and shape[0] > 512:
             continue
         x = rng_array(shape, dtype, shape[1] + shape[2] + 1)
-        for fname in ("db4", "haar", "db2", "db3", "db5"):
+        for fname in CASES_3D.INV_FILTERS:
             wt = W.wavelet(getattr(W.WT, fname))
+            one = CASES_3D.inv_instance(tname, len(wt.qmf), shape[0]) is not None
             yd = W.dwt(dev(W, x), wt, L)
             W.set_option("WL_I3D_ONE", 0)
             x0 = host(W, W.idwt(yd, wt, L))
             k0 = W.last_kernel()
             assert k0 != "k_inv3d_one", k0
             W.clear_options()
-            if fname == "db4":
-                assert np.array_equal(x0, oracle.dwt_filter(host(W, yd), wt.qmf, L, fw=False)), (shape, fname)
+            xe = oracle.dwt_filter(host(W, yd), wt.qmf, L, fw=False)
+            if not np.array_equal(x0, xe):
+                raise AssertionError(("two-pass tier", shape, L, fname, int((x0 != xe).sum()), float(np.abs(x0 - xe).max())))
             for tk in (32, 4, 8, 16):
                 for key in ("WL_I3D_ONE_MIN", "WL_I3D_ONE_MIN_LONG", "WL_I3D_ONE_MIN_ANY", "WL_I3D_ONE_WAVES"):
                     W.set_option(key, 0)
@@ -2053,7 +2104,10 @@ def test_3d_inverse_one_pass_level(gpu, W, oracle, dtype):
                 k = W.last_kernel()
                 W.clear_options()
                 assert k == ("k_inv3d_one" if len(wt.qmf) <= 8 else k0), (shape, fname, k)
+                assert (k == "k_inv3d_one") == one, (shape, fname, k)
                 assert np.array_equal(x0, x1), (shape, L, fname, tk, int((x0 != x1).sum()))
+                if not np.array_equal(x1, xe):
+                    raise AssertionError(("one-pass", shape, L, fname, tk, int((x1 != xe).sum()), float(np.abs(x1 - xe).max())))
     for n in (128, 256):                               # the default gate: 2^20 elements for 2 / 4 taps (2^27 for 6 / 8 taps, Float32 only)
         x = rng_array((n, n, n), dtype, 78)
         wt = W.wavelet(W.WT.db2)
@@ -2064,6 +2118,7 @@ def test_3d_inverse_one_pass_level(gpu, W, oracle, dtype):
         x0 = host(W, W.idwt(yd, wt, 2))
         W.clear_options()
         assert np.array_equal(x0, x1), (n, int((x0 != x1).sum()))
+        assert np.array_equal(x1, oracle.dwt_filter(host(W, yd), wt.qmf, 2, fw=False)), n
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])

@@ -123,10 +123,12 @@ def test_soak_ti_denoise_batch(gpu, W):
     assert int((got != want).sum().item()) == 0
 
 
-@pytest.mark.parametrize("wname,inverse,expect", [("db4", False, "k_fwd3d_one"), ("db2", True, "k_inv3d_one"), ("db3", False, "k_fwd3d_one")])
+@pytest.mark.parametrize("wname,inverse,expect", [("db4", False, "k_fwd3d_one"), ("db2", True, "k_inv3d_one"), ("db3", False, "k_fwd3d_one"),
+                                                   ("sym5", False, "k_fwd3d_one")])
 def test_soak_3d_one_pass_levels(gpu, W, wname, inverse, expect):
     """Round 6: the one-pass 3-D levels (k_fwd3d_one: landing ring of F + 2 planes tied to the dim-3 sums, vmcnt(F + 1);
-    k_inv3d_one: two rounds of SH + 2 columns in flight, vmcnt(SH + 2)) on a 512 x 512 x 128 box (256 MiB in rotation x 3)."""
+    k_inv3d_one: two rounds of SH + 2 columns in flight, vmcnt(SH + 2)) on a 512 x 512 x 128 box (256 MiB in rotation x 3).  sym5: 10 taps
+    on four waves per workgroup, segments of several groups of five steps (the LDS exchange buffers alternate across group boundaries)."""
     import torch
     gen = torch.Generator(device="cuda").manual_seed(777)
     wt = W.wavelet(getattr(W.WT, wname))

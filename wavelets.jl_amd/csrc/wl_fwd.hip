@@ -1518,7 +1518,12 @@ int filter_fwd_levels(void *ws, bool ws_gen, int cu_count, int path, hipStream_t
                     (n[0] >> 2) * (n[1] >> 2) >= (int64_t)env_int_raw("WL_TILEB_MIN", 1 << 21) && fwd2d_pair_tile_ok(F, n[0], n[1], cu_count)) {
                     const bool last4 = (l + 3 == L);
                     T *ll2buf = llbuf, *ll4buf = pp ? w.A : w.B;
-                    if (aligned16(ll4buf)) {
+                    // the tiles write the level-(l+3) approximation while the pair workgroups still read `cur`: after a non-fused
+                    // pair (l > 1) the other ping-pong buffer IS cur -- then the two-level pair below runs instead (the last four
+                    // levels write it into y, not into ll4buf)
+                    const uintptr_t c_lo = (uintptr_t)cur, c_hi = (uintptr_t)(cur + cur_st.s[1] * (n[1] - 1) + n[0]);
+                    const uintptr_t q_lo = (uintptr_t)ll4buf, q_hi = (uintptr_t)(ll4buf + (n[0] >> 4) * (n[1] >> 4));
+                    if (aligned16(ll4buf) && (last4 || q_hi <= c_lo || c_hi <= q_lo)) {
                         WL_TRY(fwd2d_pair_tile_launch(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], ll2buf, n[0] >> 2, last4 ? (T *)nullptr : ll4buf,
                                                       n[0] >> 4, n[0], n[1], cu_count, tl_sync));
                         if (!dominant) dominant = "k_fwd2d_pair_tile";

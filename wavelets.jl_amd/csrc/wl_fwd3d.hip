@@ -119,6 +119,9 @@ __device__ __forceinline__ void gload_s_tied(V &dst, const T *sbase, uint32_t vo
     }
 }
 
+// LDS exchange buffers of k_fwd3d_one (see the step)
+constexpr int fwd3d_xbufs(int F) { return F <= 8 ? 2 : 3; }
+
 template <typename T, int RPL, int F, int NW>
 __global__ void __launch_bounds__(64 * NW, 2) k_fwd3d_one(Fwd3DArgs<T, F> a)
 {
@@ -126,6 +129,7 @@ __global__ void __launch_bounds__(64 * NW, 2) k_fwd3d_one(Fwd3DArgs<T, F> a)
     typedef typename Vx<T, RPL>::type V;                       // the lane's RPL rows
     typedef typename Vx<T, 4>::type X4;                        // two exchange rows: one 16- / 32-byte LDS access
     constexpr int SH = (F - 2) / 2, KR = F + 2, RS = (F <= 8) ? 8 : 10, U = RS / 2, D = KR;      // (10 taps: a 10-slot ring, groups of 5 steps)
+    static_assert(fwd3d_xbufs(F) == ((U & 1) ? 3 : 2), "exchange buffers: two for groups of even length, three for odd ones");
     constexpr int NQ = RPL / 2, NE = 10 + 2 * (NQ - 1);        // scaling (and detail) rows a lane produces; its dim-1 window in rows
     static_assert(F >= 2 && F <= 10 && (F % 2) == 0, "column ring of 8 (10) slots");
     static_assert(F <= 8 || (sizeof(T) == 4 && RPL == 2), "10 taps: Float32 on 8-byte lanes only (ring of 10 x 4 planes)");
@@ -152,7 +156,7 @@ __global__ void __launch_bounds__(64 * NW, 2) k_fwd3d_one(Fwd3DArgs<T, F> a)
     const int n1 = a.n1, n2 = a.n2, h1 = n1 >> 1, h2 = n2 >> 1;
     constexpr int rows1 = 64 * RPL * NW + 16;                   // exchange rows per plane (T2 each): the line + a copy of its first 8 rows
     const bool active = RPL * lp < n0;
-    T2 *const x1 = reinterpret_cast<T2 *>(smem_raw);            // [2][4][rows1]
+    T2 *const x1 = reinterpret_cast<T2 *>(smem_raw);            // [fwd3d_xbufs(F)][4][rows1]
 
     const int ko = NQ * lp;
     int kod = ko + 4;  if (kod >= h0) kod -= h0;
@@ -229,7 +233,11 @@ __global__ void __launch_bounds__(64 * NW, 2) k_fwd3d_one(Fwd3DArgs<T, F> a)
         column(2 * t + F - 2, (2 * u + F - 2) % RS, true);
         column(2 * t + F - 1, (2 * u + F - 1) % RS, pfb);
         // ---- dim-2 pass on the column ring, per output plane; {A, B}[r] = scaling / detail (column k / kd) of row r ----
-        T2 *const wbuf = x1 + (u & 1) * 4 * rows1;                 // (t and u have the same parity: groups of U = 4 steps)
+        // exchange buffer: one barrier per step, so consecutive steps -- across the boundary of two groups too -- must not share one (the
+        // dim-2 writes of step t + 1 may start while a slower wave still reads step t).  Groups of U = 4 steps alternate two buffers; the
+        // 10-tap groups (U = 5) end in a third one, or their last step and the next group's first would both take buffer 0
+        const int xb = ((U & 1) && u == U - 1) ? 2 : (u & 1);
+        T2 *const wbuf = x1 + xb * 4 * rows1;
 #pragma unroll
         for (int z = 0; z < 4; ++z) {
             V sa = smul<T, V, RPL>(a.tp.h[0], ring[(2 * u) % RS][z]);
@@ -355,7 +363,7 @@ template bool fwd3d_one_ok<double>(int, const double *, int64_t, int64_t, const 
 template <typename T, int RPL, int F, int NW>
 static hipError_t launch_fwd3d_inst(hipStream_t st, unsigned nwg, const Fwd3DArgs<T, F> &a)
 {
-    const size_t shmem = (size_t)2 * 4 * (64 * RPL * NW + 16) * 2 * sizeof(T);
+    const size_t shmem = (size_t)fwd3d_xbufs(F) * 4 * (64 * RPL * NW + 16) * 2 * sizeof(T);
     static thread_local int attr_dev[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
     int dev = 0;
     (void)hipGetDevice(&dev);
