@@ -7,10 +7,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import oracle
 import wavelets_jl_amd as W
+import lifting_schemes as LS
 
 FILTERS = ["haar", "db2", "db3", "db4", "db5", "db6", "db7", "db8", "db9", "db10", "sym4", "sym5", "sym6", "sym8", "sym10",
            "coif2", "coif4", "coif6", "coif8", "batt2", "batt4", "batt6", "vaid", "beyl"]
-SCHEMES = ["haar", "db2", "cdf97"]
+# the reference's table schemes and the user-defined ones of tests/lifting_schemes.py (twins of the known shapes, custom shapes,
+# near misses, shifts up to the int32 limits)
+SCHEMES = ["haar", "db2", "cdf97"] + sorted(LS.TWINS) + sorted(LS.CUSTOM) + sorted(LS.NEAR_MISSES)[::4] + sorted(LS.LARGE_SHIFTS)
 
 
 def rand_len(r, lo, hi):
@@ -57,7 +60,7 @@ def one_case(r, verbose=False):
             for i in range(1, min(len(tree), 2 ** depth - 1)):
                 tree[i] = 1 if (tree[(i + 1) // 2 - 1] and r.random() < p) else 0
         if lifting:
-            sch = W.wavelet(getattr(W.WT, str(r.choice(SCHEMES))), W.WT.Lifting)
+            sch = LS.scheme(W, str(r.choice(SCHEMES)))
             ye = oracle.wpt_lifting(x, sch, tree)
             y = W.to_host(W.wpt(xd, sch, tree)); kf = W.last_kernel()
             xr = W.to_host(W.iwpt(W.to_device(ye), sch, tree)); ki = W.last_kernel()
@@ -91,7 +94,7 @@ def one_case(r, verbose=False):
         return kf, ki
     if lifting:
         name = str(r.choice(SCHEMES))
-        wt = W.wavelet(getattr(W.WT, name), W.WT.Lifting)
+        wt = LS.scheme(W, name)
         ye = oracle.dwt_lifting(x, wt, L)
         xe = oracle.dwt_lifting(ye, wt, L, fw=False)
     else:

@@ -3,6 +3,7 @@ denoise pipeline, through the C ABI, BIT-EXACT against the CPU oracle on the sam
 import numpy as np
 import pytest
 
+import lifting_schemes as LS
 from conftest import rng_array
 from test_oracle_ext import doppler
 
@@ -255,8 +256,8 @@ def test_ti_fused_thresholds_all_kinds(gpu, W, oracle):
 def test_denoise_ti_lifting_batch_bitexact(gpu, W, oracle, dtype):
     """wl_denoise_ti_lifting (round 4): the translation-invariant branch of denoise for lifting schemes as one device-resident
     batch -- value for value the reference's per-spin sequence (denoising.jl:36-67) as restated by the oracle"""
-    for sname in ("cdf97", "db2"):
-        sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+    for sname in ("cdf97", "db2", "twin_cdf97", "twin_db2"):
+        sch = LS.scheme(W, sname)
         v = (doppler(2048) + 0.05 * np.random.default_rng(14).standard_normal(2048)).astype(dtype)
         for nsp, L, dnt in ((8, 6, W.VisuShrink(2048)), (5, 3, W.VisuShrink(W.SoftTH(), 1.5)), (3, 0, W.VisuShrink(W.HardTH(), 0.7))):
             e = _oracle_denoise(oracle, W, v, sch, L, dnt, True, (nsp,))

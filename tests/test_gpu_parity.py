@@ -6,10 +6,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import lifting_schemes as LS
 import onepass3d_cases as CASES_3D
 from conftest import golden, golden_cases, make_filter, rng_array
 
 pytestmark = pytest.mark.gpu
+
+# user schemes with the step sequences of cdf9/7, db2 and haar and other coefficients: the shape-specialised kernels with
+# coefficients they were not written around (tests/lifting_schemes.py)
+TWINS = tuple(LS.TWINS)
 
 
 def dev(W, a):
@@ -874,13 +879,14 @@ def test_randomized_shapes_near_dispatch_thresholds(gpu, W, oracle):
     # lifting lines around the stream / tail thresholds
     for n in (504, 512, 520, 8192, 8200, 16384, 16392, 32768 + 8, 65536):
         x = rng_array((n,), np.float32 if n % 16 else np.float64, n)
-        sch = W.wavelet(getattr(W.WT, ("cdf97", "db2", "haar")[n % 3]), W.WT.Lifting)
+        sname = ("cdf97", "db2", "haar")[n % 3]
         L = int(rs.integers(1, W.maxtransformlevels(n) + 1))
-        ye = oracle.dwt_lifting(x, sch, L)
-        assert np.array_equal(host(W, W.dwt(dev(W, x), sch, L)), ye), (n, sch.name, L, W.last_kernel())
-        t = dev(W, ye)
-        W.idwt_(t, sch, L)
-        assert np.array_equal(host(W, t), oracle.dwt_lifting(ye, sch, L, fw=False)), (n, sch.name, L, "inv in place")
+        for sch in (LS.scheme(W, sname), LS.scheme(W, "twin_" + sname)):
+            ye = oracle.dwt_lifting(x, sch, L)
+            assert np.array_equal(host(W, W.dwt(dev(W, x), sch, L)), ye), (n, sch.name, L, W.last_kernel())
+            t = dev(W, ye)
+            W.idwt_(t, sch, L)
+            assert np.array_equal(host(W, t), oracle.dwt_lifting(ye, sch, L, fw=False)), (n, sch.name, L, "inv in place")
     # batched columns with leading dimension / line counts around the slab and alignment rules
     for (n, ns) in ((520, 3), (4096, 5), (16392, 2), (32768, 9)):
         x = rng_array((n, ns), np.float32, n + ns)
@@ -919,8 +925,8 @@ LSHAPES = [(2,), (4,), (8,), (40,), (1024,), (1 << 15,), (2, 2), (8, 8), (32, 32
 def test_lifting_fwd_inv_bitexact(gpu, W, oracle, dtype, shape):
     x = rng_array(shape, dtype, 5 + sum(shape))
     Lmax = W.maxtransformlevels(x)
-    for sname in ("cdf97", "db2", "haar", "db1"):
-        sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+    for sname in ("cdf97", "db2", "haar", "db1") + TWINS:
+        sch = LS.scheme(W, sname)
         for L in sorted({0, 1, Lmax}):
             ye = oracle.dwt_lifting(x, sch, L)
             y = host(W, W.dwt(dev(W, x), sch, L))
@@ -941,8 +947,8 @@ def test_lifting_cubes_fast_vs_generic(gpu, W, oracle):
     kernels (256^3), forward and inverse."""
     for n, L in ((128, 7), (128, 2), (256, 3)):
         x = rng_array((n, n, n), np.float32, n)
-        for sname in ("cdf97", "db2", "haar"):
-            sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+        for sname in ("cdf97", "db2", "haar") + TWINS:
+            sch = LS.scheme(W, sname)
             y = host(W, W.dwt(dev(W, x), sch, L))
             assert "k_lift_short_lines" in W.last_kernel()
             if n <= 128:
@@ -970,10 +976,10 @@ def test_lifting_2d_tile_kernel(gpu, W, oracle):
             if n >= 2048 and dtype == np.float64:
                 continue
             x = rng_array((n, n), dtype, n + 5)
-            for sname in ("cdf97", "db2", "haar"):
+            for sname in ("cdf97", "db2", "haar") + TWINS:
                 if n == 4096 and sname != "cdf97":
                     continue
-                sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+                sch = LS.scheme(W, sname)
                 for L in Ls:
                     if tmax:
                         W.set_option("WL_LIFT_TILE_MAX", tmax)
@@ -1017,8 +1023,8 @@ def test_lifting_2d_axis_stream_kernel(gpu, W, oracle, tp, fused):
             if n == 2048 and dtype == np.float64:
                 continue
             x = rng_array((n, n), dtype, n)
-            for sname in ("cdf97", "db2", "haar"):
-                sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+            for sname in ("cdf97", "db2", "haar") + TWINS:
+                sch = LS.scheme(W, sname)
                 for L in Ls:
                     ye = oracle.dwt_lifting(x, sch, L)
                     y = host(W, W.dwt(dev(W, x), sch, L))
@@ -1043,8 +1049,8 @@ def test_lifting_lines_fast_paths(gpu, W, oracle, dtype):
     the generic family forced through wl_ctx_set_path(1): all bit-identical to the oracle."""
     for n, Ls in (((1 << 16), (16, 1, 3)), (3 << 15, (15, 2)), ((1 << 18), (18, 5))):
         x = rng_array((n,), dtype, n % 1000)
-        for sname in ("cdf97", "db2", "haar"):
-            sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+        for sname in ("cdf97", "db2", "haar") + TWINS:
+            sch = LS.scheme(W, sname)
             for L in Ls:
                 ye = oracle.dwt_lifting(x, sch, L)
                 y = host(W, W.dwt(dev(W, x), sch, L))
@@ -1085,8 +1091,8 @@ def test_lifting_register_tail(gpu, W, oracle, dtype):
     while n <= nmax:
         x = rng_array((n,), dtype, n)
         Lmax = W.maxtransformlevels(n)
-        for sname in ("cdf97", "db2", "haar"):
-            sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+        for sname in ("cdf97", "db2", "haar") + TWINS:
+            sch = LS.scheme(W, sname)
             for L in sorted({1, 2, Lmax // 2, Lmax - 1, Lmax} - {0}):
                 if L > Lmax:
                     continue
@@ -1132,8 +1138,8 @@ def test_lifting_register_tail_2d(gpu, W, oracle, dtype):
     column in registers, compile-time wrap and in-bounds / boundary summation forms): every block size from 2 to 64, every
     depth, the three scheme shapes, forward and inverse, in place, as the end of a larger transform -- bit for bit against
     the oracle and against the LDS workgroup tail it replaces."""
-    for sname in ("cdf97", "db2", "haar"):
-        sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+    for sname in ("cdf97", "db2", "haar") + TWINS:
+        sch = LS.scheme(W, sname)
         n = 2
         while n <= 64:
             x = rng_array((n, n), dtype, n + len(sname))
@@ -1167,8 +1173,8 @@ def test_lifting_lds_tail_2d_thread_per_line(gpu, W, oracle, dtype):
     the sizes the register tail normally takes here too), every depth, the three scheme shapes, forward and inverse, in place,
     as the end of a larger transform -- bit for bit against the oracle and against the register tail / tile launches."""
     nmax = 128 if dtype == np.float32 else 64
-    for sname in ("cdf97", "db2", "haar"):
-        sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+    for sname in ("cdf97", "db2", "haar") + TWINS:
+        sch = LS.scheme(W, sname)
         n = 2
         while n <= nmax:
             x = rng_array((n, n), dtype, n + 2 * len(sname))
@@ -1201,8 +1207,8 @@ def test_lifting_lds_tail_3d(gpu, W, oracle, dtype):
     LDS, a thread per line, planes -> rows -> columns and back): every cube from 8 to 64, every depth, the three scheme shapes,
     forward and inverse, in place, as the end of a larger transform -- bit for bit against the oracle and against the per-axis
     launches it replaces."""
-    for sname in ("cdf97", "db2", "haar"):
-        sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+    for sname in ("cdf97", "db2", "haar") + TWINS:
+        sch = LS.scheme(W, sname)
         for n in (8, 16, 32, 64):
             x = rng_array((n, n, n), dtype, n + len(sname))
             for L in range(1, W.maxtransformlevels(n) + 1):
@@ -1234,8 +1240,8 @@ def test_lifting_any_even_size_tile_kernel(gpu, W, oracle, dtype):
     position): sizes that are not multiples of 8, blocks barely larger than a tile, partial edge tiles, levels below the
     streaming kernels of a larger transform; the three scheme shapes, forward and inverse -- bit for bit against the oracle
     and against the one-thread-per-element kernels it replaces."""
-    for sname in ("cdf97", "db2", "haar"):
-        sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+    for sname in ("cdf97", "db2", "haar") + TWINS:
+        sch = LS.scheme(W, sname)
         for n, Ls in ((66, (1,)), (100, (1, 2)), (130, (1,)), (250, (1,)), (500, (1, 2)), (1000, (3,)), (132, (2,)), (3000, (3,)), (72, (3,))):
             if n >= 3000 and (sname != "cdf97" or dtype == np.float64):
                 continue
@@ -1252,8 +1258,8 @@ def test_lifting_any_even_size_tile_kernel(gpu, W, oracle, dtype):
                         assert np.array_equal(host(W, W.dwt(dev(W, x), sch, L)), ye), (sname, n, L, "generic")
                         assert np.array_equal(host(W, W.idwt(dev(W, ye), sch, L)), xe), (sname, n, L, "generic inv")
     # the rank-generic driver (3-D volumes of any even size, in-place 2-D level 1): one k_lift_any launch per axis and level
-    for sname in ("cdf97", "db2", "haar"):
-        sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+    for sname in ("cdf97", "db2", "haar") + TWINS:
+        sch = LS.scheme(W, sname)
         for n, L in ((10, 1), (36, 2), (100, 2), (6, 1)):
             x = rng_array((n, n, n), dtype, n)
             ye = oracle.dwt_lifting(x, sch, L)
@@ -1285,8 +1291,8 @@ def test_lifting_lines_any_even_length(gpu, W, oracle, dtype):
     """k_lift1d_gtile (one 1-D lifting level of lines of ANY even length: a lane owns 28 pairs and holds their 32-pair window
     in registers): lengths that are not multiples of 8 or have a large odd factor, alone, below the streaming kernels and
     above the LDS tail, in place, batched columns -- bit for bit against the oracle."""
-    for sname in ("cdf97", "db2", "haar"):
-        sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+    for sname in ("cdf97", "db2", "haar") + TWINS:
+        sch = LS.scheme(W, sname)
         for n, L in ((1000000, 6), (3000, 3), (4100, 2), (2100, 1), (6 * 4096, 13), (100004, 2), (2052, 2)):
             if n >= 1000000 and sname != "cdf97":
                 continue
@@ -1517,7 +1523,7 @@ def test_wpt_bitexact(gpu, W, oracle, dtype):
                 assert np.array_equal(y, ye), (n, fname, tree.tolist())
                 assert np.array_equal(host(W, W.iwpt(dev(W, ye), wt, tree)), oracle.wpt_filter(ye, wt.qmf, tree, fw=False))
             for sname in ("cdf97", "db2"):
-                sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+                sch = LS.scheme(W, sname)
                 ye = oracle.wpt_lifting(x, sch, tree)
                 assert np.array_equal(host(W, W.wpt(dev(W, x), sch, tree)), ye), (n, sname, tree.tolist())
                 assert np.array_equal(host(W, W.iwpt(dev(W, ye), sch, tree)), oracle.wpt_lifting(ye, sch, tree, fw=False))
@@ -1632,8 +1638,8 @@ def test_wpt_fast_paths_bitexact_and_pinned(gpu, W, oracle):
     for n, L in ((1 << 16, 6), (1 << 18, 3)):
         x = rng_array((n,), np.float32, 5)
         tree = W.maketree(n, L, "full")
-        for sname in ("cdf97", "db2"):
-            sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+        for sname in ("cdf97", "db2", "twin_cdf97", "twin_db2"):
+            sch = LS.scheme(W, sname)
             ye = oracle.wpt_lifting(x, sch, tree)
             assert np.array_equal(host(W, W.wpt(dev(W, x), sch, tree)), ye), (n, sname)
             assert W.last_kernel().startswith("k_lift1d") or W.last_kernel().startswith("k_tail_lift"), W.last_kernel()
@@ -2254,10 +2260,10 @@ def test_lifting_two_level_tiles_2d(gpu, W, oracle, dtype):
     for n, Ls in ((128, (1, 2, 3, 7)), (256, (2, 8)), (512, (3, 4)), (1024, (2, 10)), (2048, (5,)), (192, (2, 6)), (4096, (5,))):
         x = rng_array((n, n), dtype, n)
         xd = dev(W, x)
-        for sname in ("cdf97", "db2", "haar"):
+        for sname in ("cdf97", "db2", "haar") + TWINS:
             if n >= 2048 and sname != "cdf97":
                 continue
-            sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+            sch = LS.scheme(W, sname)
             for L in Ls:
                 W.set_option("WL_LIFT_TILE2_MAX", 4096)               # (default: Float32 blocks of <= 1024 rows; forced on for every size
                 W.set_option("WL_LIFT_TILE2_F64", 1)                  #  and for Float64 here)

@@ -10,6 +10,7 @@
 import numpy as np
 import pytest
 
+import lifting_schemes as LS
 from conftest import rng_array
 
 pytestmark = pytest.mark.gpu
@@ -127,6 +128,11 @@ LIFT_CASES = [
     ("2-D lifting any even size", (1000, 1000), "cdf97", 3, np.float32),
     ("2-D lifting db2", (512, 512), "db2", 9, np.float32),
     ("3-D lifting cube", (64, 64, 64), "cdf97", 6, np.float32),
+    # user schemes with the shapes of cdf9/7, db2 and haar (tests/lifting_schemes.py): the same kernels, other coefficients
+    ("1-D lifting cdf9/7 twin", (1 << 18,), "twin_cdf97", 18, np.float32),
+    ("2-D lifting cdf9/7 twin", (1024, 1024), "twin_cdf97", 10, np.float32),
+    ("2-D lifting db2 twin", (512, 512), "twin_db2", 9, np.float64),
+    ("1-D lifting haar twin", (300000,), "twin_haar", 5, np.float32),
 ]
 
 
@@ -135,7 +141,7 @@ def test_guard_bands_lifting(gpu, W, oracle, misalign):
     """lifting transforms: in place (dwt!(y, scheme)) and out of place (dwt_oop!), forward and inverse"""
     import torch
     for label, shape, sname, L, dtype in LIFT_CASES:
-        sch = W.wavelet(getattr(W.WT, sname), W.WT.Lifting)
+        sch = LS.scheme(W, sname)
         N = int(np.prod(shape))
         a = rng_array(shape, dtype, N % 9973 + 5 + misalign)
         g = Guarded(torch, dtype, [N, N], misalign)

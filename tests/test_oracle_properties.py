@@ -169,6 +169,26 @@ def test_closed_form_lift_bitexact(oracle, W, dtype):
                     oracle.lift(w_o, half, is_upd, st.param.shift, c)
                     w_c = cf.lift_step(w.copy(), half, is_upd, st.param.shift, c)
                     assert np.array_equal(w_o, w_c), (sname, half, st, np.abs(w_o - w_c).max())
+    # user steps (tests/lifting_schemes.py): nc = 1, 2, 3 with distinct coefficients, shifts -6..6 and +-(k * half + r) up to the
+    # int32 limits (operand indices that wrap many times; the oracle computes them in 64 bits like the reference's mod1)
+    coefs = ((0.8125,), (0.3, -1.7), (-0.45, 0.2, 1.35))
+    for half in (1, 2, 3, 4, 5, 6, 7, 8, 9, 20, 32):
+        shifts = set(range(-6, 7)) | {2 ** 31 - 1, -(2 ** 31 - 1), -2 ** 31}
+        for k in (1, 2, 3, 1000, 2 ** 20 + 3, (2 ** 31 - 1) // half):
+            for r in (0, 1, half - 1):
+                v = k * half + r
+                if v <= 2 ** 31 - 1:
+                    shifts |= {v, -v}
+        for shift in sorted(shifts):
+            for c0 in coefs:
+                for sign in (-1.0, 1.0):
+                    c = (np.array(c0) * sign).astype(dtype)
+                    for is_upd in (False, True):
+                        w = rng_array((2 * half,), dtype, half * 7 + len(c) + (shift % 97))
+                        w_o = w.copy()
+                        oracle.lift(w_o, half, is_upd, shift, c)
+                        w_c = cf.lift_step(w.copy(), half, is_upd, shift, c)
+                        assert np.array_equal(w_o, w_c), (half, shift, c, is_upd, np.abs(w_o - w_c).max())
 
 
 def test_threaded_2d_oracle_is_bit_identical(oracle, W):

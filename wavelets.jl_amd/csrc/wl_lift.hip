@@ -423,19 +423,21 @@ __device__ __forceinline__ void tail_lift_steps(T *w, int half, const LiftScheme
         T *tgt = w + (sp.is_update ? half : 0);
         const T *op = w + (sp.is_update ? 0 : half);
         for (int j = tid; j < half; j += nthr) {
-            const int j0 = j - sp.shift;
+            // j0 and the in-bounds test in 64 bits with the unreduced shift (any int32 shift: j - shift overflows int),
+            // each wrapped operand index reduced by one pmod -- the reference's Int64 mod1, as in k_generic_lift_step
+            const int64_t j0 = (int64_t)j - sp.shift;
             const bool inb = (j0 >= 0) && (j0 + sp.nc - 1 <= half - 1);
             T x = tgt[j];
             if (inb) {
-                T acc = sp.c[0] * op[j0];
-                if (sp.nc > 1) acc = acc + sp.c[1] * op[j0 + 1];
-                if (sp.nc > 2) acc = acc + sp.c[2] * op[j0 + 2];
+                const int i0 = (int)j0;
+                T acc = sp.c[0] * op[i0];
+                if (sp.nc > 1) acc = acc + sp.c[1] * op[i0 + 1];
+                if (sp.nc > 2) acc = acc + sp.c[2] * op[i0 + 2];
                 x = x + acc;
             } else {
                 for (int k = 0; k < sp.nc; ++k) {
-                    int i = j0 + k;
-                    while (i < 0) i += half;
-                    while (i >= half) i -= half;
+                    int64_t i = j0 + k;
+                    if (i < 0 || i >= half) i = pmod(i, half);
                     x = x + sp.c[k] * op[i];
                 }
             }
@@ -827,19 +829,19 @@ __device__ __forceinline__ void tail_lift_steps_lines(T *w, int half, int nlines
             l_split_idx(e, half, l, j);
             T *tgt = w + l * m + toff;
             const T *op = w + l * m + ooff;
-            const int j0 = j - shift;
+            const int64_t j0 = (int64_t)j - shift;              // (64 bits and one pmod: see tail_lift_steps)
             const bool inb = (j0 >= 0) && (j0 + nc - 1 <= half - 1);
             T x = tgt[j];
             if (inb) {
-                T acc = c0 * op[j0];
-                if (nc > 1) acc = acc + c1 * op[j0 + 1];
-                if (nc > 2) acc = acc + c2 * op[j0 + 2];
+                const int i0 = (int)j0;
+                T acc = c0 * op[i0];
+                if (nc > 1) acc = acc + c1 * op[i0 + 1];
+                if (nc > 2) acc = acc + c2 * op[i0 + 2];
                 x = x + acc;
             } else {
                 for (int k = 0; k < nc; ++k) {
-                    int i = j0 + k;
-                    while (i < 0) i += half;
-                    while (i >= half) i -= half;
+                    int64_t i = j0 + k;
+                    if (i < 0 || i >= half) i = pmod(i, half);
                     x = x + (k == 0 ? c0 : (k == 1 ? c1 : c2)) * op[i];
                 }
             }
