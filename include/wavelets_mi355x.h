@@ -195,6 +195,21 @@ WL_API int wl_dwtc_lifting_oop(wl_ctx *ctx, int dtype, void *y, const void *x,
 WL_API int wl_dwt_filter_batch(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nimages,
                         int64_t image_stride, const double *qmf, int flen, int L, int fw, void *stream);
 
+/* y[:, :, i] = dwt(x[:, :, i], scheme, L) (fw = 0: idwt) for nimages SQUARE images of dims[0] x dims[1], laid out as for
+ * wl_dwt_filter_batch; the scheme is passed as for wl_dwt_lifting.  The same results, bit for bit, as nimages calls of
+ * wl_dwt_lifting_oop with ndims = 2 (transforms_lifting.jl:128-196 per image), but every level is ONE launch over all images
+ * (groups of 65535) and the deepest levels of every image finish in one launch, a workgroup per image.  y == x is allowed and is
+ * dwt!(y, scheme, L) of every image; L = 0 copies the images and leaves the padding between them alone.  Status codes in this
+ * order: WL_EINVAL_ARG, WL_EINVAL_DTYPE, WL_EINVAL_CUBE (dims[0] != dims[1]), WL_EDIMS, WL_EINVAL_L, WL_EINVAL_SIZE,
+ * WL_EINVAL_SCHEME.  Workspace: nothing is allocated once wl_workspace_bytes_full(dtype, 1, {nimages * image_stride}, L)
+ * bytes are reserved.  What the tile and tail tiers really hold is the approximation ping-pong of every image of a group,
+ * 2 * (min(nimages, 65535) * dims[0]^2 / 2 + 64) elements; an in-place batch of images of more than 64 rows adds a dense copy
+ * of the group, and schemes or alignments the fast tiers refuse use the full amount.                                       */
+WL_API int wl_dwt_lifting_batch(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nimages,
+                         int64_t image_stride, int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
+                         const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2, int L, int fw,
+                         void *stream);
+
 /* ---- wavelet packet transform (1-D) --------------------------------------------------- */
 /* y = wpt(x, filter, tree) / iwpt.  tree: one byte per node of the BitVector
  * (length 2^maxtransformlevels(n) - 1, util_main.jl:301-344), HOST pointer; it is copied before the call returns (the node
@@ -283,7 +298,7 @@ WL_API int wl_denoise_ti_filter(wl_ctx *ctx, int dtype, void *y, const void *x, 
                          const double *qmf, int flen, int L, int th, double t_unit, const int64_t *nspin,
                          double sigma_host, void *stream);
 /* The same for a lifting scheme (wt::GLS; scheme arguments as wl_dwt_lifting): shifted signals run as one batched-lines
- * transform, shifted images one 2-D lifting transform per plane; sigma and everything else stay on the device.
+ * transform, shifted images one batched 2-D lifting transform per group of spins; sigma and everything else stay on the device.
  * replaces the translation-invariant branch of denoise(x, wt::GLS; TI=true), denoising.jl:36-67 (round 4).               */
 WL_API int wl_denoise_ti_lifting(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims,
                           int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,

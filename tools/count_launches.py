@@ -1,0 +1,40 @@
+"""Launches per call from a kernel trace of `tools/time_batch.py launches`:
+
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -- python tools/time_batch.py launches > calls.txt
+    python tools/count_launches.py <dir> calls.txt
+
+The traced script separates its calls by fills of a marker tensor; the library's kernels (namespace wl) dispatched between
+fill k and fill k + 1 are the launches of call k.  Markdown rows: call, launches, kernels in dispatch order.
+"""
+import csv
+import glob
+import os
+import re
+import sys
+
+
+def main(trace_dir, calls_txt):
+    files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        sys.exit("no *kernel_trace.csv under " + trace_dir)
+    rows = []
+    for f in files:
+        with open(f, newline="") as fh:
+            for r in csv.DictReader(fh):
+                rows.append((int(r["Start_Timestamp"]), r["Kernel_Name"]))
+    rows.sort()
+    labels = [m.group(2) for m in (re.match(r"call (\d+): (.*)", l) for l in open(calls_txt)) if m]
+    fills = [i for i, (_, name) in enumerate(rows) if "FillFunctor" in name]
+    fills = fills[-(len(labels) + 1):]                       # (the marker tensor's own zero fill comes first)
+    if len(fills) != len(labels) + 1:
+        sys.exit("found %d marker fills for %d calls" % (len(fills), len(labels)))
+    print("| call | launches | kernels |")
+    print("|---|---|---|")
+    for k, label in enumerate(labels):
+        names = [re.sub(r"^void ", "", re.sub(r"\(.*$", "", n)) for _, n in rows[fills[k] + 1:fills[k + 1]] if "wl::" in n]
+        short = [re.sub(r"<.*$", "", n.split("wl::")[-1].replace("(anonymous namespace)::", "")) for n in names]
+        print("| %s | %d | %s |" % (label, len(names), ", ".join(short)))
+
+
+if __name__ == "__main__":
+    main(sys.argv[1], sys.argv[2])

@@ -297,6 +297,24 @@ int dwt_lifting_impl(wl_ctx *ctx, hipStream_t st, const BoxSpec &b, T *y, const 
     return wl_lifting_box<T>(ctx, st, b, y, x, sc, L, fw);
 }
 
+// a batch of square images: the box of wl_dwt_filter_batch (third extent = images), images in groups of at most 65535
+template <typename T>
+int lifting_batch_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n, int64_t nimages, int64_t image_stride,
+                       const LiftScheme<T> &sc, int L, int fw)
+{
+    BoxSpec b;
+    b.nd = 3; b.nt = 2;
+    b.dims[0] = n; b.dims[1] = n;
+    b.full.s[0] = 1; b.full.s[1] = n; b.full.s[2] = image_stride;
+    // images in groups of at most 65535 (one grid plane / workgroup per image in the batched kernels)
+    for (int64_t i0 = 0; i0 < nimages; i0 += 65535) {
+        b.dims[2] = (nimages - i0 < 65535) ? (nimages - i0) : 65535;
+        int rc = wl_lifting_box<T>(ctx, st, b, y + i0 * image_stride, x + i0 * image_stride, sc, L, fw);
+        if (rc) return rc;
+    }
+    return WL_OK;
+}
+
 }  // namespace
 
 template <typename T>
@@ -335,6 +353,14 @@ int wl_lifting_box(wl_ctx *ctx, hipStream_t st, const BoxSpec &b, T *y, const T 
         int handled = 0;
         rc = lifting_2d_fast<T>(ctx->ws, ctx->cu_count, st, b.dims[0], b.full.s[1], y, x, sc, L, fw, &handled,
                                 &ctx->last_kernel, &ctx->last_hip);
+        if (rc) return rc;
+        if (handled) return WL_OK;
+    }
+    // a batch of square images (third extent = images, any image stride): every level one launch over all of them
+    if (ctx->path == 0 && b.nd == 3 && b.nt == 2 && b.full.s[0] == 1 && b.dims[0] == b.dims[1] && b.dims[2] <= 65535) {
+        int handled = 0;
+        rc = lifting_2d_fast<T>(ctx->ws, ctx->cu_count, st, b.dims[0], b.full.s[1], y, x, sc, L, fw, &handled,
+                                &ctx->last_kernel, &ctx->last_hip, b.dims[2], b.full.s[2]);
         if (rc) return rc;
         if (handled) return WL_OK;
     }
@@ -990,6 +1016,31 @@ int wl_dwt_filter_batch(wl_ctx *ctx, int dtype, void *y, const void *x, const in
         if (rc) return rc;
     }
     return WL_OK;
+}
+
+int wl_dwt_lifting_batch(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nimages, int64_t image_stride,
+                         int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef, const int32_t *step_shift,
+                         const double *coefs_flat, double norm1, double norm2, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !dims) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (dims[0] != dims[1]) return WL_EINVAL_CUBE;           // the square rule comes first in the reference (transforms_lifting.jl:131-132)
+    if (dims[0] < 1 || nimages < 1 || image_stride < dims[0] * dims[1]) return WL_EDIMS;
+    if (L < 0) return WL_EINVAL_L;
+    if (!sufficientpoweroftwo(dims[0], L)) return WL_EINVAL_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == WL_F32) {
+        LiftScheme<float> sc;
+        int rc = make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
+        if (rc) return rc;
+        WL_SCOPE(ctx);
+        return lifting_batch_impl<float>(ctx, st, (float *)y, (const float *)x, dims[0], nimages, image_stride, sc, L, fw);
+    }
+    LiftScheme<double> sc;
+    int rc = make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
+    if (rc) return rc;
+    WL_SCOPE(ctx);
+    return lifting_batch_impl<double>(ctx, st, (double *)y, (const double *)x, dims[0], nimages, image_stride, sc, L, fw);
 }
 
 int wl_wpt_filter_full(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, const double *qmf, int flen, int L, int fw, void *stream)

@@ -1023,7 +1023,7 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
 // The same device-resident sequence as denoise_ti_impl -- sigma from the level-1 transform without a host round trip, the spins
 // shifted / transformed / thresholded / inverted / un-shifted / accumulated B at a time -- with the lifting transforms of the
 // library: a batch of shifted SIGNALS is one batched-lines call (the fused line kernels over all spins), a batch of shifted
-// IMAGES is one 2-D lifting transform per plane (the 2-D lifting kernels are not plane-batched).
+// IMAGES is one batched 2-D lifting transform (every level one launch over all spins of the group, as wl_dwt_lifting_batch).
 template <typename T>
 int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, const LiftScheme<T> &scf,
                             const LiftScheme<T> &sci, int L, int th, double t_unit, const int64_t *nspin, double sigma_host)
@@ -1034,8 +1034,9 @@ int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
     if (rc != WL_OK) return rc;
     SelState *sel = (SelState *)ctx->aux;
     const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
-    // transform workspace: the batched-lines box (1-D) or one plane (2-D), then the shifted copies Z and their coefficients XT
-    auto tws = [&](int64_t B) { return ws_elems(ndims == 1 ? N * B : N, 1); };
+    // transform workspace of the batched box (B lines, or B images: the approximation ping-pong of every image), then the shifted
+    // copies Z and their coefficients XT
+    auto tws = [&](int64_t B) { return ws_elems(N * B, 1); };
     auto need = [&](int64_t B) { return (tws(B) + (size_t)2 * N * B + (size_t)n0 + 64) * sizeof(T); };
     int64_t B = pns;
     while (B > 1 && need(B) > cap) B = (B + 1) / 2;
@@ -1082,11 +1083,11 @@ int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
             bb.full = dense_strides(bb.dims);
             return wl_lifting_box<T>(ctx, st, bb, dst, src, sc, L, fw);
         }
-        for (int64_t p = 0; p < nb; ++p) {
-            int r = wl_lifting_box<T>(ctx, st, b1, dst + p * N, src + p * N, sc, L, fw);
-            if (r != WL_OK) return r;
-        }
-        return WL_OK;
+        BoxSpec bb;                                          // nb images = the third extent of one batched call
+        bb.nd = 3; bb.nt = 2;
+        bb.dims[0] = n0; bb.dims[1] = n1; bb.dims[2] = nb;
+        bb.full = dense_strides(bb.dims);
+        return wl_lifting_box<T>(ctx, st, bb, dst, src, sc, L, fw);
     };
     for (int64_t b0 = 0; b0 < pns; b0 += B) {
         const int64_t nb = (pns - b0 < B) ? (pns - b0) : B;

@@ -38,9 +38,13 @@ int lifting_lines_fast(void *ws, int cu_count, hipStream_t st, int64_t n, int64_
 
 // 2-D lifting transform of a square n0 x n0 array (leading dimension ldy) through the fused line
 // kernels + tiled transposes.  *handled = 1 when it was enqueued.
+// Batch: nimg (<= 65535) independent images, image i at element offset i * img_stride of x and of y; every level is one launch
+// (or the same fixed handful as for one image) over all of them.  The workspace is carved for nimg * n0 * n0 elements: the
+// approximation ping-pong holds a dense h x h block per image.
 template <typename T>
 int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t ldy, T *y, const T *x,
-                    const LiftScheme<T> &sc, int L, int fw, int *handled, const char **kernel_name, int *hip_err);
+                    const LiftScheme<T> &sc, int L, int fw, int *handled, const char **kernel_name, int *hip_err,
+                    int64_t nimg = 1, int64_t img_stride = 0);
 
 // Level-1 source view of a batch of planes (translation-invariant denoise): plane p of the batch is NOT materialised; it is
 // read from row-shifted copy (spin0 + p) % mod of the image with its columns rotated by (spin0 + p) / mod -- a circular shift
@@ -100,19 +104,20 @@ hipError_t fwd2d_tileB_launch(hipStream_t st, const Taps<float> &taps, const flo
 
 // Deep tail of a forward transform (wl_tail.hip): every remaining level of a small power-of-two block / line in one launch.
 // one 2-D lifting level of a square block of 128 ... 2048 rows (a multiple of 64) in one launch of 64 x 64 tiles (wl_lift_tile.hip);
-// id = the scheme shape (even: forward, odd: inverse); arguments as the level kernels of wl_lift.hip
+// id = the scheme shape (even: forward, odd: inverse); arguments as the level kernels of wl_lift.hip.  nimg (<= 65535) independent
+// images per launch, image i at element offset i * bs_* of the source, the destination and the approximation buffer.
 bool lift2d_tile_ok(int id, int64_t n);
 bool lift2d_tile2_ok(int id, int64_t n);
 bool lift2d_tile2_inv_ok(int id, int64_t n);
 template <typename T>
 hipError_t lift2d_tile2_inv_launch(int id, hipStream_t st, const LiftScheme<T> &sc, const T *x, int64_t ldx, T *out, int64_t ldo, const T *ll, int64_t ldl,
-                                   int64_t n);
+                                   int64_t n, int64_t nimg = 1, int64_t bs_x = 0, int64_t bs_out = 0, int64_t bs_ll = 0);
 template <typename T>
 hipError_t lift2d_tile2_fwd_launch(int id, hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t lds, T *y, int64_t ldy, T *ll, int64_t ldl,
-                                   int64_t n);
+                                   int64_t n, int64_t nimg = 1, int64_t bs_src = 0, int64_t bs_y = 0, int64_t bs_ll = 0);
 template <typename T>
 hipError_t lift2d_tile_launch(int id, int fw, hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t lds, T *y, int64_t ldy, T *ll,
-                              int64_t ldl, int64_t n);
+                              int64_t ldl, int64_t n, int64_t nimg = 1, int64_t bs_src = 0, int64_t bs_y = 0, int64_t bs_ll = 0);
 
 // one lifting pass along any axis of a box of any even extent, known scheme shapes (wl_lift.hip)
 template <typename T>

@@ -806,6 +806,7 @@ struct LiftTail2DArgs {
     int nlev;
     int ld;                         // LDS leading dimension (n0 | 1)
     int cap;                        // elements per LDS buffer
+    int64_t bs_src, bs_y;           // batch of independent images (one workgroup each, blockIdx.x): image strides of src and y
 };
 
 // e -> (e / d, e % d) without the emulated integer division when d is a power of two (the usual case)
@@ -858,6 +859,8 @@ __global__ void __launch_bounds__(1024) k_tail_lift2d(LiftTail2DArgs<T> a, LiftS
     T *P = reinterpret_cast<T *>(smem_raw);       // the block (leading dimension ld)
     T *W = P + a.cap;                             // work lines
     T *Q = W + a.cap;                             // inverse only: columns-pass result
+    a.src += (int64_t)blockIdx.x * a.bs_src;
+    a.y += (int64_t)blockIdx.x * a.bs_y;
     const int tid = threadIdx.x;
     int nthr = blockDim.x;
     bool multi = nthr > 64;
@@ -978,6 +981,7 @@ struct LiftTailRegArgs {
     const T *src; int64_t lds;
     T *y; int64_t ldy;
     int m0, nlev;
+    int64_t bs_src, bs_y;           // batch of independent images (one workgroup each, blockIdx.x): image strides of src and y
     T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
     T norm1, norm2;
 };
@@ -1093,6 +1097,8 @@ __global__ void __launch_bounds__(64) k_tail_lift2d_reg(LiftTailRegArgs<T> a)
 {
     constexpr int ld = 64 | 1;
     __shared__ T P[ld * 64];
+    a.src += (int64_t)blockIdx.x * a.bs_src;
+    a.y += (int64_t)blockIdx.x * a.bs_y;
     const int lane = threadIdx.x;
     const int m0 = a.m0, lg = 31 - __clz(m0);
     for (int idx = lane; idx < m0 * m0; idx += 64) {
@@ -1114,21 +1120,21 @@ template <typename T>
 static bool tail_lift2d_reg_ok(int id, int n0) { return id >= 0 && id <= 5 && n0 >= 2 && n0 <= 64 && (n0 & (n0 - 1)) == 0; }
 template <typename T, int FW>
 static hipError_t launch_tail_lift2d_reg(int id, hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t lds, T *y, int64_t ldy,
-                                         int n0, int nlev)
+                                         int n0, int nlev, int64_t nimg = 1, int64_t bs_src = 0, int64_t bs_y = 0)
 {
     LiftTailRegArgs<T> a;
-    a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.m0 = n0; a.nlev = nlev;
+    a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.m0 = n0; a.nlev = nlev; a.bs_src = bs_src; a.bs_y = bs_y;
     for (int i = 0; i < LIFT_FAST_STEPS; ++i)
         for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
     a.norm1 = sc.norm1; a.norm2 = sc.norm2;
     if (FW) {
-        if (id == 0) hipLaunchKernelGGL((k_tail_lift2d_reg<T, 0, 1>), dim3(1), dim3(64), 0, st, a);
-        else if (id == 2) hipLaunchKernelGGL((k_tail_lift2d_reg<T, 2, 1>), dim3(1), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((k_tail_lift2d_reg<T, 4, 1>), dim3(1), dim3(64), 0, st, a);
+        if (id == 0) hipLaunchKernelGGL((k_tail_lift2d_reg<T, 0, 1>), dim3((unsigned)nimg), dim3(64), 0, st, a);
+        else if (id == 2) hipLaunchKernelGGL((k_tail_lift2d_reg<T, 2, 1>), dim3((unsigned)nimg), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((k_tail_lift2d_reg<T, 4, 1>), dim3((unsigned)nimg), dim3(64), 0, st, a);
     } else {
-        if (id == 1) hipLaunchKernelGGL((k_tail_lift2d_reg<T, 1, 0>), dim3(1), dim3(64), 0, st, a);
-        else if (id == 3) hipLaunchKernelGGL((k_tail_lift2d_reg<T, 3, 0>), dim3(1), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((k_tail_lift2d_reg<T, 5, 0>), dim3(1), dim3(64), 0, st, a);
+        if (id == 1) hipLaunchKernelGGL((k_tail_lift2d_reg<T, 1, 0>), dim3((unsigned)nimg), dim3(64), 0, st, a);
+        else if (id == 3) hipLaunchKernelGGL((k_tail_lift2d_reg<T, 3, 0>), dim3((unsigned)nimg), dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((k_tail_lift2d_reg<T, 5, 0>), dim3((unsigned)nimg), dim3(64), 0, st, a);
     }
     return hipGetLastError();
 }
@@ -1218,6 +1224,8 @@ __global__ void __launch_bounds__(256) k_tail_lift2d_lds(LiftTailRegArgs<T> a)
     constexpr int LD = MM + 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T *P = reinterpret_cast<T *>(smem_raw);
+    a.src += (int64_t)blockIdx.x * a.bs_src;
+    a.y += (int64_t)blockIdx.x * a.bs_y;
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int m0 = a.m0, lg = 31 - __clz(m0);
     for (int idx = tid; idx < m0 * m0; idx += nthr) {
@@ -1239,7 +1247,7 @@ template <typename T> constexpr int tail2l_max() { return sizeof(T) == 4 ? 128 :
 template <typename T>
 static bool tail_lift2d_lds_ok(int id, int64_t n) { return id >= 0 && id <= 5 && n >= 2 && n <= tail2l_max<T>() && (n & (n - 1)) == 0; }
 template <typename T, int ID, int FW>
-static hipError_t launch_tail_lift2d_lds_id(hipStream_t st, const LiftTailRegArgs<T> &a)
+static hipError_t launch_tail_lift2d_lds_id(hipStream_t st, const LiftTailRegArgs<T> &a, int64_t nimg)
 {
     constexpr int MM = tail2l_max<T>();
     const size_t shmem = (size_t)(MM + 1) * MM * sizeof(T);
@@ -1253,26 +1261,26 @@ static hipError_t launch_tail_lift2d_lds_id(hipStream_t st, const LiftTailRegArg
         if (e != hipSuccess) return e;
         for (int i = 0; i < 8; ++i) if (attr_dev[i] < 0) { attr_dev[i] = dev; break; }
     }
-    hipLaunchKernelGGL((k_tail_lift2d_lds<T, ID, FW, MM>), dim3(1), dim3(256), shmem, st, a);
+    hipLaunchKernelGGL((k_tail_lift2d_lds<T, ID, FW, MM>), dim3((unsigned)nimg), dim3(256), shmem, st, a);
     return hipGetLastError();
 }
 template <typename T, int FW>
 static hipError_t launch_tail_lift2d_lds(int id, hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t lds, T *y, int64_t ldy,
-                                         int n0, int nlev)
+                                         int n0, int nlev, int64_t nimg = 1, int64_t bs_src = 0, int64_t bs_y = 0)
 {
     LiftTailRegArgs<T> a;
-    a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.m0 = n0; a.nlev = nlev;
+    a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.m0 = n0; a.nlev = nlev; a.bs_src = bs_src; a.bs_y = bs_y;
     for (int i = 0; i < LIFT_FAST_STEPS; ++i)
         for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
     a.norm1 = sc.norm1; a.norm2 = sc.norm2;
     if (FW) {
-        if (id == 0) return launch_tail_lift2d_lds_id<T, 0, 1>(st, a);
-        if (id == 2) return launch_tail_lift2d_lds_id<T, 2, 1>(st, a);
-        return launch_tail_lift2d_lds_id<T, 4, 1>(st, a);
+        if (id == 0) return launch_tail_lift2d_lds_id<T, 0, 1>(st, a, nimg);
+        if (id == 2) return launch_tail_lift2d_lds_id<T, 2, 1>(st, a, nimg);
+        return launch_tail_lift2d_lds_id<T, 4, 1>(st, a, nimg);
     }
-    if (id == 1) return launch_tail_lift2d_lds_id<T, 1, 0>(st, a);
-    if (id == 3) return launch_tail_lift2d_lds_id<T, 3, 0>(st, a);
-    return launch_tail_lift2d_lds_id<T, 5, 0>(st, a);
+    if (id == 1) return launch_tail_lift2d_lds_id<T, 1, 0>(st, a, nimg);
+    if (id == 3) return launch_tail_lift2d_lds_id<T, 3, 0>(st, a, nimg);
+    return launch_tail_lift2d_lds_id<T, 5, 0>(st, a, nimg);
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -1476,6 +1484,7 @@ struct LiftGTileArgs {
     T *y; int64_t ldy;              // fw: coefficient array;  inv: result block
     T *ll; int64_t ldl;             // fw: approximation destination or nullptr (-> y);  inv: approximation source or nullptr (-> src)
     int n;                          // block size (even)
+    int64_t bs_src, bs_y, bs_ll;    // batch of independent images (blockIdx.z): image strides of src, y and ll
     T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
     T norm1, norm2;
 };
@@ -1518,6 +1527,9 @@ __global__ void __launch_bounds__(64) k_lift2d_gtile(LiftGTileArgs<T> a)
     constexpr int HP = LiftReach<ID>::HP, OWN = 32 - 2 * HP, ld = 65;
     static_assert(OWN >= 8, "scheme reach too large for the tile");
     __shared__ T P[ld * 64];
+    a.src += (int64_t)blockIdx.z * a.bs_src;
+    a.y += (int64_t)blockIdx.z * a.bs_y;
+    if (a.ll) a.ll += (int64_t)blockIdx.z * a.bs_ll;
     const int lane = threadIdx.x;
     const int n = a.n, h = n >> 1;
     int pr0 = (int)blockIdx.x * OWN - HP, pc0 = (int)blockIdx.y * OWN - HP;       // first pair of the tile per dimension (periodic)
@@ -1619,10 +1631,11 @@ template <typename T>
 static bool lift2d_gtile_ok(int id, int64_t n) { return id >= 0 && id <= 5 && n >= 2 && (n % 2) == 0 && n < ((int64_t)1 << 30); }
 template <typename T, int FW>
 static hipError_t launch_lift2d_gtile(int id, hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t lds, T *y, int64_t ldy, T *ll,
-                                      int64_t ldl, int64_t n)
+                                      int64_t ldl, int64_t n, int64_t nimg = 1, int64_t bs_src = 0, int64_t bs_y = 0, int64_t bs_ll = 0)
 {
     LiftGTileArgs<T> a;
     a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.ll = ll; a.ldl = ldl; a.n = (int)n;
+    a.bs_src = bs_src; a.bs_y = bs_y; a.bs_ll = bs_ll;
     for (int i = 0; i < LIFT_FAST_STEPS; ++i)
         for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
     a.norm1 = sc.norm1; a.norm2 = sc.norm2;
@@ -1632,7 +1645,7 @@ static hipError_t launch_lift2d_gtile(int id, hipStream_t st, const LiftScheme<T
         constexpr int OWN = 32 - 2 * LiftReach<ID_>::HP;                                                        \
         const unsigned g = (unsigned)((h + OWN - 1) / OWN);                                                     \
         if (g > 65535) return hipErrorInvalidValue;                                                             \
-        hipLaunchKernelGGL((k_lift2d_gtile<T, ID_, FW>), dim3(g, g), dim3(64), 0, st, a);                       \
+        hipLaunchKernelGGL((k_lift2d_gtile<T, ID_, FW>), dim3(g, g, (unsigned)nimg), dim3(64), 0, st, a);       \
     }
     if (FW) {
         if (id == 0) WL_LGT(0) else if (id == 2) WL_LGT(2) else WL_LGT(4)
@@ -1644,10 +1657,11 @@ static hipError_t launch_lift2d_gtile(int id, hipStream_t st, const LiftScheme<T
 }
 
 template <typename T, int FW>
-static hipError_t launch_tail_lift2d(hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t lds, T *y, int64_t ldy, int n0, int nlev)
+static hipError_t launch_tail_lift2d(hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t lds, T *y, int64_t ldy, int n0, int nlev,
+                                     int64_t nimg = 1, int64_t bs_src = 0, int64_t bs_y = 0)
 {
     LiftTail2DArgs<T> a;
-    a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.n0 = n0; a.nlev = nlev;
+    a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.n0 = n0; a.nlev = nlev; a.bs_src = bs_src; a.bs_y = bs_y;
     a.ld = n0 | 1;
     a.cap = (a.ld * n0 + 15) & ~15;
     const size_t shmem = (size_t)(FW ? 2 : 3) * a.cap * sizeof(T);
@@ -1664,7 +1678,7 @@ static hipError_t launch_tail_lift2d(hipStream_t st, const LiftScheme<T> &sc, co
     const int work = n0 * n0;
     int threads = work >= 2048 ? 1024 : (work >= 512 ? 256 : 64);
     if (opt("WL_LIFT_TAIL_THREADS", 0) >= 64) threads = (int)opt("WL_LIFT_TAIL_THREADS", 0);
-    hipLaunchKernelGGL((k_tail_lift2d<T, FW>), dim3(1), dim3(threads), shmem, st, a, sc);
+    hipLaunchKernelGGL((k_tail_lift2d<T, FW>), dim3((unsigned)nimg), dim3(threads), shmem, st, a, sc);
     return hipGetLastError();
 }
 
@@ -2903,18 +2917,33 @@ static void launch_lines_id(int id, hipStream_t st, const Lift1DArgs<T> &a, int6
 // size fits neither (not a power of two below 512) use the generic kernels.
 template <typename T>
 int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t ldy, T *y, const T *x,
-                    const LiftScheme<T> &sc, int L, int fw, int *handled, const char **kernel_name, int *hip_err)
+                    const LiftScheme<T> &sc, int L, int fw, int *handled, const char **kernel_name, int *hip_err, int64_t nimg, int64_t xs)
 {
     *handled = 0;
     constexpr int VEC = 16 / sizeof(T);
     const int id = match_shape<T>(sc);
-    if (id < 0 || L < 1 || n0 < 2) return WL_OK;
-    // the streaming / line kernels use 16-byte accesses; the tile and tail kernels take any leading dimension
-    const bool aligned = (ldy % VEC) == 0 && al16(x) && al16(y);
+    if (id < 0 || L < 1 || n0 < 2 || nimg < 1 || nimg > 65535) return WL_OK;
+    if (nimg == 1) xs = 0;
 #define WL_E(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { if (hip_err) *hip_err = (int)e__; return WL_EHIP; } } while (0)
 #define WL_EL() WL_E(hipGetLastError())
-    const int64_t N = n0 * n0;
+    const int64_t N = n0 * n0 * nimg;
     Work<T> w = carve<T>(ws, N);
+    // A batch is transformed level by level over all its images: image i of the source at xsrc + i * xbs, of the level-l approximation
+    // (dense h x h) at llbuf + i * h * h.  In-place batch (y == x): the whole-level kernels may not read the array they write, and the
+    // contiguous-line kernels the single image falls back to there (k_lift1d_stream) know one image only, so the batch is copied to T1
+    // (unused by the 2-D transform) once and transformed out of place from there: one extra launch, the same two trips through memory
+    // as the single image's two-pass level 1.  Images of <= 64 rows are read into LDS whole by the tails: no copy.  One image: nothing
+    // changes.
+    const T *xsrc = x;
+    int64_t ldx = ldy, xbs = xs;
+    if (nimg > 1 && x == y && (n0 > 64 || l_env("WL_NO_LIFT_TAIL2D", 0) != 0)) {
+        Extent3 ext = {{n0, n0, nimg}};
+        Strides3 sst = {{1, ldy, xs}}, dst = {{1, n0, n0 * n0}};
+        WL_E(generic_copy_box<T>(st, x, sst, w.T1, dst, ext));
+        xsrc = w.T1; ldx = n0; xbs = n0 * n0;
+    }
+    // the streaming / line kernels use 16-byte accesses; the tile and tail kernels take any leading dimension
+    const bool aligned = (ldy % VEC) == 0 && al16(x) && al16(y) && (xs % VEC) == 0 && al16(xsrc);
     Lift1DArgs<T> a;
     LiftAxisArgs<T> ax;
     LiftShortArgs<T> sa;
@@ -2926,35 +2955,35 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
         }
     a.norm1 = ax.norm1 = sa.norm1 = sc.norm1;
     a.norm2 = ax.norm2 = sa.norm2 = sc.norm2;
-    Strides3 full = {{1, ldy, ldy * n0}};
+    Strides3 full = {{1, ldy, nimg > 1 ? xs : ldy * n0}}, xfull = {{1, ldx, nimg > 1 ? xbs : ldx * n0}};
     auto lines_ok = [](int64_t n) { return n >= 512 && (n % 64) == 0; };
     auto fused_ok = [](int64_t n) { return n >= 128 && (n % 8) == 0; };     // k_lift2d_*: a lane's 4 rows wrap at most once
     bool any_fast = false, fused = false, gtile = false, tiled = false, ldstail = false;
 
     if (fw) {
-        const T *cur = x;
-        int64_t cur_ls = ldy;
+        const T *cur = xsrc;
+        int64_t cur_ls = ldx, cur_bs = xbs;
         int pp = 0;
         for (int l = 1; l <= L; ++l) {
             const int64_t n = n0 >> (l - 1), h = n >> 1;
             const bool last = (l == L);
             T *llbuf = pp ? w.B : w.A;
             T *lld = last ? y : llbuf;
-            const int64_t ldd = last ? ldy : h;
+            const int64_t ldd = last ? ldy : h, lld_bs = last ? xs : h * h;
             // every remaining level of a block <= 128 x 128 (Float32) in one workgroup's LDS, a thread per line (k_tail_lift2d_lds)
             // (measured r04, cdf9/7 forward: 64^2 all levels 11.2 us against 13.5 in the one-wave register tail; 128^2 24.4 against
             //  23.3 for a tile launch + the register tail -- a 128-sample line per thread keeps two waves busy, the tile kernel 16)
             if ((id == 0 || id == 2 || id == 4) && tail_lift2d_lds_ok<T>(id, n) && n >= l_env("WL_LIFT_LDSTAIL2D_FMIN", 64) &&
                 n <= l_env("WL_LIFT_LDSTAIL2D_FMAX", 64) && l_env("WL_NO_LIFT_TAIL2D", 0) == 0 && l_env("WL_LIFT_LDSTAIL2D", 1) != 0) {
-                WL_E((launch_tail_lift2d_lds<T, 1>(id, st, sc, cur, cur_ls, y, ldy, (int)n, L - l + 1)));
+                WL_E((launch_tail_lift2d_lds<T, 1>(id, st, sc, cur, cur_ls, y, ldy, (int)n, L - l + 1, nimg, cur_bs, xs)));
                 any_fast = true; ldstail = (l == 1);          // (names the call only when the tail is the whole transform)
                 break;
             }
             if (n <= 64 && l_env("WL_NO_LIFT_TAIL2D", 0) == 0) {        // every remaining level inside one workgroup / one wave
                 if ((id == 0 || id == 2 || id == 4) && tail_lift2d_reg_ok<T>(id, (int)n) && l_env("WL_LIFT_REGTAIL2D", 1) != 0)
-                    WL_E((launch_tail_lift2d_reg<T, 1>(id, st, sc, cur, cur_ls, y, ldy, (int)n, L - l + 1)));
+                    WL_E((launch_tail_lift2d_reg<T, 1>(id, st, sc, cur, cur_ls, y, ldy, (int)n, L - l + 1, nimg, cur_bs, xs)));
                 else
-                    WL_E((launch_tail_lift2d<T, 1>(st, sc, cur, cur_ls, y, ldy, (int)n, L - l + 1)));
+                    WL_E((launch_tail_lift2d<T, 1>(st, sc, cur, cur_ls, y, ldy, (int)n, L - l + 1, nimg, cur_bs, xs)));
                 any_fast = true;
                 break;
             }
@@ -2964,18 +2993,18 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
             if (aligned && (sizeof(T) == 4 || l_env("WL_LIFT_TILE2_F64", 0) != 0) && l_env("WL_LIFT_TILE", 1) != 0 && l_env("WL_LIFT_TILE2", 1) != 0 && (L - l + 1) >= 2 && n <= l_env("WL_LIFT_TILE2_MAX", 1024) &&
                 lift2d_tile2_ok(id, n) && (cur_ls % VEC) == 0 && al16(cur) && al16(llbuf) && cur != y) {
                 const bool last2 = (l + 1 == L);
-                WL_E((lift2d_tile2_fwd_launch<T>(id, st, sc, cur, cur_ls, y, ldy, last2 ? (T *)nullptr : llbuf, n >> 2, n)));
+                WL_E((lift2d_tile2_fwd_launch<T>(id, st, sc, cur, cur_ls, y, ldy, last2 ? (T *)nullptr : llbuf, n >> 2, n, nimg, cur_bs, xs, (n >> 2) * (n >> 2))));
                 any_fast = true; tiled = true;
-                cur = llbuf; cur_ls = n >> 2; pp ^= 1;
+                cur = llbuf; cur_ls = n >> 2; cur_bs = (n >> 2) * (n >> 2); pp ^= 1;
                 ++l;
                 continue;
             }
             // cache-resident levels: 64 x 64 tiles, one launch per level without the marching kernels' latency chain
             if (aligned && l_env("WL_LIFT_TILE", 1) != 0 && n <= l_env("WL_LIFT_TILE_MAX", 2048) && lift2d_tile_ok(id, n) && (id == 0 || id == 2 || id == 4) &&
                 (cur_ls % VEC) == 0 && al16(cur) && al16(llbuf) && cur != y) {
-                WL_E((lift2d_tile_launch<T>(id, 1, st, sc, cur, cur_ls, y, ldy, last ? (T *)nullptr : llbuf, h, n)));
+                WL_E((lift2d_tile_launch<T>(id, 1, st, sc, cur, cur_ls, y, ldy, last ? (T *)nullptr : llbuf, h, n, nimg, cur_bs, xs, h * h)));
                 any_fast = true; tiled = true;
-                cur = llbuf; cur_ls = h; pp ^= 1;
+                cur = llbuf; cur_ls = h; cur_bs = h * h; pp ^= 1;
                 continue;
             }
             if (aligned && fused_ok(n) && n > l_env("WL_LIFT_GTILE_MAX", 0) && (id == 0 || id == 2 || id == 4) && l_env("WL_NO_LIFT2D_FUSED", 0) == 0 && (cur_ls % VEC) == 0 &&
@@ -2986,20 +3015,21 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
                     for (int k = 0; k < WL_MAX_NCOEF; ++k) q2.c[i][k] = a.c[i][k];
                 q2.norm1 = a.norm1; q2.norm2 = a.norm2;
                 q2.src = cur; q2.lds = cur_ls; q2.y = y; q2.ldy = ldy; q2.ll = last ? (T *)nullptr : llbuf; q2.ldl = h; q2.n0 = n; q2.n1 = n;
-                q2.bs_src = q2.bs_y = q2.bs_ll = 0; q2.nll = 1;
-                if (id == 0) WL_E((launch_lift2d_fwd<T, 0>(st, q2, cu_count)));
-                else if (id == 2) WL_E((launch_lift2d_fwd<T, 2>(st, q2, cu_count)));
-                else WL_E((launch_lift2d_fwd<T, 4>(st, q2, cu_count)));
+                q2.bs_src = cur_bs; q2.bs_y = xs; q2.bs_ll = h * h; q2.nll = (int)nimg;
+                if (id == 0) WL_E((launch_lift2d_fwd<T, 0>(st, q2, cu_count, nimg)));
+                else if (id == 2) WL_E((launch_lift2d_fwd<T, 2>(st, q2, cu_count, nimg)));
+                else WL_E((launch_lift2d_fwd<T, 4>(st, q2, cu_count, nimg)));
                 any_fast = true; fused = true;
-                cur = llbuf; cur_ls = h; pp ^= 1;
+                cur = llbuf; cur_ls = h; cur_bs = h * h; pp ^= 1;
                 continue;
             }
-            if (aligned && n > l_env("WL_LIFT_GTILE_MAX", 0) && (lines_ok(n) || short_lift_ok(n))) {
+            // (a batch takes the two-pass route only where its dim-1 pass is k_lift_short_lines, which has an image index)
+            if (aligned && n > l_env("WL_LIFT_GTILE_MAX", 0) && ((nimg == 1 && lines_ok(n)) || short_lift_ok(n))) {
                 any_fast = true;
                 // rows (dim 2): one streaming pass along the strided axis, T0 = [s-columns | d-columns]
-                ax.src = cur; ax.lds = cur_ls; ax.bs_src = 0; ax.dst = w.T0; ax.ldd = n; ax.bs_dst = 0; ax.R = n; ax.C = n;
-                WL_E((launch_lift_axis_id<T, 1>(id, st, ax, 1, cu_count)));
-                if (lines_ok(n)) {
+                ax.src = cur; ax.lds = cur_ls; ax.bs_src = nimg > 1 ? cur_bs : 0; ax.dst = w.T0; ax.ldd = n; ax.bs_dst = nimg > 1 ? n * n : 0; ax.R = n; ax.C = n;
+                WL_E((launch_lift_axis_id<T, 1>(id, st, ax, nimg, cu_count)));
+                if (nimg == 1 && lines_ok(n)) {
                     a.b = nullptr; a.b_ls = 0; a.n = n; a.ntiles = (h + 247) / 248;
                     // columns [0, h): s -> LL, d -> y[h.., j]
                     a.a = w.T0; a.a_ls = n; a.o0 = lld; a.o0_ls = ldd; a.o1 = y + h; a.o1_ls = ldy;
@@ -3009,18 +3039,18 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
                     launch_lines_id<T, 1>(id, st, a, h, cu_count); WL_EL();
                 } else {
                     // every column of T0 in one launch; columns [0, h) send their approximation to the next level's buffer
-                    sa.b = nullptr; sa.b2 = sa.b3 = 0; sa.a3 = sa.o03 = sa.o13 = sa.ll3 = 0;
+                    sa.b = nullptr; sa.b2 = sa.b3 = 0; sa.a3 = n * n; sa.o03 = sa.o13 = xs; sa.ll3 = h * h;
                     sa.a = w.T0; sa.a2 = n; sa.o0 = y; sa.o02 = ldy; sa.o1 = y + h; sa.o12 = ldy;
-                    sa.ll = last ? (T *)nullptr : llbuf; sa.ll2 = h; sa.l2 = (int)h; sa.l3 = 1;
-                    WL_E((launch_lift_short_id<T, 1>(id, st, sa, (int)n, (int)n, 1)));
+                    sa.ll = last ? (T *)nullptr : llbuf; sa.ll2 = h; sa.l2 = (int)h; sa.l3 = nimg;
+                    WL_E((launch_lift_short_id<T, 1>(id, st, sa, (int)n, (int)n, nimg)));
                 }
             } else if ((id == 0 || id == 2 || id == 4) && lift2d_gtile_ok<T>(id, n) && cur != y && l_env("WL_LIFT_GTILE", 1) != 0) {
                 // any even size: one tile launch instead of twelve one-thread-per-element launches
-                WL_E((launch_lift2d_gtile<T, 1>(id, st, sc, cur, cur_ls, y, ldy, last ? (T *)nullptr : llbuf, h, n)));
+                WL_E((launch_lift2d_gtile<T, 1>(id, st, sc, cur, cur_ls, y, ldy, last ? (T *)nullptr : llbuf, h, n, nimg, cur_bs, xs, h * h)));
                 any_fast = true; gtile = true;
             } else {
-                Extent3 ext = {{n, n, 1}}, lo = {{h, h, 1}};
-                Strides3 box = {{1, n, n * n}}, cst = {{1, cur_ls, cur_ls * n}}, lst = {{1, ldd, ldd * h}};
+                Extent3 ext = {{n, n, nimg}}, lo = {{h, h, nimg}};                      // (the generic kernels leave the third extent alone)
+                Strides3 box = {{1, n, n * n}}, cst = {{1, cur_ls, nimg > 1 ? cur_bs : cur_ls * n}}, lst = {{1, ldd, nimg > 1 ? lld_bs : ldd * h}};
                 // rows (axis 1) then columns (axis 0), as generic_lifting_fwd
                 WL_E(generic_lift_split<T>(st, cur, cst, w.W, box, ext, 1));
                 for (int q = 0; q < sc.nsteps; ++q) WL_E(generic_lift_step<T>(st, sc.step[q], w.W, box, ext, 1));
@@ -3029,11 +3059,11 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
                 for (int q = 0; q < sc.nsteps; ++q) WL_E(generic_lift_step<T>(st, sc.step[q], w.W, box, ext, 0));
                 WL_E(generic_lift_finish_fwd<T>(st, sc.norm1, sc.norm2, w.W, box, y, full, last ? (T *)nullptr : llbuf, lst, ext, 0, lo));
             }
-            cur = llbuf; cur_ls = h; pp ^= 1;
+            cur = llbuf; cur_ls = h; cur_bs = h * h; pp ^= 1;
         }
     } else {
         const T *llsrc = nullptr;
-        int64_t ll_ls = 0;
+        int64_t ll_ls = 0, ll_bs = 0;
         int pp = 0;
         int l_start = L;
         if (l_env("WL_NO_LIFT_TAIL2D", 0) == 0) {
@@ -3047,64 +3077,64 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
             if (l_lo <= L) {
                 const int64_t n = n0 >> (l_lo - 1);
                 T *out = (l_lo == 1) ? y : (pp ? w.B : w.A);
-                const int64_t ldo = (l_lo == 1) ? ldy : n;
+                const int64_t ldo = (l_lo == 1) ? ldy : n, out_bs = (l_lo == 1) ? xs : n * n;
                 if (lds128) {
-                    WL_E((launch_tail_lift2d_lds<T, 0>(id, st, sc, x, ldy, out, ldo, (int)n, L - l_lo + 1)));
+                    WL_E((launch_tail_lift2d_lds<T, 0>(id, st, sc, xsrc, ldx, out, ldo, (int)n, L - l_lo + 1, nimg, xbs, out_bs)));
                     ldstail = (l_lo == 1);
                 } else if ((id == 1 || id == 3 || id == 5) && tail_lift2d_reg_ok<T>(id, (int)n) && l_env("WL_LIFT_REGTAIL2D", 1) != 0)
-                    WL_E((launch_tail_lift2d_reg<T, 0>(id, st, sc, x, ldy, out, ldo, (int)n, L - l_lo + 1)));
+                    WL_E((launch_tail_lift2d_reg<T, 0>(id, st, sc, xsrc, ldx, out, ldo, (int)n, L - l_lo + 1, nimg, xbs, out_bs)));
                 else
-                    WL_E((launch_tail_lift2d<T, 0>(st, sc, x, ldy, out, ldo, (int)n, L - l_lo + 1)));
+                    WL_E((launch_tail_lift2d<T, 0>(st, sc, xsrc, ldx, out, ldo, (int)n, L - l_lo + 1, nimg, xbs, out_bs)));
                 any_fast = true;
-                llsrc = out; ll_ls = ldo; pp ^= 1;
+                llsrc = out; ll_ls = ldo; ll_bs = out_bs; pp ^= 1;
                 l_start = l_lo - 1;
             }
         }
         for (int l = l_start; l >= 1; --l) {
             const int64_t n = n0 >> (l - 1), h = n >> 1;
             T *out = (l == 1) ? y : (pp ? w.B : w.A);
-            const int64_t ldo = (l == 1) ? ldy : n;
+            const int64_t ldo = (l == 1) ? ldy : n, out_bs = (l == 1) ? xs : n * n;
             // (round 5) two reconstruction levels per launch (output 2 n <= 1024 rows, Float32): the coarser level's result is produced in
             // LDS where the finer level's staging expects its approximation quadrant (k_lift2d_tile2_inv)
             if (aligned && (sizeof(T) == 4 || l_env("WL_LIFT_TILE2_F64", 0) != 0) && l_env("WL_LIFT_TILE", 1) != 0 && l_env("WL_LIFT_TILE2", 1) != 0 && l >= 2 &&
                 2 * n <= l_env("WL_LIFT_TILE2_MAX", 1024) && lift2d_tile2_inv_ok(id, 2 * n) && (!llsrc || (al16(llsrc) && (ll_ls % 2) == 0))) {
                 const int64_t nf = 2 * n;
                 T *out2 = (l - 1 == 1) ? y : (pp ? w.B : w.A);
-                const int64_t ldo2 = (l - 1 == 1) ? ldy : nf;
-                if (out2 != x) {
-                    WL_E((lift2d_tile2_inv_launch<T>(id, st, sc, x, ldy, out2, ldo2, llsrc, ll_ls, nf)));
+                const int64_t ldo2 = (l - 1 == 1) ? ldy : nf, out2_bs = (l - 1 == 1) ? xs : nf * nf;
+                if (out2 != xsrc) {
+                    WL_E((lift2d_tile2_inv_launch<T>(id, st, sc, xsrc, ldx, out2, ldo2, llsrc, ll_ls, nf, nimg, xbs, out2_bs, ll_bs)));
                     any_fast = true; tiled = true;
-                    llsrc = out2; ll_ls = ldo2; pp ^= 1;
+                    llsrc = out2; ll_ls = ldo2; ll_bs = out2_bs; pp ^= 1;
                     --l;
                     continue;
                 }
             }
             if (aligned && l_env("WL_LIFT_TILE", 1) != 0 && n <= l_env("WL_LIFT_TILE_MAX", 2048) && lift2d_tile_ok(id, n) && (id == 1 || id == 3 || id == 5) &&
-                (!llsrc || (al16(llsrc) && (ll_ls % 2) == 0)) && out != x) {
-                WL_E((lift2d_tile_launch<T>(id, 0, st, sc, x, ldy, out, ldo, const_cast<T *>(llsrc), ll_ls, n)));
+                (!llsrc || (al16(llsrc) && (ll_ls % 2) == 0)) && out != xsrc) {
+                WL_E((lift2d_tile_launch<T>(id, 0, st, sc, xsrc, ldx, out, ldo, const_cast<T *>(llsrc), ll_ls, n, nimg, xbs, out_bs, ll_bs)));
                 any_fast = true; tiled = true;
-                llsrc = out; ll_ls = ldo; pp ^= 1;
+                llsrc = out; ll_ls = ldo; ll_bs = out_bs; pp ^= 1;
                 continue;
             }
             if (aligned && fused_ok(n) && n > l_env("WL_LIFT_GTILE_MAX", 0) && (id == 1 || id == 3 || id == 5) && l_env("WL_NO_LIFT2D_FUSED", 0) == 0 && (ldo % VEC) == 0 && al16(out) &&
-                (!llsrc || (al16(llsrc) && (ll_ls % 2) == 0)) && out != x) {   // (in place, level 1 writes y while reading it)
+                (!llsrc || (al16(llsrc) && (ll_ls % 2) == 0)) && out != xsrc) {   // (in place, level 1 writes y while reading it)
                 Lift2DArgs<T> q2;
                 for (int i = 0; i < LIFT_FAST_STEPS; ++i)
                     for (int k = 0; k < WL_MAX_NCOEF; ++k) q2.c[i][k] = a.c[i][k];
                 q2.norm1 = a.norm1; q2.norm2 = a.norm2;
-                q2.src = x; q2.lds = ldy; q2.y = out; q2.ldy = ldo; q2.ll = const_cast<T *>(llsrc); q2.ldl = ll_ls; q2.n0 = n; q2.n1 = n;
-                q2.bs_src = q2.bs_y = q2.bs_ll = 0; q2.nll = 1;
-                if (id == 1) WL_E((launch_lift2d_inv<T, 1>(st, q2, cu_count)));
-                else if (id == 3) WL_E((launch_lift2d_inv<T, 3>(st, q2, cu_count)));
-                else WL_E((launch_lift2d_inv<T, 5>(st, q2, cu_count)));
+                q2.src = xsrc; q2.lds = ldx; q2.y = out; q2.ldy = ldo; q2.ll = const_cast<T *>(llsrc); q2.ldl = ll_ls; q2.n0 = n; q2.n1 = n;
+                q2.bs_src = xbs; q2.bs_y = out_bs; q2.bs_ll = ll_bs; q2.nll = (int)nimg;
+                if (id == 1) WL_E((launch_lift2d_inv<T, 1>(st, q2, cu_count, nimg)));
+                else if (id == 3) WL_E((launch_lift2d_inv<T, 3>(st, q2, cu_count, nimg)));
+                else WL_E((launch_lift2d_inv<T, 5>(st, q2, cu_count, nimg)));
                 any_fast = true; fused = true;
-                llsrc = out; ll_ls = ldo; pp ^= 1;
+                llsrc = out; ll_ls = ldo; ll_bs = out_bs; pp ^= 1;
                 continue;
             }
-            if (aligned && n > l_env("WL_LIFT_GTILE_MAX", 0) && (lines_ok(n) || short_lift_ok(n))) {
+            if (aligned && n > l_env("WL_LIFT_GTILE_MAX", 0) && ((nimg == 1 && lines_ok(n)) || short_lift_ok(n))) {
                 any_fast = true;
                 // columns: merged column j -> T0[:, j]
-                if (lines_ok(n)) {
+                if (nimg == 1 && lines_ok(n)) {
                     a.o0 = w.T0; a.o0_ls = n; a.o1 = nullptr; a.o1_ls = 0; a.n = n; a.ntiles = (h + 247) / 248;
                     if (llsrc) { a.a = llsrc; a.a_ls = ll_ls; } else { a.a = x; a.a_ls = ldy; }
                     a.b = x + h; a.b_ls = ldy;
@@ -3112,28 +3142,28 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
                     a.a = x + h * ldy; a.a_ls = ldy; a.b = x + h * ldy + h; a.b_ls = ldy; a.o0 = w.T0 + h * n;
                     launch_lines_id<T, 0>(id, st, a, h, cu_count); WL_EL();
                 } else {
-                    sa.o1 = nullptr; sa.o12 = sa.o13 = 0; sa.a3 = sa.b3 = sa.o03 = sa.ll3 = 0;
-                    sa.o0 = w.T0; sa.o02 = n; sa.a = x; sa.a2 = ldy; sa.b = x + h; sa.b2 = ldy;
-                    sa.ll = const_cast<T *>(llsrc); sa.ll2 = ll_ls; sa.l2 = (int)h; sa.l3 = 1;
-                    WL_E((launch_lift_short_id<T, 0>(id, st, sa, (int)n, (int)n, 1)));
+                    sa.o1 = nullptr; sa.o12 = sa.o13 = 0; sa.a3 = sa.b3 = xbs; sa.o03 = n * n; sa.ll3 = ll_bs;
+                    sa.o0 = w.T0; sa.o02 = n; sa.a = xsrc; sa.a2 = ldx; sa.b = xsrc + h; sa.b2 = ldx;
+                    sa.ll = const_cast<T *>(llsrc); sa.ll2 = ll_ls; sa.l2 = (int)h; sa.l3 = nimg;
+                    WL_E((launch_lift_short_id<T, 0>(id, st, sa, (int)n, (int)n, nimg)));
                 }
                 // rows (dim 2): streaming pass along the strided axis straight into the result
-                ax.src = w.T0; ax.lds = n; ax.bs_src = 0; ax.dst = out; ax.ldd = ldo; ax.bs_dst = 0; ax.R = n; ax.C = n;
-                WL_E((launch_lift_axis_id<T, 0>(id, st, ax, 1, cu_count)));
-            } else if ((id == 1 || id == 3 || id == 5) && lift2d_gtile_ok<T>(id, n) && out != x && l_env("WL_LIFT_GTILE", 1) != 0) {
-                WL_E((launch_lift2d_gtile<T, 0>(id, st, sc, x, ldy, out, ldo, const_cast<T *>(llsrc), ll_ls, n)));
+                ax.src = w.T0; ax.lds = n; ax.bs_src = nimg > 1 ? n * n : 0; ax.dst = out; ax.ldd = ldo; ax.bs_dst = nimg > 1 ? out_bs : 0; ax.R = n; ax.C = n;
+                WL_E((launch_lift_axis_id<T, 0>(id, st, ax, nimg, cu_count)));
+            } else if ((id == 1 || id == 3 || id == 5) && lift2d_gtile_ok<T>(id, n) && out != xsrc && l_env("WL_LIFT_GTILE", 1) != 0) {
+                WL_E((launch_lift2d_gtile<T, 0>(id, st, sc, xsrc, ldx, out, ldo, const_cast<T *>(llsrc), ll_ls, n, nimg, xbs, out_bs, ll_bs)));
                 any_fast = true; gtile = true;
             } else {
-                Extent3 ext = {{n, n, 1}}, lo = {{h, h, 1}};
-                Strides3 box = {{1, n, n * n}}, lst = {{1, ll_ls, ll_ls * h}}, ost = {{1, ldo, ldo * n}};
-                WL_E(generic_lift_norm_inv<T>(st, sc.norm1, sc.norm2, x, full, llsrc, lst, w.W, box, ext, 0, lo));
+                Extent3 ext = {{n, n, nimg}}, lo = {{h, h, nimg}};
+                Strides3 box = {{1, n, n * n}}, lst = {{1, ll_ls, nimg > 1 ? ll_bs : ll_ls * h}}, ost = {{1, ldo, nimg > 1 ? out_bs : ldo * n}};
+                WL_E(generic_lift_norm_inv<T>(st, sc.norm1, sc.norm2, xsrc, xfull, llsrc, lst, w.W, box, ext, 0, lo));
                 for (int q = 0; q < sc.nsteps; ++q) WL_E(generic_lift_step<T>(st, sc.step[q], w.W, box, ext, 0));
                 WL_E(generic_lift_merge<T>(st, w.W, box, w.T0, box, ext, 0));
                 WL_E(generic_lift_norm_inv<T>(st, sc.norm1, sc.norm2, w.T0, box, (const T *)nullptr, box, w.W, box, ext, 1, lo));
                 for (int q = 0; q < sc.nsteps; ++q) WL_E(generic_lift_step<T>(st, sc.step[q], w.W, box, ext, 1));
                 WL_E(generic_lift_merge<T>(st, w.W, box, out, ost, ext, 1));
             }
-            llsrc = out; ll_ls = ldo; pp ^= 1;
+            llsrc = out; ll_ls = ldo; ll_bs = out_bs; pp ^= 1;
         }
     }
     *handled = 1;
@@ -3271,8 +3301,8 @@ template int lifting_3d_fast<double>(void *, int, hipStream_t, int64_t, double *
                                      int *, const char **, int *);
 
 template int lifting_2d_fast<float>(void *, int, hipStream_t, int64_t, int64_t, float *, const float *, const LiftScheme<float> &,
-                                    int, int, int *, const char **, int *);
+                                    int, int, int *, const char **, int *, int64_t, int64_t);
 template int lifting_2d_fast<double>(void *, int, hipStream_t, int64_t, int64_t, double *, const double *,
-                                     const LiftScheme<double> &, int, int, int *, const char **, int *);
+                                     const LiftScheme<double> &, int, int, int *, const char **, int *, int64_t, int64_t);
 
 }  // namespace wl

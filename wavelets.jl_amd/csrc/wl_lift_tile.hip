@@ -24,9 +24,20 @@ struct LiftTileArgs {
     T *y; int64_t ldy;              // fw: coefficient array            inv: result block n x n
     T *ll; int64_t ldl;             // fw: approximation destination or nullptr (-> y);  inv: approximation source or nullptr (-> src)
     int n;
+    int64_t bs_src, bs_y, bs_ll;    // batch of independent images (blockIdx.z): image strides of src, y and ll
     T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
     T norm1, norm2;
 };
+
+// the image of this workgroup (blockIdx.z) of a batch
+template <typename T>
+__device__ __forceinline__ void tile_select_image(LiftTileArgs<T> &a)
+{
+    const int64_t img = (int64_t)blockIdx.z;
+    a.src += img * a.bs_src;
+    a.y += img * a.bs_y;
+    if (a.ll) a.ll += img * a.bs_ll;
+}
 
 template <int ID>
 struct TileGeom {
@@ -91,6 +102,7 @@ __device__ __forceinline__ int wrap_into(int v, const int m)
 template <typename T, int ID>
 __global__ void __launch_bounds__(256) k_lift2d_tile_fwd(LiftTileArgs<T> a)
 {
+    tile_select_image<T>(a);
     typedef TileGeom<ID> G;
     constexpr int VEC = 16 / sizeof(T);
     typedef T V __attribute__((ext_vector_type(VEC)));
@@ -203,6 +215,7 @@ struct TileGeom2 {
 template <typename T, int ID>
 __global__ void __launch_bounds__(512) k_lift2d_tile2_fwd(LiftTileArgs<T> a)
 {
+    tile_select_image<T>(a);
     typedef TileGeom2<ID> G;
     constexpr int VEC = 16 / sizeof(T);
     typedef T V __attribute__((ext_vector_type(VEC)));
@@ -352,6 +365,7 @@ __global__ void __launch_bounds__(512) k_lift2d_tile2_fwd(LiftTileArgs<T> a)
 template <typename T, int ID>
 __global__ void __launch_bounds__(256) k_lift2d_tile_inv(LiftTileArgs<T> a)
 {
+    tile_select_image<T>(a);
     typedef TileGeom<ID> G;
     constexpr int VEC = 16 / sizeof(T);
     typedef T V __attribute__((ext_vector_type(VEC)));
@@ -460,6 +474,7 @@ struct TileGeomInv2 {
 template <typename T, int ID>
 __global__ void __launch_bounds__(256) k_lift2d_tile2_inv(LiftTileArgs<T> a)
 {
+    tile_select_image<T>(a);
     typedef TileGeomInv2<ID> G;
     constexpr int VEC = 16 / sizeof(T);
     typedef T V __attribute__((ext_vector_type(VEC)));
@@ -609,11 +624,11 @@ __global__ void __launch_bounds__(256) k_lift2d_tile2_inv(LiftTileArgs<T> a)
 }
 
 template <typename T, int ID, int FW>
-hipError_t launch_tile_id(hipStream_t st, const LiftTileArgs<T> &a)
+hipError_t launch_tile_id(hipStream_t st, const LiftTileArgs<T> &a, unsigned nimg)
 {
     const unsigned g = (unsigned)(a.n / 64);
-    if (FW) hipLaunchKernelGGL((k_lift2d_tile_fwd<T, ID>), dim3(g, g), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_lift2d_tile_inv<T, ID>), dim3(g, g), dim3(256), 0, st, a);
+    if (FW) hipLaunchKernelGGL((k_lift2d_tile_fwd<T, ID>), dim3(g, g, nimg), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_lift2d_tile_inv<T, ID>), dim3(g, g, nimg), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
@@ -624,7 +639,7 @@ bool lift2d_tile_ok(int id, int64_t n) { return id >= 0 && id <= 5 && n >= 128 &
 bool lift2d_tile2_ok(int id, int64_t n) { return (id == 0 || id == 2 || id == 4) && n >= 128 && n <= 16384 && (n % 64) == 0; }
 
 template <typename T, int ID>
-static hipError_t launch_tile2_fwd_id(hipStream_t st, const LiftTileArgs<T> &a)
+static hipError_t launch_tile2_fwd_id(hipStream_t st, const LiftTileArgs<T> &a, unsigned nimg)
 {
     constexpr size_t shmem = (size_t)TileGeom2<ID>::ELEMS * sizeof(T);
     static thread_local int done_dev = -1;
@@ -636,14 +651,14 @@ static hipError_t launch_tile2_fwd_id(hipStream_t st, const LiftTileArgs<T> &a)
         done_dev = dev;
     }
     const unsigned g = (unsigned)(a.n / 64);
-    hipLaunchKernelGGL((k_lift2d_tile2_fwd<T, ID>), dim3(g, g), dim3(512), shmem, st, a);
+    hipLaunchKernelGGL((k_lift2d_tile2_fwd<T, ID>), dim3(g, g, nimg), dim3(512), shmem, st, a);
     return hipGetLastError();
 }
 
 bool lift2d_tile2_inv_ok(int id, int64_t n) { return (id == 1 || id == 3 || id == 5) && n >= 256 && n <= 16384 && (n % 64) == 0; }
 
 template <typename T, int ID>
-static hipError_t launch_tile2_inv_id(hipStream_t st, const LiftTileArgs<T> &a)
+static hipError_t launch_tile2_inv_id(hipStream_t st, const LiftTileArgs<T> &a, unsigned nimg)
 {
     constexpr size_t shmem = (size_t)TileGeomInv2<ID>::ELEMS * sizeof(T);
     static thread_local int done_dev = -1;
@@ -655,7 +670,7 @@ static hipError_t launch_tile2_inv_id(hipStream_t st, const LiftTileArgs<T> &a)
         done_dev = dev;
     }
     const unsigned g = (unsigned)(a.n / 64);
-    hipLaunchKernelGGL((k_lift2d_tile2_inv<T, ID>), dim3(g, g), dim3(256), shmem, st, a);
+    hipLaunchKernelGGL((k_lift2d_tile2_inv<T, ID>), dim3(g, g, nimg), dim3(256), shmem, st, a);
     return hipGetLastError();
 }
 
@@ -663,69 +678,76 @@ static hipError_t launch_tile2_inv_id(hipStream_t st, const LiftTileArgs<T> &a)
 // corner), out = the n x n reconstruction of the finer level
 template <typename T>
 hipError_t lift2d_tile2_inv_launch(int id, hipStream_t st, const LiftScheme<T> &sc, const T *x, int64_t ldx, T *out, int64_t ldo, const T *ll, int64_t ldl,
-                                   int64_t n)
+                                   int64_t n, int64_t nimg, int64_t bs_x, int64_t bs_out, int64_t bs_ll)
 {
+    if (nimg < 1 || nimg > 65535) return hipErrorInvalidValue;
     LiftTileArgs<T> a;
     a.src = x; a.lds = ldx; a.y = out; a.ldy = ldo; a.ll = const_cast<T *>(ll); a.ldl = ldl; a.n = (int)n;
+    a.bs_src = bs_x; a.bs_y = bs_out; a.bs_ll = bs_ll;
     for (int i = 0; i < LIFT_FAST_STEPS; ++i)
         for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
     a.norm1 = sc.norm1; a.norm2 = sc.norm2;
     switch (id) {
-    case 1: return launch_tile2_inv_id<T, 1>(st, a);
-    case 3: return launch_tile2_inv_id<T, 3>(st, a);
-    case 5: return launch_tile2_inv_id<T, 5>(st, a);
+    case 1: return launch_tile2_inv_id<T, 1>(st, a, (unsigned)nimg);
+    case 3: return launch_tile2_inv_id<T, 3>(st, a, (unsigned)nimg);
+    case 5: return launch_tile2_inv_id<T, 5>(st, a, (unsigned)nimg);
     default: return hipErrorInvalidValue;
     }
 }
 template hipError_t lift2d_tile2_inv_launch<float>(int, hipStream_t, const LiftScheme<float> &, const float *, int64_t, float *, int64_t, const float *, int64_t,
-                                                   int64_t);
+                                                   int64_t, int64_t, int64_t, int64_t, int64_t);
 template hipError_t lift2d_tile2_inv_launch<double>(int, hipStream_t, const LiftScheme<double> &, const double *, int64_t, double *, int64_t, const double *,
-                                                    int64_t, int64_t);
+                                                    int64_t, int64_t, int64_t, int64_t, int64_t, int64_t);
 
 // ll: destination of the level-2 approximation (dense, leading dimension ldl) or nullptr (-> the top-left corner of y)
 template <typename T>
 hipError_t lift2d_tile2_fwd_launch(int id, hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t lds, T *y, int64_t ldy, T *ll, int64_t ldl,
-                                   int64_t n)
+                                   int64_t n, int64_t nimg, int64_t bs_src, int64_t bs_y, int64_t bs_ll)
 {
+    if (nimg < 1 || nimg > 65535) return hipErrorInvalidValue;
     LiftTileArgs<T> a;
     a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.ll = ll; a.ldl = ldl; a.n = (int)n;
+    a.bs_src = bs_src; a.bs_y = bs_y; a.bs_ll = bs_ll;
     for (int i = 0; i < LIFT_FAST_STEPS; ++i)
         for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
     a.norm1 = sc.norm1; a.norm2 = sc.norm2;
     switch (id) {
-    case 0: return launch_tile2_fwd_id<T, 0>(st, a);
-    case 2: return launch_tile2_fwd_id<T, 2>(st, a);
-    case 4: return launch_tile2_fwd_id<T, 4>(st, a);
+    case 0: return launch_tile2_fwd_id<T, 0>(st, a, (unsigned)nimg);
+    case 2: return launch_tile2_fwd_id<T, 2>(st, a, (unsigned)nimg);
+    case 4: return launch_tile2_fwd_id<T, 4>(st, a, (unsigned)nimg);
     default: return hipErrorInvalidValue;
     }
 }
-template hipError_t lift2d_tile2_fwd_launch<float>(int, hipStream_t, const LiftScheme<float> &, const float *, int64_t, float *, int64_t, float *, int64_t, int64_t);
+template hipError_t lift2d_tile2_fwd_launch<float>(int, hipStream_t, const LiftScheme<float> &, const float *, int64_t, float *, int64_t, float *, int64_t, int64_t, int64_t, int64_t,
+                                                   int64_t, int64_t);
 template hipError_t lift2d_tile2_fwd_launch<double>(int, hipStream_t, const LiftScheme<double> &, const double *, int64_t, double *, int64_t, double *, int64_t,
-                                                    int64_t);
+                                                    int64_t, int64_t, int64_t, int64_t, int64_t);
 
 template <typename T>
 hipError_t lift2d_tile_launch(int id, int fw, hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t lds, T *y, int64_t ldy, T *ll,
-                              int64_t ldl, int64_t n)
+                              int64_t ldl, int64_t n, int64_t nimg, int64_t bs_src, int64_t bs_y, int64_t bs_ll)
 {
+    if (nimg < 1 || nimg > 65535) return hipErrorInvalidValue;
     LiftTileArgs<T> a;
     a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.ll = ll; a.ldl = ldl; a.n = (int)n;
+    a.bs_src = bs_src; a.bs_y = bs_y; a.bs_ll = bs_ll;
     for (int i = 0; i < LIFT_FAST_STEPS; ++i)
         for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
     a.norm1 = sc.norm1; a.norm2 = sc.norm2;
     switch (id) {
-    case 0: return fw ? launch_tile_id<T, 0, 1>(st, a) : hipErrorInvalidValue;
-    case 2: return fw ? launch_tile_id<T, 2, 1>(st, a) : hipErrorInvalidValue;
-    case 4: return fw ? launch_tile_id<T, 4, 1>(st, a) : hipErrorInvalidValue;
-    case 1: return fw ? hipErrorInvalidValue : launch_tile_id<T, 1, 0>(st, a);
-    case 3: return fw ? hipErrorInvalidValue : launch_tile_id<T, 3, 0>(st, a);
-    case 5: return fw ? hipErrorInvalidValue : launch_tile_id<T, 5, 0>(st, a);
+    case 0: return fw ? launch_tile_id<T, 0, 1>(st, a, (unsigned)nimg) : hipErrorInvalidValue;
+    case 2: return fw ? launch_tile_id<T, 2, 1>(st, a, (unsigned)nimg) : hipErrorInvalidValue;
+    case 4: return fw ? launch_tile_id<T, 4, 1>(st, a, (unsigned)nimg) : hipErrorInvalidValue;
+    case 1: return fw ? hipErrorInvalidValue : launch_tile_id<T, 1, 0>(st, a, (unsigned)nimg);
+    case 3: return fw ? hipErrorInvalidValue : launch_tile_id<T, 3, 0>(st, a, (unsigned)nimg);
+    case 5: return fw ? hipErrorInvalidValue : launch_tile_id<T, 5, 0>(st, a, (unsigned)nimg);
     default: return hipErrorInvalidValue;
     }
 }
 
 template hipError_t lift2d_tile_launch<float>(int, int, hipStream_t, const LiftScheme<float> &, const float *, int64_t, float *, int64_t, float *,
-                                              int64_t, int64_t);
+                                              int64_t, int64_t, int64_t, int64_t, int64_t, int64_t);
 template hipError_t lift2d_tile_launch<double>(int, int, hipStream_t, const LiftScheme<double> &, const double *, int64_t, double *, int64_t,
-                                               double *, int64_t, int64_t);
+                                               double *, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t);
 
 }  // namespace wl

@@ -240,6 +240,21 @@ for (f, fw) in ((:dwt_batch, true), (:idwt_batch, false))
     end
 end
 
+# the same for a lifting scheme (square images only, as the reference's 2-D lifting transform: transforms_lifting.jl:131-132)
+for (f, fw) in ((:dwt_batch, true), (:idwt_batch, false))
+    @eval function $f(x::ROCArray{T,3}, scheme::GLS,
+                      L::Integer=min(Util.maxtransformlevels(size(x, 1)), Util.maxtransformlevels(size(x, 2)))) where {T<:Union{Float32,Float64}}
+        y = similar(x)
+        isup, nc, sh, cf = flatten(scheme)
+        GC.@preserve y x check(ccall((:wl_dwt_lifting_batch, LIB), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Int64, Int64, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64},
+                     Cdouble, Cdouble, Cint, Cint, Ptr{Cvoid}),
+                    ctx(), DT[T], pointer(y), pointer(x), Int64[size(x, 1), size(x, 2)], size(x, 3), size(x, 1) * size(x, 2),
+                    length(isup), isup, nc, sh, cf, scheme.norm1, scheme.norm2, L, $fw, stream()))
+        return y
+    end
+end
+
 # ---- multi-GPU dwtc: shard the columns of a batch over the devices of one node --------------------------------------
 # The path has no exchange step (SURVEY.md 8e): columns are independent, so rank r of `world` transforms the contiguous
 # column block `shard_range(nsignals, r, world)` on its own GPU with its own context; only the wavelet description (a few

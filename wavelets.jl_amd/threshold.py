@@ -254,7 +254,7 @@ def denoise(x, wt=_DEFAULT, L: Optional[int] = None, dnt: Optional[DNFT] = None,
     if (TI and isinstance(wt, GLS) and (x.dim() == 1 or (x.dim() == 2 and len(nsp) == 2)) and isinstance(dnt.th, THType)
             and dnt.th.code is not None and 0 <= dnt.th.code <= 3):
         # the same device-resident batch for a lifting scheme (wl_denoise_ti_lifting, round 4): shifted signals as one
-        # batched-lines transform, shifted images one 2-D lifting transform per plane; sigma never leaves the device
+        # batched-lines transform, shifted images one batched 2-D lifting transform per group of spins; sigma never leaves the device
         sig = -1.0 if estnoise is noisest else float(estnoise(x, wt))
         if estnoise is not noisest and not (sig >= 0 and sig * float(dnt.t) >= 0):
             raise AssertionError("t >= 0")

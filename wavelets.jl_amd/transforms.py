@@ -466,20 +466,31 @@ def idwtc_(y, x, wt, L: Optional[int] = None) -> torch.Tensor:
 # ---- a batch of independent images --------------------------------------------------------------
 def _xwt_batch(x, wt, L, fw, y=None):
     """x: n0 x n1 x B (column-major: image i = x[:, :, i]); every image gets its own 2-D transform, all in one chain of
-    launches (wl_dwt_filter_batch).  The reference has no batched form: this equals `stack(dwt(x[:, :, i], wt, L) for i)`."""
+    launches (wl_dwt_filter_batch for an orthogonal filter, wl_dwt_lifting_batch for a lifting scheme).  The reference has no
+    batched form: this equals `stack(dwt(x[:, :, i], wt, L) for i)`."""
+    if not isinstance(wt, (OrthoFilter, GLS)):
+        raise TypeError("dwt_batch is defined for orthogonal filters and lifting schemes")
+    if isinstance(x, torch.Tensor):
+        if x.dim() != 3:
+            raise TypeError("dwt_batch expects an n0 x n1 x B array")
+        if isinstance(wt, GLS) and int(x.shape[0]) != int(x.shape[1]):
+            raise ArgumentError("array must be square/cube")          # what dwt(x[:, :, i], wt::GLS) raises (transforms_lifting.jl:131-132)
     x = _prep_in(x)
-    if x.dim() != 3:
-        raise TypeError("dwt_batch expects an n0 x n1 x B array")
-    if not isinstance(wt, OrthoFilter):
-        raise TypeError("dwt_batch is defined for orthogonal filters")
     n0, n1, nb = (int(v) for v in x.shape)
     L = min(Util.maxtransformlevels(n0), Util.maxtransformlevels(n1)) if L is None else int(L)
     y = similar(x) if y is None else y
     _check_pair(y, x)                        # (a caller-supplied y: same shape / type / device, dense column-major)
     lib = _lib.load()
     h, st = _context(x.device)
-    q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
     dims = (C.c_int64 * 2)(n0, n1)
+    if isinstance(wt, GLS):
+        iu, nc, sh, cf = wt.flatten()
+        # (y may be x: the in-place transform of every image)
+        rc = lib.wl_dwt_lifting_batch(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), dims, nb, n0 * n1,
+                                      len(iu), _i32p(iu), _i32p(nc), _i32p(sh), _f64p(cf), wt.norm1, wt.norm2, L, 1 if fw else 0, st)
+        _check(rc, h)
+        return y
+    q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
     rc = lib.wl_dwt_filter_batch(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), dims, nb, n0 * n1,
                                  _f64p(q), len(q), L, 1 if fw else 0, st)
     _check(rc, h)
