@@ -195,6 +195,24 @@ WL_API int wl_dwtc_lifting_oop(wl_ctx *ctx, int dtype, void *y, const void *x,
 WL_API int wl_dwt_filter_batch(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nimages,
                         int64_t image_stride, const double *qmf, int flen, int L, int fw, void *stream);
 
+/* ---- a batch of independent 3-D transforms ----------------------------------------------- */
+/* y[:, :, :, i] = dwt(x[:, :, :, i], filter, L) (fw = 0: idwt) for nvolumes boxes of dims[0] x dims[1] x dims[2]
+ * (column-major, dense), volume i at element offset i * volume_stride (>= dims[0]*dims[1]*dims[2]) of x and of y.
+ * The same results, bit for bit, as nvolumes calls of wl_dwt_filter with ndims = 3 (transforms_filter.jl:192-294 per volume;
+ * any box with a 2^L factor per dimension, not only cubes), but every level that one of the one-launch 3-D kernels takes --
+ * boxes of <= 4096 elements (all remaining levels), the LDS blocks up to 2^18 elements, the one-pass kernels above -- is ONE
+ * launch over all volumes (groups of 65535): patches of a CT / MRI volume, video blocks, whose single transform is launch latency.
+ * Other levels (the axis-pass, any-extent and generic families), odd or > 10-tap filters, wl_ctx_set_path(ctx, 1) and a
+ * volume_stride that leaves a volume base off a 16-byte boundary run volume after volume.  L = 0 copies the volumes; the padding
+ * between volumes is never written at any L.  The call only enqueues (capturable in a hipGraph).  Status codes in this order:
+ * WL_EINVAL_ARG, WL_EINVAL_DTYPE, WL_EINVAL_FILTER, WL_EDIMS, WL_EINVAL_L, WL_EINVAL_SIZE, WL_EALIAS (y == x).
+ * Workspace, with N = dims[0]*dims[1]*dims[2] and G = min(nvolumes, 65535): the approximation ping-pong of every volume of a
+ * group plus one volume's inter-pass buffers, 2 * (G * (N / 8) + 64) + 3 N + 64 elements; nothing is allocated once
+ * wl_workspace_bytes_full(dtype, 1, {nvolumes * volume_stride}, L) bytes are reserved.  A batched lifting transform of
+ * volumes does not exist (wl_dwt_lifting_batch is 2-D).                                                                    */
+WL_API int wl_dwt_filter_batch3(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nvolumes,
+                         int64_t volume_stride, const double *qmf, int flen, int L, int fw, void *stream);
+
 /* y[:, :, i] = dwt(x[:, :, i], scheme, L) (fw = 0: idwt) for nimages SQUARE images of dims[0] x dims[1], laid out as for
  * wl_dwt_filter_batch; the scheme is passed as for wl_dwt_lifting.  The same results, bit for bit, as nimages calls of
  * wl_dwt_lifting_oop with ndims = 2 (transforms_lifting.jl:128-196 per image), but every level is ONE launch over all images
@@ -287,8 +305,11 @@ WL_API int wl_arrayadd(wl_ctx *ctx, int dtype, void *y, const void *z, int64_t n
 /* y[i] = T(y[i] * s) with s::Float64 -- rmul!(y, 1/pns), denoising.jl:66.                  */
 WL_API int wl_rmul(wl_ctx *ctx, int dtype, void *y, int64_t n, double s, void *stream);
 
-/* denoise(x, wt::OrthoFilter; L, dnt, TI = true, nspin) fused on the device (denoising.jl:21-67), 1-D vectors and square
- * matrices: all prod(nspin) circularly shifted copies are transformed, thresholded and transformed back as ONE batch
+/* denoise(x, wt::OrthoFilter; L, dnt, TI = true, nspin) fused on the device (denoising.jl:21-67), 1-D vectors, square
+ * matrices and cubes (WL_EINVAL_CUBE unless all extents are equal; nspin has ndims entries, spin i shifts by
+ * nspin2circ(nspin, i), first dimension fastest; cubes of up to 2^20 - 1 per side, WL_EINVAL_SIZE beyond): the spins of a cube
+ * run as a batch of volumes (the level loops of wl_dwt_filter_batch3), and prod(nspin) == 1 is the plain denoise of the array
+ * with sigma kept on the device.  All prod(nspin) circularly shifted copies are transformed, thresholded and transformed back as ONE batch
  * (in groups when the buffers would exceed the context's cap), then un-shifted and summed in spin order -- the summation
  * order of the reference, so the result carries the same roundings -- and scaled by 1/prod(nspin).  The noise estimate
  * sigma = noisest(x, wt) = mad!(level-1 detail range) / 0.6745 is computed on the device and consumed there (no host
@@ -297,7 +318,8 @@ WL_API int wl_rmul(wl_ctx *ctx, int dtype, void *y, int64_t n, double s, void *s
 WL_API int wl_denoise_ti_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims,
                          const double *qmf, int flen, int L, int th, double t_unit, const int64_t *nspin,
                          double sigma_host, void *stream);
-/* The same for a lifting scheme (wt::GLS; scheme arguments as wl_dwt_lifting): shifted signals run as one batched-lines
+/* The same for a lifting scheme (wt::GLS; scheme arguments as wl_dwt_lifting), vectors and square matrices only (there is no
+ * batched lifting transform of volumes: ndims = 3 is WL_EDIMS): shifted signals run as one batched-lines
  * transform, shifted images one batched 2-D lifting transform per group of spins; sigma and everything else stay on the device.
  * replaces the translation-invariant branch of denoise(x, wt::GLS; TI=true), denoising.jl:36-67 (round 4).               */
 WL_API int wl_denoise_ti_lifting(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims,

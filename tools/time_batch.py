@@ -5,6 +5,9 @@
     python tools/time_batch.py launches   one call of every lifting configuration, a torch fill between them: run it under
                                           `rocprofv3 --kernel-trace` and count the library's kernels between the fills
                                           (tools/count_launches.py)
+    python tools/time_batch.py volumes    batch of volumes (db4, Float32, full depth): wl_dwt_filter_batch3 against the same number
+                                          of single wl_dwt_filter calls, forward and inverse, rotating inputs
+    python tools/time_batch.py denoise3d  W.denoise(cube, TI=True) with the default 8 x 8 x 8 spins, host wall time
 """
 import os, sys, statistics
 import torch
@@ -103,6 +106,65 @@ def lifting_launches():
     torch.cuda.synchronize()
 
 
+def t_stats(fns, reps=20):
+    """median, min and max (us) of `reps` timed calls that rotate through `fns` (the same call on different inputs)"""
+    for f in fns:
+        f()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for k, (a, b) in enumerate(ev):
+        a.record(); fns[k % len(fns)](); b.record()
+    torch.cuda.synchronize()
+    ts = sorted(a.elapsed_time(b) * 1e3 for a, b in ev)
+    return statistics.median(ts), ts[0], ts[-1]
+
+
+def volumes_table():
+    db4 = W.wavelet(W.WT.db4)
+    print("| volumes | L | direction | batch us (min .. max) | kernel | single calls in a loop us (min .. max) | speed-up |")
+    print("|---|---|---|---|---|---|---|")
+    for n, nb in ((32, 512), (64, 512), (128, 64)):
+        L = W.maxtransformlevels(n)
+        xs = [torch.randn(nb, n, n, n, dtype=torch.float32, device="cuda").permute(3, 2, 1, 0) for _ in range(3)]
+        yb = W.similar(xs[0])
+        cs = [W.dwt_batch(x, db4, L) for x in xs]                # coefficients: the inputs of the inverse
+        y1 = W.similar(xs[0][..., 0])
+        for name, fb, f1, ins in (("dwt", W.dwt_batch, W.dwt_oop_, xs), ("idwt", W.idwt_batch, W.idwt_oop_, cs)):
+            batch = [(lambda x=x: fb(x, db4, L, y=yb)) for x in ins]
+            def loop(x):
+                for i in range(nb):
+                    f1(y1, x[..., i], db4, L)
+            singles = [(lambda x=x: loop(x)) for x in ins]
+            tb = t_stats(batch, 21)
+            kb = W.last_kernel()
+            ts = t_stats(singles, 21)
+            print(f"| {nb} x {n}^3 | {L} | {name} | {tb[0]:.1f} ({tb[1]:.1f} .. {tb[2]:.1f}) | {kb} | {ts[0]:.1f} ({ts[1]:.1f} .. {ts[2]:.1f}) | "
+                  f"{ts[0] / tb[0]:.2f} |", flush=True)
+
+
+def denoise3d_table():
+    """host wall time of the whole call (a synchronise before and after), median of `reps`; runs on any build of the package, so the
+    same script times the per-spin host loop of an older build"""
+    import time
+    print("| cube | median ms (min .. max) | reps | kernel |")
+    print("|---|---|---|---|")
+    for n, reps in ((32, 7), (64, 7), (128, 5)):
+        xs = [W.to_device((torch.randn(n, n, n) * 0.05 + torch.linspace(0, 1, n)[:, None, None]).numpy().astype("float32")) for _ in range(2)]
+        W.denoise(xs[0], TI=True)
+        torch.cuda.synchronize()
+        ts = []
+        for k in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            W.denoise(xs[k % 2], TI=True)
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        ts.sort()
+        print(f"| {n}^3 Float32, sym5, L = {min(W.maxtransformlevels(n), 6)}, 512 spins | {statistics.median(ts):.2f} ({ts[0]:.2f} .. {ts[-1]:.2f}) | {reps} | "
+              f"{W.last_kernel()} |", flush=True)
+
+
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "filter"
-    {"filter": filter_table, "lifting": lifting_table, "launches": lifting_launches}[mode]()
+    {"filter": filter_table, "lifting": lifting_table, "launches": lifting_launches, "volumes": volumes_table,
+     "denoise3d": denoise3d_table}[mode]()

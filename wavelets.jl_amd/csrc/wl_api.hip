@@ -315,6 +315,41 @@ int lifting_batch_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
     return WL_OK;
 }
 
+// a batch of volumes (wl_dwt_filter_batch3): volumes in groups of at most 65535, the level loops of wl_batch3d.hip
+template <typename T>
+int dwt_filter_batch3_impl(wl_ctx *ctx, hipStream_t st, const int64_t dims[3], int64_t nvol, int64_t vs, T *y, const T *x, const double *qmf,
+                           int flen, int L, int fw)
+{
+    const int64_t N = dims[0] * dims[1] * dims[2];
+    if (L == 0) {
+        // every volume is dense: one copy of an N x nvol matrix with leading dimension vs (the padding is not touched)
+        const Strides3 s = {{1, vs, 0}};
+        for (int64_t i0 = 0; i0 < nvol; i0 += 65535) {
+            const Extent3 ext = {{N, (nvol - i0 < 65535) ? (nvol - i0) : 65535, 1}};
+            WL_HIP(ctx, generic_copy_box<T>(st, x + i0 * vs, s, y + i0 * vs, s, ext));
+        }
+        ctx->last_kernel = "copy";
+        return WL_OK;
+    }
+    Taps<T> taps;
+    make_taps<T>(qmf, flen, taps);
+    const int64_t gmax = nvol < 65535 ? nvol : 65535;
+    // 3-D levels outside the tail want one volume's T0 / T1 (as dwt_filter_impl does for a 3-D box): ask for them up front
+    const size_t full_bytes = ws_vols_elems(N, gmax) * sizeof(T);
+    int rc = ensure_ws(ctx, full_bytes, st);
+    if (rc) return rc;
+    for (int64_t i0 = 0; i0 < nvol; i0 += 65535) {
+        const int64_t nv = (nvol - i0 < 65535) ? (nvol - i0) : 65535;
+        rc = fw ? filter_fwd_levels_vols<T>(ctx->ws, true, ctx->cu_count, ctx->path, st, dims, nv, vs, vs, y + i0 * vs, x + i0 * vs, taps, L,
+                                            &ctx->last_kernel, &ctx->last_hip)
+                : filter_inv_levels_vols<T>(ctx->ws, true, ctx->cu_count, ctx->path, st, dims, nv, vs, vs, y + i0 * vs, x + i0 * vs, taps, L,
+                                            &ctx->last_kernel, &ctx->last_hip);
+        if (rc == WL_RETRY_GEN) return WL_EINVAL_ARG;          // (the full workspace is held: no level can ask for more)
+        if (rc) return rc;
+    }
+    return WL_OK;
+}
+
 }  // namespace
 
 template <typename T>
@@ -1016,6 +1051,23 @@ int wl_dwt_filter_batch(wl_ctx *ctx, int dtype, void *y, const void *x, const in
         if (rc) return rc;
     }
     return WL_OK;
+}
+
+int wl_dwt_filter_batch3(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nvolumes, int64_t volume_stride,
+                         const double *qmf, int flen, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !dims || !qmf) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || nvolumes < 1 || volume_stride < dims[0] * dims[1] * dims[2]) return WL_EDIMS;
+    if (L < 0) return WL_EINVAL_L;
+    if (!sufficientpoweroftwo(dims[0], L) || !sufficientpoweroftwo(dims[1], L) || !sufficientpoweroftwo(dims[2], L)) return WL_EINVAL_SIZE;
+    if (y == x) return WL_EALIAS;
+    WL_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == WL_F32 ? dwt_filter_batch3_impl<float>(ctx, st, dims, nvolumes, volume_stride, (float *)y, (const float *)x, qmf, flen, L, fw)
+                           : dwt_filter_batch3_impl<double>(ctx, st, dims, nvolumes, volume_stride, (double *)y, (const double *)x, qmf, flen, L,
+                                                            fw);
 }
 
 int wl_dwt_lifting_batch(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nimages, int64_t image_stride,

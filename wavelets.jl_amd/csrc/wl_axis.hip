@@ -450,47 +450,54 @@ static hipError_t launch_axis(hipStream_t st, const Taps<T> &taps, const T *src,
     default: break;                                          \
     }
 
+// Which kernel family fast3d_fwd_level takes for this level -- 0: none (not eligible), 1: k_fwd3d_one, 2: k_level3_lds, 3: the
+// single-axis passes.  The level loops of a batch of volumes (wl_batch3d.hip) ask before they launch: tiers 1 and 2 take every
+// volume in one launch.
 // One forward 3-D level: box (n0,n1,n2) read from `cur` (strides 1, c1, c2 with c1 == n0), details to y
 // (dense full array strides 1, y1, y2), LLL corner to `ll` (dense h0,h1,h2) or to y when ll == nullptr.
 // T0/T1: dense scratch of the box size.  Returns false when the shape is not eligible.
 template <typename T>
-bool fast3d_fwd_level(hipStream_t st, const Taps<T> &taps, const T *cur, int64_t c1, int64_t c2, T *y, int64_t y1, int64_t y2,
-                      T *ll, const int64_t n[3], T *T0, T *T1, int cu_count, hipError_t *err, const char **kname)
+int fast3d_fwd_tier(int F, const T *cur, int64_t c1, int64_t c2, const T *y, int64_t y1, int64_t y2, const T *ll, const int64_t n[3],
+                    const T *T0, const T *T1)
 {
     constexpr int VEC = 16 / sizeof(T);
-    const int F = taps.F;
-    *err = hipSuccess;
-    if (kname) *kname = "k_fwd_axis_stream";
     // round 6: the whole level in one pass over HBM where the one-pass kernel takes the shape (wl_fwd3d.hip)
-    if (fwd3d_one_ok<T>(F, cur, c1, c2, y, y1, y2, ll, n)) {
-        *err = fwd3d_one_launch<T>(st, taps, cur, c1, c2, y, y1, y2, ll, n, cu_count);
-        if (kname) *kname = "k_fwd3d_one";
-        return true;
-    }
+    if (fwd3d_one_ok<T>(F, cur, c1, c2, y, y1, y2, ll, n)) return 1;
     // ... and the small levels between the streaming sizes and the one-workgroup tail in one launch each (wl_level3.hip)
-    if (level3_lds_ok<T>(F, n) && cur != y) {
-        *err = level3_lds_launch<T>(st, taps, 1, cur, c1, c2, y, y1, y2, (const T *)nullptr, ll, n);
-        if (kname) *kname = "k_level3_lds";
-        return true;
-    }
-    const int64_t n0 = n[0], n1 = n[1], n2 = n[2], h0 = n0 >> 1, h1 = n1 >> 1, h2 = n2 >> 1;
+    if (level3_lds_ok<T>(F, n) && cur != y) return 2;
+    const int64_t n0 = n[0], n1 = n[1], n2 = n[2];
     if ((F % 2) != 0 || F > 10 || !short_ok(n0) || n1 < 16 || n2 < 16 || (n1 % 16) != 0 || (n2 % 16) != 0 || c1 != n0 ||
         (c2 % VEC) != 0 || (y1 % VEC) != 0 || (y2 % VEC) != 0 || !a_al16(cur) || !a_al16(y) || !a_al16(T0) || !a_al16(T1) ||
         (ll && !a_al16(ll)) || n1 > 32767) {
         // not a shape of the axis kernels: the one-pass level from 2^19 elements, the LDS blocks up to 2^20, before the any-extent
         // kernels take it (three passes per level)
-        if (fwd3d_one_ok<T>(F, cur, c1, c2, y, y1, y2, ll, n, true)) {
-            *err = fwd3d_one_launch<T>(st, taps, cur, c1, c2, y, y1, y2, ll, n, cu_count);
-            if (kname) *kname = "k_fwd3d_one";
-            return true;
-        }
-        if (level3_lds_ok<T>(F, n, true) && cur != y) {
-            *err = level3_lds_launch<T>(st, taps, 1, cur, c1, c2, y, y1, y2, (const T *)nullptr, ll, n);
-            if (kname) *kname = "k_level3_lds";
-            return true;
-        }
-        return false;
+        if (fwd3d_one_ok<T>(F, cur, c1, c2, y, y1, y2, ll, n, true)) return 1;
+        if (level3_lds_ok<T>(F, n, true) && cur != y) return 2;
+        return 0;
     }
+    return F >= 2 ? 3 : 0;
+}
+
+template <typename T>
+bool fast3d_fwd_level(hipStream_t st, const Taps<T> &taps, const T *cur, int64_t c1, int64_t c2, T *y, int64_t y1, int64_t y2,
+                      T *ll, const int64_t n[3], T *T0, T *T1, int cu_count, hipError_t *err, const char **kname)
+{
+    const int F = taps.F;
+    *err = hipSuccess;
+    if (kname) *kname = "k_fwd_axis_stream";
+    const int tier = fast3d_fwd_tier<T>(F, cur, c1, c2, y, y1, y2, ll, n, T0, T1);
+    if (tier == 1) {
+        *err = fwd3d_one_launch<T>(st, taps, cur, c1, c2, y, y1, y2, ll, n, cu_count);
+        if (kname) *kname = "k_fwd3d_one";
+        return true;
+    }
+    if (tier == 2) {
+        *err = level3_lds_launch<T>(st, taps, 1, cur, c1, c2, y, y1, y2, (const T *)nullptr, ll, n);
+        if (kname) *kname = "k_level3_lds";
+        return true;
+    }
+    if (tier == 0) return false;
+    const int64_t n0 = n[0], n1 = n[1], n2 = n[2], h0 = n0 >> 1, h1 = n1 >> 1, h2 = n2 >> 1;
     bool ok = false;
     WL_DISPATCH_FA(F, {
         // An option, OFF by default (round 5, measured): the level in SLABS of output plane pairs -- the axis-3 pass of a slab writes
@@ -551,42 +558,47 @@ bool fast3d_fwd_level(hipStream_t st, const Taps<T> &taps, const T *cur, int64_t
     return ok;
 }
 
+// (fast3d_inv_tier: the choice of fast3d_inv_level, as fast3d_fwd_tier)
 // One inverse 3-D level (output box n): approximation from `llsrc` (dense h0,h1,h2) or from x when nullptr,
 // details from x (dense full strides 1, x1, x2); result to `out` (strides 1, o1, o2 with o1 == n0).
+template <typename T>
+int fast3d_inv_tier(int F, const T *x, int64_t x1, int64_t x2, const T *llsrc, const T *out, int64_t o1, int64_t o2, const int64_t n[3],
+                    const T *T0, const T *T1)
+{
+    constexpr int VEC = 16 / sizeof(T);
+    if (inv3d_one_ok<T>(F, x, x1, x2, llsrc, out, o1, o2, n)) return 1;
+    if (level3_lds_ok<T>(F, n) && x != out && llsrc != out) return 2;
+    const int64_t n0 = n[0], n1 = n[1], n2 = n[2], h0 = n0 >> 1;
+    if ((F % 2) != 0 || F > 10 || !short_ok(n0) || n1 < 16 || n2 < 16 || (n1 % 16) != 0 || (n2 % 16) != 0 || o1 != n0 ||
+        (o2 % VEC) != 0 || (x1 % VEC) != 0 || (x2 % VEC) != 0 || !a_al16(x) || !a_al16(out) || !a_al16(T0) || !a_al16(T1) ||
+        (llsrc && !a_al16(llsrc)) || n1 > 32767 || (h0 % 4) != 0) {
+        if (inv3d_one_ok<T>(F, x, x1, x2, llsrc, out, o1, o2, n, true)) return 1;
+        if (level3_lds_ok<T>(F, n, true) && x != out && llsrc != out) return 2;
+        return 0;
+    }
+    return F >= 2 ? 3 : 0;
+}
+
 template <typename T>
 bool fast3d_inv_level(hipStream_t st, const Taps<T> &taps, const T *x, int64_t x1, int64_t x2, const T *llsrc,
                       T *out, int64_t o1, int64_t o2, const int64_t n[3], T *T0, T *T1, int cu_count, hipError_t *err, const char **kname)
 {
-    constexpr int VEC = 16 / sizeof(T);
     const int F = taps.F;
     *err = hipSuccess;
     if (kname) *kname = "k_inv_axis_stream";
-    if (inv3d_one_ok<T>(F, x, x1, x2, llsrc, out, o1, o2, n)) {
+    const int tier = fast3d_inv_tier<T>(F, x, x1, x2, llsrc, out, o1, o2, n, T0, T1);
+    if (tier == 1) {
         *err = inv3d_one_launch<T>(st, taps, x, x1, x2, llsrc, out, o1, o2, n, cu_count);
         if (kname) *kname = "k_inv3d_one";
         return true;
     }
-    if (level3_lds_ok<T>(F, n) && x != out && llsrc != out) {
+    if (tier == 2) {
         *err = level3_lds_launch<T>(st, taps, 0, x, x1, x2, out, o1, o2, llsrc, (T *)nullptr, n);
         if (kname) *kname = "k_level3_lds";
         return true;
     }
+    if (tier == 0) return false;
     const int64_t n0 = n[0], n1 = n[1], n2 = n[2], h0 = n0 >> 1, h1 = n1 >> 1, h2 = n2 >> 1;
-    if ((F % 2) != 0 || F > 10 || !short_ok(n0) || n1 < 16 || n2 < 16 || (n1 % 16) != 0 || (n2 % 16) != 0 || o1 != n0 ||
-        (o2 % VEC) != 0 || (x1 % VEC) != 0 || (x2 % VEC) != 0 || !a_al16(x) || !a_al16(out) || !a_al16(T0) || !a_al16(T1) ||
-        (llsrc && !a_al16(llsrc)) || n1 > 32767 || (h0 % 4) != 0) {
-        if (inv3d_one_ok<T>(F, x, x1, x2, llsrc, out, o1, o2, n, true)) {
-            *err = inv3d_one_launch<T>(st, taps, x, x1, x2, llsrc, out, o1, o2, n, cu_count);
-            if (kname) *kname = "k_inv3d_one";
-            return true;
-        }
-        if (level3_lds_ok<T>(F, n, true) && x != out && llsrc != out) {
-            *err = level3_lds_launch<T>(st, taps, 0, x, x1, x2, out, o1, o2, llsrc, (T *)nullptr, n);
-            if (kname) *kname = "k_level3_lds";
-            return true;
-        }
-        return false;
-    }
     bool ok = false;
     WL_DISPATCH_FA(F, {
         // columns + rows of every plane in ONE launch when the planes are big enough for the fused 2-D inverse kernel
@@ -708,6 +720,11 @@ bool long_axis_level(hipStream_t st, const Taps<T> &taps, int fw, const T *src, 
 WL_INST_LONG(float)
 WL_INST_LONG(double)
 
+#define WL_INST_TIER(T)                                                                                                                  \
+    template int fast3d_fwd_tier<T>(int, const T *, int64_t, int64_t, const T *, int64_t, int64_t, const T *, const int64_t[3], const T *, const T *); \
+    template int fast3d_inv_tier<T>(int, const T *, int64_t, int64_t, const T *, const T *, int64_t, int64_t, const int64_t[3], const T *, const T *);
+WL_INST_TIER(float)
+WL_INST_TIER(double)
 template bool fast3d_fwd_level<float>(hipStream_t, const Taps<float> &, const float *, int64_t, int64_t, float *, int64_t, int64_t,
                                       float *, const int64_t[3], float *, float *, int, hipError_t *, const char **);
 template bool fast3d_fwd_level<double>(hipStream_t, const Taps<double> &, const double *, int64_t, int64_t, double *, int64_t, int64_t,

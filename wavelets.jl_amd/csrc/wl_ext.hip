@@ -732,30 +732,37 @@ __global__ void __launch_bounds__(EXT_THREADS) k_rmul(T *__restrict__ y, int64_t
 
 // ---- translation-invariant denoising as ONE batch (denoising.jl:36-67) ---------------------------------------------------
 // spin i (1-based) shifts dimension d by nspin2circ(nspin, i)[d] (denoising.jl:112-121: first dimension fastest)
-struct TiGeom { int64_t n0, n1, N; int64_t nsp0, nsp1; int64_t b0; };
-__device__ __forceinline__ void ti_shift_of(const TiGeom &g, int64_t spin0, int64_t &s0, int64_t &s1)
+// (vectors: n1 = n2 = 1; matrices: n2 = 1; nsp of an absent dimension = 1)
+struct TiGeom { int64_t n0, n1, n2, N; int64_t nsp0, nsp1, nsp2; int64_t b0; };
+__device__ __forceinline__ void ti_shift_of(const TiGeom &g, int64_t spin0, int64_t &s0, int64_t &s1, int64_t &s2)
 {
     s0 = (spin0 % g.nsp0) % g.n0;
     s1 = ((spin0 / g.nsp0) % g.nsp1) % g.n1;
+    s2 = ((spin0 / (g.nsp0 * g.nsp1)) % g.nsp2) % g.n2;
 }
 // Z[b] = circshift(x, +shift(b0 + b)): z[i] = x[i - shift] (Util.circshift!, util_main.jl:105-130).
-// grid: x = groups of 4 rows, y = column, z = spin (no integer division per element; 16-byte stores, the shifted reads are
+// grid: x = groups of 4 rows, y = groups of 8 columns (a column = one (i1, i2) of a cube: n1 * n2 of them, walked with a grid
+// stride so that the grid stays within 65535), z = spin (no integer division per element; 16-byte stores, the shifted reads are
 // four scalar loads from a contiguous run)
 template <typename T>
 __global__ void __launch_bounds__(256) k_ti_shift(T *__restrict__ Z, const T *__restrict__ x, TiGeom g)
 {
     typedef T V4 __attribute__((ext_vector_type(4)));
     const int64_t b = blockIdx.z;
-    int64_t s0, s1;
-    ti_shift_of(g, g.b0 + b, s0, s1);
+    int64_t s0, s1, s2;
+    ti_shift_of(g, g.b0 + b, s0, s1, s2);
     const int n0 = (int)g.n0, sh = (int)s0;
+    const int64_t ncol = g.n1 * g.n2;
     const bool vec = (n0 & 3) == 0 && (reinterpret_cast<uintptr_t>(Z) % (4 * sizeof(T))) == 0;
     // eight columns per workgroup (a workgroup per column is a single 16-byte store per thread: launch-rate bound)
-    for (int64_t i1 = (int64_t)blockIdx.y * 8; i1 < g.n1 && i1 < (int64_t)blockIdx.y * 8 + 8; ++i1) {
-        int64_t j1 = i1 - s1;
+    for (int64_t c0 = (int64_t)blockIdx.y * 8; c0 < ncol; c0 += (int64_t)gridDim.y * 8)
+    for (int64_t c = c0; c < ncol && c < c0 + 8; ++c) {
+        const int64_t i2 = c / g.n1, i1 = c - i2 * g.n1;
+        int64_t j1 = i1 - s1, j2 = i2 - s2;
         if (j1 < 0) j1 += g.n1;
-        const T *src = x + g.n0 * j1;
-        T *dst = Z + b * g.N + g.n0 * i1;
+        if (j2 < 0) j2 += g.n2;
+        const T *src = x + g.n0 * (j1 + g.n1 * j2);
+        T *dst = Z + b * g.N + g.n0 * c;
         for (int i0 = 4 * (int)(blockIdx.x * blockDim.x + threadIdx.x); i0 < n0; i0 += 4 * (int)(gridDim.x * blockDim.x)) {
             T v[4];
 #pragma unroll
@@ -773,38 +780,44 @@ __global__ void __launch_bounds__(256) k_ti_shift(T *__restrict__ Z, const T *__
     }
 }
 // y += circshift(Z[b], -shift(b0 + b)) for b = 0 .. nb-1 IN THAT ORDER (arrayadd! once per spin: the summation order
-// of the reference, so the sums carry the same roundings).  grid: x = groups of 4 rows, y = column.  The shifts of the
+// of the reference, so the sums carry the same roundings).  grid: x = groups of 4 rows, y = column ((i1, i2) of a cube, grid
+// stride: at most 65535 workgroups along y).  The shifts of the
 // batch sit in LDS (no integer division per spin and lane); the spins are read eight at a time, loads before the adds.
 template <typename T>
 __global__ void __launch_bounds__(256) k_ti_accumulate(T *__restrict__ y, const T *__restrict__ Z, TiGeom g, int64_t nb, int first)
 {
-    __shared__ int sh0[256], sh1[256];
-    const int n0 = (int)g.n0, n1 = (int)g.n1, i1 = (int)blockIdx.y;
+    __shared__ int sh0[256], sh1[256], sh2[256];
+    const int n0 = (int)g.n0, n1 = (int)g.n1, n2 = (int)g.n2;
+    const int64_t ncol = g.n1 * g.n2;
     for (int64_t bb0 = 0; bb0 < nb; bb0 += 256) {
         const int nbb = (int)((nb - bb0 < 256) ? (nb - bb0) : 256);
         __syncthreads();
         if ((int)threadIdx.x < nbb) {
-            int64_t s0, s1;
-            ti_shift_of(g, g.b0 + bb0 + threadIdx.x, s0, s1);
+            int64_t s0, s1, s2;
+            ti_shift_of(g, g.b0 + bb0 + threadIdx.x, s0, s1, s2);
             sh0[threadIdx.x] = (int)s0;
             sh1[threadIdx.x] = (int)s1;
+            sh2[threadIdx.x] = (int)s2;
         }
         __syncthreads();
+        for (int64_t col = blockIdx.y; col < ncol; col += gridDim.y) {
+        const int i2 = (int)(col / n1), i1 = (int)(col - (int64_t)i2 * n1);
         // a thread owns rows ib + tid + 256 e (e < 4): consecutive lanes read consecutive addresses of every shifted plane (the
         // shifts are arbitrary, so 16-byte loads are out; four rows per lane side by side cost four partial lines per load)
         for (int ib = 4 * (int)(blockIdx.x * blockDim.x); ib < n0; ib += 4 * (int)(gridDim.x * blockDim.x)) {
             const int ibt = ib + (int)threadIdx.x;
             T acc[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc[e] = ((first && bb0 == 0) || ibt + 256 * e >= n0) ? (T)0 : y[ibt + 256 * e + (int64_t)n0 * i1];
+            for (int e = 0; e < 4; ++e) acc[e] = ((first && bb0 == 0) || ibt + 256 * e >= n0) ? (T)0 : y[ibt + 256 * e + (int64_t)n0 * col];
             for (int b8 = 0; b8 < nbb; b8 += 8) {
                 T v[8][4];
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     if (b8 + u < nbb) {
-                        int j1 = i1 + sh1[b8 + u];
+                        int j1 = i1 + sh1[b8 + u], j2 = i2 + sh2[b8 + u];
                         if (j1 >= n1) j1 -= n1;
-                        const T *zp = Z + (bb0 + b8 + u) * g.N + (int64_t)n0 * j1;
+                        if (j2 >= n2) j2 -= n2;
+                        const T *zp = Z + (bb0 + b8 + u) * g.N + (int64_t)n0 * (j1 + (int64_t)n1 * j2);
                         const int s = sh0[b8 + u];
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
@@ -823,7 +836,8 @@ __global__ void __launch_bounds__(256) k_ti_accumulate(T *__restrict__ y, const 
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                if (ibt + 256 * e < n0) y[ibt + 256 * e + (int64_t)n0 * i1] = acc[e];
+                if (ibt + 256 * e < n0) y[ibt + 256 * e + (int64_t)n0 * col] = acc[e];
+        }
         }
     }
 }
@@ -860,13 +874,17 @@ template <typename T>
 int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, const double *qmf, int flen, int L,
                     int th, double t_unit, const int64_t *nspin, double sigma_host)
 {
-    const int64_t n0 = dims[0], n1 = (ndims == 2) ? dims[1] : 1, N = n0 * n1;
-    const int64_t nsp0 = nspin[0], nsp1 = (ndims == 2) ? nspin[1] : 1, pns = nsp0 * nsp1;
+    const int64_t n0 = dims[0], n1 = (ndims >= 2) ? dims[1] : 1, n2 = (ndims == 3) ? dims[2] : 1, N = n0 * n1 * n2;
+    const int64_t nsp0 = nspin[0], nsp1 = (ndims >= 2) ? nspin[1] : 1, nsp2 = (ndims == 3) ? nspin[2] : 1, pns = nsp0 * nsp1 * nsp2;
+    const int64_t vdims[3] = {n0, n1, n2};
     Taps<T> taps;
     make_taps<T>(qmf, flen, taps);
     int rc = ensure_aux(ctx);
     if (rc != WL_OK) return rc;
     SelState *sel = (SelState *)ctx->aux;
+    // cubes: the spins of a group are a batch of volumes (filter_*_levels_vols, wl_batch3d.hip: every level of the one-launch 3-D
+    // kernels one launch over all spins); its workspace is the approximation ping-pong per spin + one volume's generic buffers
+    auto tw_elems = [&](int64_t B) { return ndims == 3 ? ws_vols_elems(N, B) : ws_elems(N * B, ndims); };
     // spins per batch: the whole set unless the buffers (2 N B for the shifted copies and their coefficients, plus the
     // transform workspace of the batch box) would pass the cap
     // Virtual shifts (Float32 square images on the LDS-exchange level kernel): a circular shift along dim 2 is an offset of the
@@ -881,7 +899,7 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
     const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
     // (one spin: no shifted copy Z, see below)
     const size_t ncopies = (pns == 1) ? 1 : 2;
-    auto need = [&](int64_t B) { return (ws_elems(N * B, ndims) + ncopies * (size_t)N * B + zr_elems + (size_t)n0 + 64) * sizeof(T); };
+    auto need = [&](int64_t B) { return (tw_elems(B) + ncopies * (size_t)N * B + zr_elems + (size_t)n0 + 64) * sizeof(T); };
     int64_t B = pns;
     while (B > 1 && need(B) > cap) B = (B + 1) / 2;
     if (B > 65535) B = 65535;
@@ -892,7 +910,7 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
     }
     if (rc != WL_OK) return rc;
     T *tw = (T *)ctx->ws;                                   // transform workspace of the batch box (with the generic buffers)
-    T *Z = tw + ws_elems(N * B, ndims);
+    T *Z = tw + tw_elems(B);
     T *XT = Z + (pns == 1 ? 0 : N * B);
     T *ZR = XT + N * B;                                     // row-shifted copies (virtual shifts only)
     T *dr = ZR + zr_elems;                                  // detail range of the noise estimate (n0/2 samples)
@@ -902,9 +920,9 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
     if (!(sigma_host >= 0)) {
         BoxSpec b1;
         b1.nd = ndims; b1.nt = ndims;
-        b1.dims[0] = n0; b1.dims[1] = n1; b1.dims[2] = 1;
+        b1.dims[0] = n0; b1.dims[1] = n1; b1.dims[2] = n2;
         b1.full = dense_strides(b1.dims);
-        if (n0 < 2 || (n0 % 2) != 0 || (ndims == 2 && (n1 % 2) != 0)) return WL_EINVAL_SIZE;
+        if (n0 < 2 || (n0 % 2) != 0 || (ndims >= 2 && (n1 % 2) != 0) || (ndims == 3 && (n2 % 2) != 0)) return WL_EINVAL_SIZE;
         rc = filter_fwd_levels<T>(tw, true, ctx->cu_count, ctx->path, st, b1, XT, x, taps, 1, &ctx->last_kernel, &ctx->last_hip);
         if (rc != WL_OK) return rc;
         const int64_t lo = (int64_t)llround((double)n0 / 2 + 1) - 1, hi = n0;        // detailrange(n0, 1), 0-based half open
@@ -928,7 +946,7 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
     if (pns == 1) {
         BoxSpec b1;
         b1.nd = ndims; b1.nt = ndims;
-        b1.dims[0] = n0; b1.dims[1] = n1; b1.dims[2] = 1;
+        b1.dims[0] = n0; b1.dims[1] = n1; b1.dims[2] = n2;
         b1.full = dense_strides(b1.dims);
         const T *coef_src = x;
         if (L > 0) {
@@ -957,19 +975,28 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
     bb.nd = ndims + 1; bb.nt = ndims;
     bb.dims[0] = n0; bb.dims[1] = (ndims == 2) ? n1 : 0; bb.dims[2] = 1;
     TiGeom g;
-    g.n0 = n0; g.n1 = n1; g.N = N; g.nsp0 = nsp0; g.nsp1 = nsp1;
+    g.n0 = n0; g.n1 = n1; g.n2 = n2; g.N = N; g.nsp0 = nsp0; g.nsp1 = nsp1; g.nsp2 = nsp2;
     const unsigned gxs = (unsigned)((n0 / 4 + 255) / 256 > 0 ? ((n0 / 4 + 255) / 256 > 64 ? 64 : (n0 / 4 + 255) / 256) : 1);
+    // columns (i1, i2) of the shift / accumulate kernels: grid-stride beyond 65535 workgroups along y
+    const int64_t ncol = n1 * n2;
+    const unsigned gy_shift = (unsigned)((ncol + 7) / 8 > 65535 ? 65535 : (ncol + 7) / 8), gy_acc = (unsigned)(ncol > 65535 ? 65535 : ncol);
     if (virt) {
         TiGeom gr = g;                                      // spins 0 .. nsp0-1 shift dim 1 only
         gr.nsp1 = 1; gr.b0 = 0;
-        hipLaunchKernelGGL((k_ti_shift<T>), dim3(gxs, (unsigned)((n1 + 7) / 8), (unsigned)nsp0), dim3(256), 0, st, ZR, x, gr);
+        hipLaunchKernelGGL((k_ti_shift<T>), dim3(gxs, gy_shift, (unsigned)nsp0), dim3(256), 0, st, ZR, x, gr);
     }
     for (int64_t b0 = 0; b0 < pns; b0 += B) {
         const int64_t nb = (pns - b0 < B) ? (pns - b0) : B;
         g.b0 = b0;
         if (ndims == 2) { bb.dims[2] = nb; }
         else { bb.dims[1] = nb; bb.dims[2] = 1; }
-        bb.full = dense_strides(bb.dims);
+        bb.full = dense_strides(bb.dims);                   // (cubes: the batch of volumes below, not a box)
+        auto fwd_group = [&](T *dst, const T *src) -> int {
+            if (ndims == 3)
+                return filter_fwd_levels_vols<T>(tw, true, ctx->cu_count, ctx->path, st, vdims, nb, N, N, dst, src, taps, L, &ctx->last_kernel,
+                                                 &ctx->last_hip);
+            return filter_fwd_levels<T>(tw, true, ctx->cu_count, ctx->path, st, bb, dst, src, taps, L, &ctx->last_kernel, &ctx->last_hip);
+        };
         bool shifted = false, thresholded_l1 = false;
         int64_t th_c0 = n0, th_c1 = n1;                      // what the level kernels left unthresholded: the low corner of every plane
         if (virt) {
@@ -990,9 +1017,9 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
             thresholded_l1 = shifted && fuse_th;
         }
         if (!shifted) {                                     // (materialised shifted planes: every other case)
-            hipLaunchKernelGGL((k_ti_shift<T>), dim3(gxs, (unsigned)((n1 + 7) / 8), (unsigned)nb), dim3(256), 0, st, Z, x, g);
+            hipLaunchKernelGGL((k_ti_shift<T>), dim3(gxs, gy_shift, (unsigned)nb), dim3(256), 0, st, Z, x, g);
             if (L > 0) {
-                rc = filter_fwd_levels<T>(tw, true, ctx->cu_count, ctx->path, st, bb, XT, Z, taps, L, &ctx->last_kernel, &ctx->last_hip);
+                rc = fwd_group(XT, Z);
                 if (rc != WL_OK) return rc;
             }
         }
@@ -1009,10 +1036,11 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
         }
         if (L > 0) {
             const char *kn = nullptr;
-            rc = filter_inv_levels<T>(tw, true, ctx->cu_count, ctx->path, st, bb, Z, XT, taps, L, &kn, &ctx->last_hip);
+            rc = ndims == 3 ? filter_inv_levels_vols<T>(tw, true, ctx->cu_count, ctx->path, st, vdims, nb, N, N, Z, XT, taps, L, &kn, &ctx->last_hip)
+                            : filter_inv_levels<T>(tw, true, ctx->cu_count, ctx->path, st, bb, Z, XT, taps, L, &kn, &ctx->last_hip);
             if (rc != WL_OK) return rc;
         }
-        hipLaunchKernelGGL((k_ti_accumulate<T>), dim3(gxs, (unsigned)n1), dim3(256), 0, st, y, Z, g, nb, b0 == 0 ? 1 : 0);
+        hipLaunchKernelGGL((k_ti_accumulate<T>), dim3(gxs, gy_acc), dim3(256), 0, st, y, Z, g, nb, b0 == 0 ? 1 : 0);
     }
     hipLaunchKernelGGL((k_rmul<T>), dim3(ext_blocks(N, 4, ctx->cu_count)), dim3(EXT_THREADS), 0, st, y, N, 1.0 / (double)pns, vec_ok16(y));
     WL_HIP(ctx, hipGetLastError());
@@ -1073,7 +1101,7 @@ int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
         }
     }
     TiGeom g;
-    g.n0 = n0; g.n1 = n1; g.N = N; g.nsp0 = nsp0; g.nsp1 = nsp1;
+    g.n0 = n0; g.n1 = n1; g.n2 = 1; g.N = N; g.nsp0 = nsp0; g.nsp1 = nsp1; g.nsp2 = 1;
     const unsigned gxs = (unsigned)((n0 / 4 + 255) / 256 > 0 ? ((n0 / 4 + 255) / 256 > 64 ? 64 : (n0 / 4 + 255) / 256) : 1);
     auto transform = [&](T *dst, const T *src, int64_t nb, const LiftScheme<T> &sc, int fw) -> int {
         if (ndims == 1) {                                    // nb signals = nb lines of one batched call
@@ -1232,7 +1260,7 @@ int wl_denoise_ti_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndi
     if (rc != WL_OK) return rc;
     WL_SCOPE(ctx);
     if (!y || !x || !dims || !qmf || !nspin) return WL_EINVAL_ARG;
-    if (ndims < 1 || ndims > 2) return WL_EDIMS;
+    if (ndims < 1 || ndims > 3) return WL_EDIMS;
     if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
     // threshold!(xt, dnt.th, sigma*t) (denoising.jl:58) has methods for Hard / Soft / Semisoft / Stein only (threshold_main.jl:21-80)
     if (th < WL_TH_HARD || th > WL_TH_STEIN) return WL_EINVAL_ARG;
@@ -1241,7 +1269,9 @@ int wl_denoise_ti_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndi
     if (sigma_host != sigma_host || (sigma_host >= 0 && !(sigma_host * t_unit >= 0))) return WL_EINVAL_ARG;
     for (int d = 0; d < ndims; ++d)
         if (dims[d] < 1 || nspin[d] < 1) return WL_EDIMS;
-    if (ndims == 2 && dims[0] != dims[1]) return WL_EINVAL_CUBE;            // iscube(x) (denoising.jl:29)
+    if (ndims >= 2 && dims[0] != dims[1]) return WL_EINVAL_CUBE;            // iscube(x) (denoising.jl:29)
+    if (ndims == 3 && dims[0] != dims[2]) return WL_EINVAL_CUBE;
+    if (ndims == 3 && dims[0] >= ((int64_t)1 << 20)) return WL_EINVAL_SIZE; // (32-bit extents and column counts in the shift kernels)
     if (ndims == 2 && dims[1] > 65535) return WL_EINVAL_SIZE;               // (one grid row per column in the shift kernels)
     if (L < 0) return WL_EINVAL_L;
     for (int d = 0; d < ndims; ++d)
@@ -1251,7 +1281,9 @@ int wl_denoise_ti_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndi
     hipStream_t st = (hipStream_t)stream;
     rc = dtype == WL_F32 ? denoise_ti_impl<float>(ctx, st, (float *)y, (const float *)x, ndims, dims, qmf, flen, L, th, t_unit, nspin, sigma_host)
                          : denoise_ti_impl<double>(ctx, st, (double *)y, (const double *)x, ndims, dims, qmf, flen, L, th, t_unit, nspin, sigma_host);
-    if (rc == WL_OK) ctx->last_kernel = "denoise_ti_batch";
+    int64_t pns = 1;
+    for (int d = 0; d < ndims; ++d) pns *= nspin[d];
+    if (rc == WL_OK && pns > 1) ctx->last_kernel = "denoise_ti_batch";       // (one spin: "denoise_one_spin", set by the branch that ran)
     return rc;
 }
 

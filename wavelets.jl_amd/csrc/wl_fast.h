@@ -139,12 +139,13 @@ bool inv2d_tile2_ok(int F, int64_t M, int64_t N);
 template <typename T>
 hipError_t inv2d_tile2_launch(hipStream_t st, const Taps<T> &taps, const T *x, int64_t ldx, const T *ll, int64_t ldl, T *dst, int64_t ldd,
                               int M, int N);
-// 3-D boxes of <= 4096 elements: all remaining forward levels / the deepest inverse levels in one workgroup (wl_tail.hip)
+// 3-D boxes of <= 4096 elements: all remaining forward levels / the deepest inverse levels in one workgroup (wl_tail.hip);
+// nvol (<= 65535) independent volumes, one workgroup each, volume i at element offset i * src_item / i * y_item
 template <typename T>
 bool tail3_ok(int F, int64_t n0, int64_t n1, int64_t n2, int nlev);
 template <typename T>
 hipError_t launch_tail3(hipStream_t st, const Taps<T> &taps, int fw, const T *src, int64_t s1, int64_t s2, T *y, int64_t y1, int64_t y2,
-                        int n0, int n1, int n2, int nlev);
+                        int n0, int n1, int n2, int nlev, int nvol = 1, int64_t src_item = 0, int64_t y_item = 0);
 template <typename T>
 bool tail2_inv_ok(int F, int nt, int64_t n0, int64_t n1, int nlev, const T *out, int64_t out_item);
 template <typename T>
@@ -194,27 +195,40 @@ template <typename T>
 int lifting_3d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, T *y, const T *x,
                     const LiftScheme<T> &sc, int L, int fw, int *handled, const char **kernel_name, int *hip_err);
 
+// A batch of independent volumes for the one-launch 3-D level kernels (wl_fwd3d.hip, wl_inv3d.hip, wl_level3.hip): nvol (<= 65535)
+// volumes per launch, volume i at element offset i * bs_src of the source, i * bs_dst of the destination and i * bs_ll of the dense
+// approximation buffer.  The default is today's single-volume launch.
+struct VolBatch { int64_t nvol, bs_src, bs_dst, bs_ll; };
+
 // One forward 3-D level in one pass over HBM (wl_fwd3d.hip): even F <= 8, lines of 128 ... 1024, both element types.
 template <typename T>
 bool fwd3d_one_ok(int F, const T *cur, int64_t c1, int64_t c2, const T *y, int64_t y1, int64_t y2, const T *ll, const int64_t n[3], bool any_tier = false);
 template <typename T>
 hipError_t fwd3d_one_launch(hipStream_t st, const Taps<T> &taps, const T *cur, int64_t c1, int64_t c2, T *y, int64_t y1, int64_t y2,
-                            T *ll, const int64_t n[3], int cu_count);
+                            T *ll, const int64_t n[3], int cu_count, const VolBatch &vb = VolBatch{1, 0, 0, 0});
 
 // One inverse 3-D level in one pass over HBM (wl_inv3d.hip): even F <= 8, lines of 32 ... 1024, both element types.
 template <typename T>
 bool inv3d_one_ok(int F, const T *x, int64_t x1, int64_t x2, const T *ll, const T *out, int64_t o1, int64_t o2, const int64_t n[3], bool any_tier = false);
 template <typename T>
 hipError_t inv3d_one_launch(hipStream_t st, const Taps<T> &taps, const T *x, int64_t x1, int64_t x2, const T *ll, T *out, int64_t o1, int64_t o2,
-                            const int64_t n[3], int cu_count);
+                            const int64_t n[3], int cu_count, const VolBatch &vb = VolBatch{1, 0, 0, 0});
 
 // One small 3-D level (4096 < elements <= 2^18) in one launch, forward or inverse (wl_level3.hip): LDS blocks of 4^3 / 8^3 pairs.
 template <typename T>
 bool level3_lds_ok(int F, const int64_t n[3], bool any_tier = false);
 template <typename T>
 hipError_t level3_lds_launch(hipStream_t st, const Taps<T> &taps, int fw, const T *src, int64_t s1, int64_t s2, T *dst, int64_t d1, int64_t d2,
-                             const T *llr, T *llw, const int64_t n[3]);
+                             const T *llr, T *llw, const int64_t n[3], const VolBatch &vb = VolBatch{1, 0, 0, 0});
 
+// Which family fast3d_fwd_level / fast3d_inv_level take for a level -- 0: not eligible, 1: k_fwd3d_one / k_inv3d_one, 2: k_level3_lds,
+// 3: the single-axis passes (wl_axis.hip).
+template <typename T>
+int fast3d_fwd_tier(int F, const T *cur, int64_t c1, int64_t c2, const T *y, int64_t y1, int64_t y2, const T *ll, const int64_t n[3],
+                    const T *T0, const T *T1);
+template <typename T>
+int fast3d_inv_tier(int F, const T *x, int64_t x1, int64_t x2, const T *llsrc, const T *out, int64_t o1, int64_t o2, const int64_t n[3],
+                    const T *T0, const T *T1);
 // One 3-D filter-bank level assembled from single-axis streaming passes (wl_axis.hip); false = not eligible.
 template <typename T>
 bool fast3d_fwd_level(hipStream_t st, const Taps<T> &taps, const T *cur, int64_t c1, int64_t c2, T *y, int64_t y1, int64_t y2,
@@ -239,5 +253,22 @@ template <typename T> bool wpt_inv_multi_ok(int F, int64_t n, int64_t nj, int NL
 template <typename T> hipError_t wpt_inv_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask = nullptr);
 template <typename T> bool wpt_tail_ok(int F, int64_t n, int64_t nj, int ndepth);
 template <typename T> hipError_t wpt_tail_launch(hipStream_t st, const Taps<T> &taps, int fw, const T *src, T *dst, int64_t n, int64_t nj, int ndepth, const uint8_t *mask = nullptr);
+
+// ---- a batch of independent volumes (wl_batch3d.hip) ----
+// All L levels of the 3-D transform of nvol (<= 65535) dense boxes dims[0] x dims[1] x dims[2], volume i at element offset i * xs of x
+// and i * ys of y.  A level that k_tail3, k_level3_lds or k_fwd3d_one / k_inv3d_one accepts (the choice order of the single-volume
+// loops) is ONE launch over all volumes; every other level runs volume after volume through the single-volume level code.  Context
+// option WL_BATCH3_LOOP != 0, path 1, odd or > 10-tap filters and strides that leave a volume base off a 16-byte boundary send the
+// whole transform through the single-volume loops, volume after volume.  Bit-identical either way.
+// Workspace (elements): ws_vols_elems(N, nvol) -- the approximation ping-pong per volume, 2 * (nvol * (N >> 3) + 64), plus one
+// volume's T0 / T1 / W (3 N + 64) when ws_gen; WL_RETRY_GEN when a level needs those and ws_gen is false.
+inline size_t ws_vols_ab_elems(int64_t N, int64_t nvol) { return 2 * (size_t)(nvol * (N >> 3) + 64); }
+inline size_t ws_vols_elems(int64_t N, int64_t nvol) { return ws_vols_ab_elems(N, nvol) + (size_t)(3 * N + 64); }
+template <typename T>
+int filter_fwd_levels_vols(void *ws, bool ws_gen, int cu_count, int path, hipStream_t st, const int64_t dims[3], int64_t nvol, int64_t xs,
+                           int64_t ys, T *y, const T *x, const Taps<T> &taps, int L, const char **kernel_name, int *hip_err);
+template <typename T>
+int filter_inv_levels_vols(void *ws, bool ws_gen, int cu_count, int path, hipStream_t st, const int64_t dims[3], int64_t nvol, int64_t xs,
+                           int64_t ys, T *y, const T *x, const Taps<T> &taps, int L, const char **kernel_name, int *hip_err);
 
 }  // namespace wl

@@ -44,6 +44,12 @@ struct Fwd3DArgs {
     int n0, n1, n2;
     int TJ;                                // owned dim-2 columns per segment (multiple of 8)
     int nseg, ntile;
+    // a batch of volumes: the grid is nvol slots of `slot` workgroups (one volume: slot = nwg = the grid; several: nwg rounded up to a
+    // multiple of 8, so that workgroup b of every volume lands on XCD b & 7 as it does for one volume -- the volume is the
+    // slowest-varying part of the index and the tile -> XCD mapping inside a volume stays what it is); volume v at element offsets
+    // v * bs_src / bs_y / bs_ll
+    uint32_t nwg, slot;
+    int64_t bs_src, bs_y, bs_ll;
     TapsF<T, F> tp;
 };
 
@@ -140,7 +146,11 @@ __global__ void __launch_bounds__(64 * NW, 2) k_fwd3d_one(Fwd3DArgs<T, F> a)
     constexpr bool multi = NW > 1;
     const int lp = (int)threadIdx.x;
     // XCD b & 7 owns a contiguous range of tiles (all their segments): tiles that share raw planes share an L2
-    const uint32_t b = blockIdx.x, nwg = gridDim.x;
+    const uint32_t vol = blockIdx.x / a.slot, b = blockIdx.x - vol * a.slot, nwg = a.nwg;
+    if (b >= nwg) return;                                       // (the padding of a slot: whole workgroups, before any barrier)
+    a.src += (int64_t)vol * a.bs_src;
+    a.y += (int64_t)vol * a.bs_y;
+    if (a.ll != nullptr) a.ll += (int64_t)vol * a.bs_ll;
     const uint32_t q8 = nwg >> 3, r8 = nwg & 7, xcd = b & 7;
     const uint32_t first = xcd * q8 + (xcd < r8 ? xcd : r8);
     const uint32_t logical = first + (b >> 3);
@@ -361,8 +371,12 @@ template bool fwd3d_one_ok<double>(int, const double *, int64_t, int64_t, const 
 
 // (hipFuncSetAttribute(MaxDynamicSharedMemorySize) is sticky per (function, device): once)
 template <typename T, int RPL, int F, int NW>
-static hipError_t launch_fwd3d_inst(hipStream_t st, unsigned nwg, const Fwd3DArgs<T, F> &a)
+static hipError_t launch_fwd3d_inst(hipStream_t st, unsigned nwg, const Fwd3DArgs<T, F> &a0, const VolBatch &vb)
 {
+    Fwd3DArgs<T, F> a = a0;
+    a.nwg = nwg; a.slot = vb.nvol > 1 ? ((nwg + 7u) & ~7u) : nwg;
+    a.bs_src = vb.bs_src; a.bs_y = vb.bs_dst; a.bs_ll = vb.bs_ll;
+    if ((uint64_t)a.slot * (uint64_t)vb.nvol >= ((uint64_t)1 << 31)) return hipErrorInvalidValue;
     const size_t shmem = (size_t)fwd3d_xbufs(F) * 4 * (64 * RPL * NW + 16) * 2 * sizeof(T);
     static thread_local int attr_dev[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
     int dev = 0;
@@ -374,13 +388,13 @@ static hipError_t launch_fwd3d_inst(hipStream_t st, unsigned nwg, const Fwd3DArg
         if (e != hipSuccess) return e;
         for (int i = 0; i < 8; ++i) if (attr_dev[i] < 0) { attr_dev[i] = dev; break; }
     }
-    hipLaunchKernelGGL((k_fwd3d_one<T, RPL, F, NW>), dim3(nwg), dim3(64 * NW), shmem, st, a);
+    hipLaunchKernelGGL((k_fwd3d_one<T, RPL, F, NW>), dim3(a.slot * (unsigned)vb.nvol), dim3(64 * NW), shmem, st, a);
     return hipGetLastError();
 }
 
 template <typename T, int F>
 static hipError_t launch_fwd3d_f(hipStream_t st, const Taps<T> &taps, const T *cur, int64_t c1, int64_t c2, T *y, int64_t y1,
-                                 int64_t y2, T *ll, const int64_t n[3], int cu_count)
+                                 int64_t y2, T *ll, const int64_t n[3], int cu_count, const VolBatch &vb)
 {
     Fwd3DArgs<T, F> a;
     a.src = cur; a.c1 = c1; a.c2 = c2; a.y = y; a.y1 = y1; a.y2 = y2; a.ll = ll;
@@ -405,45 +419,46 @@ static hipError_t launch_fwd3d_f(hipStream_t st, const Taps<T> &taps, const T *c
     const unsigned nwg = (unsigned)(a.ntile * a.nseg);
     if constexpr (F == 10) {
         if constexpr (sizeof(T) == 4) {
-            if (W == 1) return launch_fwd3d_inst<T, 2, F, 1>(st, nwg, a);
-            if (W == 2) return launch_fwd3d_inst<T, 2, F, 2>(st, nwg, a);
-            if (W == 4) return launch_fwd3d_inst<T, 2, F, 4>(st, nwg, a);
-            return launch_fwd3d_inst<T, 2, F, 8>(st, nwg, a);
+            if (W == 1) return launch_fwd3d_inst<T, 2, F, 1>(st, nwg, a, vb);
+            if (W == 2) return launch_fwd3d_inst<T, 2, F, 2>(st, nwg, a, vb);
+            if (W == 4) return launch_fwd3d_inst<T, 2, F, 4>(st, nwg, a, vb);
+            return launch_fwd3d_inst<T, 2, F, 8>(st, nwg, a, vb);
         } else {
             return hipErrorInvalidValue;
         }
     } else if constexpr (sizeof(T) == 4) {
-        if (rpl == 2 && W == 1) return launch_fwd3d_inst<T, 2, F, 1>(st, nwg, a);
-        if (rpl == 2 && W == 2) return launch_fwd3d_inst<T, 2, F, 2>(st, nwg, a);
-        if (rpl == 2 && W == 4) return launch_fwd3d_inst<T, 2, F, 4>(st, nwg, a);
-        if (rpl == 2) return launch_fwd3d_inst<T, 2, F, 8>(st, nwg, a);
-        if (W == 1) return launch_fwd3d_inst<T, 4, F, 1>(st, nwg, a);
-        if (W == 2) return launch_fwd3d_inst<T, 4, F, 2>(st, nwg, a);
-        return launch_fwd3d_inst<T, 4, F, 4>(st, nwg, a);
+        if (rpl == 2 && W == 1) return launch_fwd3d_inst<T, 2, F, 1>(st, nwg, a, vb);
+        if (rpl == 2 && W == 2) return launch_fwd3d_inst<T, 2, F, 2>(st, nwg, a, vb);
+        if (rpl == 2 && W == 4) return launch_fwd3d_inst<T, 2, F, 4>(st, nwg, a, vb);
+        if (rpl == 2) return launch_fwd3d_inst<T, 2, F, 8>(st, nwg, a, vb);
+        if (W == 1) return launch_fwd3d_inst<T, 4, F, 1>(st, nwg, a, vb);
+        if (W == 2) return launch_fwd3d_inst<T, 4, F, 2>(st, nwg, a, vb);
+        return launch_fwd3d_inst<T, 4, F, 4>(st, nwg, a, vb);
     } else {
-        if (W == 1) return launch_fwd3d_inst<T, 2, F, 1>(st, nwg, a);
-        if (W == 2) return launch_fwd3d_inst<T, 2, F, 2>(st, nwg, a);
-        if (W == 4) return launch_fwd3d_inst<T, 2, F, 4>(st, nwg, a);
-        return launch_fwd3d_inst<T, 2, F, 8>(st, nwg, a);
+        if (W == 1) return launch_fwd3d_inst<T, 2, F, 1>(st, nwg, a, vb);
+        if (W == 2) return launch_fwd3d_inst<T, 2, F, 2>(st, nwg, a, vb);
+        if (W == 4) return launch_fwd3d_inst<T, 2, F, 4>(st, nwg, a, vb);
+        return launch_fwd3d_inst<T, 2, F, 8>(st, nwg, a, vb);
     }
 }
 
 template <typename T>
 hipError_t fwd3d_one_launch(hipStream_t st, const Taps<T> &taps, const T *cur, int64_t c1, int64_t c2, T *y, int64_t y1, int64_t y2,
-                            T *ll, const int64_t n[3], int cu_count)
+                            T *ll, const int64_t n[3], int cu_count, const VolBatch &vb)
 {
+    if (vb.nvol < 1 || vb.nvol > 65535) return hipErrorInvalidValue;
     switch (taps.F) {
-    case 2: return launch_fwd3d_f<T, 2>(st, taps, cur, c1, c2, y, y1, y2, ll, n, cu_count);
-    case 4: return launch_fwd3d_f<T, 4>(st, taps, cur, c1, c2, y, y1, y2, ll, n, cu_count);
-    case 6: return launch_fwd3d_f<T, 6>(st, taps, cur, c1, c2, y, y1, y2, ll, n, cu_count);
-    case 8: return launch_fwd3d_f<T, 8>(st, taps, cur, c1, c2, y, y1, y2, ll, n, cu_count);
-    case 10: return launch_fwd3d_f<T, 10>(st, taps, cur, c1, c2, y, y1, y2, ll, n, cu_count);
+    case 2: return launch_fwd3d_f<T, 2>(st, taps, cur, c1, c2, y, y1, y2, ll, n, cu_count, vb);
+    case 4: return launch_fwd3d_f<T, 4>(st, taps, cur, c1, c2, y, y1, y2, ll, n, cu_count, vb);
+    case 6: return launch_fwd3d_f<T, 6>(st, taps, cur, c1, c2, y, y1, y2, ll, n, cu_count, vb);
+    case 8: return launch_fwd3d_f<T, 8>(st, taps, cur, c1, c2, y, y1, y2, ll, n, cu_count, vb);
+    case 10: return launch_fwd3d_f<T, 10>(st, taps, cur, c1, c2, y, y1, y2, ll, n, cu_count, vb);
     default: return hipErrorInvalidValue;
     }
 }
 template hipError_t fwd3d_one_launch<float>(hipStream_t, const Taps<float> &, const float *, int64_t, int64_t, float *, int64_t, int64_t, float *,
-                                            const int64_t[3], int);
+                                            const int64_t[3], int, const VolBatch &);
 template hipError_t fwd3d_one_launch<double>(hipStream_t, const Taps<double> &, const double *, int64_t, int64_t, double *, int64_t, int64_t, double *,
-                                             const int64_t[3], int);
+                                             const int64_t[3], int, const VolBatch &);
 
 }  // namespace wl

@@ -36,6 +36,10 @@ struct Inv3DArgs {
     int n0, n1, n2;                        // output extents of the level
     int TK;                                // output plane pairs per segment (multiple of SH + 1)
     int nseg, ntile;
+    // a batch of volumes, as in k_fwd3d_one: nvol slots of `slot` workgroups (one volume: slot = nwg = the grid; several: nwg rounded
+    // up to a multiple of 8, which keeps workgroup b of every volume on XCD b & 7), volume v at element offsets v * bs_x / bs_ll / bs_out
+    uint32_t nwg, slot;
+    int64_t bs_x, bs_ll, bs_out;
     TapsF<T, F> tp;
 };
 
@@ -80,7 +84,11 @@ __global__ void __launch_bounds__(64 * NW, 2) k_inv3d_one(Inv3DArgs<T, F> a)
 
     constexpr bool multi = NW > 1;
     const int lp = (int)threadIdx.x;
-    const uint32_t b = blockIdx.x, nwg = gridDim.x;
+    const uint32_t vol = blockIdx.x / a.slot, b = blockIdx.x - vol * a.slot, nwg = a.nwg;
+    if (b >= nwg) return;                                       // (the padding of a slot: whole workgroups, before any barrier)
+    a.x += (int64_t)vol * a.bs_x;
+    a.out += (int64_t)vol * a.bs_out;
+    if (a.ll != nullptr) a.ll += (int64_t)vol * a.bs_ll;
     const uint32_t q8 = nwg >> 3, r8 = nwg & 7, xcd = b & 7;
     const uint32_t first = xcd * q8 + (xcd < r8 ? xcd : r8);
     const uint32_t logical = first + (b >> 3);
@@ -310,8 +318,12 @@ template bool inv3d_one_ok<float>(int, const float *, int64_t, int64_t, const fl
 template bool inv3d_one_ok<double>(int, const double *, int64_t, int64_t, const double *, const double *, int64_t, int64_t, const int64_t[3], bool);
 
 template <typename T, int RPL, int F, int NW>
-static hipError_t launch_inv3d_inst(hipStream_t st, unsigned nwg, const Inv3DArgs<T, F> &a)
+static hipError_t launch_inv3d_inst(hipStream_t st, unsigned nwg, const Inv3DArgs<T, F> &a0, const VolBatch &vb)
 {
+    Inv3DArgs<T, F> a = a0;
+    a.nwg = nwg; a.slot = vb.nvol > 1 ? ((nwg + 7u) & ~7u) : nwg;
+    a.bs_x = vb.bs_src; a.bs_out = vb.bs_dst; a.bs_ll = vb.bs_ll;
+    if ((uint64_t)a.slot * (uint64_t)vb.nvol >= ((uint64_t)1 << 31)) return hipErrorInvalidValue;
     constexpr int SH = (F - 2) / 2, NC = SH + 2, CP = 4 + 64 * RPL * NW + 8;
     const size_t shmem = (size_t)2 * NC * CP * sizeof(T);
     static thread_local int attr_dev[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
@@ -324,13 +336,13 @@ static hipError_t launch_inv3d_inst(hipStream_t st, unsigned nwg, const Inv3DArg
         if (e != hipSuccess) return e;
         for (int i = 0; i < 8; ++i) if (attr_dev[i] < 0) { attr_dev[i] = dev; break; }
     }
-    hipLaunchKernelGGL((k_inv3d_one<T, RPL, F, NW>), dim3(nwg), dim3(64 * NW), shmem, st, a);
+    hipLaunchKernelGGL((k_inv3d_one<T, RPL, F, NW>), dim3(a.slot * (unsigned)vb.nvol), dim3(64 * NW), shmem, st, a);
     return hipGetLastError();
 }
 
 template <typename T, int F>
 static hipError_t launch_inv3d_f(hipStream_t st, const Taps<T> &taps, const T *x, int64_t x1, int64_t x2, const T *ll, T *out, int64_t o1,
-                                 int64_t o2, const int64_t n[3], int cu_count)
+                                 int64_t o2, const int64_t n[3], int cu_count, const VolBatch &vb)
 {
     constexpr int R = (F - 2) / 2 + 1;
     Inv3DArgs<T, F> a;
@@ -353,35 +365,36 @@ static hipError_t launch_inv3d_f(hipStream_t st, const Taps<T> &taps, const T *x
     a.tp = shrink<T, F>(taps);
     const unsigned nwg = (unsigned)(a.ntile * a.nseg);
     if constexpr (sizeof(T) == 4) {
-        if (rpl == 2 && W == 1) return launch_inv3d_inst<T, 2, F, 1>(st, nwg, a);
-        if (rpl == 2 && W == 2) return launch_inv3d_inst<T, 2, F, 2>(st, nwg, a);
-        if (rpl == 2 && W == 4) return launch_inv3d_inst<T, 2, F, 4>(st, nwg, a);
-        if (rpl == 2) return launch_inv3d_inst<T, 2, F, 8>(st, nwg, a);
-        if (W == 1) return launch_inv3d_inst<T, 4, F, 1>(st, nwg, a);
-        if (W == 2) return launch_inv3d_inst<T, 4, F, 2>(st, nwg, a);
-        return launch_inv3d_inst<T, 4, F, 4>(st, nwg, a);
+        if (rpl == 2 && W == 1) return launch_inv3d_inst<T, 2, F, 1>(st, nwg, a, vb);
+        if (rpl == 2 && W == 2) return launch_inv3d_inst<T, 2, F, 2>(st, nwg, a, vb);
+        if (rpl == 2 && W == 4) return launch_inv3d_inst<T, 2, F, 4>(st, nwg, a, vb);
+        if (rpl == 2) return launch_inv3d_inst<T, 2, F, 8>(st, nwg, a, vb);
+        if (W == 1) return launch_inv3d_inst<T, 4, F, 1>(st, nwg, a, vb);
+        if (W == 2) return launch_inv3d_inst<T, 4, F, 2>(st, nwg, a, vb);
+        return launch_inv3d_inst<T, 4, F, 4>(st, nwg, a, vb);
     } else {
-        if (W == 1) return launch_inv3d_inst<T, 2, F, 1>(st, nwg, a);
-        if (W == 2) return launch_inv3d_inst<T, 2, F, 2>(st, nwg, a);
-        return launch_inv3d_inst<T, 2, F, 4>(st, nwg, a);
+        if (W == 1) return launch_inv3d_inst<T, 2, F, 1>(st, nwg, a, vb);
+        if (W == 2) return launch_inv3d_inst<T, 2, F, 2>(st, nwg, a, vb);
+        return launch_inv3d_inst<T, 2, F, 4>(st, nwg, a, vb);
     }
 }
 
 template <typename T>
 hipError_t inv3d_one_launch(hipStream_t st, const Taps<T> &taps, const T *x, int64_t x1, int64_t x2, const T *ll, T *out, int64_t o1, int64_t o2,
-                            const int64_t n[3], int cu_count)
+                            const int64_t n[3], int cu_count, const VolBatch &vb)
 {
+    if (vb.nvol < 1 || vb.nvol > 65535) return hipErrorInvalidValue;
     switch (taps.F) {
-    case 2: return launch_inv3d_f<T, 2>(st, taps, x, x1, x2, ll, out, o1, o2, n, cu_count);
-    case 4: return launch_inv3d_f<T, 4>(st, taps, x, x1, x2, ll, out, o1, o2, n, cu_count);
-    case 6: return launch_inv3d_f<T, 6>(st, taps, x, x1, x2, ll, out, o1, o2, n, cu_count);
-    case 8: return launch_inv3d_f<T, 8>(st, taps, x, x1, x2, ll, out, o1, o2, n, cu_count);
+    case 2: return launch_inv3d_f<T, 2>(st, taps, x, x1, x2, ll, out, o1, o2, n, cu_count, vb);
+    case 4: return launch_inv3d_f<T, 4>(st, taps, x, x1, x2, ll, out, o1, o2, n, cu_count, vb);
+    case 6: return launch_inv3d_f<T, 6>(st, taps, x, x1, x2, ll, out, o1, o2, n, cu_count, vb);
+    case 8: return launch_inv3d_f<T, 8>(st, taps, x, x1, x2, ll, out, o1, o2, n, cu_count, vb);
     default: return hipErrorInvalidValue;
     }
 }
 template hipError_t inv3d_one_launch<float>(hipStream_t, const Taps<float> &, const float *, int64_t, int64_t, const float *, float *, int64_t, int64_t,
-                                            const int64_t[3], int);
+                                            const int64_t[3], int, const VolBatch &);
 template hipError_t inv3d_one_launch<double>(hipStream_t, const Taps<double> &, const double *, int64_t, int64_t, const double *, double *, int64_t,
-                                             int64_t, const int64_t[3], int);
+                                             int64_t, const int64_t[3], int, const VolBatch &);
 
 }  // namespace wl

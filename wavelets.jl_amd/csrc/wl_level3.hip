@@ -23,6 +23,7 @@ struct Level3Args {
     const T *llr; T *llw;              // approximation octant, dense (h0, h1, h2): forward writes llw (or dst when null), inverse reads llr (or src)
     int n0, n1, n2;                    // extents of the level (inverse: of its OUTPUT)
     int nb0, nb1;                      // blocks along dim 1 / dim 2 (blockIdx.x = b0 + nb0 * (b1 + nb1 * b2))
+    int64_t bs_src, bs_dst, bs_ll;     // a batch of volumes: volume blockIdx.y at these element offsets of src / dst / llr, llw
     TapsF<T, F> tp;
 };
 
@@ -38,6 +39,10 @@ __global__ void __launch_bounds__(256) k_level3_lds(Level3Args<T, F> a)
     const int tid = threadIdx.x, nthr = blockDim.x;
     auto gq = [&](const int m) __attribute__((always_inline)) { return (m & 1) ? -a.tp.h[m] : a.tp.h[m]; };
 
+    a.src += (int64_t)blockIdx.y * a.bs_src;
+    a.dst += (int64_t)blockIdx.y * a.bs_dst;
+    if (a.llr != nullptr) a.llr += (int64_t)blockIdx.y * a.bs_ll;
+    if (a.llw != nullptr) a.llw += (int64_t)blockIdx.y * a.bs_ll;
     const int b = blockIdx.x;
     const int b0 = b % a.nb0, b1 = (b / a.nb0) % a.nb1, b2 = b / (a.nb0 * a.nb1);
     const int n0 = a.n0, n1 = a.n1, n2 = a.n2, h0 = n0 >> 1, h1 = n1 >> 1, h2 = n2 >> 1;
@@ -167,7 +172,7 @@ template bool level3_lds_ok<float>(int, const int64_t[3], bool);
 template bool level3_lds_ok<double>(int, const int64_t[3], bool);
 
 template <typename T, int F, int P, int FW>
-static hipError_t launch_level3_inst(hipStream_t st, const Level3Args<T, F> &a0, const int64_t n[3])
+static hipError_t launch_level3_inst(hipStream_t st, const Level3Args<T, F> &a0, const int64_t n[3], unsigned nvol)
 {
     constexpr int SH = (F - 2) / 2, E = FW ? (2 * P + F - 2) : 2 * (P + SH), Q = 2 * P;
     Level3Args<T, F> a = a0;
@@ -184,15 +189,16 @@ static hipError_t launch_level3_inst(hipStream_t st, const Level3Args<T, F> &a0,
         if (e != hipSuccess) return e;
         for (int i = 0; i < 8; ++i) if (attr_dev[i] < 0) { attr_dev[i] = dev; break; }
     }
-    hipLaunchKernelGGL((k_level3_lds<T, F, P, FW>), dim3(nwg), dim3(256), shmem, st, a);
+    hipLaunchKernelGGL((k_level3_lds<T, F, P, FW>), dim3(nwg, nvol), dim3(256), shmem, st, a);
     return hipGetLastError();
 }
 
 template <typename T, int F, int FW>
 static hipError_t launch_level3_f(hipStream_t st, const Taps<T> &taps, const T *src, int64_t s1, int64_t s2, T *dst, int64_t d1, int64_t d2,
-                                  const T *llr, T *llw, const int64_t n[3])
+                                  const T *llr, T *llw, const int64_t n[3], const VolBatch &vb)
 {
     Level3Args<T, F> a;
+    a.bs_src = vb.bs_src; a.bs_dst = vb.bs_dst; a.bs_ll = vb.bs_ll;
     a.src = src; a.s1 = s1; a.s2 = s2; a.dst = dst; a.d1 = d1; a.d2 = d2; a.llr = llr; a.llw = llw;
     a.n0 = (int)n[0]; a.n1 = (int)n[1]; a.n2 = (int)n[2]; a.nb0 = a.nb1 = 0;
     a.tp = shrink<T, F>(taps);
@@ -202,17 +208,18 @@ static hipError_t launch_level3_f(hipStream_t st, const Taps<T> &taps, const T *
     constexpr int E8 = FW ? (16 + F - 2) : 2 * (8 + (F - 2) / 2);
     constexpr bool fits8 = (size_t)(E8 * E8 * E8 + 16 * E8 * E8) * sizeof(T) <= 160 * 1024;      // (Float64, 10 taps: 184 KB)
     if constexpr (fits8) {
-        if (p8) return launch_level3_inst<T, F, 8, FW>(st, a, n);
+        if (p8) return launch_level3_inst<T, F, 8, FW>(st, a, n, (unsigned)vb.nvol);
     }
-    return launch_level3_inst<T, F, 4, FW>(st, a, n);
+    return launch_level3_inst<T, F, 4, FW>(st, a, n, (unsigned)vb.nvol);
 }
 
 template <typename T>
 hipError_t level3_lds_launch(hipStream_t st, const Taps<T> &taps, int fw, const T *src, int64_t s1, int64_t s2, T *dst, int64_t d1, int64_t d2,
-                             const T *llr, T *llw, const int64_t n[3])
+                             const T *llr, T *llw, const int64_t n[3], const VolBatch &vb)
 {
-#define WL_L3F(F_) case F_: return fw ? launch_level3_f<T, F_, 1>(st, taps, src, s1, s2, dst, d1, d2, llr, llw, n) \
-                                      : launch_level3_f<T, F_, 0>(st, taps, src, s1, s2, dst, d1, d2, llr, llw, n)
+    if (vb.nvol < 1 || vb.nvol > 65535) return hipErrorInvalidValue;
+#define WL_L3F(F_) case F_: return fw ? launch_level3_f<T, F_, 1>(st, taps, src, s1, s2, dst, d1, d2, llr, llw, n, vb) \
+                                      : launch_level3_f<T, F_, 0>(st, taps, src, s1, s2, dst, d1, d2, llr, llw, n, vb)
     switch (taps.F) {
     WL_L3F(2); WL_L3F(4); WL_L3F(6); WL_L3F(8); WL_L3F(10);
     default: return hipErrorInvalidValue;
@@ -220,8 +227,8 @@ hipError_t level3_lds_launch(hipStream_t st, const Taps<T> &taps, int fw, const 
 #undef WL_L3F
 }
 template hipError_t level3_lds_launch<float>(hipStream_t, const Taps<float> &, int, const float *, int64_t, int64_t, float *, int64_t, int64_t,
-                                             const float *, float *, const int64_t[3]);
+                                             const float *, float *, const int64_t[3], const VolBatch &);
 template hipError_t level3_lds_launch<double>(hipStream_t, const Taps<double> &, int, const double *, int64_t, int64_t, double *, int64_t, int64_t,
-                                              const double *, double *, const int64_t[3]);
+                                              const double *, double *, const int64_t[3], const VolBatch &);
 
 }  // namespace wl

@@ -409,12 +409,15 @@ struct Tail3Args {
     T *y; int64_t y1, y2;           // forward: coefficient array; inverse: result box
     int lg0, lg1, lg2;              // extents 2^lg (inverse: OUTPUT extents of the last level done here)
     int nlev;
+    int64_t src_item, y_item;       // per-blockIdx.x offsets (a batch of volumes: one workgroup each)
     TapsF<T, F> tp;
 };
 
 template <typename T, int F, int FW>
 __global__ void __launch_bounds__(512) k_tail3(Tail3Args<T, F> a)
 {
+    a.src += (int64_t)blockIdx.x * a.src_item;
+    a.y += (int64_t)blockIdx.x * a.y_item;
     constexpr int NW = (F == 2) ? 2 : 2 * F - 2, SH = (F - 2) / 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x, nthr = blockDim.x;
@@ -552,10 +555,11 @@ bool tail3_ok(int F, int64_t n0, int64_t n1, int64_t n2, int nlev)
 
 template <typename T, int F, int FW>
 static hipError_t launch_tail3_f(hipStream_t st, const Taps<T> &taps, const T *src, int64_t s1, int64_t s2, T *y, int64_t y1, int64_t y2,
-                                 int n0, int n1, int n2, int nlev)
+                                 int n0, int n1, int n2, int nlev, int nvol, int64_t src_item, int64_t y_item)
 {
     Tail3Args<T, F> a;
     a.src = src; a.s1 = s1; a.s2 = s2; a.y = y; a.y1 = y1; a.y2 = y2; a.nlev = nlev;
+    a.src_item = src_item; a.y_item = y_item;
     a.lg0 = a.lg1 = a.lg2 = 0;
     while ((1 << a.lg0) < n0) ++a.lg0;
     while ((1 << a.lg1) < n1) ++a.lg1;
@@ -566,17 +570,18 @@ static hipError_t launch_tail3_f(hipStream_t st, const Taps<T> &taps, const T *s
     const int threads = total >= 2048 ? 512 : (total >= 512 ? 256 : 64);
     hipError_t ea = tail2_lds_attr(reinterpret_cast<const void *>(&k_tail3<T, F, FW>), shmem);
     if (ea != hipSuccess) return ea;
-    hipLaunchKernelGGL((k_tail3<T, F, FW>), dim3(1), dim3(threads), shmem, st, a);
+    hipLaunchKernelGGL((k_tail3<T, F, FW>), dim3((unsigned)nvol), dim3(threads), shmem, st, a);
     return hipGetLastError();
 }
 
 template <typename T>
 hipError_t launch_tail3(hipStream_t st, const Taps<T> &taps, int fw, const T *src, int64_t s1, int64_t s2, T *y, int64_t y1, int64_t y2,
-                        int n0, int n1, int n2, int nlev)
+                        int n0, int n1, int n2, int nlev, int nvol, int64_t src_item, int64_t y_item)
 {
+    if (nvol < 1 || nvol > 65535) return hipErrorInvalidValue;
 #define WL_T3(FF_)                                                                                                        \
-    case FF_: return fw ? launch_tail3_f<T, FF_, 1>(st, taps, src, s1, s2, y, y1, y2, n0, n1, n2, nlev)                   \
-                        : launch_tail3_f<T, FF_, 0>(st, taps, src, s1, s2, y, y1, y2, n0, n1, n2, nlev);
+    case FF_: return fw ? launch_tail3_f<T, FF_, 1>(st, taps, src, s1, s2, y, y1, y2, n0, n1, n2, nlev, nvol, src_item, y_item) \
+                        : launch_tail3_f<T, FF_, 0>(st, taps, src, s1, s2, y, y1, y2, n0, n1, n2, nlev, nvol, src_item, y_item);
     switch (taps.F) {
         WL_T3(2) WL_T3(4) WL_T3(6) WL_T3(8) WL_T3(10)
     default: return hipErrorInvalidValue;
@@ -586,9 +591,9 @@ hipError_t launch_tail3(hipStream_t st, const Taps<T> &taps, int fw, const T *sr
 template bool tail3_ok<float>(int, int64_t, int64_t, int64_t, int);
 template bool tail3_ok<double>(int, int64_t, int64_t, int64_t, int);
 template hipError_t launch_tail3<float>(hipStream_t, const Taps<float> &, int, const float *, int64_t, int64_t, float *, int64_t, int64_t, int, int,
-                                        int, int);
+                                        int, int, int, int64_t, int64_t);
 template hipError_t launch_tail3<double>(hipStream_t, const Taps<double> &, int, const double *, int64_t, int64_t, double *, int64_t, int64_t, int,
-                                         int, int, int);
+                                         int, int, int, int, int64_t, int64_t);
 
 template bool tail2_ok<float>(int, int, int64_t, int64_t, int, int);
 template bool tail2_ok<double>(int, int, int64_t, int64_t, int, int);

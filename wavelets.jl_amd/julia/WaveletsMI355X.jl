@@ -240,6 +240,20 @@ for (f, fw) in ((:dwt_batch, true), (:idwt_batch, false))
     end
 end
 
+# ---- a batch of independent volumes: x[:, :, :, i] -> dwt(x[:, :, :, i], filter, L), every level of the one-launch 3-D kernels ONE
+#      launch over all volumes (orthogonal filters only: there is no batched lifting transform of volumes) ----
+for (f, fw) in ((:dwt_batch, true), (:idwt_batch, false))
+    @eval function $f(x::ROCArray{T,4}, filter::OrthoFilter,
+                      L::Integer=minimum(Util.maxtransformlevels(size(x, d)) for d in 1:3)) where {T<:Union{Float32,Float64}}
+        y = similar(x)
+        GC.@preserve y x check(ccall((:wl_dwt_filter_batch3, LIB), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Int64, Int64, Ptr{Float64}, Cint, Cint, Cint, Ptr{Cvoid}),
+                    ctx(), DT[T], pointer(y), pointer(x), Int64[size(x, 1), size(x, 2), size(x, 3)], size(x, 4),
+                    size(x, 1) * size(x, 2) * size(x, 3), filter.qmf, length(filter.qmf), L, $fw, stream()))
+        return y
+    end
+end
+
 # the same for a lifting scheme (square images only, as the reference's 2-D lifting transform: transforms_lifting.jl:131-132)
 for (f, fw) in ((:dwt_batch, true), (:idwt_batch, false))
     @eval function $f(x::ROCArray{T,3}, scheme::GLS,
@@ -360,7 +374,7 @@ end
 
 # ---- denoise, translation-invariant branch (denoising.jl:36-67) as one device-resident batch ----------------------
 # The generic method of the reference already works on ROCArrays through the methods above (one spin at a time, a host
-# round trip for sigma).  For orthogonal filters on vectors and square matrices this method runs all prod(nspin) spins
+# round trip for sigma).  For orthogonal filters on vectors, square matrices and cubes this method runs all prod(nspin) spins
 # as one batch and keeps sigma on the device; other argument combinations fall through to the generic method.
 using Wavelets.Threshold: DNFT, VisuShrink, noisest
 function Threshold.denoise(x::ROCArray{T,N}, wt::OrthoFilter=Threshold.DEFAULT_WAVELET;
@@ -370,7 +384,7 @@ function Threshold.denoise(x::ROCArray{T,N}, wt::OrthoFilter=Threshold.DEFAULT_W
     # only the reference's own TI branch: threshold!(xt, th, t) exists for Hard / Soft / Semisoft / Stein (Pos / Neg take no t:
     # the generic method raises its MethodError); matrices need one nspin entry per dimension
     nspt = nspin isa Int ? (nspin,) : nspin
-    if !(TI && (N == 1 || (N == 2 && length(nspt) == 2)) && get(THCODE, typeof(dnt.th), Cint(9)) <= 3)
+    if !(TI && (N == 1 || (N == 2 && length(nspt) == 2) || (N == 3 && length(nspt) == 3)) && get(THCODE, typeof(dnt.th), Cint(9)) <= 3)
         return invoke(Threshold.denoise, Tuple{AbstractArray,Union{Wavelets.WT.DiscreteWavelet,Nothing}}, x, wt;
                       L=L, dnt=dnt, estnoise=estnoise, TI=TI, nspin=nspin)
     end
@@ -378,7 +392,7 @@ function Threshold.denoise(x::ROCArray{T,N}, wt::OrthoFilter=Threshold.DEFAULT_W
     sigma = estnoise === noisest ? -1.0 : Float64(estnoise(x, wt))
     estnoise === noisest || (sigma >= 0 && sigma * dnt.t >= 0) || throw(AssertionError("t >= 0"))   # threshold_main.jl:24 (+Inf passes, NaN does not)
     y = similar(x)
-    nsp = N == 1 ? Int64[prod(nspt), 1, 1] : Int64[nspt..., 1]      # vectors: prod(nspin) spins shifted by 0 .. pns-1 (denoising.jl:38-42)
+    nsp = N == 1 ? Int64[prod(nspt), 1, 1] : (N == 2 ? Int64[nspt..., 1] : Int64[nspt...])      # vectors: prod(nspin) spins shifted by 0 .. pns-1 (denoising.jl:38-42)
     GC.@preserve y x check(ccall((:wl_denoise_ti_filter, LIB), Cint,
                 (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Float64}, Cint, Cint, Cint, Cdouble, Ptr{Int64},
                  Cdouble, Ptr{Cvoid}),

@@ -228,9 +228,9 @@ def denoise(x, wt=_DEFAULT, L: Optional[int] = None, dnt: Optional[DNFT] = None,
     one_spin = (not TI) and estnoise is noisest and wt is not None
     if one_spin:
         nsp = tuple(1 for _ in range(x.dim()))
-    if ((TI or one_spin) and isinstance(wt, OrthoFilter) and (x.dim() == 1 or (x.dim() == 2 and len(nsp) == 2)) and isinstance(dnt.th, THType)
-            and dnt.th.code is not None and 0 <= dnt.th.code <= 3):
-        # the translation-invariant branch for orthogonal filters, vectors and square matrices: one device-resident batch
+    if ((TI or one_spin) and isinstance(wt, OrthoFilter) and (x.dim() == 1 or (x.dim() == 2 and len(nsp) == 2) or (x.dim() == 3 and len(nsp) == 3))
+            and isinstance(dnt.th, THType) and dnt.th.code is not None and 0 <= dnt.th.code <= 3):
+        # the translation-invariant branch for orthogonal filters, vectors, square matrices and cubes: one device-resident batch
         # (wl_denoise_ti_filter) -- all spins transformed / thresholded / inverted together, the noise estimate consumed on
         # the device, nothing allocated per spin, no host synchronisation.  Same arithmetic in the same order as the loop below.
         sig = -1.0 if estnoise is noisest else float(estnoise(x, wt))

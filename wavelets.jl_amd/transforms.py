@@ -244,13 +244,13 @@ def _dtype_code(x: torch.Tensor) -> int:
     raise TypeError(f"element type {x.dtype} is not supported (Float32/Float64 only; Complex is out of scope)")
 
 
-def _prep_in(x) -> torch.Tensor:
+def _prep_in(x, maxdim: int = 3) -> torch.Tensor:
     if not isinstance(x, torch.Tensor):
         raise TypeError("expected a torch tensor resident on an MI355X device (use to_device(array)); "
                         "there is no CPU path")
     if x.device.type != "cuda":
         raise HIPError("tensor is not on a HIP device; there is no CPU path")
-    if x.dim() < 1 or x.dim() > 3:
+    if x.dim() < 1 or x.dim() > maxdim:
         raise DimensionMismatch("only 1-D, 2-D and 3-D arrays are supported")
     if not x.dtype.is_floating_point and not x.dtype.is_complex:
         x = x.to(torch.float64)        # Int -> Float (transforms_main.jl:188-190)
@@ -467,15 +467,21 @@ def idwtc_(y, x, wt, L: Optional[int] = None) -> torch.Tensor:
 def _xwt_batch(x, wt, L, fw, y=None):
     """x: n0 x n1 x B (column-major: image i = x[:, :, i]); every image gets its own 2-D transform, all in one chain of
     launches (wl_dwt_filter_batch for an orthogonal filter, wl_dwt_lifting_batch for a lifting scheme).  The reference has no
-    batched form: this equals `stack(dwt(x[:, :, i], wt, L) for i)`."""
+    batched form: this equals `stack(dwt(x[:, :, i], wt, L) for i)`.
+    x: n0 x n1 x n2 x B with an orthogonal filter: a batch of volumes, volume i = x[:, :, :, i] (wl_dwt_filter_batch3); there is
+    no batched lifting transform of volumes."""
     if not isinstance(wt, (OrthoFilter, GLS)):
         raise TypeError("dwt_batch is defined for orthogonal filters and lifting schemes")
     if isinstance(x, torch.Tensor):
-        if x.dim() != 3:
-            raise TypeError("dwt_batch expects an n0 x n1 x B array")
+        if x.dim() == 4 and isinstance(wt, GLS):
+            raise TypeError("dwt_batch of volumes (n0 x n1 x n2 x B) is defined for orthogonal filters only")
+        if x.dim() not in (3, 4):
+            raise TypeError("dwt_batch expects an n0 x n1 x B array (images) or an n0 x n1 x n2 x B array (volumes)")
         if isinstance(wt, GLS) and int(x.shape[0]) != int(x.shape[1]):
             raise ArgumentError("array must be square/cube")          # what dwt(x[:, :, i], wt::GLS) raises (transforms_lifting.jl:131-132)
-    x = _prep_in(x)
+    x = _prep_in(x, maxdim=4)                # (a batch of volumes is the one 4-D array the package takes)
+    if x.dim() == 4:
+        return _xwt_batch3(x, wt, L, fw, y)
     n0, n1, nb = (int(v) for v in x.shape)
     L = min(Util.maxtransformlevels(n0), Util.maxtransformlevels(n1)) if L is None else int(L)
     y = similar(x) if y is None else y
@@ -493,6 +499,21 @@ def _xwt_batch(x, wt, L, fw, y=None):
     q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
     rc = lib.wl_dwt_filter_batch(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), dims, nb, n0 * n1,
                                  _f64p(q), len(q), L, 1 if fw else 0, st)
+    _check(rc, h)
+    return y
+
+
+def _xwt_batch3(x, wt, L, fw, y):
+    n0, n1, n2, nb = (int(v) for v in x.shape)
+    L = min(Util.maxtransformlevels(n) for n in (n0, n1, n2)) if L is None else int(L)
+    y = similar(x) if y is None else y
+    _check_pair(y, x)
+    lib = _lib.load()
+    h, st = _context(x.device)
+    dims = (C.c_int64 * 3)(n0, n1, n2)
+    q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
+    rc = lib.wl_dwt_filter_batch3(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), dims, nb, n0 * n1 * n2,
+                                  _f64p(q), len(q), L, 1 if fw else 0, st)
     _check(rc, h)
     return y
 
