@@ -208,8 +208,8 @@ WL_API int wl_dwt_filter_batch(wl_ctx *ctx, int dtype, void *y, const void *x, c
  * WL_EINVAL_ARG, WL_EINVAL_DTYPE, WL_EINVAL_FILTER, WL_EDIMS, WL_EINVAL_L, WL_EINVAL_SIZE, WL_EALIAS (y == x).
  * Workspace, with N = dims[0]*dims[1]*dims[2] and G = min(nvolumes, 65535): the approximation ping-pong of every volume of a
  * group plus one volume's inter-pass buffers, 2 * (G * (N / 8) + 64) + 3 N + 64 elements; nothing is allocated once
- * wl_workspace_bytes_full(dtype, 1, {nvolumes * volume_stride}, L) bytes are reserved.  A batched lifting transform of
- * volumes does not exist (wl_dwt_lifting_batch is 2-D).                                                                    */
+ * wl_workspace_bytes_full(dtype, 1, {nvolumes * volume_stride}, L) bytes are reserved.  Lifting schemes on a batch of
+ * volumes: wl_dwt_lifting_batch3.                                                                                          */
 WL_API int wl_dwt_filter_batch3(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nvolumes,
                          int64_t volume_stride, const double *qmf, int flen, int L, int fw, void *stream);
 
@@ -227,6 +227,27 @@ WL_API int wl_dwt_lifting_batch(wl_ctx *ctx, int dtype, void *y, const void *x, 
                          int64_t image_stride, int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
                          const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2, int L, int fw,
                          void *stream);
+
+/* y[:, :, :, i] = dwt(x[:, :, :, i], scheme, L) (fw = 0: idwt) for nvolumes CUBES of dims[0..2], volume i at element offset
+ * i * volume_stride (>= dims[0]^3) of x and of y; the scheme is passed as for wl_dwt_lifting.  The same results, bit for bit, as
+ * nvolumes calls of wl_dwt_lifting_oop with ndims = 3 (transforms_lifting.jl:200-272 per volume), but every launch of the single
+ * cube's level loop is ONE launch over all volumes (groups of 65535): the plane, row and column passes, the fused plane kernel
+ * from 128 per side, and the deepest levels (<= 32^3 Float32, 16^3 Float64) in one launch, a workgroup per volume.  Batched are
+ * the cubes the single call has fast kernels for -- the cdf9/7-, db2- and haar-shaped schemes, a power-of-two side of 8 .. 512,
+ * 16-byte aligned x and y -- with a volume_stride that keeps every volume base 16-byte aligned; every other scheme, side or
+ * stride, wl_ctx_set_path(ctx, 1) and the context option WL_LIFT_BATCH3_LOOP = 1 run volume after volume.  y == x is allowed and
+ * is dwt!(y, scheme, L) of every volume; L = 0 copies the volumes; the padding between volumes is never written at any L.  The
+ * call only enqueues (capturable in a hipGraph).  Status codes in this order: WL_EINVAL_ARG, WL_EINVAL_DTYPE, WL_EINVAL_CUBE (the
+ * extents are not all equal), WL_EDIMS (an extent or nvolumes < 1, volume_stride < dims[0]^3), WL_EINVAL_L, WL_EINVAL_SIZE,
+ * WL_EINVAL_SCHEME.  Workspace: nothing is allocated once wl_workspace_bytes_full(dtype, 1, {nvolumes * volume_stride}, L)
+ * bytes are reserved.  What the batched tiers really hold, with N = dims[0]^3 and G = min(nvolumes, 65535): nothing when the
+ * one-workgroup tail is the whole transform (side <= 32 Float32, 16 Float64); else the approximation ping-pong and the two dense
+ * inter-pass buffers of a group, 2 * (G * (N / 8) + 64) + 2 G N + 64 elements.  The volume-after-volume loop holds one volume's
+ * full workspace.                                                                                                          */
+WL_API int wl_dwt_lifting_batch3(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nvolumes,
+                          int64_t volume_stride, int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
+                          const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2, int L, int fw,
+                          void *stream);
 
 /* ---- wavelet packet transform (1-D) --------------------------------------------------- */
 /* y = wpt(x, filter, tree) / iwpt.  tree: one byte per node of the BitVector
@@ -318,9 +339,11 @@ WL_API int wl_rmul(wl_ctx *ctx, int dtype, void *y, int64_t n, double s, void *s
 WL_API int wl_denoise_ti_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims,
                          const double *qmf, int flen, int L, int th, double t_unit, const int64_t *nspin,
                          double sigma_host, void *stream);
-/* The same for a lifting scheme (wt::GLS; scheme arguments as wl_dwt_lifting), vectors and square matrices only (there is no
- * batched lifting transform of volumes: ndims = 3 is WL_EDIMS): shifted signals run as one batched-lines
- * transform, shifted images one batched 2-D lifting transform per group of spins; sigma and everything else stay on the device.
+/* The same for a lifting scheme (wt::GLS; scheme arguments as wl_dwt_lifting), vectors, square matrices and cubes (the rules of
+ * wl_denoise_ti_filter: WL_EINVAL_CUBE unless all extents are equal, WL_EINVAL_SIZE from 2^20 per side): shifted signals run as
+ * one batched-lines transform, shifted images one batched 2-D lifting transform, shifted cubes one batched 3-D lifting transform
+ * (the level loop of wl_dwt_lifting_batch3; a scheme it has no kernels for runs cube after cube) per group of spins; sigma and
+ * everything else stay on the device.
  * replaces the translation-invariant branch of denoise(x, wt::GLS; TI=true), denoising.jl:36-67 (round 4).               */
 WL_API int wl_denoise_ti_lifting(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims,
                           int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,

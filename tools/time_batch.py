@@ -8,6 +8,9 @@
     python tools/time_batch.py volumes    batch of volumes (db4, Float32, full depth): wl_dwt_filter_batch3 against the same number
                                           of single wl_dwt_filter calls, forward and inverse, rotating inputs
     python tools/time_batch.py denoise3d  W.denoise(cube, TI=True) with the default 8 x 8 x 8 spins, host wall time
+    python tools/time_batch.py lifting_volumes    batch of cubes (cdf9/7, Float32, full depth): wl_dwt_lifting_batch3 against the same
+                                          number of single wl_dwt_lifting_oop calls, forward and inverse, rotating inputs
+    python tools/time_batch.py lifting_denoise3d  W.denoise(cube, cdf9/7 scheme, TI=True) with the default 8 x 8 x 8 spins, host wall time
 """
 import os, sys, statistics
 import torch
@@ -142,29 +145,64 @@ def volumes_table():
                   f"{ts[0] / tb[0]:.2f} |", flush=True)
 
 
-def denoise3d_table():
+def lifting_volumes_table():
+    """runs on any build of the package: one without the batched transform of cubes (dwt_batch raises TypeError) fills the loop
+    columns only"""
+    cdf = W.wavelet(W.WT.cdf97, W.WT.Lifting)
+    print("| volumes | L | direction | batch us (min .. max) | kernel | single calls in a loop us (min .. max) | speed-up |")
+    print("|---|---|---|---|---|---|---|")
+    for n, nb in ((32, 512), (64, 64), (128, 8)):
+        L = W.maxtransformlevels(n)
+        xs = [torch.randn(nb, n, n, n, dtype=torch.float32, device="cuda").permute(3, 2, 1, 0) for _ in range(3)]
+        yb = W.similar(xs[0])
+        y1 = W.similar(xs[0][..., 0])
+        try:
+            cs = [W.dwt_batch(x, cdf, L) for x in xs]            # coefficients: the inputs of the inverse
+            have_batch = True
+        except TypeError:
+            cs = [W.similar(x) for x in xs]
+            for c, x in zip(cs, xs):
+                for i in range(nb):
+                    W.dwt_oop_(c[..., i], x[..., i], cdf, L)
+            have_batch = False
+        for name, fb, f1, ins in (("dwt", W.dwt_batch, W.dwt_oop_, xs), ("idwt", W.idwt_batch, W.idwt_oop_, cs)):
+            batch = [(lambda x=x: fb(x, cdf, L, y=yb)) for x in ins]
+            def loop(x):
+                for i in range(nb):
+                    f1(y1, x[..., i], cdf, L)
+            singles = [(lambda x=x: loop(x)) for x in ins]
+            tb, kb = (t_stats(batch, 21), W.last_kernel()) if have_batch else (None, "-")
+            ts = t_stats(singles, 21)
+            bt = f"{tb[0]:.1f} ({tb[1]:.1f} .. {tb[2]:.1f})" if tb else "-"
+            sp = f"{ts[0] / tb[0]:.2f}" if tb else "-"
+            print(f"| {nb} x {n}^3 | {L} | {name} | {bt} | {kb} | {ts[0]:.1f} ({ts[1]:.1f} .. {ts[2]:.1f}) | {sp} |", flush=True)
+
+
+def denoise3d_table(wt=None, cubes=((32, 7), (64, 7), (128, 5)), label="sym5"):
     """host wall time of the whole call (a synchronise before and after), median of `reps`; runs on any build of the package, so the
     same script times the per-spin host loop of an older build"""
     import time
     print("| cube | median ms (min .. max) | reps | kernel |")
     print("|---|---|---|---|")
-    for n, reps in ((32, 7), (64, 7), (128, 5)):
+    kw = {} if wt is None else {"wt": wt}
+    for n, reps in cubes:
         xs = [W.to_device((torch.randn(n, n, n) * 0.05 + torch.linspace(0, 1, n)[:, None, None]).numpy().astype("float32")) for _ in range(2)]
-        W.denoise(xs[0], TI=True)
+        W.denoise(xs[0], TI=True, **kw)
         torch.cuda.synchronize()
         ts = []
         for k in range(reps):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            W.denoise(xs[k % 2], TI=True)
+            W.denoise(xs[k % 2], TI=True, **kw)
             torch.cuda.synchronize()
             ts.append((time.perf_counter() - t0) * 1e3)
         ts.sort()
-        print(f"| {n}^3 Float32, sym5, L = {min(W.maxtransformlevels(n), 6)}, 512 spins | {statistics.median(ts):.2f} ({ts[0]:.2f} .. {ts[-1]:.2f}) | {reps} | "
+        print(f"| {n}^3 Float32, {label}, L = {min(W.maxtransformlevels(n), 6)}, 512 spins | {statistics.median(ts):.2f} ({ts[0]:.2f} .. {ts[-1]:.2f}) | {reps} | "
               f"{W.last_kernel()} |", flush=True)
 
 
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "filter"
     {"filter": filter_table, "lifting": lifting_table, "launches": lifting_launches, "volumes": volumes_table,
-     "denoise3d": denoise3d_table}[mode]()
+     "denoise3d": denoise3d_table, "lifting_volumes": lifting_volumes_table,
+     "lifting_denoise3d": lambda: denoise3d_table(W.wavelet(W.WT.cdf97, W.WT.Lifting), ((32, 5), (64, 5)), "cdf9/7 (lifting)")}[mode]()

@@ -412,6 +412,53 @@ int wl_lifting_box(wl_ctx *ctx, hipStream_t st, const BoxSpec &b, T *y, const T 
 template int wl_lifting_box<float>(wl_ctx *, hipStream_t, const BoxSpec &, float *, const float *, const LiftScheme<float> &, int, int);
 template int wl_lifting_box<double>(wl_ctx *, hipStream_t, const BoxSpec &, double *, const double *, const LiftScheme<double> &, int, int);
 
+// the lifting transform of a batch of cubes of side n, cube i at element offset i * vs of x and of y (wl_dwt_lifting_batch3; the spins
+// of a cube in wl_ext.hip): groups of at most 65535 cubes through the batched level loop of lifting_3d_fast where it is eligible,
+// else (option WL_LIFT_BATCH3_LOOP, path 1, one cube, and whatever lifting_3d_fast declines) cube after cube through wl_lifting_box
+template <typename T>
+int wl_lifting_vols(wl_ctx *ctx, hipStream_t st, int64_t n, int64_t nvol, int64_t vs, T *y, const T *x, const LiftScheme<T> &sc, int L, int fw)
+{
+    const int64_t N = n * n * n;
+    if (L == 0) {
+        // every cube is dense: one copy of an N x nvol matrix with leading dimension vs (the padding is not touched)
+        const Strides3 s = {{1, vs, 0}};
+        for (int64_t i0 = 0; i0 < nvol && y != x; i0 += 65535) {
+            const Extent3 ext = {{N, (nvol - i0 < 65535) ? (nvol - i0) : 65535, 1}};
+            WL_HIP(ctx, generic_copy_box<T>(st, x + i0 * vs, s, y + i0 * vs, s, ext));
+        }
+        ctx->last_kernel = "copy";
+        return WL_OK;
+    }
+    const int64_t gmax = nvol < 65535 ? nvol : 65535;
+    // (every group starts a multiple of vs from x: one answer for all of them; the last, shorter group needs no more than the first)
+    const int64_t need = (opt("WL_LIFT_BATCH3_LOOP", 0) != 0 || ctx->path != 0 || nvol == 1) ? -1 : lifting_3d_fast_ws<T>(sc, n, L, fw, x, y, gmax, vs, vs);
+    if (need >= 0) {
+        int rc = ensure_ws(ctx, (size_t)need * sizeof(T), st);
+        if (rc) return rc;
+        for (int64_t i0 = 0; i0 < nvol; i0 += 65535) {
+            const int64_t nv = (nvol - i0 < 65535) ? (nvol - i0) : 65535;
+            int handled = 0;
+            rc = lifting_3d_fast<T>(ctx->ws, ctx->cu_count, st, n, y + i0 * vs, x + i0 * vs, sc, L, fw, &handled, &ctx->last_kernel, &ctx->last_hip,
+                                    nv, vs, vs);
+            if (rc) return rc;
+            if (!handled) return WL_EINVAL_ARG;               // (lifting_3d_fast_ws said eligible: not reached)
+        }
+        ctx->last_kernel = "k_lift_axis_stream+k_lift_short_lines_batch";      // (whatever the size of the last group)
+        return WL_OK;
+    }
+    BoxSpec b;
+    b.nd = 3; b.nt = 3;
+    b.dims[0] = b.dims[1] = b.dims[2] = n;
+    b.full = dense_strides(b.dims);
+    for (int64_t i = 0; i < nvol; ++i) {
+        int rc = wl_lifting_box<T>(ctx, st, b, y + i * vs, x + i * vs, sc, L, fw);
+        if (rc) return rc;
+    }
+    return WL_OK;
+}
+template int wl_lifting_vols<float>(wl_ctx *, hipStream_t, int64_t, int64_t, int64_t, float *, const float *, const LiftScheme<float> &, int, int);
+template int wl_lifting_vols<double>(wl_ctx *, hipStream_t, int64_t, int64_t, int64_t, double *, const double *, const LiftScheme<double> &, int, int);
+
 // ==========================================================================================
 extern "C" {
 
@@ -1093,6 +1140,32 @@ int wl_dwt_lifting_batch(wl_ctx *ctx, int dtype, void *y, const void *x, const i
     if (rc) return rc;
     WL_SCOPE(ctx);
     return lifting_batch_impl<double>(ctx, st, (double *)y, (const double *)x, dims[0], nimages, image_stride, sc, L, fw);
+}
+
+int wl_dwt_lifting_batch3(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nvolumes, int64_t volume_stride,
+                          int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef, const int32_t *step_shift,
+                          const double *coefs_flat, double norm1, double norm2, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !dims) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (dims[0] != dims[1] || dims[0] != dims[2]) return WL_EINVAL_CUBE;     // the cube rule comes first in the reference (transforms_lifting.jl:203)
+    // (a side of 2^21 or more: the volume has 2^63 elements or more, above every stride an int64 holds)
+    if (dims[0] < 1 || nvolumes < 1 || dims[0] >= ((int64_t)1 << 21) || volume_stride < dims[0] * dims[1] * dims[2]) return WL_EDIMS;
+    if (L < 0) return WL_EINVAL_L;
+    if (!sufficientpoweroftwo(dims[0], L)) return WL_EINVAL_SIZE;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == WL_F32) {
+        LiftScheme<float> sc;
+        int rc = make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
+        if (rc) return rc;
+        WL_SCOPE(ctx);
+        return wl_lifting_vols<float>(ctx, st, dims[0], nvolumes, volume_stride, (float *)y, (const float *)x, sc, L, fw);
+    }
+    LiftScheme<double> sc;
+    int rc = make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
+    if (rc) return rc;
+    WL_SCOPE(ctx);
+    return wl_lifting_vols<double>(ctx, st, dims[0], nvolumes, volume_stride, (double *)y, (const double *)x, sc, L, fw);
 }
 
 int wl_wpt_filter_full(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, const double *qmf, int flen, int L, int fw, void *stream)

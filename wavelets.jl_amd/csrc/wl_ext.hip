@@ -1051,20 +1051,26 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
 // The same device-resident sequence as denoise_ti_impl -- sigma from the level-1 transform without a host round trip, the spins
 // shifted / transformed / thresholded / inverted / un-shifted / accumulated B at a time -- with the lifting transforms of the
 // library: a batch of shifted SIGNALS is one batched-lines call (the fused line kernels over all spins), a batch of shifted
-// IMAGES is one batched 2-D lifting transform (every level one launch over all spins of the group, as wl_dwt_lifting_batch).
+// IMAGES is one batched 2-D lifting transform (every level one launch over all spins of the group, as wl_dwt_lifting_batch), a batch
+// of shifted CUBES one batched 3-D lifting transform (wl_lifting_vols, as wl_dwt_lifting_batch3; a scheme of no known shape runs
+// cube after cube inside it).
 template <typename T>
 int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, const LiftScheme<T> &scf,
                             const LiftScheme<T> &sci, int L, int th, double t_unit, const int64_t *nspin, double sigma_host)
 {
-    const int64_t n0 = dims[0], n1 = (ndims == 2) ? dims[1] : 1, N = n0 * n1;
-    const int64_t nsp0 = nspin[0], nsp1 = (ndims == 2) ? nspin[1] : 1, pns = nsp0 * nsp1;
+    const int64_t n0 = dims[0], n1 = (ndims >= 2) ? dims[1] : 1, n2 = (ndims == 3) ? dims[2] : 1, N = n0 * n1 * n2;
+    const int64_t nsp0 = nspin[0], nsp1 = (ndims >= 2) ? nspin[1] : 1, nsp2 = (ndims == 3) ? nspin[2] : 1, pns = nsp0 * nsp1 * nsp2;
     int rc = ensure_aux(ctx);
     if (rc != WL_OK) return rc;
     SelState *sel = (SelState *)ctx->aux;
     const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
-    // transform workspace of the batched box (B lines, or B images: the approximation ping-pong of every image), then the shifted
-    // copies Z and their coefficients XT
-    auto tws = [&](int64_t B) { return ws_elems(N * B, 1); };
+    // transform workspace of the batched box (B lines, or B images: the approximation ping-pong of every image; B cubes: the ping-pong
+    // and the two dense inter-pass buffers of the batched 3-D level loop, and no less than one cube's own), then the shifted copies Z
+    // and their coefficients XT
+    auto tws = [&](int64_t B) {
+        if (ndims == 3) { const size_t a = ws_lift_vols_elems(N, B), b = ws_elems(N, 1); return a > b ? a : b; }
+        return ws_elems(N * B, 1);
+    };
     auto need = [&](int64_t B) { return (tws(B) + (size_t)2 * N * B + (size_t)n0 + 64) * sizeof(T); };
     int64_t B = pns;
     while (B > 1 && need(B) > cap) B = (B + 1) / 2;
@@ -1078,11 +1084,11 @@ int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
     T *dr = XT + N * B;
     BoxSpec b1;                                              // one signal / image
     b1.nd = ndims; b1.nt = ndims;
-    b1.dims[0] = n0; b1.dims[1] = n1; b1.dims[2] = 1;
+    b1.dims[0] = n0; b1.dims[1] = n1; b1.dims[2] = n2;
     b1.full = dense_strides(b1.dims);
-    // ---- sigma = noisest(x, wt): level-1 transform, MAD of y1[detailrange(y1, 1)] ----
+    // ---- sigma = noisest(x, wt): level-1 transform, MAD of y1[detailrange(y1, 1)] (linear indexing with size(x, 1)) ----
     if (!(sigma_host >= 0)) {
-        if (n0 < 2 || (n0 % 2) != 0 || (ndims == 2 && (n1 % 2) != 0)) return WL_EINVAL_SIZE;
+        if (n0 < 2 || (n0 % 2) != 0 || (ndims >= 2 && (n1 % 2) != 0) || (ndims == 3 && (n2 % 2) != 0)) return WL_EINVAL_SIZE;
         rc = wl_lifting_box<T>(ctx, st, b1, XT, x, scf, 1, 1);
         if (rc != WL_OK) return rc;
         const int64_t lo = (int64_t)llround((double)n0 / 2 + 1) - 1, hi = n0;
@@ -1101,8 +1107,11 @@ int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
         }
     }
     TiGeom g;
-    g.n0 = n0; g.n1 = n1; g.n2 = 1; g.N = N; g.nsp0 = nsp0; g.nsp1 = nsp1; g.nsp2 = 1;
+    g.n0 = n0; g.n1 = n1; g.n2 = n2; g.N = N; g.nsp0 = nsp0; g.nsp1 = nsp1; g.nsp2 = nsp2;
     const unsigned gxs = (unsigned)((n0 / 4 + 255) / 256 > 0 ? ((n0 / 4 + 255) / 256 > 64 ? 64 : (n0 / 4 + 255) / 256) : 1);
+    // columns (i1, i2) of the shift / accumulate kernels: grid-stride beyond 65535 workgroups along y
+    const int64_t ncol = n1 * n2;
+    const unsigned gy_shift = (unsigned)((ncol + 7) / 8 > 65535 ? 65535 : (ncol + 7) / 8), gy_acc = (unsigned)(ncol > 65535 ? 65535 : ncol);
     auto transform = [&](T *dst, const T *src, int64_t nb, const LiftScheme<T> &sc, int fw) -> int {
         if (ndims == 1) {                                    // nb signals = nb lines of one batched call
             BoxSpec bb;
@@ -1111,6 +1120,7 @@ int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
             bb.full = dense_strides(bb.dims);
             return wl_lifting_box<T>(ctx, st, bb, dst, src, sc, L, fw);
         }
+        if (ndims == 3) return wl_lifting_vols<T>(ctx, st, n0, nb, N, dst, src, sc, L, fw);      // nb cubes = one batch of volumes
         BoxSpec bb;                                          // nb images = the third extent of one batched call
         bb.nd = 3; bb.nt = 2;
         bb.dims[0] = n0; bb.dims[1] = n1; bb.dims[2] = nb;
@@ -1120,14 +1130,14 @@ int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
     for (int64_t b0 = 0; b0 < pns; b0 += B) {
         const int64_t nb = (pns - b0 < B) ? (pns - b0) : B;
         g.b0 = b0;
-        hipLaunchKernelGGL((k_ti_shift<T>), dim3(gxs, (unsigned)((n1 + 7) / 8), (unsigned)nb), dim3(256), 0, st, Z, x, g);
+        hipLaunchKernelGGL((k_ti_shift<T>), dim3(gxs, gy_shift, (unsigned)nb), dim3(256), 0, st, Z, x, g);
         rc = transform(XT, Z, nb, scf, 1);                   // (L = 0: a copy, as the reference's dwt is)
         if (rc != WL_OK) return rc;
         hipLaunchKernelGGL((k_threshold_dev<T>), dim3(ext_blocks(N * nb, 4, ctx->cu_count)), dim3(EXT_THREADS), 0, st, XT, N * nb, th, &sel->result,
                            t_unit, sigma_host, vec_ok16(XT));
         rc = transform(Z, XT, nb, sci, 0);
         if (rc != WL_OK) return rc;
-        hipLaunchKernelGGL((k_ti_accumulate<T>), dim3(gxs, (unsigned)n1), dim3(256), 0, st, y, Z, g, nb, b0 == 0 ? 1 : 0);
+        hipLaunchKernelGGL((k_ti_accumulate<T>), dim3(gxs, gy_acc), dim3(256), 0, st, y, Z, g, nb, b0 == 0 ? 1 : 0);
     }
     hipLaunchKernelGGL((k_rmul<T>), dim3(ext_blocks(N, 4, ctx->cu_count)), dim3(EXT_THREADS), 0, st, y, N, 1.0 / (double)pns, vec_ok16(y));
     WL_HIP(ctx, hipGetLastError());
@@ -1296,12 +1306,14 @@ int wl_denoise_ti_lifting(wl_ctx *ctx, int dtype, void *y, const void *x, int nd
     if (rc != WL_OK) return rc;
     WL_SCOPE(ctx);
     if (!y || !x || !dims || !nspin) return WL_EINVAL_ARG;
-    if (ndims < 1 || ndims > 2) return WL_EDIMS;
+    if (ndims < 1 || ndims > 3) return WL_EDIMS;
     if (th < WL_TH_HARD || th > WL_TH_STEIN) return WL_EINVAL_ARG;
     if (sigma_host != sigma_host || (sigma_host >= 0 && !(sigma_host * t_unit >= 0))) return WL_EINVAL_ARG;
     for (int d = 0; d < ndims; ++d)
         if (dims[d] < 1 || nspin[d] < 1) return WL_EDIMS;
-    if (ndims == 2 && dims[0] != dims[1]) return WL_EINVAL_CUBE;
+    if (ndims >= 2 && dims[0] != dims[1]) return WL_EINVAL_CUBE;
+    if (ndims == 3 && dims[0] != dims[2]) return WL_EINVAL_CUBE;
+    if (ndims == 3 && dims[0] >= ((int64_t)1 << 20)) return WL_EINVAL_SIZE; // (32-bit extents and column counts in the shift kernels)
     if (ndims == 2 && dims[1] > 65535) return WL_EINVAL_SIZE;
     if (L < 0) return WL_EINVAL_L;
     for (int d = 0; d < ndims; ++d)

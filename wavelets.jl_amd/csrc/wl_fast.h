@@ -190,10 +190,21 @@ template <typename T>
 bool inv2d_planes(hipStream_t st, const Taps<T> &taps, const T *x, int64_t x1, int64_t x2, const T *ll, T *dst, int64_t n0, int64_t n1,
                   int64_t nplanes, int nll, int cu_count, hipError_t *err, const char **kernel = nullptr, int64_t dst_plane_stride = 0);
 
-// 3-D lifting transform of a cube (2^k <= 512 per side) through the axis-streaming and short-line kernels.
+// 3-D lifting transform of a cube (2^k <= 512 per side) through the axis-streaming and short-line kernels, or of a batch of nvol
+// (<= 65535) such cubes, cube i at element offset i * xs of x and i * ys of y: every launch of the single cube's level loop is then one
+// launch over all cubes (the same kernel instances; *kernel_name gets "_batch" appended).  Eligible (*handled = 1): a known scheme
+// shape, a side 2^k in 8 .. 512, 16-byte aligned x and y and, for nvol > 1, strides that keep every cube base 16-byte aligned.
+// Nothing is enqueued when *handled comes back 0.
+// Workspace (elements), lifting_3d_fast_ws: -1 not eligible; 0 when k_tail_lift3d holds the whole transform (side <= 32 Float32 / 16
+// Float64); else ws_elems(N) for one cube and ws_lift_vols_elems(N, nvol) for a batch -- the approximation ping-pong
+// (nvol * N / 8 + 64 per side) and the dense inter-pass buffers T0 / T1 (nvol * N each).
+inline size_t ws_lift_vols_elems(int64_t N, int64_t nvol) { return 2 * (size_t)(nvol * (N >> 3) + 64) + 2 * (size_t)(N * nvol) + 64; }
+template <typename T>
+int64_t lifting_3d_fast_ws(const LiftScheme<T> &sc, int64_t n0, int L, int fw, const T *x, const T *y, int64_t nvol, int64_t xs, int64_t ys);
 template <typename T>
 int lifting_3d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, T *y, const T *x,
-                    const LiftScheme<T> &sc, int L, int fw, int *handled, const char **kernel_name, int *hip_err);
+                    const LiftScheme<T> &sc, int L, int fw, int *handled, const char **kernel_name, int *hip_err, int64_t nvol = 1,
+                    int64_t xs = 0, int64_t ys = 0);
 
 // A batch of independent volumes for the one-launch 3-D level kernels (wl_fwd3d.hip, wl_inv3d.hip, wl_level3.hip): nvol (<= 65535)
 // volumes per launch, volume i at element offset i * bs_src of the source, i * bs_dst of the destination and i * bs_ll of the dense

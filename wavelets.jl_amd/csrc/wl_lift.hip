@@ -1297,13 +1297,14 @@ template <typename T>
 struct LiftTail3Args {
     const T *src; int64_t s1, s2;   // fw: the level's input cube;  inv: the coefficient array (its m0^3 corner)
     T *y; int64_t y1, y2;           // fw: the coefficient array;   inv: the m0^3 result
+    int64_t sv, yv;                 // a batch of cubes: workgroup blockIdx.x owns cube blockIdx.x, at src + blockIdx.x * sv and y + blockIdx.x * yv
     int m0, nlev;
     T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
     T norm1, norm2;
 };
 
 template <typename T, int ID, int M, int MM>
-__device__ __forceinline__ void tail3_fwd_level(T *P, const LiftTail3Args<T> &a, bool last, int tid, int nthr)
+__device__ __forceinline__ void tail3_fwd_level(T *P, const LiftTail3Args<T> &a, T *yb, bool last, int tid, int nthr)
 {
     constexpr int H = M / 2, L1 = MM + 1, L2 = (MM + 1) * MM;
     const int u = tid % M, v = tid / M;                      // the two coordinates a line does not run along
@@ -1344,19 +1345,19 @@ __device__ __forceinline__ void tail3_fwd_level(T *P, const LiftTail3Args<T> &a,
     // the seven detail octants are final (the approximation octant too after the last level): lanes along dim 1
     for (int idx = tid; idx < M * M * M; idx += nthr) {
         const int i = idx % M, j = (idx / M) % M, k = idx / (M * M);
-        if (last || i >= H || j >= H || k >= H) a.y[i + (int64_t)j * a.y1 + (int64_t)k * a.y2] = P[i + j * L1 + k * L2];
+        if (last || i >= H || j >= H || k >= H) yb[i + (int64_t)j * a.y1 + (int64_t)k * a.y2] = P[i + j * L1 + k * L2];
     }
 }
 template <typename T, int ID, int M, int MM>
-__device__ __forceinline__ void tail3_fwd_from(T *P, const LiftTail3Args<T> &a, int m0, int nlev, int tid, int nthr)
+__device__ __forceinline__ void tail3_fwd_from(T *P, const LiftTail3Args<T> &a, T *yb, int m0, int nlev, int tid, int nthr)
 {
     if (m0 == M) {
-        tail3_fwd_level<T, ID, M, MM>(P, a, nlev == 1, tid, nthr);
+        tail3_fwd_level<T, ID, M, MM>(P, a, yb, nlev == 1, tid, nthr);
         if constexpr (M >= 4) {
-            if (nlev > 1) tail3_fwd_from<T, ID, M / 2, MM>(P, a, M / 2, nlev - 1, tid, nthr);
+            if (nlev > 1) tail3_fwd_from<T, ID, M / 2, MM>(P, a, yb, M / 2, nlev - 1, tid, nthr);
         }
     } else {
-        if constexpr (M >= 4) tail3_fwd_from<T, ID, M / 2, MM>(P, a, m0, nlev, tid, nthr);
+        if constexpr (M >= 4) tail3_fwd_from<T, ID, M / 2, MM>(P, a, yb, m0, nlev, tid, nthr);
     }
 }
 // one inverse level with output M^3 in P (normalize -> steps -> merge per line; columns, rows, planes)
@@ -1413,18 +1414,20 @@ __global__ void __launch_bounds__(1024) k_tail_lift3d(LiftTail3Args<T> a)
     T *P = reinterpret_cast<T *>(smem_raw);
     const int tid = threadIdx.x, nthr = blockDim.x;
     const int m0 = a.m0, lg = 31 - __clz(m0);
+    const T *const xb = a.src + (int64_t)blockIdx.x * a.sv;
+    T *const yb = a.y + (int64_t)blockIdx.x * a.yv;
     for (int idx = tid; idx < m0 * m0 * m0; idx += nthr) {
         const int i = idx & (m0 - 1), j = (idx >> lg) & (m0 - 1), k = idx >> (2 * lg);
-        P[i + j * L1 + k * L2] = a.src[i + (int64_t)j * a.s1 + (int64_t)k * a.s2];
+        P[i + j * L1 + k * L2] = xb[i + (int64_t)j * a.s1 + (int64_t)k * a.s2];
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     if (FW) {
-        tail3_fwd_from<T, ID, MM, MM>(P, a, m0, a.nlev, tid, nthr);
+        tail3_fwd_from<T, ID, MM, MM>(P, a, yb, m0, a.nlev, tid, nthr);
     } else {
         tail3_inv_upto<T, ID, MM, MM>(P, a, m0, a.nlev, tid);
         for (int idx = tid; idx < m0 * m0 * m0; idx += nthr) {
             const int i = idx & (m0 - 1), j = (idx >> lg) & (m0 - 1), k = idx >> (2 * lg);
-            a.y[i + (int64_t)j * a.y1 + (int64_t)k * a.y2] = P[i + j * L1 + k * L2];
+            yb[i + (int64_t)j * a.y1 + (int64_t)k * a.y2] = P[i + j * L1 + k * L2];
         }
     }
 }
@@ -1432,7 +1435,7 @@ template <typename T> constexpr int tail3_max() { return sizeof(T) == 4 ? 32 : 1
 template <typename T>
 static bool tail_lift3d_ok(int id, int64_t n) { return id >= 0 && id <= 5 && n >= 2 && n <= tail3_max<T>() && (n & (n - 1)) == 0; }
 template <typename T, int ID, int FW>
-static hipError_t launch_tail_lift3d_id(hipStream_t st, const LiftTail3Args<T> &a)
+static hipError_t launch_tail_lift3d_id(hipStream_t st, const LiftTail3Args<T> &a, int64_t nvol)
 {
     constexpr int MM = tail3_max<T>();
     const size_t shmem = (size_t)(MM + 1) * MM * MM * sizeof(T);
@@ -1448,26 +1451,26 @@ static hipError_t launch_tail_lift3d_id(hipStream_t st, const LiftTail3Args<T> &
     }
     const int lines = a.m0 * a.m0;
     const int threads = lines >= 1024 ? 1024 : (lines >= 256 ? 256 : 64);
-    hipLaunchKernelGGL((k_tail_lift3d<T, ID, FW, MM>), dim3(1), dim3(threads), shmem, st, a);
+    hipLaunchKernelGGL((k_tail_lift3d<T, ID, FW, MM>), dim3((unsigned)nvol), dim3(threads), shmem, st, a);
     return hipGetLastError();
 }
 template <typename T, int FW>
 static hipError_t launch_tail_lift3d(int id, hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t s1, int64_t s2, T *y, int64_t y1,
-                                     int64_t y2, int m0, int nlev)
+                                     int64_t y2, int m0, int nlev, int64_t nvol = 1, int64_t sv = 0, int64_t yv = 0)
 {
     LiftTail3Args<T> a;
-    a.src = src; a.s1 = s1; a.s2 = s2; a.y = y; a.y1 = y1; a.y2 = y2; a.m0 = m0; a.nlev = nlev;
+    a.src = src; a.s1 = s1; a.s2 = s2; a.y = y; a.y1 = y1; a.y2 = y2; a.m0 = m0; a.nlev = nlev; a.sv = sv; a.yv = yv;
     for (int i = 0; i < LIFT_FAST_STEPS; ++i)
         for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
     a.norm1 = sc.norm1; a.norm2 = sc.norm2;
     if (FW) {
-        if (id == 0) return launch_tail_lift3d_id<T, 0, 1>(st, a);
-        if (id == 2) return launch_tail_lift3d_id<T, 2, 1>(st, a);
-        return launch_tail_lift3d_id<T, 4, 1>(st, a);
+        if (id == 0) return launch_tail_lift3d_id<T, 0, 1>(st, a, nvol);
+        if (id == 2) return launch_tail_lift3d_id<T, 2, 1>(st, a, nvol);
+        return launch_tail_lift3d_id<T, 4, 1>(st, a, nvol);
     }
-    if (id == 1) return launch_tail_lift3d_id<T, 1, 0>(st, a);
-    if (id == 3) return launch_tail_lift3d_id<T, 3, 0>(st, a);
-    return launch_tail_lift3d_id<T, 5, 0>(st, a);
+    if (id == 1) return launch_tail_lift3d_id<T, 1, 0>(st, a, nvol);
+    if (id == 3) return launch_tail_lift3d_id<T, 3, 0>(st, a, nvol);
+    return launch_tail_lift3d_id<T, 5, 0>(st, a, nvol);
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -2413,12 +2416,17 @@ struct Lift2DArgs {
     int64_t bs_src, bs_y, bs_ll; int nll;
     T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
     T norm1, norm2;
+    // a batch of cubes of 2^vsh planes: block blockIdx.y is plane blockIdx.y mod 2^vsh of cube blockIdx.y >> vsh.  The cubes lie vs
+    // elements (below 2^31) apart in the coefficient array (fw: y, inv: src); the block to transform / the result block is dense over
+    // all planes of the batch (bs_src / bs_y apart), ll holds the nll planes of every cube back to back.  The defaults leave one run of
+    // blocks (every user but the batched 3-D level loop).
+    int vsh = 30, vs = 0;
 };
 
 // R: ring slots = steps per unrolled iteration; loads run PF = R - DL + AMIN - 1 column pairs ahead (R = 8 everywhere: 16 was
 // measured on the small, latency-bound levels and lost).
 template <typename T, int ID, int R, bool FAST>
-__device__ __forceinline__ void lift2d_fwd_body(const Lift2DArgs<T> &a)
+__device__ __forceinline__ void lift2d_fwd_body(const Lift2DArgs<T> &a, T *const yb, T *const llp, const int64_t ldl)
 {
     typedef Shape<ID> SH;
     typedef Cascade<ID> CS;
@@ -2460,10 +2468,6 @@ __device__ __forceinline__ void lift2d_fwd_body(const Lift2DArgs<T> &a)
     };
 #pragma unroll
     for (int c = 0; c < PF; ++c) load_pair(tau0 + c, c % R);
-    T *const yb = a.y + (int64_t)blockIdx.y * a.bs_y;
-    const bool to_ll = (a.ll != nullptr) && ((int)blockIdx.y < a.nll);
-    T *const llp = to_ll ? a.ll + (int64_t)blockIdx.y * a.bs_ll : yb;
-    const int64_t ldl = to_ll ? a.ldl : a.ldy;
     auto step = [&](const int64_t t, const int u) __attribute__((always_inline)) {
         const int64_t tau = tau0 + t;
         load_pair(tau + PF, (u + PF) % R);
@@ -2554,8 +2558,15 @@ __device__ __forceinline__ bool lift2d_interior(const Lift2DArgs<T> &a)
 template <typename T, int ID, int R = 8>
 __global__ void __launch_bounds__(64) k_lift2d_fwd(Lift2DArgs<T> a)
 {
-    if (lift2d_interior<T>(a)) lift2d_fwd_body<T, ID, R, true>(a);
-    else lift2d_fwd_body<T, ID, R, false>(a);
+    // the destinations of this block, worked out once for both bodies (yb: its plane of y, llp / ldl: where its approximation
+    // quadrant goes): as part of either body they cost the cdf9/7 instances scalar-register spills
+    const int bv = (int)blockIdx.y >> a.vsh, bp = (int)blockIdx.y - (bv << a.vsh);     // cube, plane within it
+    T *const yb = a.y + (int64_t)bp * a.bs_y + (int64_t)bv * a.vs;
+    const bool to_ll = (a.ll != nullptr) && (bp < a.nll);
+    T *const llp = to_ll ? a.ll + (int64_t)(bv * a.nll + bp) * a.bs_ll : yb;
+    const int64_t ldl = to_ll ? a.ldl : a.ldy;
+    if (lift2d_interior<T>(a)) lift2d_fwd_body<T, ID, R, true>(a, yb, llp, ldl);
+    else lift2d_fwd_body<T, ID, R, false>(a, yb, llp, ldl);
 }
 
 // The inverse: per step the raw coefficient column pair (left-half column p: approximation rows + detail rows, and
@@ -2582,9 +2593,10 @@ __device__ __forceinline__ void lift2d_inv_body(const Lift2DArgs<T> &a)
     const int64_t p0 = (int64_t)chunk * a.TP;
     const int64_t pend = (p0 + a.TP < h1) ? (p0 + a.TP) : h1;
     // left-half columns take their approximation rows from ll when given
-    const T *xb = a.src + (int64_t)blockIdx.y * a.bs_src;
-    const bool from_ll = (a.ll != nullptr) && ((int)blockIdx.y < a.nll);
-    const T *ls_base = (from_ll ? a.ll + (int64_t)blockIdx.y * a.bs_ll : xb) + kw;
+    const int bv = (int)blockIdx.y >> a.vsh, bp = (int)blockIdx.y - (bv << a.vsh);     // cube, plane within it
+    const T *xb = a.src + (int64_t)bp * a.bs_src + (int64_t)bv * a.vs;
+    const bool from_ll = (a.ll != nullptr) && (bp < a.nll);
+    const T *ls_base = (from_ll ? a.ll + (int64_t)(bv * a.nll + bp) * a.bs_ll : xb) + kw;
     const int64_t ls_ld = from_ll ? a.ldl : a.lds;
     const T *ld_base = xb + h0 + kw;
     const T *rs_base = xb + h1 * a.lds + kw;
@@ -2682,6 +2694,36 @@ __global__ void __launch_bounds__(64) k_lift2d_inv(Lift2DArgs<T> a)
     else lift2d_inv_body<T, ID, R, false>(a);
 }
 
+// gridDim.y holds at most 65535 blocks: a longer batch goes out in several launches -- whole cubes per launch when the batch is one of
+// cubes (a launch then starts at plane 0 of a cube), runs of blocks otherwise (only the first nll blocks use ll).
+// WL_LIFT2D_GRID_Y: test knob, a lower limit (never below the planes of one cube).
+template <typename T, typename F>
+static hipError_t lift2d_launch_split(const Lift2DArgs<T> &a, int64_t nbatch, bool fw, F launch)
+{
+    int64_t gy = opt("WL_LIFT2D_GRID_Y", 65535);
+    if (gy < 1 || gy > 65535) gy = 65535;
+    if (nbatch <= gy) { launch(a, nbatch); return hipGetLastError(); }
+    const int64_t npv = (int64_t)1 << a.vsh;                        // planes per cube (2^30 without cubes)
+    const bool cubes = a.vsh < 30;
+    if (cubes && gy < npv) gy = npv;                                // (a cube has at most 512 planes)
+    if (nbatch <= gy) { launch(a, nbatch); return hipGetLastError(); }
+    const int64_t step = cubes ? (gy / npv) * npv : gy;
+    for (int64_t b0 = 0; b0 < nbatch; b0 += step) {
+        Lift2DArgs<T> b = a;
+        if (cubes) {
+            const int64_t v0 = b0 / npv;
+            b.src = a.src + (fw ? b0 * a.bs_src : v0 * (int64_t)a.vs); b.y = a.y + (fw ? v0 * (int64_t)a.vs : b0 * a.bs_y);
+            if (a.ll) b.ll = a.ll + v0 * a.nll * a.bs_ll;
+        } else {
+            if (npv < nbatch) return hipErrorInvalidValue;         // (a cube of more than 65535 planes: no caller has one)
+            b.src = a.src + b0 * a.bs_src; b.y = a.y + b0 * a.bs_y; if (a.ll) b.ll = a.ll + b0 * a.bs_ll;
+            b.nll = (int)((int64_t)a.nll > b0 ? (int64_t)a.nll - b0 : 0);
+        }
+        launch(b, (nbatch - b0 < step) ? (nbatch - b0) : step);
+    }
+    return hipGetLastError();
+}
+
 template <typename T, int ID>
 static hipError_t launch_lift2d_inv(hipStream_t st, Lift2DArgs<T> a, int cu_count, int64_t nbatch = 1)
 {
@@ -2701,8 +2743,9 @@ static hipError_t launch_lift2d_inv(hipStream_t st, Lift2DArgs<T> a, int cu_coun
     a.TP = TP;
     a.nchunks = (int)((h1 + TP - 1) / TP);
     // (a 16-slot ring -- loads 12 pairs ahead -- was measured on the small, latency-bound levels: slower, 13.4 vs 12.1 us)
-    hipLaunchKernelGGL((k_lift2d_inv<T, ID, 8>), dim3((unsigned)(a.nstrips * a.nchunks), (unsigned)nbatch), dim3(64), 0, st, a);
-    return hipGetLastError();
+    return lift2d_launch_split<T>(a, nbatch, false, [&](const Lift2DArgs<T> &b, int64_t nb) {
+        hipLaunchKernelGGL((k_lift2d_inv<T, ID, 8>), dim3((unsigned)(a.nstrips * a.nchunks), (unsigned)nb), dim3(64), 0, st, b);
+    });
 }
 
 template <typename T, int ID>
@@ -2723,8 +2766,9 @@ static hipError_t launch_lift2d_fwd(hipStream_t st, Lift2DArgs<T> a, int cu_coun
     if (tpo >= 8 && (tpo % 8) == 0) TP = tpo;
     a.TP = TP;
     a.nchunks = (int)((h1 + TP - 1) / TP);
-    hipLaunchKernelGGL((k_lift2d_fwd<T, ID, 8>), dim3((unsigned)(a.nstrips * a.nchunks), (unsigned)nbatch), dim3(64), 0, st, a);
-    return hipGetLastError();
+    return lift2d_launch_split<T>(a, nbatch, true, [&](const Lift2DArgs<T> &b, int64_t nb) {
+        hipLaunchKernelGGL((k_lift2d_fwd<T, ID, 8>), dim3((unsigned)(a.nstrips * a.nchunks), (unsigned)nb), dim3(64), 0, st, b);
+    });
 }
 
 template <typename T, int ID, int FW, int RPL>
@@ -2782,6 +2826,11 @@ struct LiftShortArgs {
     T *o1; int64_t o12, o13;         // fw: d dest       inv: unused
     // low-low corner (i2 < l2, i3 < l3): fw: s goes to ll instead of o0; inv: the approximation comes from ll
     T *ll; int64_t ll2, ll3; int l2; int64_t l3;
+    // a batch of cubes: line index i3 is plane (i3 & vmask) of cube (i3 >> vsh), the cubes av / bv / o0v / o1v / llv elements (below
+    // 2^31: one 32 x 32 -> 64-bit multiply-add per offset) apart; the corner is tested on the plane within the cube.  The defaults leave i3
+    // whole (every user but the batched 3-D level loop).
+    int vsh = 62; int64_t vmask = INT64_MAX;
+    int av = 0, bv = 0, o0v = 0, o1v = 0, llv = 0;
     int n, G, c2;
     int64_t nlines;
     T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
@@ -2799,19 +2848,21 @@ __global__ void __launch_bounds__(256) k_lift_short_lines(LiftShortArgs<T> a)
     const int64_t li = wave * lpw + g;
     const bool valid = li < a.nlines;
     const int64_t lc = valid ? li : 0;
-    const int64_t i3 = lc / a.c2, i2 = lc - i3 * a.c2;
+    const int64_t i3g = lc / a.c2, i2 = lc - i3g * a.c2;
+    const int64_t i3 = i3g & a.vmask;
+    const int iv = (int)(i3g >> a.vsh);
     const int64_t half = a.n >> 1;
     const bool corner = a.ll != nullptr && i2 < a.l2 && i3 < a.l3;
     T s[PPL], d[PPL];
     if (FW) {
         T v[2 * PPL];
-        ldv_l<T, 2 * PPL>(a.a + i2 * a.a2 + i3 * a.a3 + 2 * PPL * r, v);
+        ldv_l<T, 2 * PPL>(a.a + i2 * a.a2 + i3 * a.a3 + (int64_t)iv * a.av + 2 * PPL * r, v);
 #pragma unroll
         for (int j = 0; j < PPL; ++j) { s[j] = v[2 * j]; d[j] = v[2 * j + 1]; }                 // Util.split!
     } else {
         T sv[PPL], dv[PPL];
-        ldv_l<T, PPL>((corner ? a.ll + i2 * a.ll2 + i3 * a.ll3 : a.a + i2 * a.a2 + i3 * a.a3) + PPL * r, sv);
-        ldv_l<T, PPL>(a.b + i2 * a.b2 + i3 * a.b3 + PPL * r, dv);
+        ldv_l<T, PPL>((corner ? a.ll + i2 * a.ll2 + i3 * a.ll3 + (int64_t)iv * a.llv : a.a + i2 * a.a2 + i3 * a.a3 + (int64_t)iv * a.av) + PPL * r, sv);
+        ldv_l<T, PPL>(a.b + i2 * a.b2 + i3 * a.b3 + (int64_t)iv * a.bv + PPL * r, dv);
 #pragma unroll
         for (int j = 0; j < PPL; ++j) { s[j] = a.norm1 * sv[j]; d[j] = a.norm2 * dv[j]; }       // normalize! (inverse first)
     }
@@ -2857,14 +2908,14 @@ __global__ void __launch_bounds__(256) k_lift_short_lines(LiftShortArgs<T> a)
 #pragma unroll
         for (int j = 0; j < PPL; ++j) { so[j] = s[j] * a.norm1; dO[j] = d[j] * a.norm2; }        // normalize!
         if (valid) {
-            stv_l<T, PPL>((corner ? a.ll + i2 * a.ll2 + i3 * a.ll3 : a.o0 + i2 * a.o02 + i3 * a.o03) + PPL * r, so);
-            stv_l<T, PPL>(a.o1 + i2 * a.o12 + i3 * a.o13 + PPL * r, dO);
+            stv_l<T, PPL>((corner ? a.ll + i2 * a.ll2 + i3 * a.ll3 + (int64_t)iv * a.llv : a.o0 + i2 * a.o02 + i3 * a.o03 + (int64_t)iv * a.o0v) + PPL * r, so);
+            stv_l<T, PPL>(a.o1 + i2 * a.o12 + i3 * a.o13 + (int64_t)iv * a.o1v + PPL * r, dO);
         }
     } else {
         T v[2 * PPL];
 #pragma unroll
         for (int j = 0; j < PPL; ++j) { v[2 * j] = s[j]; v[2 * j + 1] = d[j]; }                  // Util.merge!
-        if (valid) stv_l<T, 2 * PPL>(a.o0 + i2 * a.o02 + i3 * a.o03 + 2 * PPL * r, v);
+        if (valid) stv_l<T, 2 * PPL>(a.o0 + i2 * a.o02 + i3 * a.o03 + (int64_t)iv * a.o0v + 2 * PPL * r, v);
     }
 }
 
@@ -3176,16 +3227,42 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
 // 3-D (cube) lifting transform, cubes of 2^k <= 512 per side: planes and rows along the strided axes
 // (k_lift_axis_stream, rows batched over the planes), columns as short lines with the LLL corner routed to the
 // approximation buffer.  Other sizes: not handled (generic kernels).
+// A batch of nvol cubes (cube v at x + v * xs and y + v * ys) runs level by level over all its cubes: every launch of the single cube
+// is one launch here.  The inter-pass buffers T0 / T1 and the approximation ping-pong hold the cubes of a level densely, cube v of
+// an n^3 level at v * n^3, so the row pass sees n * nvol planes and the plane-indexed kernels split a plane index with a shift.
+template <typename T>
+static int lift3d_shape(const LiftScheme<T> &sc, int64_t n0, int L, const T *x, const T *y, int64_t nvol, int64_t xs, int64_t ys)
+{
+    constexpr int VEC = 16 / sizeof(T);
+    const int id = match_shape<T>(sc);
+    if (id < 0 || L < 1 || n0 < 8 || n0 > 512 || (n0 & (n0 - 1)) != 0 || !al16(x) || !al16(y)) return -1;
+    if ((n0 >> (L - 1)) < 2) return -1;
+    if (nvol < 1 || nvol > 65535 || (nvol > 1 && ((xs % VEC) != 0 || (ys % VEC) != 0 || xs >= ((int64_t)1 << 31) || ys >= ((int64_t)1 << 31)))) return -1;
+    return id;
+}
+template <typename T>
+int64_t lifting_3d_fast_ws(const LiftScheme<T> &sc, int64_t n0, int L, int fw, const T *x, const T *y, int64_t nvol, int64_t xs, int64_t ys)
+{
+    const int id = lift3d_shape<T>(sc, n0, L, x, y, nvol, xs, ys);
+    if (id < 0) return -1;
+    // the whole transform inside k_tail_lift3d (the tail takes the shapes of its own direction: 0 / 2 / 4 forward, 1 / 3 / 5 inverse)
+    if ((id & 1) == (fw ? 0 : 1) && tail_lift3d_ok<T>(id, n0) && l_env("WL_LIFT_TAIL3D", 1) != 0) return 0;
+    const int64_t N = n0 * n0 * n0;
+    return (int64_t)(nvol > 1 ? ws_lift_vols_elems(N, nvol) : ws_elems(N));
+}
 template <typename T>
 int lifting_3d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, T *y, const T *x,
-                    const LiftScheme<T> &sc, int L, int fw, int *handled, const char **kernel_name, int *hip_err)
+                    const LiftScheme<T> &sc, int L, int fw, int *handled, const char **kernel_name, int *hip_err, int64_t nvol, int64_t xs, int64_t ys)
 {
     *handled = 0;
-    const int id = match_shape<T>(sc);
-    if (id < 0 || L < 1 || n0 < 8 || n0 > 512 || (n0 & (n0 - 1)) != 0 || !al16(x) || !al16(y)) return WL_OK;
-    if ((n0 >> (L - 1)) < 2) return WL_OK;
+    const int id = lift3d_shape<T>(sc, n0, L, x, y, nvol, xs, ys);
+    if (id < 0) return WL_OK;
+    if (nvol == 1) xs = ys = 0;
     const int64_t N = n0 * n0 * n0;
     Work<T> w = carve<T>(ws, N);
+    if (nvol > 1) {                                         // (ws_lift_vols_elems)
+        w.A = (T *)ws; w.B = w.A + (nvol * (N >> 3) + 64); w.T0 = w.B + (nvol * (N >> 3) + 64); w.T1 = w.T0 + N * nvol; w.W = nullptr;
+    }
     LiftAxisArgs<T> ax;
     LiftShortArgs<T> sa;
     for (int i = 0; i < LIFT_FAST_STEPS; ++i)
@@ -3196,23 +3273,24 @@ int lifting_3d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, T *y, co
     ax.norm1 = sa.norm1 = sc.norm1;
     ax.norm2 = sa.norm2 = sc.norm2;
     const int64_t y1 = n0, y2 = n0 * n0;
+    auto lg2 = [](int64_t n) { int k = 0; while (((int64_t)1 << k) < n) ++k; return k; };
     if (fw) {
         const T *cur = x;
-        int64_t c1 = n0, c2 = n0 * n0;
+        int64_t c1 = n0, c2 = n0 * n0, cv = xs;
         int pp = 0;
         for (int l = 1; l <= L; ++l) {
             const int64_t n = n0 >> (l - 1), h = n >> 1;
             const bool last = (l == L);
             T *llbuf = pp ? w.B : w.A;
-            // every remaining level inside one workgroup's LDS (k_tail_lift3d)
+            // every remaining level inside one workgroup's LDS (k_tail_lift3d), a workgroup per cube
             if ((id == 0 || id == 2 || id == 4) && tail_lift3d_ok<T>(id, n) && l_env("WL_LIFT_TAIL3D", 1) != 0) {
-                WL_E((launch_tail_lift3d<T, 1>(id, st, sc, cur, c1, c2, y, y1, y2, (int)n, L - l + 1)));
+                WL_E((launch_tail_lift3d<T, 1>(id, st, sc, cur, c1, c2, y, y1, y2, (int)n, L - l + 1, nvol, cv, ys)));
                 break;
             }
             // planes (dim 3): the cube is an (n*n) x n matrix when its first two dims are dense
             if (c1 == n) {
-                ax.src = cur; ax.lds = c2; ax.bs_src = 0; ax.dst = w.T0; ax.ldd = n * n; ax.bs_dst = 0; ax.R = n * n; ax.C = n;
-                WL_E((launch_lift_axis_id<T, 1>(id, st, ax, 1, cu_count)));
+                ax.src = cur; ax.lds = c2; ax.bs_src = cv; ax.dst = w.T0; ax.ldd = n * n; ax.bs_dst = nvol > 1 ? n * n * n : 0; ax.R = n * n; ax.C = n;
+                WL_E((launch_lift_axis_id<T, 1>(id, st, ax, nvol, cu_count)));
             } else {       // (not reached: level 1 reads the dense cube, deeper levels the dense approximation buffer)
                 return WL_OK;
             }
@@ -3224,34 +3302,38 @@ int lifting_3d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, T *y, co
                 q2.norm1 = ax.norm1; q2.norm2 = ax.norm2;
                 q2.src = w.T0; q2.lds = n; q2.y = y; q2.ldy = y1; q2.ll = last ? (T *)nullptr : llbuf; q2.ldl = h; q2.n0 = n; q2.n1 = n;
                 q2.bs_src = n * n; q2.bs_y = y2; q2.bs_ll = h * h; q2.nll = (int)h;
-                if (id == 0) WL_E((launch_lift2d_fwd<T, 0>(st, q2, cu_count, n)));
-                else if (id == 2) WL_E((launch_lift2d_fwd<T, 2>(st, q2, cu_count, n)));
-                else WL_E((launch_lift2d_fwd<T, 4>(st, q2, cu_count, n)));
-                cur = llbuf; c1 = h; c2 = h * h; pp ^= 1;
+                q2.vsh = lg2(n); q2.vs = (int)ys;
+                if (id == 0) WL_E((launch_lift2d_fwd<T, 0>(st, q2, cu_count, n * nvol)));
+                else if (id == 2) WL_E((launch_lift2d_fwd<T, 2>(st, q2, cu_count, n * nvol)));
+                else WL_E((launch_lift2d_fwd<T, 4>(st, q2, cu_count, n * nvol)));
+                cur = llbuf; c1 = h; c2 = h * h; cv = nvol > 1 ? h * h * h : 0; pp ^= 1;
                 continue;
             }
-            // rows (dim 2): n matrices of n x n
+            // rows (dim 2): n matrices of n x n per cube
             ax.src = w.T0; ax.lds = n; ax.bs_src = n * n; ax.dst = w.T1; ax.ldd = n; ax.bs_dst = n * n; ax.R = n; ax.C = n;
-            WL_E((launch_lift_axis_id<T, 1>(id, st, ax, n, cu_count)));
+            WL_E((launch_lift_axis_id<T, 1>(id, st, ax, n * nvol, cu_count)));
             // columns (dim 1): the low-low corner sends its approximation on to the next level's buffer
-            sa.b = nullptr; sa.b2 = sa.b3 = 0;
-            sa.a = w.T1; sa.a2 = n; sa.a3 = n * n;
-            sa.o0 = y; sa.o02 = y1; sa.o03 = y2; sa.o1 = y + h; sa.o12 = y1; sa.o13 = y2;
-            sa.ll = last ? (T *)nullptr : llbuf; sa.ll2 = h; sa.ll3 = h * h; sa.l2 = (int)h; sa.l3 = h;
-            WL_E((launch_lift_short_id<T, 1>(id, st, sa, (int)n, (int)n, n)));
-            cur = llbuf; c1 = h; c2 = h * h; pp ^= 1;
+            sa.b = nullptr; sa.b2 = sa.b3 = 0; sa.bv = 0;
+            sa.a = w.T1; sa.a2 = n; sa.a3 = n * n; sa.av = (int)(n * n * n);
+            sa.o0 = y; sa.o02 = y1; sa.o03 = y2; sa.o0v = (int)ys; sa.o1 = y + h; sa.o12 = y1; sa.o13 = y2; sa.o1v = (int)ys;
+            sa.ll = last ? (T *)nullptr : llbuf; sa.ll2 = h; sa.ll3 = h * h; sa.llv = (int)(h * h * h); sa.l2 = (int)h; sa.l3 = h;
+            sa.vsh = lg2(n); sa.vmask = n - 1;
+            WL_E((launch_lift_short_id<T, 1>(id, st, sa, (int)n, (int)n, n * nvol)));
+            cur = llbuf; c1 = h; c2 = h * h; cv = nvol > 1 ? h * h * h : 0; pp ^= 1;
         }
     } else {
         const T *llsrc = nullptr;
         int pp = 0;
         int l_top = L;
-        // the deepest levels (outputs of <= 32^3 Float32 / 16^3 Float64) inside one workgroup's LDS (k_tail_lift3d)
+        // the deepest levels (outputs of <= 32^3 Float32 / 16^3 Float64) inside one workgroup's LDS (k_tail_lift3d), a workgroup per cube:
+        // each writes its cube's slot of the ping-pong buffer (or its cube of y)
         if ((id == 1 || id == 3 || id == 5) && l_env("WL_LIFT_TAIL3D", 1) != 0 && tail_lift3d_ok<T>(id, n0 >> (L - 1))) {
             int lt = L;
             while (lt > 1 && tail_lift3d_ok<T>(id, n0 >> (lt - 2))) --lt;
             const int64_t m0 = n0 >> (lt - 1);
             T *out = (lt == 1) ? y : (pp ? w.B : w.A);
-            WL_E((launch_tail_lift3d<T, 0>(id, st, sc, x, y1, y2, out, (lt == 1) ? y1 : m0, (lt == 1) ? y2 : m0 * m0, (int)m0, L - lt + 1)));
+            WL_E((launch_tail_lift3d<T, 0>(id, st, sc, x, y1, y2, out, (lt == 1) ? y1 : m0, (lt == 1) ? y2 : m0 * m0, (int)m0, L - lt + 1, nvol, xs,
+                                           (lt == 1) ? ys : m0 * m0 * m0)));
             llsrc = out; pp ^= 1;
             l_top = lt - 1;
         }
@@ -3267,38 +3349,43 @@ int lifting_3d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, T *y, co
                 q2.norm1 = ax.norm1; q2.norm2 = ax.norm2;
                 q2.src = x; q2.lds = y1; q2.y = w.T1; q2.ldy = n; q2.ll = const_cast<T *>(llsrc); q2.ldl = h; q2.n0 = n; q2.n1 = n;
                 q2.bs_src = y2; q2.bs_y = n * n; q2.bs_ll = h * h; q2.nll = (int)h;
-                if (id == 1) WL_E((launch_lift2d_inv<T, 1>(st, q2, cu_count, n)));
-                else if (id == 3) WL_E((launch_lift2d_inv<T, 3>(st, q2, cu_count, n)));
-                else WL_E((launch_lift2d_inv<T, 5>(st, q2, cu_count, n)));
+                q2.vsh = lg2(n); q2.vs = (int)xs;
+                if (id == 1) WL_E((launch_lift2d_inv<T, 1>(st, q2, cu_count, n * nvol)));
+                else if (id == 3) WL_E((launch_lift2d_inv<T, 3>(st, q2, cu_count, n * nvol)));
+                else WL_E((launch_lift2d_inv<T, 5>(st, q2, cu_count, n * nvol)));
                 planes = true;
             }
             if (!planes) {
-            // columns first: merged lines into T0 (dense n^3); the low-low corner reads the deeper reconstruction
-            sa.o1 = nullptr; sa.o12 = sa.o13 = 0;
-            sa.a = x; sa.a2 = y1; sa.a3 = y2; sa.b = x + h; sa.b2 = y1; sa.b3 = y2;
-            sa.o0 = w.T0; sa.o02 = n; sa.o03 = n * n;
-            sa.ll = const_cast<T *>(llsrc); sa.ll2 = h; sa.ll3 = h * h; sa.l2 = (int)h; sa.l3 = h;
-            WL_E((launch_lift_short_id<T, 0>(id, st, sa, (int)n, (int)n, n)));
+            // columns first: merged lines into T0 (dense n^3 per cube); the low-low corner reads the deeper reconstruction
+            sa.o1 = nullptr; sa.o12 = sa.o13 = 0; sa.o1v = 0;
+            sa.a = x; sa.a2 = y1; sa.a3 = y2; sa.av = (int)xs; sa.b = x + h; sa.b2 = y1; sa.b3 = y2; sa.bv = (int)xs;
+            sa.o0 = w.T0; sa.o02 = n; sa.o03 = n * n; sa.o0v = (int)(n * n * n);
+            sa.ll = const_cast<T *>(llsrc); sa.ll2 = h; sa.ll3 = h * h; sa.llv = (int)(h * h * h); sa.l2 = (int)h; sa.l3 = h;
+            sa.vsh = lg2(n); sa.vmask = n - 1;
+            WL_E((launch_lift_short_id<T, 0>(id, st, sa, (int)n, (int)n, n * nvol)));
             // rows (dim 2)
             ax.src = w.T0; ax.lds = n; ax.bs_src = n * n; ax.dst = w.T1; ax.ldd = n; ax.bs_dst = n * n; ax.R = n; ax.C = n;
-            WL_E((launch_lift_axis_id<T, 0>(id, st, ax, n, cu_count)));
+            WL_E((launch_lift_axis_id<T, 0>(id, st, ax, n * nvol, cu_count)));
             }
-            // planes (dim 3); the result of level 1 goes to y (dense cube), deeper ones to the dense n^3 buffer
-            ax.src = w.T1; ax.lds = n * n; ax.bs_src = 0; ax.dst = out; ax.ldd = (l == 1) ? y2 : n * n; ax.bs_dst = 0; ax.R = n * n; ax.C = n;
-            WL_E((launch_lift_axis_id<T, 0>(id, st, ax, 1, cu_count)));
+            // planes (dim 3); the result of level 1 goes to y (dense cubes, ys apart), deeper ones to the dense n^3 slots of the buffer
+            ax.src = w.T1; ax.lds = n * n; ax.bs_src = nvol > 1 ? n * n * n : 0; ax.dst = out; ax.ldd = (l == 1) ? y2 : n * n;
+            ax.bs_dst = (l == 1) ? ys : (nvol > 1 ? n * n * n : 0); ax.R = n * n; ax.C = n;
+            WL_E((launch_lift_axis_id<T, 0>(id, st, ax, nvol, cu_count)));
             llsrc = out; pp ^= 1;
         }
     }
 #undef WL_E
 #undef WL_EL
     *handled = 1;
-    if (kernel_name) *kernel_name = "k_lift_axis_stream+k_lift_short_lines";
+    if (kernel_name) *kernel_name = nvol > 1 ? "k_lift_axis_stream+k_lift_short_lines_batch" : "k_lift_axis_stream+k_lift_short_lines";
     return WL_OK;
 }
 template int lifting_3d_fast<float>(void *, int, hipStream_t, int64_t, float *, const float *, const LiftScheme<float> &, int, int, int *,
-                                    const char **, int *);
+                                    const char **, int *, int64_t, int64_t, int64_t);
 template int lifting_3d_fast<double>(void *, int, hipStream_t, int64_t, double *, const double *, const LiftScheme<double> &, int, int,
-                                     int *, const char **, int *);
+                                     int *, const char **, int *, int64_t, int64_t, int64_t);
+template int64_t lifting_3d_fast_ws<float>(const LiftScheme<float> &, int64_t, int, int, const float *, const float *, int64_t, int64_t, int64_t);
+template int64_t lifting_3d_fast_ws<double>(const LiftScheme<double> &, int64_t, int, int, const double *, const double *, int64_t, int64_t, int64_t);
 
 template int lifting_2d_fast<float>(void *, int, hipStream_t, int64_t, int64_t, float *, const float *, const LiftScheme<float> &,
                                     int, int, int *, const char **, int *, int64_t, int64_t);

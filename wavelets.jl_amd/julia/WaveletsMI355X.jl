@@ -241,7 +241,7 @@ for (f, fw) in ((:dwt_batch, true), (:idwt_batch, false))
 end
 
 # ---- a batch of independent volumes: x[:, :, :, i] -> dwt(x[:, :, :, i], filter, L), every level of the one-launch 3-D kernels ONE
-#      launch over all volumes (orthogonal filters only: there is no batched lifting transform of volumes) ----
+#      launch over all volumes (lifting schemes on cubes: the GLS method below) ----
 for (f, fw) in ((:dwt_batch, true), (:idwt_batch, false))
     @eval function $f(x::ROCArray{T,4}, filter::OrthoFilter,
                       L::Integer=minimum(Util.maxtransformlevels(size(x, d)) for d in 1:3)) where {T<:Union{Float32,Float64}}
@@ -265,6 +265,21 @@ for (f, fw) in ((:dwt_batch, true), (:idwt_batch, false))
                      Cdouble, Cdouble, Cint, Cint, Ptr{Cvoid}),
                     ctx(), DT[T], pointer(y), pointer(x), Int64[size(x, 1), size(x, 2)], size(x, 3), size(x, 1) * size(x, 2),
                     length(isup), isup, nc, sh, cf, scheme.norm1, scheme.norm2, L, $fw, stream()))
+        return y
+    end
+end
+
+# ... and a batch of cubes (wl_dwt_lifting_batch3: every launch of the single cube's level loop ONE launch over all volumes)
+for (f, fw) in ((:dwt_batch, true), (:idwt_batch, false))
+    @eval function $f(x::ROCArray{T,4}, scheme::GLS,
+                      L::Integer=minimum(Util.maxtransformlevels(size(x, d)) for d in 1:3)) where {T<:Union{Float32,Float64}}
+        y = similar(x)
+        isup, nc, sh, cf = flatten(scheme)
+        GC.@preserve y x check(ccall((:wl_dwt_lifting_batch3, LIB), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Int64, Int64, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64},
+                     Cdouble, Cdouble, Cint, Cint, Ptr{Cvoid}),
+                    ctx(), DT[T], pointer(y), pointer(x), Int64[size(x, 1), size(x, 2), size(x, 3)], size(x, 4),
+                    size(x, 1) * size(x, 2) * size(x, 3), length(isup), isup, nc, sh, cf, scheme.norm1, scheme.norm2, L, $fw, stream()))
         return y
     end
 end
@@ -407,7 +422,7 @@ function Threshold.denoise(x::ROCArray{T,N}, wt::GLS;
                            estnoise::Function=noisest, TI::Bool=false,
                            nspin::Union{Int,Tuple}=tuple([8 for i = 1:ndims(x)]...)) where {T<:Union{Float32,Float64},N,S<:DNFT}
     nspt = nspin isa Int ? (nspin,) : nspin
-    if !(TI && (N == 1 || (N == 2 && length(nspt) == 2)) && get(THCODE, typeof(dnt.th), Cint(9)) <= 3)
+    if !(TI && (N == 1 || (N == 2 && length(nspt) == 2) || (N == 3 && length(nspt) == 3)) && get(THCODE, typeof(dnt.th), Cint(9)) <= 3)
         return invoke(Threshold.denoise, Tuple{AbstractArray,Union{Wavelets.WT.DiscreteWavelet,Nothing}}, x, wt;
                       L=L, dnt=dnt, estnoise=estnoise, TI=TI, nspin=nspin)
     end
@@ -416,7 +431,7 @@ function Threshold.denoise(x::ROCArray{T,N}, wt::GLS;
     estnoise === noisest || (sigma >= 0 && sigma * dnt.t >= 0) || throw(AssertionError("t >= 0"))
     y = similar(x)
     isup, nc, sh, cf = flatten(wt)
-    nsp = N == 1 ? Int64[prod(nspt), 1, 1] : Int64[nspt..., 1]
+    nsp = N == 1 ? Int64[prod(nspt), 1, 1] : (N == 2 ? Int64[nspt..., 1] : Int64[nspt...])
     GC.@preserve y x check(ccall((:wl_denoise_ti_lifting, LIB), Cint,
                 (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Int64}, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64},
                  Cdouble, Cdouble, Cint, Cint, Cdouble, Ptr{Int64}, Cdouble, Ptr{Cvoid}),

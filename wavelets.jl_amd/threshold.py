@@ -251,10 +251,11 @@ def denoise(x, wt=_DEFAULT, L: Optional[int] = None, dnt: Optional[DNFT] = None,
             return y
         # (no room for the batch's workspace -- about ws + 2 N prod(nspin) elements, 5.5 N for one spin: the reference's own
         #  sequence below runs the same device kernels one spin at a time and needs only the transform's two buffers)
-    if (TI and isinstance(wt, GLS) and (x.dim() == 1 or (x.dim() == 2 and len(nsp) == 2)) and isinstance(dnt.th, THType)
-            and dnt.th.code is not None and 0 <= dnt.th.code <= 3):
+    if (TI and isinstance(wt, GLS) and (x.dim() == 1 or (x.dim() == 2 and len(nsp) == 2) or (x.dim() == 3 and len(nsp) == 3))
+            and isinstance(dnt.th, THType) and dnt.th.code is not None and 0 <= dnt.th.code <= 3):
         # the same device-resident batch for a lifting scheme (wl_denoise_ti_lifting, round 4): shifted signals as one
-        # batched-lines transform, shifted images one batched 2-D lifting transform per group of spins; sigma never leaves the device
+        # batched-lines transform, shifted images one batched 2-D and shifted cubes one batched 3-D lifting transform per group of
+        # spins; sigma never leaves the device
         sig = -1.0 if estnoise is noisest else float(estnoise(x, wt))
         if estnoise is not noisest and not (sig >= 0 and sig * float(dnt.t) >= 0):
             raise AssertionError("t >= 0")

@@ -468,16 +468,18 @@ def _xwt_batch(x, wt, L, fw, y=None):
     """x: n0 x n1 x B (column-major: image i = x[:, :, i]); every image gets its own 2-D transform, all in one chain of
     launches (wl_dwt_filter_batch for an orthogonal filter, wl_dwt_lifting_batch for a lifting scheme).  The reference has no
     batched form: this equals `stack(dwt(x[:, :, i], wt, L) for i)`.
-    x: n0 x n1 x n2 x B with an orthogonal filter: a batch of volumes, volume i = x[:, :, :, i] (wl_dwt_filter_batch3); there is
-    no batched lifting transform of volumes."""
+    x: n0 x n1 x n2 x B: a batch of volumes, volume i = x[:, :, :, i] -- any box with an orthogonal filter
+    (wl_dwt_filter_batch3), cubes with a lifting scheme (wl_dwt_lifting_batch3; y may be x).  A 4-D array that is no batch of cubes
+    raises TypeError with a lifting scheme ("defined for cubes only": the method does not exist for it), where the C entry point
+    reports WL_EINVAL_CUBE -- the one place where this mirror differs from the ABI."""
     if not isinstance(wt, (OrthoFilter, GLS)):
         raise TypeError("dwt_batch is defined for orthogonal filters and lifting schemes")
     if isinstance(x, torch.Tensor):
-        if x.dim() == 4 and isinstance(wt, GLS):
-            raise TypeError("dwt_batch of volumes (n0 x n1 x n2 x B) is defined for orthogonal filters only")
+        if x.dim() == 4 and isinstance(wt, GLS) and not (int(x.shape[0]) == int(x.shape[1]) == int(x.shape[2])):
+            raise TypeError("dwt_batch of volumes (n0 x n1 x n2 x B) with a lifting scheme is defined for cubes only")
         if x.dim() not in (3, 4):
             raise TypeError("dwt_batch expects an n0 x n1 x B array (images) or an n0 x n1 x n2 x B array (volumes)")
-        if isinstance(wt, GLS) and int(x.shape[0]) != int(x.shape[1]):
+        if x.dim() == 3 and isinstance(wt, GLS) and int(x.shape[0]) != int(x.shape[1]):
             raise ArgumentError("array must be square/cube")          # what dwt(x[:, :, i], wt::GLS) raises (transforms_lifting.jl:131-132)
     x = _prep_in(x, maxdim=4)                # (a batch of volumes is the one 4-D array the package takes)
     if x.dim() == 4:
@@ -511,6 +513,13 @@ def _xwt_batch3(x, wt, L, fw, y):
     lib = _lib.load()
     h, st = _context(x.device)
     dims = (C.c_int64 * 3)(n0, n1, n2)
+    if isinstance(wt, GLS):
+        iu, nc, sh, cf = wt.flatten()
+        # (y may be x: the in-place transform of every volume)
+        rc = lib.wl_dwt_lifting_batch3(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), dims, nb, n0 * n1 * n2,
+                                       len(iu), _i32p(iu), _i32p(nc), _i32p(sh), _f64p(cf), wt.norm1, wt.norm2, L, 1 if fw else 0, st)
+        _check(rc, h)
+        return y
     q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
     rc = lib.wl_dwt_filter_batch3(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), dims, nb, n0 * n1 * n2,
                                   _f64p(q), len(q), L, 1 if fw else 0, st)
