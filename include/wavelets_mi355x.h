@@ -350,6 +350,63 @@ WL_API int wl_denoise_ti_lifting(wl_ctx *ctx, int dtype, void *y, const void *x,
                           const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2,
                           int L, int th, double t_unit, const int64_t *nspin, double sigma_host, void *stream);
 
+/* ---- denoise of a batch of independent units: per-unit noise estimates and thresholds on the device ---------------------- */
+/* result[i] = mad!(y[i*stride .. i*stride + n)) for i < nunits: per-unit Statistics.median!, abs deviations, median! again
+ * (denoising.jl:103-110), each in the element type and widened to double.  y is overwritten by the absolute deviations of its
+ * unit, the padding between units is never written.  result: DEVICE pointer, nunits doubles.  NaN in a unit -> NaN for that
+ * unit only.  One workgroup per unit: the keys of a unit of up to 8192 Float32 / 4096 Float64 values (context option
+ * WL_MAD_LDS_MAX lowers the limit; 0 = never) live in LDS (k_mad_units_lds); a longer unit is streamed from memory once per radix
+ * byte with the histograms in LDS (k_mad_units_stream).  No workspace.  Enqueues only: no synchronisation, capturable in a
+ * hipGraph.  Status codes in this order: WL_EINVAL_ARG (NULL pointers), WL_EINVAL_DTYPE, WL_EDIMS (n < 1, nunits < 1,
+ * stride < n), WL_EINVAL_SIZE (n >= 2^31: the per-unit counters are 32-bit).                                                */
+WL_API int wl_mad_batch(wl_ctx *ctx, int dtype, void *y, int64_t n, int64_t nunits, int64_t stride, double *result, void *stream);
+
+/* y[.., i] = denoise(x[.., i], OrthoFilter(qmf); L, dnt = (th, t_unit), TI = false) for nunits independent units:
+ * ndims = 1 signals of dims[0] samples, 2 square images, 3 cubes (WL_EINVAL_CUBE otherwise), unit i at element offset
+ * i * unit_stride (>= prod(dims)) of x and of y.  Per unit, the reference's own sequence (denoising.jl:30, 69-78):
+ * sigma_i = noisest(x_i, wt) = mad!(level-1 detail range, linear indexing: rows [n0/2, n0) of the first column) / 0.6745,
+ * c = dwt(x_i, wt, L); threshold!(c, th, sigma_i * t_unit) with the product in Float64; y_i = idwt(c, wt, L).
+ * Same bits as nunits single calls.  ONE forward transform per unit: for L >= 1 the level-1 detail range of the L-level
+ * coefficients is final after level 1 (deeper levels touch only the low corner), so sigma_i is read from the coefficients the
+ * denoise needs anyway; L = 0 with sigma_in == NULL runs a level-1 batch for the estimate alone (dwt / idwt are copies then).
+ * The transforms are the level loops of wl_dwtc_filter / wl_dwt_filter_batch / wl_dwt_filter_batch3 over all units of a group, the
+ * noise estimate one launch (the kernels of wl_mad_batch, reading the coefficients without overwriting them), the threshold one
+ * launch with t read per unit.  Where those level loops run every level over all units at once (lines and images; cubes with
+ * filters of up to 10 taps; the lifting schemes the fast tiers accept) the number of launches does not depend on nunits within a
+ * group; cubes with longer filters, the generic lifting fallback and the cube-after-cube fallback of wl_dwt_lifting_batch3
+ * transform unit after unit, as they do in those entry points, and only the estimate and the threshold are one launch each
+ * there.  x is not modified; the padding
+ * between units of y is never written.
+ * sigma_in: optional DEVICE array of nunits doubles used instead of the estimate (a custom estnoise; not validated);
+ * sigma_out: optional DEVICE array that receives the sigma used for each unit.
+ * th: WL_TH_HARD..WL_TH_STEIN; t_unit >= 0.  Enqueues only: no synchronisation, capturable in a hipGraph once the workspace is
+ * held.  Status codes in this order: WL_EINVAL_ARG (NULL ctx / y / x / dims / qmf, th outside 0..3, t_unit negative or NaN),
+ * WL_EINVAL_DTYPE, WL_EINVAL_FILTER, WL_EINVAL_CUBE, WL_EDIMS (ndims outside 1..3, an extent or nunits < 1, unit_stride <
+ * prod(dims), an extent whose unit no int64 stride holds), WL_EINVAL_L, WL_EINVAL_SIZE (no 2^L factor, or an odd extent when the
+ * estimate is needed -- sigma_in == NULL -- because noisest needs level 1), WL_EALIAS (y == x).
+ * Workspace (wl_workspace_bytes_full does not cover it), with N = prod(dims), S = unit_stride and G units per group -- all
+ * nunits, halved until the sum is below the context's cap (option WL_TI_WS_CAP_MB, default 8192) and at most 65535; groups
+ * change no bit --, each part rounded up to 256 bytes:
+ *   the transform workspace of a group    signals / images: 2 * (G N / 2^ndims + 64) + 3 G N + 64 elements,
+ *                                         cubes: 2 * (G * (N / 8) + 64) + 3 N + 64 elements
+ * + the coefficients C of the group       G * S elements (the caller's stride)
+ * + the sigmas of the group               G doubles.                                                                          */
+WL_API int wl_denoise_batch_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims,
+                                   int64_t nunits, int64_t unit_stride, const double *qmf, int flen, int L, int th,
+                                   double t_unit, const double *sigma_in, double *sigma_out, void *stream);
+/* The same for a GLS (scheme arguments as wl_dwt_lifting): out-of-place forward x -> y (the level loops of wl_dwtc_lifting_oop /
+ * wl_dwt_lifting_batch / wl_dwt_lifting_batch3 with their fallbacks for schemes and strides the fast tiers refuse), the estimate and
+ * the threshold on y, the inverse in place on y.  y == x is allowed.  Status codes in the order above with WL_EINVAL_SCHEME in the
+ * place of WL_EINVAL_FILTER and no WL_EALIAS.  Workspace: the lifting transform workspace of a group -- signals / images
+ * 2 * (G N / 2 + 64) + 3 G N + 64 elements; cubes the larger of 2 * (G * (N / 8) + 64) + 2 G N + 64 and one cube's
+ * 2 * (N / 2 + 64) + 3 N + 64 -- + G doubles, + G * S elements only for L = 0 with sigma_in == NULL (the level-1 coefficients
+ * of the estimate).                                                                                                           */
+WL_API int wl_denoise_batch_lifting(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims,
+                                    int64_t nunits, int64_t unit_stride, int nsteps, const int32_t *step_is_update,
+                                    const int32_t *step_ncoef, const int32_t *step_shift, const double *coefs_flat,
+                                    double norm1, double norm2, int L, int th, double t_unit,
+                                    const double *sigma_in, double *sigma_out, void *stream);
+
 /* ---- best-basis search of packet trees (src/Threshold/entropy.jl) ----------------------- */
 /* Entropy measures: ShannonEntropy (-s log s) and LogEnergyEntropy (-log s) of s = (x / nrm)^2; s == 0 contributes -0.0.    */
 enum wl_entropy { WL_ENTROPY_SHANNON = 0, WL_ENTROPY_LOGENERGY = 1 };

@@ -1,10 +1,12 @@
 """Launches per call from a kernel trace of `tools/time_batch.py launches`:
 
     rocprofv3 --kernel-trace --output-format csv -d <dir> -- python tools/time_batch.py launches > calls.txt
-    python tools/count_launches.py <dir> calls.txt
+    python tools/count_launches.py <dir> calls.txt [--all]
 
 The traced script separates its calls by fills of a marker tensor; the library's kernels (namespace wl) dispatched between
-fill k and fill k + 1 are the launches of call k.  Markdown rows: call, launches, kernels in dispatch order.
+fill k and fill k + 1 are the launches of call k.  Markdown rows: call, launches, kernels in dispatch order.  --all counts every
+kernel between the fills (the callers around the hot path live outside namespace wl, and a host loop adds torch's own kernels),
+runs of one kernel folded to `name x count`.
 """
 import csv
 import glob
@@ -13,7 +15,7 @@ import re
 import sys
 
 
-def main(trace_dir, calls_txt):
+def main(trace_dir, calls_txt, every=False):
     files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
     if not files:
         sys.exit("no *kernel_trace.csv under " + trace_dir)
@@ -31,10 +33,19 @@ def main(trace_dir, calls_txt):
     print("| call | launches | kernels |")
     print("|---|---|---|")
     for k, label in enumerate(labels):
-        names = [re.sub(r"^void ", "", re.sub(r"\(.*$", "", n)) for _, n in rows[fills[k] + 1:fills[k + 1]] if "wl::" in n]
-        short = [re.sub(r"<.*$", "", n.split("wl::")[-1].replace("(anonymous namespace)::", "")) for n in names]
+        names = [re.sub(r"^void ", "", re.sub(r"\(.*$", "", n.replace("(anonymous namespace)::", ""))) for _, n in rows[fills[k] + 1:fills[k + 1]]
+                 if every or "wl::" in n]
+        short = [re.sub(r"<.*$", "", n.split("wl::")[-1]) for n in names]
+        if every:
+            folded = []
+            for n in short:
+                if folded and folded[-1][0] == n:
+                    folded[-1][1] += 1
+                else:
+                    folded.append([n, 1])
+            short = [n if c == 1 else "%s x %d" % (n, c) for n, c in folded]
         print("| %s | %d | %s |" % (label, len(names), ", ".join(short)))
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2])
+    main(sys.argv[1], sys.argv[2], "--all" in sys.argv[3:])

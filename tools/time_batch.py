@@ -11,6 +11,13 @@
     python tools/time_batch.py lifting_volumes    batch of cubes (cdf9/7, Float32, full depth): wl_dwt_lifting_batch3 against the same
                                           number of single wl_dwt_lifting_oop calls, forward and inverse, rotating inputs
     python tools/time_batch.py lifting_denoise3d  W.denoise(cube, cdf9/7 scheme, TI=True) with the default 8 x 8 x 8 spins, host wall time
+    python tools/time_batch.py denoise_batch [reps [case ...]]   one W.denoise_batch call against the loop of single W.denoise calls
+                                          over the units, host wall time, the two alternating; on a build without denoise_batch the
+                                          loop alone (the baseline a user runs today)
+    python tools/time_batch.py denoise_batch_launches   one batched call at two unit counts and the loop over the units, a torch
+                                          fill between them (the inputs and warm calls of a case get an interval of their own), the
+                                          timed cases and three 16-tap ones: run it under `rocprofv3 --kernel-trace` and count
+                                          with `tools/count_launches.py <dir> calls.txt --all`
 """
 import os, sys, statistics
 import torch
@@ -201,8 +208,104 @@ def denoise3d_table(wt=None, cubes=((32, 7), (64, 7), (128, 5)), label="sym5"):
               f"{W.last_kernel()} |", flush=True)
 
 
+DENOISE_BATCH_CASES = (("1024 x 256^2 sym5", (256, 256, 1024), "sym5", False), ("64 x 2048^2 sym5", (2048, 2048, 64), "sym5", False),
+                       ("4096 x 2^14 db4", (1 << 14, 4096), "db4", False), ("65536 x 2^10 db4", (1 << 10, 65536), "db4", False),
+                       ("512 x 32^3 sym5", (32, 32, 32, 512), "sym5", False), ("256 x 256^2 cdf9/7 lifting", (256, 256, 256), "cdf97", True),
+                       # few, very long units: the detail range (2^19 values) is past the LDS limit, the streaming MAD runs
+                       ("8 x 2^20 db4", (1 << 20, 8), "db4", False))
+
+
+def denoise_batch_table(reps=21, cases=None):
+    """medians of `reps` repetitions on three rotating inputs, min .. max beside them: host wall time around a final synchronise,
+    the batched call and the loop alternating in one run"""
+    import time
+    have_batch = hasattr(W, "denoise_batch")
+    print("| batch (Float32) | denoise_batch ms (min .. max) | kernel | loop of W.denoise ms (min .. max) | speed-up |")
+    print("|---|---|---|---|---|")
+    for k, (label, shape, wname, lifting) in enumerate(DENOISE_BATCH_CASES):
+        if cases and k not in cases:
+            continue
+        wt = W.wavelet(getattr(W.WT, wname), W.WT.Lifting) if lifting else W.wavelet(getattr(W.WT, wname))
+        nb = shape[-1]
+        ramp = torch.linspace(0, 1, shape[0], device="cuda").reshape((shape[0],) + (1,) * (len(shape) - 1))
+        xs = [W.julia_layout(ramp + 0.05 * torch.randn(*shape, device="cuda")) for _ in range(3)]
+        y = W.similar(xs[0])
+
+        def loop(x):
+            for i in range(x.shape[-1]):
+                W.denoise(x[..., i], wt)
+
+        def wall(f, x):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f(x)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        batch = (lambda x: W.denoise_batch(x, wt, y=y)) if have_batch else None
+        kb = "-"
+        if have_batch:
+            batch(xs[0])
+            kb = W.last_kernel()
+        loop(xs[0][..., :min(nb, 8)])
+        tb, tl = [], []
+        for r in range(reps):
+            if have_batch:
+                tb.append(wall(batch, xs[r % 3]))
+            tl.append(wall(loop, xs[r % 3]))
+        tb.sort(); tl.sort()
+        bt = f"{statistics.median(tb):.3f} ({tb[0]:.3f} .. {tb[-1]:.3f})" if tb else "-"
+        sp = f"{statistics.median(tl) / statistics.median(tb):.1f}" if tb else "-"
+        print(f"| {label} | {bt} | {kb} | {statistics.median(tl):.3f} ({tl[0]:.3f} .. {tl[-1]:.3f}) | {sp} |", flush=True)
+        del xs, y
+
+
+def denoise_batch_launches():
+    """the batched call at B = 8 and B = 32 units (the launch count must not depend on B) and the loop of W.denoise over 8 units"""
+    mark = torch.zeros(1024, device="cuda")
+    k = 0
+    # (db8: 16 taps, the long-filter family that the batched level loops run unit after unit on images and cubes)
+    extra = (("32 x 2^10 db8", (1 << 10, 32), "db8", False), ("32 x 64^2 db8", (64, 64, 32), "db8", False), ("32 x 32^3 db8", (32, 32, 32, 32), "db8", False))
+    for label, shape, wname, lifting in DENOISE_BATCH_CASES + extra:
+        wt = W.wavelet(getattr(W.WT, wname), W.WT.Lifting) if lifting else W.wavelet(getattr(W.WT, wname))
+        torch.cuda.synchronize()
+        mark.fill_(float(k))                                 # (the inputs and the warm calls of a case get an interval of their own)
+        torch.cuda.synchronize()
+        x = W.julia_layout(torch.randn(*shape[:-1], 32, device="cuda"))
+        x8 = W.julia_layout(x[..., :8])
+        y, y8 = W.similar(x), W.similar(x8)
+        W.denoise_batch(x, wt, y=y)
+        W.denoise(x8[..., 0], wt)
+        torch.cuda.synchronize()
+        print(f"call {k}: (inputs and warm calls, {label.split(' x ', 1)[1]})", flush=True)
+        k += 1
+
+        def loop():
+            for i in range(8):
+                W.denoise(x8[..., i], wt)
+
+        unit = label.split(" x ", 1)[1]
+        for lab, f in ((f"denoise_batch 32 x {unit}", lambda: W.denoise_batch(x, wt, y=y)), (f"denoise_batch 8 x {unit}", lambda: W.denoise_batch(x8, wt, y=y8)),
+                       (f"loop of 8 W.denoise, {unit}", loop)):
+            torch.cuda.synchronize()
+            mark.fill_(float(k))
+            torch.cuda.synchronize()
+            f()
+            torch.cuda.synchronize()
+            print(f"call {k}: {lab}", flush=True)
+            k += 1
+    mark.fill_(float(k))
+    torch.cuda.synchronize()
+
+
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "filter"
+    if mode == "denoise_batch":
+        denoise_batch_table(int(sys.argv[2]) if len(sys.argv) > 2 else 21, [int(a) for a in sys.argv[3:]])
+        sys.exit(0)
+    if mode == "denoise_batch_launches":
+        denoise_batch_launches()
+        sys.exit(0)
     {"filter": filter_table, "lifting": lifting_table, "launches": lifting_launches, "volumes": volumes_table,
      "denoise3d": denoise3d_table, "lifting_volumes": lifting_volumes_table,
      "lifting_denoise3d": lambda: denoise3d_table(W.wavelet(W.WT.cdf97, W.WT.Lifting), ((32, 5), (64, 5)), "cdf9/7 (lifting)")}[mode]()

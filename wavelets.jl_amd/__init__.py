@@ -22,7 +22,8 @@ from .transforms import (dwt, idwt, dwt_, idwt_, dwt_oop_, idwt_oop_, dwtc, idwt
                          DimensionMismatch, ArgumentError, HIPError)
 from .modwt import modwt, imodwt, maxmodwttransformlevels
 from .threshold import (THType, HardTH, SoftTH, SemiSoftTH, SteinTH, BiggestTH, PosTH, NegTH, DEFAULT_TH, threshold, threshold_,
-                        DNFT, VisuShrink, denoise, noisest, mad_, median, nspin2circ, circshift, DEFAULT_WAVELET)
+                        DNFT, VisuShrink, denoise, noisest, mad_, median, nspin2circ, circshift, DEFAULT_WAVELET,
+                        denoise_batch, noisest_batch, mad_batch_)
 from .entropy import Entropy, ShannonEntropy, LogEnergyEntropy, coefentropy, bestbasistree
 from . import _lib
 
@@ -39,5 +40,6 @@ __all__ = [
     "modwt", "imodwt", "maxmodwttransformlevels",
     "THType", "HardTH", "SoftTH", "SemiSoftTH", "SteinTH", "BiggestTH", "PosTH", "NegTH", "DEFAULT_TH", "threshold", "threshold_",
     "DNFT", "VisuShrink", "denoise", "noisest", "mad_", "median", "nspin2circ", "circshift", "DEFAULT_WAVELET",
+    "denoise_batch", "noisest_batch", "mad_batch_",
     "Entropy", "ShannonEntropy", "LogEnergyEntropy", "coefentropy", "bestbasistree",
 ]

@@ -509,7 +509,9 @@ int ensure_aux(wl_ctx *ctx)
 
 // Small arrays (<= 8192 elements, e.g. the noise estimate of a 2-D array: the lower half of one column): the whole
 // median / mad! in ONE workgroup with the keys in LDS -- the multi-launch radix select above is launch-bound there.
-template <typename T>
+// (INST: a caller that must not share the instantiation of k_mad_lds -- and with it that kernel's inlining and register allocation --
+// asks for its own)
+template <typename T, int INST = 0>
 __device__ typename KeyOf<T>::U lds_select(const typename KeyOf<T>::U *keys, int n, unsigned long long k, unsigned int *hist,
                                              unsigned long long *sh)
 {
@@ -560,13 +562,13 @@ __device__ typename KeyOf<T>::U lds_select(const typename KeyOf<T>::U *keys, int
     __syncthreads();                // the next call re-initialises sh
     return r;
 }
-template <typename T>
+template <typename T, int INST = 0>
 __device__ T lds_median(typename KeyOf<T>::U *keys, int n, unsigned int *hist, unsigned long long *sh, unsigned int nan_count)
 {
     typedef typename KeyOf<T>::U U;
     const unsigned long long k1 = (unsigned long long)(n / 2), k0 = (n & 1) ? k1 : k1 - 1;
-    const U p0 = lds_select<T>(keys, n, k0, hist, sh);
-    const U p1 = (k1 == k0) ? p0 : lds_select<T>(keys, n, k1, hist, sh);
+    const U p0 = lds_select<T, INST>(keys, n, k0, hist, sh);
+    const U p1 = (k1 == k0) ? p0 : lds_select<T, INST>(keys, n, k1, hist, sh);
     const T a = KeyOf<T>::val(p0, 0), b = KeyOf<T>::val(p1, 0);
     T m = (p0 != p1) ? (a / 2 + b / 2) : a;
     if (nan_count) m = (T)NAN;
@@ -1144,6 +1146,355 @@ int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
     return WL_OK;
 }
 
+// ---- denoise of a batch of independent units (wl_mad_batch, wl_denoise_batch_filter, wl_denoise_batch_lifting) --------------
+// Per-unit noise estimate: k_mad_lds with blockIdx.x = unit, a strided source and result[unit].  write_back = 0 leaves the source
+// alone (the coefficients of a denoise are read, never overwritten by mad!: the deviations only ever exist as LDS keys).
+template <typename T>
+__global__ void __launch_bounds__(1024) k_mad_units_lds(T *v0, int n, int64_t stride, int write_back, double *__restrict__ result)
+{
+    typedef typename KeyOf<T>::U U;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    U *keys = reinterpret_cast<U *>(smem_raw);
+    __shared__ unsigned int hist[256];
+    __shared__ unsigned long long sh[2];
+    __shared__ unsigned int nans;
+    T *v = v0 + (int64_t)blockIdx.x * stride;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    if (tid == 0) nans = 0;
+    __syncthreads();
+    unsigned int mynan = 0;
+    for (int i = tid; i < n; i += nthr) {
+        const T x = v[i];
+        if (x != x) ++mynan;
+        keys[i] = KeyOf<T>::key(x, 0);
+    }
+    if (mynan) atomicAdd(&nans, mynan);
+    __syncthreads();
+    T m = lds_median<T, 1>(keys, n, hist, sh, nans);
+    __syncthreads();
+    for (int i = tid; i < n; i += nthr) {
+        const T d = KeyOf<T>::val(keys[i], 0) - m;
+        const T ad = d < 0 ? -d : d;
+        if (write_back) v[i] = ad;
+        keys[i] = KeyOf<T>::key(ad, 0);
+    }
+    __syncthreads();
+    m = lds_median<T, 1>(keys, n, hist, sh, nans);
+    if (tid == 0) result[blockIdx.x] = (double)m;
+}
+
+// the bin that holds rank kk among the 256 counts h[] -- first b with kk < h[0] + ... + h[b], 255 when none -- and the rank left
+// inside it: one wave, four bins per lane (the scan of lds_select)
+__device__ __forceinline__ void wave_pick_bin(const unsigned int *h, int lane, int shift, unsigned long long *prefix, unsigned long long *rank)
+{
+    const unsigned int h0 = h[4 * lane], h1 = h[4 * lane + 1], h2 = h[4 * lane + 2], h3 = h[4 * lane + 3];
+    const unsigned int mine = h0 + h1 + h2 + h3;
+    unsigned int incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned int o = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += o;
+    }
+    const unsigned long long kk = *rank;
+    const unsigned long long excl = incl - mine;
+    const unsigned long long m = __ballot(kk < (unsigned long long)incl);
+    const int first = m ? (__ffsll((long long)m) - 1) : 64;
+    if (lane == first) {
+        int b = 4 * lane;
+        unsigned long long cum = excl;
+        if (kk >= cum + h0) { cum += h0; ++b; if (kk >= cum + h1) { cum += h1; ++b; if (kk >= cum + h2) { cum += h2; ++b; } } }
+        *rank = kk - cum;
+        *prefix = *prefix | (((unsigned long long)b) << shift);
+    } else if (first == 64 && lane == 63) {          // (cannot happen for kk < n; mirrors the serial walk of k_sel_scan)
+        *rank = kk - (excl + h0 + h1 + h2);
+        *prefix = *prefix | (255ull << shift);
+    }
+}
+// Units too long for LDS keys: a workgroup per unit streams its n values from memory once per radix byte (the unit stays in L2 between
+// passes), the two histograms in LDS, both middle ranks resolved per pass (k_sel_hist / k_sel_scan without a selection state in
+// HBM and without global atomics).  The second median runs the same passes on |v - m| computed on the fly; the deviations are
+// stored only when write_back (wl_mad_batch).  Counters are 32-bit: n < 2^31.  blockDim.x >= 128 (a wave per rank picks its bin).
+template <typename T>
+__global__ void __launch_bounds__(1024) k_mad_units_stream(T *v0, int64_t n, int64_t stride, int write_back, double *__restrict__ result)
+{
+    typedef typename KeyOf<T>::U U;
+    constexpr int NB = KeyOf<T>::BYTES;
+    __shared__ unsigned int hist[2][256];
+    __shared__ unsigned long long pre[2], rk[2];
+    __shared__ unsigned int nans;
+    T *v = v0 + (int64_t)blockIdx.x * stride;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const unsigned long long k1 = (unsigned long long)(n / 2), k0 = (n & 1) ? k1 : k1 - 1;
+    T m0 = (T)0, m = (T)0;                      // median of the unit, then of its absolute deviations
+    for (int phase = 0; phase < 2; ++phase) {
+        __syncthreads();                        // (everybody has read pre[] of the first median)
+        if (tid == 0) {
+            pre[0] = pre[1] = 0; rk[0] = k0; rk[1] = k1;
+            if (phase == 0) nans = 0;
+        }
+        for (int pass = 0; pass < NB; ++pass) {
+            const int shift = 8 * (NB - 1 - pass);
+            for (int b = tid; b < 512; b += nthr) (&hist[0][0])[b] = 0;
+            __syncthreads();
+            const U p0 = (U)pre[0], p1 = (U)pre[1];
+            const bool same = (p0 == p1);
+            const U q0 = (pass == 0) ? (U)0 : (U)(p0 >> (shift + 8)), q1 = (pass == 0) ? (U)0 : (U)(p1 >> (shift + 8));
+            unsigned int mynan = 0;
+            for (int64_t i = tid; i < n; i += nthr) {
+                T x = v[i];
+                if (phase == 1) { const T d = x - m0; x = d < 0 ? -d : d; }
+                else if (pass == 0 && x != x) ++mynan;
+                const U key = KeyOf<T>::key(x, 0);
+                const U hi = (pass == 0) ? (U)0 : (U)(key >> (shift + 8));
+                const unsigned b = (unsigned)((key >> shift) & 0xff);
+                if (hi == q0) atomicAdd(&hist[0][b], 1u);
+                if (!same && hi == q1) atomicAdd(&hist[1][b], 1u);
+            }
+            if (mynan) atomicAdd(&nans, mynan);
+            __syncthreads();
+            const int w = tid >> 6;
+            if (w < 2) wave_pick_bin(hist[(same || w == 0) ? 0 : 1], tid & 63, shift, &pre[w], &rk[w]);
+            __syncthreads();
+        }
+        const U f0 = (U)pre[0], f1 = (U)pre[1];
+        const T a = KeyOf<T>::val(f0, 0), b = KeyOf<T>::val(f1, 0);
+        m = (f0 != f1) ? (a / 2 + b / 2) : a;
+        if (nans) m = (T)NAN;
+        if (phase == 0) m0 = m;
+    }
+    if (write_back)
+        for (int64_t i = tid; i < n; i += nthr) {
+            const T d = v[i] - m0;
+            v[i] = d < 0 ? -d : d;
+        }
+    if (tid == 0) result[blockIdx.x] = (double)m;
+}
+
+// result[u] = mad!(v[u * stride .. u * stride + n)) for u < nunits; *name = the kernel that ran
+template <typename T>
+int mad_units(wl_ctx *ctx, hipStream_t st, T *v, int64_t n, int64_t nunits, int64_t stride, int write_back, double *result, const char **name)
+{
+    int64_t lim = (int64_t)opt("WL_MAD_LDS_MAX", (long long)mad_lds_max<T>());
+    if (lim > mad_lds_max<T>()) lim = mad_lds_max<T>();       // (the keys must fit the 64 KiB of LDS a kernel gets)
+    const bool lds = n <= lim;
+    const int64_t chunk = (int64_t)1 << 20;                    // (grid size * block size stays below 2^32)
+    for (int64_t u0 = 0; u0 < nunits; u0 += chunk) {
+        const unsigned nb = (unsigned)((nunits - u0 < chunk) ? (nunits - u0) : chunk);
+        if (lds) {
+            const int threads = n >= 2048 ? 1024 : (n >= 256 ? 256 : 64);
+            hipLaunchKernelGGL((k_mad_units_lds<T>), dim3(nb), dim3(threads), (size_t)n * sizeof(typename KeyOf<T>::U), st, v + u0 * stride, (int)n,
+                               stride, write_back, result + u0);
+        } else {
+            const int threads = n >= 4096 ? 1024 : 256;
+            hipLaunchKernelGGL((k_mad_units_stream<T>), dim3(nb), dim3(threads), 0, st, v + u0 * stride, n, stride, write_back, result + u0);
+        }
+    }
+    WL_HIP(ctx, hipGetLastError());
+    *name = lds ? "k_mad_units_lds" : "k_mad_units_stream";
+    return WL_OK;
+}
+
+// sg[u] = the sigma of unit u: the caller's (a custom estnoise), or mad / 0.6745 of the estimate that sits in sg (noisest,
+// denoising.jl:100); sigma_out receives it
+__global__ void __launch_bounds__(EXT_THREADS) k_sigma_units(double *__restrict__ sg, int64_t nb, const double *__restrict__ sigma_in,
+                                                            double *__restrict__ sigma_out)
+{
+    const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= nb) return;
+    const double s = sigma_in ? sigma_in[u] : sg[u] / 0.6745;
+    sg[u] = s;
+    if (sigma_out) sigma_out[u] = s;
+}
+// threshold!(c_u, th, sigma[u] * t_unit) on the N elements of every unit u = blockIdx.y (unit stride `stride`; the padding between
+// units is not touched); the product in Float64 as k_threshold_dev forms it.  16-byte accesses where the unit's base allows them.
+template <typename T>
+__global__ void __launch_bounds__(EXT_THREADS) k_threshold_units(T *__restrict__ x, int64_t N, int64_t stride, int th, const double *__restrict__ sigma,
+                                                                 double t_unit)
+{
+    T *xu = x + (int64_t)blockIdx.y * stride;
+    const double t = sigma[blockIdx.y] * t_unit;
+    const int vec_ok = (reinterpret_cast<uintptr_t>(xu) & 15) == 0 ? 1 : 0;
+    ew_inplace<T>(xu, N, vec_ok, [=](T v, int64_t) { return threshold_one<T, double>(v, th, t); });
+}
+
+inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+// units per group: all of them, halved until the group's buffers fit under the context's cap (as the translation-invariant
+// batch), at most 65535 (a grid row / plane / workgroup per unit in the batched kernels); then the workspace is grown once
+template <typename F>
+int batch_group(wl_ctx *ctx, hipStream_t st, int64_t nunits, F need, int64_t &G)
+{
+    const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
+    G = nunits;
+    while (G > 1 && need(G) > cap) G = (G + 1) / 2;
+    if (G > 65535) G = 65535;
+    int rc = wl_ensure_ws(ctx, need(G), st, true);
+    while (rc == WL_ENOMEM && G > 1) {                      // (another allocator may own most of the HBM: smaller groups)
+        G = (G + 1) / 2;
+        rc = wl_ensure_ws(ctx, need(G), st, true);
+    }
+    return rc;
+}
+// estimate (or take), publish and apply the sigmas of one group: src = where the level-1 detail range of every unit is read from
+// (nullptr: sigma_in), coef = the coefficients that are thresholded
+template <typename T>
+int batch_sigma_threshold(wl_ctx *ctx, hipStream_t st, const T *src, T *coef, int64_t n0, int64_t N, int64_t nb, int64_t S, double *sg,
+                          const double *sigma_in, double *sigma_out, int th, double t_unit, const char **madk)
+{
+    if (!sigma_in) {
+        const int64_t lo = (int64_t)llround((double)n0 / 2 + 1) - 1, nd = n0 - lo;        // detailrange(n0, 1), 0-based half open
+        int rc = mad_units<T>(ctx, st, const_cast<T *>(src) + lo, nd, nb, S, 0, sg, madk);
+        if (rc != WL_OK) return rc;
+    } else {
+        *madk = "sigma_in";
+    }
+    hipLaunchKernelGGL(k_sigma_units, dim3((unsigned)((nb + EXT_THREADS - 1) / EXT_THREADS)), dim3(EXT_THREADS), 0, st, sg, nb, sigma_in, sigma_out);
+    hipLaunchKernelGGL((k_threshold_units<T>), dim3(ext_blocks(N, 4, ctx->cu_count), (unsigned)nb), dim3(EXT_THREADS), 0, st, coef, N, S, th, sg, t_unit);
+    WL_HIP(ctx, hipGetLastError());
+    return WL_OK;
+}
+
+// denoise(x_i, OrthoFilter; L, dnt, TI = false) of nunits units, unit i at element offset i * S: forward batch x -> C (workspace,
+// the caller's stride: a box shares its strides between source and destination), per-unit MAD read from C, per-unit threshold on C,
+// inverse batch C -> y.  For L >= 1 the level-1 detail range of the L-level coefficients is final after level 1 (later levels
+// touch only the low corner), so the one transform serves the estimate and the denoise; L = 0 with an estimate runs a level-1
+// batch for it alone and thresholds a copy of x (dwt and idwt are copies then, transforms_filter.jl:36-38).
+template <typename T>
+int denoise_batch_filter_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, int64_t nunits, int64_t S,
+                              const double *qmf, int flen, int L, int th, double t_unit, const double *sigma_in, double *sigma_out)
+{
+    const int64_t n0 = dims[0];
+    int64_t N = 1;
+    for (int d = 0; d < ndims; ++d) N *= dims[d];
+    const int64_t vdims[3] = {n0, n0, n0};
+    Taps<T> taps;
+    make_taps<T>(qmf, flen, taps);
+    auto tw_elems = [&](int64_t G) { return ndims == 3 ? ws_vols_elems(N, G) : ws_elems(N * G, ndims); };
+    auto need = [&](int64_t G) { return up256(tw_elems(G) * sizeof(T)) + up256((size_t)G * S * sizeof(T)) + up256((size_t)G * sizeof(double)); };
+    int64_t G = 1;
+    int rc = batch_group(ctx, st, nunits, need, G);
+    if (rc != WL_OK) return rc;
+    char *wsb = (char *)ctx->ws;
+    T *Cb = (T *)(wsb + up256(tw_elems(G) * sizeof(T)));
+    double *sg = (double *)(wsb + up256(tw_elems(G) * sizeof(T)) + up256((size_t)G * S * sizeof(T)));
+    const char *madk = "none", *kn = nullptr;
+    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
+        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
+        const T *xg = x + u0 * S;
+        T *yg = y + u0 * S;
+        BoxSpec bb;                                          // nb lines / images (cubes: a batch of volumes, not a box)
+        bb.nd = ndims + 1; bb.nt = ndims;
+        bb.dims[0] = n0; bb.dims[1] = (ndims == 2) ? n0 : nb; bb.dims[2] = (ndims == 2) ? nb : 1;
+        bb.full.s[0] = 1; bb.full.s[1] = (ndims == 2) ? n0 : S; bb.full.s[2] = (ndims == 2) ? S : S * nb;
+        auto fwd = [&](int lev) -> int {
+            return ndims == 3 ? filter_fwd_levels_vols<T>(wsb, true, ctx->cu_count, ctx->path, st, vdims, nb, S, S, Cb, xg, taps, lev, &kn, &ctx->last_hip)
+                              : filter_fwd_levels<T>(wsb, true, ctx->cu_count, ctx->path, st, bb, Cb, xg, taps, lev, &kn, &ctx->last_hip);
+        };
+        if (L > 0 || !sigma_in) {
+            rc = fwd(L > 0 ? L : 1);
+            if (rc == WL_RETRY_GEN) rc = WL_EINVAL_ARG;      // (the full workspace is held: no level can ask for more)
+            if (rc != WL_OK) return rc;
+        }
+        T *coef = Cb;
+        if (L == 0) {                                        // every unit is dense: one copy of an N x nb matrix with leading dimension S
+            const Strides3 s = {{1, S, 0}};
+            const Extent3 ext = {{N, nb, 1}};
+            WL_HIP(ctx, generic_copy_box<T>(st, xg, s, yg, s, ext));
+            coef = yg;
+        }
+        rc = batch_sigma_threshold<T>(ctx, st, Cb, coef, n0, N, nb, S, sg, sigma_in ? sigma_in + u0 : nullptr, sigma_out ? sigma_out + u0 : nullptr,
+                                      th, t_unit, &madk);
+        if (rc != WL_OK) return rc;
+        if (L > 0) {
+            rc = ndims == 3 ? filter_inv_levels_vols<T>(wsb, true, ctx->cu_count, ctx->path, st, vdims, nb, S, S, yg, Cb, taps, L, &kn, &ctx->last_hip)
+                            : filter_inv_levels<T>(wsb, true, ctx->cu_count, ctx->path, st, bb, yg, Cb, taps, L, &kn, &ctx->last_hip);
+            if (rc == WL_RETRY_GEN) rc = WL_EINVAL_ARG;
+            if (rc != WL_OK) return rc;
+        }
+    }
+    WL_HIP(ctx, hipGetLastError());
+    ctx->last_kernel = strcmp(madk, "k_mad_units_lds") == 0 ? "denoise_batch+k_mad_units_lds"
+                       : (strcmp(madk, "k_mad_units_stream") == 0 ? "denoise_batch+k_mad_units_stream" : "denoise_batch+sigma_in");
+    return WL_OK;
+}
+
+// the same for a lifting scheme: out-of-place forward x -> y, estimate and threshold on y, inverse in place on y (y == x allowed).
+// The transforms are those of wl_dwtc_lifting_oop (signals), wl_dwt_lifting_batch (images) and wl_dwt_lifting_batch3 (cubes) with
+// their own fallbacks for schemes and strides the fast tiers refuse.  L = 0 with an estimate: the level-1 coefficients of the
+// estimate go to a workspace buffer, y is the copy of x.
+template <typename T>
+int denoise_batch_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, int64_t nunits, int64_t S,
+                               const LiftScheme<T> &scf, const LiftScheme<T> &sci, int L, int th, double t_unit, const double *sigma_in,
+                               double *sigma_out)
+{
+    const int64_t n0 = dims[0];
+    int64_t N = 1;
+    for (int d = 0; d < ndims; ++d) N *= dims[d];
+    const bool est0 = (L == 0 && !sigma_in);
+    auto tw_elems = [&](int64_t G) -> size_t {
+        if (ndims == 3) { const size_t a = ws_lift_vols_elems(N, G), b = ws_elems(N, 1); return a > b ? a : b; }
+        return ws_elems(N * G, 1);
+    };
+    auto need = [&](int64_t G) {
+        return up256(tw_elems(G) * sizeof(T)) + up256(est0 ? (size_t)G * S * sizeof(T) : 0) + up256((size_t)G * sizeof(double));
+    };
+    int64_t G = 1;
+    int rc = batch_group(ctx, st, nunits, need, G);
+    if (rc != WL_OK) return rc;
+    char *wsb = (char *)ctx->ws;
+    T *Cb = (T *)(wsb + up256(tw_elems(G) * sizeof(T)));
+    double *sg = (double *)(wsb + up256(tw_elems(G) * sizeof(T)) + up256(est0 ? (size_t)G * S * sizeof(T) : 0));
+    const char *madk = "none";
+    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
+        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
+        const T *xg = x + u0 * S;
+        T *yg = y + u0 * S;
+        auto transform = [&](T *dst, const T *src, const LiftScheme<T> &sc, int lev, int fw) -> int {
+            if (ndims == 3) return wl_lifting_vols<T>(ctx, st, n0, nb, S, dst, src, sc, lev, fw);
+            BoxSpec bb;                                      // nb lines of one batched call / nb images as the third extent
+            bb.nd = ndims + 1; bb.nt = ndims;
+            bb.dims[0] = n0; bb.dims[1] = (ndims == 2) ? n0 : nb; bb.dims[2] = (ndims == 2) ? nb : 1;
+            bb.full.s[0] = 1; bb.full.s[1] = (ndims == 2) ? n0 : S; bb.full.s[2] = (ndims == 2) ? S : S * nb;
+            return wl_lifting_box<T>(ctx, st, bb, dst, src, sc, lev, fw);
+        };
+        if (est0) {
+            rc = transform(Cb, xg, scf, 1, 1);
+            if (rc != WL_OK) return rc;
+        }
+        rc = transform(yg, xg, scf, L, 1);                   // (L = 0: a copy unless y == x, as the reference's dwt is)
+        if (rc != WL_OK) return rc;
+        rc = batch_sigma_threshold<T>(ctx, st, est0 ? Cb : yg, yg, n0, N, nb, S, sg, sigma_in ? sigma_in + u0 : nullptr,
+                                      sigma_out ? sigma_out + u0 : nullptr, th, t_unit, &madk);
+        if (rc != WL_OK) return rc;
+        if (L > 0) {
+            rc = transform(yg, yg, sci, L, 0);
+            if (rc != WL_OK) return rc;
+        }
+    }
+    WL_HIP(ctx, hipGetLastError());
+    ctx->last_kernel = strcmp(madk, "k_mad_units_lds") == 0 ? "denoise_batch+k_mad_units_lds"
+                       : (strcmp(madk, "k_mad_units_stream") == 0 ? "denoise_batch+k_mad_units_stream" : "denoise_batch+sigma_in");
+    return WL_OK;
+}
+
+// the argument contract the two denoise_batch entry points share after their pointer / th / t_unit / dtype / wavelet rules
+int denoise_batch_check(int ndims, const int64_t *dims, int64_t nunits, int64_t unit_stride, int L, bool estimate)
+{
+    if (ndims >= 2 && ndims <= 3)
+        for (int d = 1; d < ndims; ++d)
+            if (dims[d] != dims[0]) return WL_EINVAL_CUBE;   // iscube(x) (denoising.jl:29)
+    if (ndims < 1 || ndims > 3 || dims[0] < 1 || nunits < 1) return WL_EDIMS;
+    // (a unit of 2^62 elements or more: above every stride an int64 holds)
+    if ((ndims == 2 && dims[0] >= ((int64_t)1 << 31)) || (ndims == 3 && dims[0] >= ((int64_t)1 << 21))) return WL_EDIMS;
+    int64_t N = 1;
+    for (int d = 0; d < ndims; ++d) N *= dims[d];
+    if (unit_stride < N) return WL_EDIMS;
+    if (L < 0) return WL_EINVAL_L;
+    if (L >= 62 || (dims[0] % ((int64_t)1 << L)) != 0) return WL_EINVAL_SIZE;
+    if (estimate && (dims[0] % 2) != 0) return WL_EINVAL_SIZE;                 // noisest needs level 1
+    if (estimate && dims[0] >= ((int64_t)1 << 32)) return WL_EINVAL_SIZE;      // (32-bit counters of the per-unit selection)
+    return WL_OK;
+}
+
 inline int ext_enter(wl_ctx *ctx, int dtype)
 {
     if (!ctx) return WL_EINVAL_ARG;
@@ -1334,6 +1685,67 @@ int wl_denoise_ti_lifting(wl_ctx *ctx, int dtype, void *y, const void *x, int nd
     }
     if (rc == WL_OK) ctx->last_kernel = "denoise_ti_lifting";
     return rc;
+}
+
+int wl_mad_batch(wl_ctx *ctx, int dtype, void *y, int64_t n, int64_t nunits, int64_t stride, double *result, void *stream)
+{
+    if (!ctx || !y || !result) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (n < 1 || nunits < 1 || stride < n) return WL_EDIMS;
+    if (n >= ((int64_t)1 << 31)) return WL_EINVAL_SIZE;
+    WL_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == WL_F32 ? mad_units<float>(ctx, st, (float *)y, n, nunits, stride, 1, result, &ctx->last_kernel)
+                           : mad_units<double>(ctx, st, (double *)y, n, nunits, stride, 1, result, &ctx->last_kernel);
+}
+
+int wl_denoise_batch_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, int64_t nunits,
+                            int64_t unit_stride, const double *qmf, int flen, int L, int th, double t_unit, const double *sigma_in,
+                            double *sigma_out, void *stream)
+{
+    if (!ctx || !y || !x || !dims || !qmf) return WL_EINVAL_ARG;
+    // threshold!(c, dnt.th, sigma * t) (denoising.jl:74) has methods for Hard / Soft / Semisoft / Stein only; @assert t >= 0
+    if (th < WL_TH_HARD || th > WL_TH_STEIN || !(t_unit >= 0)) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
+    int rc = denoise_batch_check(ndims, dims, nunits, unit_stride, L, sigma_in == nullptr);
+    if (rc != WL_OK) return rc;
+    if (y == x) return WL_EALIAS;
+    WL_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == WL_F32 ? denoise_batch_filter_impl<float>(ctx, st, (float *)y, (const float *)x, ndims, dims, nunits, unit_stride, qmf, flen, L,
+                                                              th, t_unit, sigma_in, sigma_out)
+                           : denoise_batch_filter_impl<double>(ctx, st, (double *)y, (const double *)x, ndims, dims, nunits, unit_stride, qmf, flen,
+                                                               L, th, t_unit, sigma_in, sigma_out);
+}
+
+int wl_denoise_batch_lifting(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, int64_t nunits,
+                             int64_t unit_stride, int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
+                             const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2, int L, int th, double t_unit,
+                             const double *sigma_in, double *sigma_out, void *stream)
+{
+    if (!ctx || !y || !x || !dims) return WL_EINVAL_ARG;
+    if (th < WL_TH_HARD || th > WL_TH_STEIN || !(t_unit >= 0)) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == WL_F32) {
+        LiftScheme<float> f, i;
+        int rc = wl_make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, 1, f);
+        if (rc == WL_OK) rc = wl_make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, 0, i);
+        if (rc == WL_OK) rc = denoise_batch_check(ndims, dims, nunits, unit_stride, L, sigma_in == nullptr);
+        if (rc != WL_OK) return rc;
+        WL_SCOPE(ctx);
+        return denoise_batch_lifting_impl<float>(ctx, st, (float *)y, (const float *)x, ndims, dims, nunits, unit_stride, f, i, L, th, t_unit,
+                                                 sigma_in, sigma_out);
+    }
+    LiftScheme<double> f, i;
+    int rc = wl_make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, 1, f);
+    if (rc == WL_OK) rc = wl_make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, 0, i);
+    if (rc == WL_OK) rc = denoise_batch_check(ndims, dims, nunits, unit_stride, L, sigma_in == nullptr);
+    if (rc != WL_OK) return rc;
+    WL_SCOPE(ctx);
+    return denoise_batch_lifting_impl<double>(ctx, st, (double *)y, (const double *)x, ndims, dims, nunits, unit_stride, f, i, L, th, t_unit,
+                                              sigma_in, sigma_out);
 }
 
 int wl_circshift(wl_ctx *ctx, int dtype, void *b, const void *a, int ndims, const int64_t *dims, const int64_t *shift, void *stream)

@@ -441,5 +441,6 @@ function Threshold.denoise(x::ROCArray{T,N}, wt::GLS;
 end
 
 include("WaveletsMI355X_bestbasis.jl")
+include("WaveletsMI355X_denoise_batch.jl")
 
 end # module

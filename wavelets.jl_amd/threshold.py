@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from . import util as Util
 from . import wt as WT
-from .transforms import (ArgumentError, DimensionMismatch, HIPError, _check, _context, _dims, _dtype_code, _prep_in, _i32p, _f64p,
+from .transforms import (ArgumentError, DimensionMismatch, HIPError, _check, _check_pair, _context, _dims, _dtype_code, _prep_in, _i32p, _f64p,
                          dwt, dwt_oop_, idwt, idwt_, idwt_oop_, is_julia_layout, julia_layout, similar)
 from .wt import GLS, OrthoFilter, wavelet
 
@@ -297,3 +297,106 @@ def denoise(x, wt=_DEFAULT, L: Optional[int] = None, dnt: Optional[DNFT] = None,
     if isinstance(wt, GLS):
         return idwt_(y, wt, L)
     return idwt(y, wt, L)
+
+
+# ---- a batch of independent units: per-unit noise estimates and thresholds on the device ------------
+def mad_batch_(y) -> torch.Tensor:
+    """mad!(y[:, i]) for every column of an n x B matrix (column-major) in one launch (wl_mad_batch): a Float64 device tensor of B
+    values; y is overwritten by the absolute deviations of its columns.  No host synchronisation."""
+    y = _dev_array(y)
+    if y.dim() != 2 or not is_julia_layout(y):
+        raise ArgumentError("mad_batch_ expects a dense column-major n x B matrix")
+    n, nb = int(y.shape[0]), int(y.shape[1])
+    out = torch.empty(nb, dtype=torch.float64, device=y.device)
+    h, st = _context(y.device)
+    _check(_lib.load().wl_mad_batch(h, _dtype_code(y), C.c_void_p(y.data_ptr()), n, nb, n, C.cast(C.c_void_p(out.data_ptr()), _lib._f64p), st), h)
+    return out
+
+
+def _batch_unit_shape(x, what: str):
+    """(unit shape, B) of a len x B / n x n x B / n x n x n x B batch; the reference's own errors for what a unit may be"""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("expected a torch tensor resident on an MI355X device (use to_device(array)); there is no CPU path")
+    if x.dim() not in (2, 3, 4):
+        raise DimensionMismatch(what + " expects a len x B matrix (signals), an n x n x B array (images) or an n x n x n x B array (cubes)")
+    unit = tuple(int(s) for s in x.shape[:-1])
+    if any(s != unit[0] for s in unit):
+        raise ArgumentError("array must be square/cube")               # iscube(x) (denoising.jl:29)
+    return unit, int(x.shape[-1])
+
+
+def _batch_transform(x, wt, L):
+    from .transforms import dwtc, dwt_batch
+    return dwtc(x, wt, L) if x.dim() == 2 else dwt_batch(x, wt, L)
+
+
+def noisest_batch(x, wt=_DEFAULT, L: int = 1) -> torch.Tensor:
+    """noisest(x[.., i], wt, L) for every unit of a batch (x: len x B, n x n x B or n x n x n x B): a Float64 device tensor of B
+    sigmas.  One batched transform, the detail range of every unit's first column gathered into an nd x B matrix, one wl_mad_batch,
+    one division by 0.6745 -- nothing synchronises with the host."""
+    wt = DEFAULT_WAVELET if wt is _DEFAULT else wt
+    if wt is not None and not isinstance(wt, (OrthoFilter, GLS)):
+        raise TypeError("wt must be an OrthoFilter, a GLS or None")
+    _batch_unit_shape(x, "noisest_batch")
+    x = _prep_in(x, maxdim=4)
+    y = x if wt is None else _batch_transform(x, wt, int(L))
+    r = Util.detailrange(int(y.shape[0]), int(L))
+    first = y[(slice(r.start - 1, r.stop - 1),) + (0,) * (y.dim() - 2) + (slice(None),)]
+    dr = similar(first)
+    dr.copy_(first)
+    return mad_batch_(dr) / 0.6745
+
+
+def denoise_batch(x, wt=_DEFAULT, L: Optional[int] = None, dnt: Optional[DNFT] = None, sigma=None, y=None, return_sigma: bool = False):
+    """denoise(x[.., i], wt; L, dnt) of every unit of a batch in one call: x is len x B (signals), n x n x B (square images) or
+    n x n x n x B (cubes), column-major.  Defaults as denoise: L = min(maxtransformlevels(unit), 6), dnt = VisuShrink(size(x, 1)).
+    Every unit gets its OWN sigma = noisest(unit, wt) and threshold, estimated and applied on the device (wl_denoise_batch_filter /
+    wl_denoise_batch_lifting): the same bits as the loop of denoise over the units, without its per-unit launches.
+    sigma: per-unit noise levels instead of the estimate -- a host sequence / array (validated: every entry >= 0, else
+    AssertionError; uploaded) or a Float64 device tensor of B values (not validated).  y: the output (lifting schemes: may be x).
+    return_sigma: also return the Float64 device tensor of the B sigmas used.
+    Not part of this call (TypeError): wt=None, BiggestTH / PosTH / NegTH, translation-invariant denoising."""
+    wt = DEFAULT_WAVELET if wt is _DEFAULT else wt
+    if not isinstance(wt, (OrthoFilter, GLS)):
+        raise TypeError("denoise_batch is defined for orthogonal filters and lifting schemes (wt=None is not part of it)")
+    unit, nb = _batch_unit_shape(x, "denoise_batch")
+    L = min(Util.maxtransformlevels(unit[0]), 6) if L is None else int(L)
+    dnt = VisuShrink(int(x.shape[0])) if dnt is None else dnt
+    if not isinstance(dnt, DNFT) or not isinstance(dnt.th, THType) or dnt.th.code is None or not 0 <= dnt.th.code <= 3:
+        raise TypeError("denoise_batch thresholds with HardTH, SoftTH, SemiSoftTH or SteinTH (threshold!(x, TH, t)); "
+                        "BiggestTH / PosTH / NegTH are not part of it")
+    if not float(dnt.t) >= 0:
+        raise AssertionError("t >= 0")
+    sig_host = None
+    if sigma is not None and not isinstance(sigma, torch.Tensor):
+        sig_host = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(-1))
+        if sig_host.size != nb:
+            raise DimensionMismatch("sigma must have one entry per unit")
+        if not bool(np.all(sig_host >= 0)):
+            raise AssertionError("t >= 0")                   # (@assert t >= 0 in threshold!, t = sigma * dnt.t: NaN fails it too)
+    x = _prep_in(x, maxdim=4)
+    y = similar(x) if y is None else y
+    _check_pair(y, x)
+    if sigma is not None:
+        sig_dev = torch.from_numpy(sig_host).to(x.device) if sig_host is not None else sigma
+        if sig_dev.device != x.device or sig_dev.dtype != torch.float64 or sig_dev.numel() != nb or not sig_dev.is_contiguous():
+            raise ArgumentError("sigma must be a contiguous Float64 tensor of B values on x's device")
+    else:
+        sig_dev = None
+    sig_out = torch.empty(nb, dtype=torch.float64, device=x.device) if return_sigma else None
+    f64 = lambda t: C.cast(C.c_void_p(t.data_ptr()), _lib._f64p) if t is not None else None
+    lib = _lib.load()
+    h, st = _context(x.device)
+    dims = (C.c_int64 * 3)(*(list(unit) + [1] * (3 - len(unit))))
+    nunit = int(np.prod(unit))
+    if isinstance(wt, GLS):
+        iu, nc, sh, cf = wt.flatten()
+        rc = lib.wl_denoise_batch_lifting(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), len(unit), dims, nb, nunit,
+                                          len(iu), _i32p(iu), _i32p(nc), _i32p(sh), _f64p(cf), wt.norm1, wt.norm2, L, dnt.th.code,
+                                          float(dnt.t), f64(sig_dev), f64(sig_out), st)
+    else:
+        q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
+        rc = lib.wl_denoise_batch_filter(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), len(unit), dims, nb, nunit,
+                                         _f64p(q), len(q), L, dnt.th.code, float(dnt.t), f64(sig_dev), f64(sig_out), st)
+    _check(rc, h)
+    return (y, sig_out) if return_sigma else y
