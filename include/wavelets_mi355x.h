@@ -435,6 +435,67 @@ WL_API int wl_bestbasistree_filter(wl_ctx *ctx, int dtype, const void *x, int64_
                                    const uint8_t *tree, int64_t ntree, int et, uint8_t *tree_out, double *node_entropy,
                                    void *stream);
 
+/* ---- complex-valued transforms (ComplexF32 / ComplexF64) --------------------------------------------------------------------- */
+/* The reference's transforms accept complex arrays (ValueType = Union{AbstractFloat, Complex}, transforms_main.jl:7).  Complex{T}
+ * is (re, im) interleaved and the taps are real, so the result is defined as re(y) = transform(re(x)), im(y) = transform(im(x)),
+ * each BIT FOR BIT what the real entry point returns for that component (for finite input equal under == to the reference's
+ * complex arithmetic with taps a + 0i, which can differ in the sign of a zero only).  In this section
+ * dtype stays the COMPONENT type (WL_F32: ComplexF32 data, WL_F64: ComplexF64), every pointer is a device pointer to interleaved
+ * data, dims / n / unit_stride count COMPLEX elements, and nunits >= 1 independent arrays sit at complex-element offset
+ * u * unit_stride (>= prod(dims)) of x and of y; nunits = 1 is the single transform.  All six calls only enqueue on `stream`.
+ *
+ * planes[(2u + c) * plane_stride + i] = component c (0 = re, 1 = im) of z[u * unit_stride + i], i < n, u < nunits: 2 * nunits planar
+ * real planes of plane_stride (>= n, in real elements) from nunits interleaved units, and back.  16-byte accesses on both sides when
+ * z, planes and every unit / plane base are 16-byte aligned (else, and for the n mod (16 / sizeof(T)) tail, an element per lane);
+ * nothing outside [0, n) of a unit or of a plane is written.  No workspace.  Status codes in this order: WL_EINVAL_ARG,
+ * WL_EINVAL_DTYPE, WL_EDIMS (n < 1, nunits < 1, unit_stride < n, plane_stride < n).                                            */
+WL_API int wl_complex_split(wl_ctx *ctx, int dtype, void *planes, int64_t plane_stride, const void *z, int64_t n, int64_t nunits,
+                            int64_t unit_stride, void *stream);
+WL_API int wl_complex_merge(wl_ctx *ctx, int dtype, void *z, const void *planes, int64_t plane_stride, int64_t n, int64_t nunits,
+                            int64_t unit_stride, void *stream);
+/* y_u = dwt(x_u, OrthoFilter(qmf), L) (fw = 0: idwt) of nunits complex arrays of ndims = 1..3 dimensions (any box with a 2^L
+ * factor per dimension).  replaces _dwt!(y, x, filter, L, fw) for Complex element types (transforms_filter.jl:13-294 with complex
+ * taps).  Per group of G units: split x into 2 G planes P, run the batched level loop of the real entry point on them -- ndims = 1
+ * wl_dwtc_filter with ld = plane_stride, 2 wl_dwt_filter_batch, 3 wl_dwt_filter_batch3, with their own fallbacks -- from P to Q,
+ * merge Q into y.  plane_stride = prod(dims) rounded up to 16 bytes, so every plane base is 16-byte aligned.  L = 0 copies the
+ * units without staging; the padding between units of y is never written.  Capturable in a hipGraph once the workspace is held.
+ * wl_last_kernel reports the inner transform's kernel.  Status codes in this order: WL_EINVAL_ARG (NULL ctx / y / x / dims / qmf),
+ * WL_EINVAL_DTYPE, WL_EINVAL_FILTER, WL_EDIMS (ndims outside 1..3, an extent or nunits < 1, unit_stride < prod(dims)), WL_EINVAL_L,
+ * WL_EINVAL_SIZE, WL_EALIAS (y == x).
+ * Workspace (wl_workspace_bytes_full does not cover it), with N = prod(dims), ps = plane_stride and G units per group -- all
+ * nunits, halved until the sum is below the context's cap (option WL_TI_WS_CAP_MB, default 8192) and at most 32767; groups change
+ * no bit --, each part rounded up to 256 bytes:
+ *   the transform workspace of 2 G planes   signals / images: 2 * (2 G N / 2^ndims + 64) + 6 G N + 64 elements,
+ *                                           volumes: 2 * (2 G * (N / 8) + 64) + 3 N + 64 elements
+ * + the planes P and Q                      2 * (2 G ps) elements.                                                              */
+WL_API int wl_dwt_filter_complex(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, int64_t nunits,
+                                 int64_t unit_stride, const double *qmf, int flen, int L, int fw, void *stream);
+/* The same for a GLS (scheme arguments as wl_dwt_lifting): vectors, SQUARE images and CUBES; y == x is allowed and is
+ * dwt!(y, scheme, L).  Split x into P, run the lifting batch loop in place on P (wl_dwtc_lifting / wl_dwt_lifting_batch /
+ * wl_dwt_lifting_batch3 with their fallbacks), merge P into y.  Status codes in this order: WL_EINVAL_ARG, WL_EINVAL_DTYPE,
+ * WL_EINVAL_SCHEME, WL_EINVAL_CUBE, WL_EDIMS, WL_EINVAL_L, WL_EINVAL_SIZE.  Workspace: the lifting workspace of 2 G planes --
+ * signals / images 2 * (G N + 64) + 6 G N + 64 elements; cubes the larger of 2 * (2 G * (N / 8) + 64) + 4 G N + 64 and one cube's
+ * 2 * (N / 2 + 64) + 3 N + 64 -- + the planes P, 2 G ps elements.                                                                 */
+WL_API int wl_dwt_lifting_complex(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, int64_t nunits,
+                                  int64_t unit_stride, int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
+                                  const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2, int L, int fw,
+                                  void *stream);
+/* y = wpt(x, filter, tree) / iwpt of ONE complex signal of n values (the packet transform has no batch form): split, the packet
+ * transform of wl_wpt_filter on each of the two planes, merge.  tree == NULL: the full tree of depth L (wl_wpt_filter_full;
+ * 0 <= L <= maxtransformlevels(n), else WL_EINVAL_L; capturable in a hipGraph).  Otherwise tree / ntree as wl_wpt_filter (HOST
+ * pointer, copied before the call returns; not capturable for a partially split tree) and L is ignored.  y must not alias x.
+ * Status codes in this order: WL_EINVAL_ARG, WL_EINVAL_DTYPE, WL_EINVAL_FILTER, WL_EDIMS, WL_EALIAS, WL_EINVAL_L / WL_EINVAL_TREE.
+ * Workspace: the packet region of one plane (wl_workspace_bytes_full(dtype, 1, {n}, L)) rounded up to 256 bytes + the planes P
+ * and Q, 2 * (2 ps) elements.                                                                                                   */
+WL_API int wl_wpt_filter_complex(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, const double *qmf, int flen,
+                                 const uint8_t *tree, int64_t ntree, int L, int fw, void *stream);
+/* The same for a GLS: wpt!(y, scheme, tree) of the copy of x (y == x allowed), the packet transform of wl_wpt_lifting in place on
+ * each plane.  Workspace: the packet region + the planes P, 2 ps elements.                                                       */
+WL_API int wl_wpt_lifting_complex(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int nsteps,
+                                  const int32_t *step_is_update, const int32_t *step_ncoef, const int32_t *step_shift,
+                                  const double *coefs_flat, double norm1, double norm2, const uint8_t *tree, int64_t ntree, int L,
+                                  int fw, void *stream);
+
 /* ---- introspection (tests / bench) ---------------------------------------------------- */
 /* Select the kernel family: 0 = auto (fast paths where they apply), 1 = generic kernels
  * only.  Both produce bit-identical results; the switch exists so tests can prove it.   */

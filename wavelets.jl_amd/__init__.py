@@ -17,7 +17,7 @@ from .util import (maxtransformlevels, sufficientpoweroftwo, detailindex, detail
                    dyadicdetailindex, dyadicdetailrange, dyadicscalingrange, dyadicdetailn, maxdyadiclevel, tl2dyadiclevel,
                    dyadiclevel2tl, mirror, upsample, downsample, wcount, testfunction)
 from .transforms import (dwt, idwt, dwt_, idwt_, dwt_oop_, idwt_oop_, dwtc, idwtc, dwtc_, idwtc_, wpt, iwpt, wpt_, iwpt_, dwt_batch, idwt_batch,
-                         to_device, to_host, similar, julia_layout, is_julia_layout,
+                         to_device, to_host, similar, julia_layout, is_julia_layout, complex_split, complex_merge, set_complex_arrays, get_complex_arrays, complex_arrays,
                          reserve_workspace, workspace_held, set_kernel_path, last_kernel, destroy_contexts, set_option, clear_options, options, set_arithmetic, get_arithmetic, arithmetic,
                          DimensionMismatch, ArgumentError, HIPError)
 from .modwt import modwt, imodwt, maxmodwttransformlevels
@@ -34,7 +34,7 @@ __all__ = [
     "ndyadicscales", "maketree", "isvalidtree", "iscube", "isdyadic",
     "dyadicdetailindex", "dyadicdetailrange", "dyadicscalingrange", "dyadicdetailn", "maxdyadiclevel", "tl2dyadiclevel",
     "dyadiclevel2tl", "mirror", "upsample", "downsample", "wcount", "testfunction",
-    "to_device", "to_host", "similar", "julia_layout", "is_julia_layout",
+    "to_device", "to_host", "similar", "julia_layout", "is_julia_layout", "complex_split", "complex_merge", "set_complex_arrays", "get_complex_arrays", "complex_arrays",
     "reserve_workspace", "workspace_held", "set_kernel_path", "last_kernel", "destroy_contexts", "set_option", "clear_options", "options", "set_arithmetic", "get_arithmetic", "arithmetic",
     "DimensionMismatch", "ArgumentError", "HIPError",
     "modwt", "imodwt", "maxmodwttransformlevels",

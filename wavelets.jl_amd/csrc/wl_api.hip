@@ -1210,3 +1210,296 @@ int wl_wpt_lifting_full(wl_ctx *ctx, int dtype, void *y, int64_t n,
 }
 
 }  // extern "C"
+
+// ---- complex-valued transforms (wl_*_complex) ----------------------------------------------------------------------------------
+// Complex{T} data is (re, im) interleaved and the taps are real: re(y) = transform(re(x)), im(y) = transform(im(x)).  A group of G
+// complex units is split into 2 G planar real planes P (k_cplx_split, wl_complex.hip), the batched level loops of the real entry
+// points run on the planes as a batch of 2 G units of stride ps -- the same bits as the real transform of each component --, and
+// the result is merged back interleaved (k_cplx_merge).  ps = the unit's element count rounded up to 16 bytes, so that every plane
+// base is 16-byte aligned (what the batched tiers ask for).  Workspace layout (bytes): [the inner level loop's region | P | Q].
+namespace {
+
+inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+template <typename T>
+inline int64_t plane_stride_of(int64_t N)
+{
+    const int64_t E = 16 / (int64_t)sizeof(T);
+    return (N + E - 1) / E * E;
+}
+
+// units per group: all of them, halved until need(G) fits under the context's cap (the cap of wl_denoise_batch_*), at most 32767
+// (2 G planes: a grid row / plane / workgroup per plane in the batched kernels); then the workspace is grown once
+template <typename F>
+int complex_group(wl_ctx *ctx, hipStream_t st, int64_t nunits, F need, int64_t &G)
+{
+    const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
+    G = nunits;
+    while (G > 1 && need(G) > cap) G = (G + 1) / 2;
+    if (G > 32767) G = 32767;
+    int rc = ensure_ws(ctx, need(G), st);
+    while (rc == WL_ENOMEM && G > 1) {                      // (another allocator may own most of the HBM: smaller groups)
+        G = (G + 1) / 2;
+        rc = ensure_ws(ctx, need(G), st);
+    }
+    return rc;
+}
+
+// L = 0: the units are copied (a 2 N x nunits real matrix with leading dimension 2 S); the padding between units is not touched
+template <typename T>
+int complex_copy_units(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t N, int64_t nunits, int64_t S)
+{
+    const Strides3 s = {{1, 2 * S, 0}};
+    for (int64_t i0 = 0; i0 < nunits && y != x; i0 += 65535) {
+        const Extent3 ext = {{2 * N, (nunits - i0 < 65535) ? (nunits - i0) : 65535, 1}};
+        WL_HIP(ctx, generic_copy_box<T>(st, x + 2 * i0 * S, s, y + 2 * i0 * S, s, ext));
+    }
+    ctx->last_kernel = "copy";
+    return WL_OK;
+}
+
+// the box of np real planes of stride ps as the batched real entry points describe it: lines (wl_dwtc_*) or images (wl_dwt_*_batch)
+inline BoxSpec planes_box(int ndims, const int64_t *dims, int64_t np, int64_t ps)
+{
+    BoxSpec b;
+    b.nd = ndims + 1; b.nt = ndims;
+    b.dims[0] = dims[0]; b.dims[1] = (ndims == 2) ? dims[1] : np; b.dims[2] = (ndims == 2) ? np : 1;
+    b.full.s[0] = 1; b.full.s[1] = (ndims == 2) ? dims[0] : ps; b.full.s[2] = (ndims == 2) ? ps : ps * np;
+    return b;
+}
+
+template <typename T>
+int dwt_filter_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, int64_t nunits, int64_t S,
+                            const double *qmf, int flen, int L, int fw)
+{
+    int64_t N = 1;
+    for (int d = 0; d < ndims; ++d) N *= dims[d];
+    if (L == 0) return complex_copy_units<T>(ctx, st, y, x, N, nunits, S);
+    const int64_t ps = plane_stride_of<T>(N);
+    Taps<T> taps;
+    make_taps<T>(qmf, flen, taps);
+    auto tw_bytes = [&](int64_t G) { return up256((ndims == 3 ? ws_vols_elems(N, 2 * G) : ws_elems(N * 2 * G, ndims)) * sizeof(T)); };
+    auto pl_bytes = [&](int64_t G) { return up256((size_t)(2 * G * ps) * sizeof(T)); };
+    auto need = [&](int64_t G) { return tw_bytes(G) + 2 * pl_bytes(G); };
+    int64_t G = 1;
+    int rc = complex_group(ctx, st, nunits, need, G);
+    if (rc != WL_OK) return rc;
+    char *wsb = (char *)ctx->ws;
+    T *P = (T *)(wsb + tw_bytes(G)), *Q = (T *)(wsb + tw_bytes(G) + pl_bytes(G));
+    const char *kn = ctx->last_kernel;
+    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
+        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
+        WL_HIP(ctx, complex_split<T>(st, ctx->cu_count, P, ps, x + 2 * u0 * S, N, nb, S));
+        if (ndims == 3) {
+            rc = fw ? filter_fwd_levels_vols<T>(wsb, true, ctx->cu_count, ctx->path, st, dims, 2 * nb, ps, ps, Q, P, taps, L, &kn, &ctx->last_hip)
+                    : filter_inv_levels_vols<T>(wsb, true, ctx->cu_count, ctx->path, st, dims, 2 * nb, ps, ps, Q, P, taps, L, &kn, &ctx->last_hip);
+        } else {
+            const BoxSpec b = planes_box(ndims, dims, 2 * nb, ps);
+            rc = fw ? filter_fwd_levels<T>(wsb, true, ctx->cu_count, ctx->path, st, b, Q, P, taps, L, &kn, &ctx->last_hip)
+                    : filter_inv_levels<T>(wsb, true, ctx->cu_count, ctx->path, st, b, Q, P, taps, L, &kn, &ctx->last_hip);
+        }
+        if (rc == WL_RETRY_GEN) rc = WL_EINVAL_ARG;          // (the full workspace is held: no level can ask for more)
+        if (rc != WL_OK) return rc;
+        WL_HIP(ctx, complex_merge<T>(st, ctx->cu_count, y + 2 * u0 * S, Q, ps, N, nb, S));
+    }
+    ctx->last_kernel = kn;
+    return WL_OK;
+}
+
+template <typename T>
+int dwt_lifting_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, int64_t nunits, int64_t S,
+                             const LiftScheme<T> &sc, int L, int fw)
+{
+    int64_t N = 1;
+    for (int d = 0; d < ndims; ++d) N *= dims[d];
+    if (L == 0) return complex_copy_units<T>(ctx, st, y, x, N, nunits, S);
+    const int64_t ps = plane_stride_of<T>(N);
+    // the lifting workspace of the planes of a group, as wl_denoise_batch_lifting sizes it (the loops below ask for no more)
+    auto tw_bytes = [&](int64_t G) -> size_t {
+        size_t e = ws_elems(N * 2 * G, 1);
+        if (ndims == 3) { const size_t a = ws_lift_vols_elems(N, 2 * G), b = ws_elems(N, 1); e = a > b ? a : b; }
+        return up256(e * sizeof(T));
+    };
+    auto need = [&](int64_t G) { return tw_bytes(G) + up256((size_t)(2 * G * ps) * sizeof(T)); };
+    int64_t G = 1;
+    int rc = complex_group(ctx, st, nunits, need, G);
+    if (rc != WL_OK) return rc;
+    const void *held = ctx->ws;
+    T *P = (T *)((char *)ctx->ws + tw_bytes(G));
+    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
+        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
+        WL_HIP(ctx, complex_split<T>(st, ctx->cu_count, P, ps, x + 2 * u0 * S, N, nb, S));
+        rc = ndims == 3 ? wl_lifting_vols<T>(ctx, st, dims[0], 2 * nb, ps, P, P, sc, L, fw)
+                        : wl_lifting_box<T>(ctx, st, planes_box(ndims, dims, 2 * nb, ps), P, P, sc, L, fw);
+        if (rc != WL_OK) return rc;
+        if (ctx->ws != held) return WL_ENOMEM;               // (a loop that outgrew the reservation would have moved P: not reached)
+        WL_HIP(ctx, complex_merge<T>(st, ctx->cu_count, y + 2 * u0 * S, P, ps, N, nb, S));
+    }
+    return WL_OK;
+}
+
+// the argument contract the two complex dwt entry points share after their pointer / dtype / wavelet rules (the order of the real
+// batch entry points): WL_EINVAL_CUBE (lifting only), WL_EDIMS, WL_EINVAL_L, WL_EINVAL_SIZE
+int complex_check(int ndims, const int64_t *dims, int64_t nunits, int64_t unit_stride, int L, bool cube)
+{
+    if (cube && ndims >= 2 && ndims <= 3)
+        for (int d = 1; d < ndims; ++d)
+            if (dims[d] != dims[0]) return WL_EINVAL_CUBE;
+    if (ndims < 1 || ndims > 3 || nunits < 1) return WL_EDIMS;
+    int64_t N = 1;
+    for (int d = 0; d < ndims; ++d) {
+        // (a unit of 2^61 values or more: above every stride in reals an int64 holds)
+        if (dims[d] < 1 || dims[d] >= ((int64_t)1 << 61) / N) return WL_EDIMS;
+        N *= dims[d];
+    }
+    if (unit_stride < N) return WL_EDIMS;
+    if (L < 0) return WL_EINVAL_L;
+    for (int d = 0; d < ndims; ++d)
+        if (!sufficientpoweroftwo(dims[d], L)) return WL_EINVAL_SIZE;
+    return WL_OK;
+}
+
+// one complex signal through the packet transform: split, wpt_impl on each plane (filters: P -> Q; lifting: in place on P), merge
+template <typename T>
+int wpt_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n, const Taps<T> *taps, const LiftScheme<T> *sc,
+                     const uint8_t *tree, int64_t ntree, int64_t last_set, int fw, int full_depth)
+{
+    const int64_t ps = plane_stride_of<T>(n);
+    const size_t inner = up256(ws_elems(n) * sizeof(T) + (size_t)(tree ? ntree : 0) + 256), pl = up256((size_t)(2 * ps) * sizeof(T));
+    int rc = ensure_ws(ctx, inner + (taps ? 2 : 1) * pl, st);
+    if (rc != WL_OK) return rc;
+    const void *held = ctx->ws;
+    T *P = (T *)((char *)ctx->ws + inner), *Q = taps ? (T *)((char *)ctx->ws + inner + pl) : P;
+    WL_HIP(ctx, complex_split<T>(st, ctx->cu_count, P, ps, x, n, 1, n));
+    for (int c = 0; c < 2; ++c) {
+        rc = wpt_impl<T>(ctx, st, Q + c * ps, P + c * ps, n, taps, sc, tree, ntree, last_set, fw, full_depth);
+        if (rc != WL_OK) return rc;
+        if (ctx->ws != held) return WL_ENOMEM;               // (not reached: wpt_impl asks for no more than `inner`)
+    }
+    WL_HIP(ctx, complex_merge<T>(st, ctx->cu_count, y, Q, ps, n, 1, n));
+    return WL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wl_complex_split(wl_ctx *ctx, int dtype, void *planes, int64_t plane_stride, const void *z, int64_t n, int64_t nunits,
+                     int64_t unit_stride, void *stream)
+{
+    if (!ctx || !planes || !z) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (n < 1 || nunits < 1 || unit_stride < n || plane_stride < n) return WL_EDIMS;
+    WL_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    WL_HIP(ctx, dtype == WL_F32 ? complex_split<float>(st, ctx->cu_count, (float *)planes, plane_stride, (const float *)z, n, nunits, unit_stride)
+                                : complex_split<double>(st, ctx->cu_count, (double *)planes, plane_stride, (const double *)z, n, nunits, unit_stride));
+    return WL_OK;
+}
+
+int wl_complex_merge(wl_ctx *ctx, int dtype, void *z, const void *planes, int64_t plane_stride, int64_t n, int64_t nunits,
+                     int64_t unit_stride, void *stream)
+{
+    if (!ctx || !planes || !z) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (n < 1 || nunits < 1 || unit_stride < n || plane_stride < n) return WL_EDIMS;
+    WL_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    WL_HIP(ctx, dtype == WL_F32 ? complex_merge<float>(st, ctx->cu_count, (float *)z, (const float *)planes, plane_stride, n, nunits, unit_stride)
+                                : complex_merge<double>(st, ctx->cu_count, (double *)z, (const double *)planes, plane_stride, n, nunits, unit_stride));
+    return WL_OK;
+}
+
+int wl_dwt_filter_complex(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, int64_t nunits,
+                          int64_t unit_stride, const double *qmf, int flen, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !dims || !qmf) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
+    int rc = complex_check(ndims, dims, nunits, unit_stride, L, false);
+    if (rc) return rc;
+    if (y == x) return WL_EALIAS;
+    WL_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    return dtype == WL_F32
+               ? dwt_filter_complex_impl<float>(ctx, st, (float *)y, (const float *)x, ndims, dims, nunits, unit_stride, qmf, flen, L, fw)
+               : dwt_filter_complex_impl<double>(ctx, st, (double *)y, (const double *)x, ndims, dims, nunits, unit_stride, qmf, flen, L, fw);
+}
+
+int wl_dwt_lifting_complex(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, int64_t nunits,
+                           int64_t unit_stride, int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
+                           const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !dims) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == WL_F32) {
+        LiftScheme<float> sc;
+        int rc = make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
+        if (rc == WL_OK) rc = complex_check(ndims, dims, nunits, unit_stride, L, true);
+        if (rc) return rc;
+        WL_SCOPE(ctx);
+        return dwt_lifting_complex_impl<float>(ctx, st, (float *)y, (const float *)x, ndims, dims, nunits, unit_stride, sc, L, fw);
+    }
+    LiftScheme<double> sc;
+    int rc = make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
+    if (rc == WL_OK) rc = complex_check(ndims, dims, nunits, unit_stride, L, true);
+    if (rc) return rc;
+    WL_SCOPE(ctx);
+    return dwt_lifting_complex_impl<double>(ctx, st, (double *)y, (const double *)x, ndims, dims, nunits, unit_stride, sc, L, fw);
+}
+
+int wl_wpt_filter_complex(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, const double *qmf, int flen, const uint8_t *tree,
+                          int64_t ntree, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !qmf) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
+    if (n < 1 || n >= ((int64_t)1 << 61)) return WL_EDIMS;
+    if (y == x) return WL_EALIAS;
+    int64_t last_set = -1;
+    if (!tree) {
+        if (L < 0 || L > wl_maxtransformlevels(n)) return WL_EINVAL_L;
+    } else if (!isvalidtree(n, tree, ntree, &last_set)) {
+        return WL_EINVAL_TREE;
+    }
+    const int full_depth = tree ? -1 : L;
+    WL_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == WL_F32) {
+        Taps<float> t; make_taps<float>(qmf, flen, t);
+        return wpt_complex_impl<float>(ctx, st, (float *)y, (const float *)x, n, &t, nullptr, tree, tree ? ntree : 0, last_set, fw, full_depth);
+    }
+    Taps<double> t; make_taps<double>(qmf, flen, t);
+    return wpt_complex_impl<double>(ctx, st, (double *)y, (const double *)x, n, &t, nullptr, tree, tree ? ntree : 0, last_set, fw, full_depth);
+}
+
+int wl_wpt_lifting_complex(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int nsteps, const int32_t *step_is_update,
+                           const int32_t *step_ncoef, const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2,
+                           const uint8_t *tree, int64_t ntree, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (n < 1 || n >= ((int64_t)1 << 61)) return WL_EDIMS;
+    int64_t last_set = -1;
+    if (!tree) {
+        if (L < 0 || L > wl_maxtransformlevels(n)) return WL_EINVAL_L;
+    } else if (!isvalidtree(n, tree, ntree, &last_set)) {
+        return WL_EINVAL_TREE;
+    }
+    const int full_depth = tree ? -1 : L;
+    WL_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == WL_F32) {
+        LiftScheme<float> sc;
+        int rc = make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
+        if (rc) return rc;
+        return wpt_complex_impl<float>(ctx, st, (float *)y, (const float *)x, n, nullptr, &sc, tree, tree ? ntree : 0, last_set, fw, full_depth);
+    }
+    LiftScheme<double> sc;
+    int rc = make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
+    if (rc) return rc;
+    return wpt_complex_impl<double>(ctx, st, (double *)y, (const double *)x, n, nullptr, &sc, tree, tree ? ntree : 0, last_set, fw, full_depth);
+}
+
+}  // extern "C"

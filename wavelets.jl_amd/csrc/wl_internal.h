@@ -190,6 +190,16 @@ hipError_t entropy_norm(hipStream_t st, const T *x, int64_t n, double *part, dou
 hipError_t bestbasis_decide(hipStream_t st, const double *ent, int64_t ntree, int Lmax, double *best, uint8_t *split, const uint8_t *tree,
                             uint8_t *tree_out);
 
+// ---- complex staging (wl_complex.hip) ----
+// planes[(2u + c) * plane_stride + i] = component c (0 re, 1 im) of the complex value z[u * unit_stride + i] (z: interleaved reals,
+// unit_stride in complex elements), i < n, u < nunits; complex_merge is the inverse.  Only bits move.
+template <typename T>
+hipError_t complex_split(hipStream_t st, int cu_count, T *planes, int64_t plane_stride, const T *z, int64_t n, int64_t nunits,
+                         int64_t unit_stride);
+template <typename T>
+hipError_t complex_merge(hipStream_t st, int cu_count, T *z, const T *planes, int64_t plane_stride, int64_t n, int64_t nunits,
+                         int64_t unit_stride);
+
 __device__ __forceinline__ int64_t pmod(int64_t a, int64_t n)
 {
     int64_t r = a % n;

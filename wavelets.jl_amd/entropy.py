@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from . import util as Util
-from .transforms import ArgumentError, _check, _context, _dtype_code, _f64p, _prep_in, _tree_arg
+from .transforms import ArgumentError, _check, _context, _dtype_code, _f64p, _prep_in, _reject_complex, _tree_arg
 from .wt import OrthoFilter
 
 
@@ -63,6 +63,7 @@ def _scalar_entropy(x, code, nrm):
 def coefentropy(x, et, nrm=None):
     """coefentropy(x, et[, nrm]) (entropy.jl:15-40).  x: a device tensor (nrm defaults to norm(x)) or a real scalar (nrm required).
     The tensor form returns a Python float holding a value of the element type."""
+    _reject_complex(x, "coefentropy")
     code = _et_code(et)
     if not isinstance(x, torch.Tensor):
         if nrm is None:
@@ -82,6 +83,7 @@ def bestbasistree(y, wt, L_or_tree=None, et=ShannonEntropy(), *, return_entropy=
     tree (default and integer L: maketree(n, L, :full)).  OrthoFilter wavelets on a device vector only: GLS has no best-basis search
     in the reference (a MethodError there), matrices none either.  return_entropy=True also returns the Float64 device tensor
     [entr_bf ; entr_af] of the node entropies the decision used."""
+    _reject_complex(y, "bestbasistree")
     if not isinstance(wt, OrthoFilter):
         raise TypeError("bestbasistree is defined for OrthoFilter wavelets only (the reference has no method for %s)" % type(wt).__name__)
     code = _et_code(et)

@@ -85,7 +85,8 @@ dims3(x) = Int64[size(x)..., ntuple(_ -> 1, 3 - ndims(x))...]
 # (ext/WaveletsGPUExt/filter_transforms_gpu.jl:171,216,271; lifting_transforms_gpu.jl:171,210,249).  The methods below mirror
 # them one for one on ROCVector / ROCMatrix / ROCArray{T,3}: each signature is a strict subtype of the extension's, so it is the
 # more specific method for same-T Float32/Float64 arguments by the subtype rule alone (no specificity heuristics, no ambiguity);
-# mixed element types (Tx != Ty), Integer and Complex arrays do not match and fall through to the extension, which promotes.
+# mixed element types (Tx != Ty) and Integer arrays do not match and fall through to the extension, which promotes; Complex{Float32} /
+# Complex{Float64} arrays have their own methods (WaveletsMI355X_complex.jl).
 # tests/test_julia_glue.py proves the element-wise `<:` statically against the reference's signatures.
 function dwt_filter_device!(y, x, filter::OrthoFilter, L::Integer, fw::Bool, ::Type{T}, N::Int) where {T}
     size(x) == size(y) || throw(DimensionMismatch("in and out array size must match"))
@@ -442,5 +443,6 @@ end
 
 include("WaveletsMI355X_bestbasis.jl")
 include("WaveletsMI355X_denoise_batch.jl")
+include("WaveletsMI355X_complex.jl")
 
 end # module

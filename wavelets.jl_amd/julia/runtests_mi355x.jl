@@ -77,6 +77,31 @@ same(a, b) = Array(b) == a          # bit-for-bit (0.0 == -0.0)
             @test same(iwpt(y, wt, tree), iwpt(ROCArray(y), wt, tree))
         end
     end
+    @testset "complex" begin
+        # re(y) = transform(re(x)), im(y) = transform(im(x)): == the reference's complex arithmetic for finite input (the sign of
+        # a zero may differ), and bit for bit the real device transform of the components
+        for T in (Float32, Float64), wt in (wavelet(WT.db4), wavelet(WT.cdf97, WT.Lifting))
+            for sz in ((4096,), (64, 64), (16, 16, 16))
+                x = randn(Complex{T}, sz...)
+                d = ROCArray(x)
+                y = dwt(d, wt)
+                @test eltype(y) == Complex{T}
+                @test Array(y) == dwt(x, wt)
+                @test same(real.(Array(y)), dwt(ROCArray(real.(x)), wt))
+                @test same(imag.(Array(y)), dwt(ROCArray(imag.(x)), wt))
+                @test Array(idwt(y, wt)) == idwt(Array(y), wt)
+            end
+            x = randn(Complex{T}, 1024)
+            for tree in (maketree(1024, 4, :full), maketree(1024, 6, :dwt))
+                @test Array(wpt(ROCArray(x), wt, tree)) == wpt(x, wt, tree)
+            end
+            @test Array(wpt(ROCArray(x), wt, 3)) == wpt(x, wt, 3)
+        end
+        z = ROCArray(randn(ComplexF64, 24)); wt = wavelet(WT.db2)
+        @test_throws ArgumentError dwt(z, wt, 4)
+        @test_throws ArgumentError dwt!(z, z, wt, 1)
+        @test_throws ArgumentError dwt(ROCArray(randn(ComplexF64, 8, 16)), wavelet(WT.db2, WT.Lifting), 1)
+    end
     @testset "argument contract" begin
         x = ROCArray(randn(Float64, 24)); wt = wavelet(WT.db2)
         @test_throws ArgumentError dwt(x, wt, 4)

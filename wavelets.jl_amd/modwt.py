@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .transforms import (ArgumentError, DimensionMismatch, HIPError, _check, _context, _dtype_code, _f64p, _prep_in,
+from .transforms import (ArgumentError, DimensionMismatch, HIPError, _check, _context, _dtype_code, _f64p, _prep_in, _reject_complex,
                          julia_layout)
 from .wt import OrthoFilter
 
@@ -30,6 +30,7 @@ def maxmodwttransformlevels(x) -> int:
 
 def modwt(x, wt: OrthoFilter, L: Optional[int] = None) -> torch.Tensor:
     """modwt(x::AbstractVector, wt::OrthoFilter, L=maxmodwttransformlevels(x)) -> n x (L+1)"""
+    _reject_complex(x, "modwt")
     if not isinstance(wt, OrthoFilter):
         raise TypeError("modwt is defined for OrthoFilter wavelets only (MethodError in the reference)")
     x = _prep_in(x)
@@ -54,6 +55,7 @@ def modwt(x, wt: OrthoFilter, L: Optional[int] = None) -> torch.Tensor:
 
 def imodwt(xw, wt: OrthoFilter) -> torch.Tensor:
     """imodwt(xw::Matrix, wt::OrthoFilter): inverse of modwt(x, wt, size(xw, 2) - 1)"""
+    _reject_complex(xw, "imodwt")
     if not isinstance(wt, OrthoFilter):
         raise TypeError("imodwt is defined for OrthoFilter wavelets only (MethodError in the reference)")
     if not isinstance(xw, torch.Tensor) or xw.device.type != "cuda":

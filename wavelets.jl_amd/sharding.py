@@ -12,6 +12,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .transforms import _reject_complex
 from .wt import GLS, LSStep, LSStepParam, OrthoFilter, Predict, Update, UpdateStep
 
 _PACK_LEN = 256
@@ -86,6 +87,7 @@ def sum_over_ranks(value: float, dist, device) -> float:
 def sharded_columnwise(transform, x_local, wt, L, dist, device):
     """Run `transform(x_local, wt, L)` (e.g. wavelets_jl_amd.dwtc) on this rank's column shard with
     rank 0's wavelet; returns (y_local, global checksum).  No signal data crosses ranks."""
+    _reject_complex(x_local, "sharded_columnwise")
     wt = broadcast_wavelet(wt, dist, device)
     y = transform(x_local, wt, L)
     local = float(torch.as_tensor(y, dtype=torch.float64).sum()) if not isinstance(y, np.ndarray) else float(y.sum())

@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from . import util as Util
 from . import wt as WT
-from .transforms import (ArgumentError, DimensionMismatch, HIPError, _check, _check_pair, _context, _dims, _dtype_code, _prep_in, _i32p, _f64p,
+from .transforms import (ArgumentError, DimensionMismatch, HIPError, _check, _check_pair, _context, _dims, _dtype_code, _prep_in, _reject_complex, _i32p, _f64p,
                          dwt, dwt_oop_, idwt, idwt_, idwt_oop_, is_julia_layout, julia_layout, similar)
 from .wt import GLS, OrthoFilter, wavelet
 
@@ -83,6 +83,7 @@ def _t_is_f64(x: torch.Tensor, t) -> int:
 
 def threshold_(x, TH: THType, t=None):
     """threshold!(x, TH, t) / threshold!(x, BiggestTH(), m) / threshold!(x, PosTH()|NegTH()) -- in place"""
+    _reject_complex(x, "threshold_")
     x = _dev_array(x)
     lib = _lib.load()
     h, st = _context(x.device)
@@ -111,6 +112,7 @@ def threshold_(x, TH: THType, t=None):
 
 def threshold(x, TH: THType, t=None):
     """threshold(x, TH[, t]): the non-in-place form (threshold_main.jl:120-127)"""
+    _reject_complex(x, "threshold")
     x = _dev_array(x)
     y = similar(x)
     y.copy_(x)
@@ -140,6 +142,7 @@ _DEFAULT = object()
 
 def mad_(y) -> float:
     """mad!(y): median absolute deviation; y is overwritten by abs.(y .- median(y)) (denoising.jl:103-110)"""
+    _reject_complex(y, "mad_")
     y = _dev_array(y)
     h, st = _context(y.device)
     out = C.c_double()
@@ -148,6 +151,7 @@ def mad_(y) -> float:
 
 
 def median(v) -> float:
+    _reject_complex(v, "median")
     v = _dev_array(v)
     h, st = _context(v.device)
     out = C.c_double()
@@ -159,6 +163,7 @@ def median(v) -> float:
 def noisest(x, wt=_DEFAULT, L: int = 1) -> float:
     """noisest(x, wt=DEFAULT_WAVELET, L=1) (denoising.jl:92-101): MAD of the level-L detail range / 0.6745.
     `y[detailrange(y, L)]` is linear indexing with size(y, 1), as in the reference."""
+    _reject_complex(x, "noisest")
     wt = DEFAULT_WAVELET if wt is _DEFAULT else wt
     x = _prep_in(x)
     y = x if wt is None else dwt(x, wt, L)
@@ -211,6 +216,7 @@ def denoise(x, wt=_DEFAULT, L: Optional[int] = None, dnt: Optional[DNFT] = None,
             nspin: Union[int, Sequence[int], None] = None) -> torch.Tensor:
     """denoise(x, wt=DEFAULT_WAVELET; L=min(maxtransformlevels(x),6), dnt=VisuShrink(size(x,1)), estnoise=noisest,
     TI=false, nspin=8 per dimension) -- denoising.jl:21-81.  wt=None is the reference's `nothing`."""
+    _reject_complex(x, "denoise")
     wt = DEFAULT_WAVELET if wt is _DEFAULT else wt
     x = _prep_in(x)
     L = min(Util.maxtransformlevels(x), 6) if L is None else int(L)
@@ -303,6 +309,7 @@ def denoise(x, wt=_DEFAULT, L: Optional[int] = None, dnt: Optional[DNFT] = None,
 def mad_batch_(y) -> torch.Tensor:
     """mad!(y[:, i]) for every column of an n x B matrix (column-major) in one launch (wl_mad_batch): a Float64 device tensor of B
     values; y is overwritten by the absolute deviations of its columns.  No host synchronisation."""
+    _reject_complex(y, "mad_batch_")
     y = _dev_array(y)
     if y.dim() != 2 or not is_julia_layout(y):
         raise ArgumentError("mad_batch_ expects a dense column-major n x B matrix")
@@ -334,6 +341,7 @@ def noisest_batch(x, wt=_DEFAULT, L: int = 1) -> torch.Tensor:
     """noisest(x[.., i], wt, L) for every unit of a batch (x: len x B, n x n x B or n x n x n x B): a Float64 device tensor of B
     sigmas.  One batched transform, the detail range of every unit's first column gathered into an nd x B matrix, one wl_mad_batch,
     one division by 0.6745 -- nothing synchronises with the host."""
+    _reject_complex(x, "noisest_batch")
     wt = DEFAULT_WAVELET if wt is _DEFAULT else wt
     if wt is not None and not isinstance(wt, (OrthoFilter, GLS)):
         raise TypeError("wt must be an OrthoFilter, a GLS or None")
@@ -356,6 +364,7 @@ def denoise_batch(x, wt=_DEFAULT, L: Optional[int] = None, dnt: Optional[DNFT] =
     AssertionError; uploaded) or a Float64 device tensor of B values (not validated).  y: the output (lifting schemes: may be x).
     return_sigma: also return the Float64 device tensor of the B sigmas used.
     Not part of this call (TypeError): wt=None, BiggestTH / PosTH / NegTH, translation-invariant denoising."""
+    _reject_complex(x, "denoise_batch")
     wt = DEFAULT_WAVELET if wt is _DEFAULT else wt
     if not isinstance(wt, (OrthoFilter, GLS)):
         raise TypeError("denoise_batch is defined for orthogonal filters and lifting schemes (wt=None is not part of it)")

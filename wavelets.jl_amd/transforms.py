@@ -241,10 +241,67 @@ def _dtype_code(x: torch.Tensor) -> int:
         return _lib.WL_F32
     if x.dtype == torch.float64:
         return _lib.WL_F64
-    raise TypeError(f"element type {x.dtype} is not supported (Float32/Float64 only; Complex is out of scope)")
+    raise TypeError(f"element type {x.dtype} is not supported here (Float32/Float64; ComplexF32/ComplexF64 in dwt / idwt / "
+                    "dwt_batch / wpt and their in-place forms after set_complex_arrays(True))")
 
 
-def _prep_in(x, maxdim: int = 3) -> torch.Tensor:
+# ComplexF32 / ComplexF64: the component type code the wl_*_complex entry points take, and the component dtype
+_COMPLEX = {torch.complex64: (_lib.WL_F32, torch.float32), torch.complex128: (_lib.WL_F64, torch.float64)}
+
+
+def _is_complex(x) -> bool:
+    return isinstance(x, torch.Tensor) and x.dtype.is_complex
+
+
+def _reject_complex(x, fname: str):
+    """Everything but the transforms: the reference's threshold!, noisest and modwt are undefined or differently defined for
+    complex values."""
+    if _is_complex(x):
+        raise TypeError(f"{fname} is not defined for complex arrays (complex element types are taken by dwt / idwt / dwt_batch / "
+                        "wpt / iwpt and their in-place forms only)")
+
+
+_COMPLEX_ARRAYS = False
+
+
+def set_complex_arrays(enabled: bool):
+    """Let dwt / idwt / dwt_batch / wpt / iwpt and their in-place forms take ComplexF32 / ComplexF64 tensors (wl_*_complex).
+    Off by default: until it is switched on a complex tensor raises TypeError in every function of the package, as it always
+    did.  Process-wide; `with W.complex_arrays(): ...` switches it on for a block."""
+    global _COMPLEX_ARRAYS
+    _COMPLEX_ARRAYS = bool(enabled)
+
+
+def get_complex_arrays() -> bool:
+    return _COMPLEX_ARRAYS
+
+
+class complex_arrays:
+    """with W.complex_arrays(): ...   -- complex tensors accepted for the block, previous setting restored afterwards."""
+
+    def __init__(self, enabled: bool = True):
+        self.enabled = enabled
+
+    def __enter__(self):
+        self.saved = _COMPLEX_ARRAYS
+        set_complex_arrays(self.enabled)
+        return self
+
+    def __exit__(self, *exc):
+        set_complex_arrays(self.saved)
+        return False
+
+
+def _complex_code(x: torch.Tensor) -> int:
+    if not _COMPLEX_ARRAYS:
+        raise TypeError(f"element type {x.dtype} is not supported (Float32/Float64; complex arrays are transformed after "
+                        "set_complex_arrays(True))")
+    if x.dtype not in _COMPLEX:
+        raise TypeError(f"element type {x.dtype} is not supported (ComplexF32 / ComplexF64 only)")
+    return _COMPLEX[x.dtype][0]
+
+
+def _prep_in(x, maxdim: int = 3, complex_ok: bool = False) -> torch.Tensor:
     if not isinstance(x, torch.Tensor):
         raise TypeError("expected a torch tensor resident on an MI355X device (use to_device(array)); "
                         "there is no CPU path")
@@ -254,7 +311,10 @@ def _prep_in(x, maxdim: int = 3) -> torch.Tensor:
         raise DimensionMismatch("only 1-D, 2-D and 3-D arrays are supported")
     if not x.dtype.is_floating_point and not x.dtype.is_complex:
         x = x.to(torch.float64)        # Int -> Float (transforms_main.jl:188-190)
-    _dtype_code(x)
+    if complex_ok and x.dtype.is_complex:
+        _complex_code(x)
+    else:
+        _dtype_code(x)
     return julia_layout(x)
 
 
@@ -275,13 +335,15 @@ def _default_L(x, L):
 
 
 # ---- core calls ----------------------------------------------------------------------------------
-def _check_one(y: torch.Tensor, vector_only: bool = False):
+def _check_one(y: torch.Tensor, vector_only: bool = False, complex_ok: bool = False):
     """What every caller-supplied array must satisfy before its data_ptr() reaches the C ABI."""
     if not isinstance(y, torch.Tensor):
         raise TypeError("expected a torch tensor resident on the GPU")
     if y.device.type != "cuda":
         raise HIPError("wavelets_jl_amd runs on MI355X (gfx950) HIP devices only; there is no CPU path")
-    if y.dtype not in (torch.float32, torch.float64):
+    if complex_ok and y.dtype.is_complex:
+        _complex_code(y)
+    elif y.dtype not in (torch.float32, torch.float64):
         raise TypeError("element type must be Float32 or Float64")
     if vector_only and y.dim() != 1:
         raise TypeError("wpt is defined for vectors only (WPTArray = AbstractVector)")
@@ -289,11 +351,11 @@ def _check_one(y: torch.Tensor, vector_only: bool = False):
         raise ArgumentError("arrays must be dense column-major (Julia layout); see to_device/similar")
 
 
-def _check_pair(y: torch.Tensor, x: torch.Tensor, vector_only: bool = False):
+def _check_pair(y: torch.Tensor, x: torch.Tensor, vector_only: bool = False, complex_ok: bool = False):
     """(y, x) handed to an out-of-place entry point: same shape (DimensionMismatch, transforms_filter.jl:25-26), same
     element type, same device, both dense column-major -- the library trusts the extents it is given."""
-    _check_one(y, vector_only)
-    _check_one(x, vector_only)
+    _check_one(y, vector_only, complex_ok)
+    _check_one(x, vector_only, complex_ok)
     if tuple(x.shape) != tuple(y.shape):
         raise DimensionMismatch("in and out array size must match")
     if x.dtype != y.dtype:
@@ -302,7 +364,36 @@ def _check_pair(y: torch.Tensor, x: torch.Tensor, vector_only: bool = False):
         raise HIPError("x and y are on different devices")
 
 
+def _complex_call(y: torch.Tensor, x: Optional[torch.Tensor], wt, L: int, fw: bool, ndims: Optional[int] = None, nunits: int = 1):
+    """wl_dwt_filter_complex / wl_dwt_lifting_complex on nunits dense complex arrays: the leading `ndims` dimensions of x (all of
+    them for a single transform), unit u at complex-element offset u * prod(shape[:ndims]).  x is None: in place on y (lifting)."""
+    if x is None:
+        _check_one(y, complex_ok=True)
+    else:
+        _check_pair(y, x, complex_ok=True)
+    src = y if x is None else x
+    lib = _lib.load()
+    h, st = _context(src.device)
+    ndims = src.dim() if ndims is None else ndims
+    shape = [int(v) for v in src.shape[:ndims]]
+    dims = (C.c_int64 * 3)(*(shape + [1] * (3 - ndims)))
+    stride = int(np.prod(shape, dtype=np.int64))
+    if isinstance(wt, OrthoFilter):
+        q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
+        rc = lib.wl_dwt_filter_complex(h, _complex_code(src), C.c_void_p(y.data_ptr()), C.c_void_p(src.data_ptr()), ndims, dims,
+                                       int(nunits), stride, _f64p(q), len(q), int(L), 1 if fw else 0, st)
+    else:
+        iu, nc, sh, cf = wt.flatten()
+        rc = lib.wl_dwt_lifting_complex(h, _complex_code(src), C.c_void_p(y.data_ptr()), C.c_void_p(src.data_ptr()), ndims, dims,
+                                        int(nunits), stride, len(iu), _i32p(iu), _i32p(nc), _i32p(sh), _f64p(cf), wt.norm1, wt.norm2,
+                                        int(L), 1 if fw else 0, st)
+    _check(rc, h)
+    return y
+
+
 def _filter_call(y: torch.Tensor, x: torch.Tensor, filt: OrthoFilter, L: int, fw: bool):
+    if _is_complex(y) or _is_complex(x):
+        return _complex_call(y, x, filt, L, fw)
     _check_pair(y, x)
     lib = _lib.load()
     h, st = _context(x.device)
@@ -314,6 +405,8 @@ def _filter_call(y: torch.Tensor, x: torch.Tensor, filt: OrthoFilter, L: int, fw
 
 
 def _lifting_call(y: torch.Tensor, x: Optional[torch.Tensor], sch: GLS, L: int, fw: bool):
+    if _is_complex(y) or _is_complex(x):
+        return _complex_call(y, x, sch, L, fw)
     if x is None:
         _check_one(y)
     else:
@@ -334,7 +427,7 @@ def _lifting_call(y: torch.Tensor, x: Optional[torch.Tensor], sch: GLS, L: int, 
 
 
 def _xwt(x, wt, L, fw):
-    x = _prep_in(x)
+    x = _prep_in(x, complex_ok=True)
     L = _default_L(x, L)
     if x.numel() == 0:                     # empty array: maxtransformlevels == 0, the transform is a copy
         if L != 0 and L is not None and int(L) > 0:
@@ -415,6 +508,7 @@ def idwt_oop_(y, x, wt, L: Optional[int] = None) -> torch.Tensor:
 
 # ---- batched column-wise ----------------------------------------------------------------------
 def _xwtc(x, wt, L, fw, y=None):
+    _reject_complex(x, "dwtc" if fw else "idwtc")
     x = _prep_in(x)
     if x.dim() != 2:
         raise DimensionMismatch("dwtc expects a len x nsignals matrix")
@@ -481,12 +575,14 @@ def _xwt_batch(x, wt, L, fw, y=None):
             raise TypeError("dwt_batch expects an n0 x n1 x B array (images) or an n0 x n1 x n2 x B array (volumes)")
         if x.dim() == 3 and isinstance(wt, GLS) and int(x.shape[0]) != int(x.shape[1]):
             raise ArgumentError("array must be square/cube")          # what dwt(x[:, :, i], wt::GLS) raises (transforms_lifting.jl:131-132)
-    x = _prep_in(x, maxdim=4)                # (a batch of volumes is the one 4-D array the package takes)
+    x = _prep_in(x, maxdim=4, complex_ok=True)                # (a batch of volumes is the one 4-D array the package takes)
     if x.dim() == 4:
         return _xwt_batch3(x, wt, L, fw, y)
     n0, n1, nb = (int(v) for v in x.shape)
     L = min(Util.maxtransformlevels(n0), Util.maxtransformlevels(n1)) if L is None else int(L)
     y = similar(x) if y is None else y
+    if _is_complex(x) or _is_complex(y):
+        return _complex_call(y, x, wt, L, fw, ndims=2, nunits=nb)
     _check_pair(y, x)                        # (a caller-supplied y: same shape / type / device, dense column-major)
     lib = _lib.load()
     h, st = _context(x.device)
@@ -509,6 +605,8 @@ def _xwt_batch3(x, wt, L, fw, y):
     n0, n1, n2, nb = (int(v) for v in x.shape)
     L = min(Util.maxtransformlevels(n) for n in (n0, n1, n2)) if L is None else int(L)
     y = similar(x) if y is None else y
+    if _is_complex(x) or _is_complex(y):
+        return _complex_call(y, x, wt, L, fw, ndims=3, nunits=nb)
     _check_pair(y, x)
     lib = _lib.load()
     h, st = _context(x.device)
@@ -555,7 +653,30 @@ def _tree_arg(n, tree_or_L):
     return np.ascontiguousarray(t, dtype=np.uint8)
 
 
+def _wpt_complex_call(y, x, wt, tree, fw):
+    """wl_wpt_filter_complex / wl_wpt_lifting_complex: one complex signal; x may be y for a lifting scheme"""
+    _check_pair(y, x, vector_only=True, complex_ok=True)
+    lib = _lib.load()
+    h, st = _context(x.device)
+    if isinstance(tree, _FullTree) or len(tree) == 0:        # (an odd length has an empty tree: the full tree of depth 0)
+        tp, nt, L = None, 0, int(tree) if isinstance(tree, _FullTree) else 0
+    else:
+        tp, nt, L = tree.ctypes.data_as(C.POINTER(C.c_uint8)), len(tree), 0
+    if isinstance(wt, OrthoFilter):
+        q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
+        rc = lib.wl_wpt_filter_complex(h, _complex_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), x.numel(),
+                                       _f64p(q), len(q), tp, nt, L, 1 if fw else 0, st)
+    else:
+        iu, nc, sh, cf = wt.flatten()
+        rc = lib.wl_wpt_lifting_complex(h, _complex_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), x.numel(), len(iu),
+                                        _i32p(iu), _i32p(nc), _i32p(sh), _f64p(cf), wt.norm1, wt.norm2, tp, nt, L, 1 if fw else 0, st)
+    _check(rc, h)
+    return y
+
+
 def _wpt_filter_call(y, x, filt, tree, fw):
+    if _is_complex(y) or _is_complex(x):
+        return _wpt_complex_call(y, x, filt, tree, fw)
     _check_pair(y, x, vector_only=True)
     lib = _lib.load()
     h, st = _context(x.device)
@@ -573,6 +694,8 @@ def _wpt_filter_call(y, x, filt, tree, fw):
 
 
 def _wpt_lifting_call(y, sch, tree, fw):
+    if _is_complex(y):
+        return _wpt_complex_call(y, y, sch, tree, fw)
     _check_one(y, vector_only=True)
     lib = _lib.load()
     h, st = _context(y.device)
@@ -590,12 +713,14 @@ def _wpt_lifting_call(y, sch, tree, fw):
 
 
 def _xwpt(x, wt, tree_or_L, fw):
-    x = _prep_in(x)
+    x = _prep_in(x, complex_ok=True)
     if x.dim() != 1:
         raise TypeError("wpt is defined for vectors only (WPTArray = AbstractVector)")
     tree = _tree_arg(x.numel(), tree_or_L)
     if isinstance(wt, OrthoFilter):
         return _wpt_filter_call(similar(x), x, wt, tree, fw)
+    if isinstance(wt, GLS) and _is_complex(x):
+        return _wpt_complex_call(similar(x), x, wt, tree, fw)          # (the copy of x is the split pass)
     if isinstance(wt, GLS):
         y = similar(x)
         y.copy_(x)
@@ -633,3 +758,40 @@ def wpt_(*args) -> torch.Tensor:
 
 def iwpt_(*args) -> torch.Tensor:
     return _xwpt_inplace(args, False)
+
+
+# ---- complex staging, for direct use ---------------------------------------------------------------
+def complex_split(z: torch.Tensor) -> torch.Tensor:
+    """Planar components of a dense complex array (wl_complex_split): a real array of shape (*z.shape, 2), column-major, with
+    [..., 0] = real(z) and [..., 1] = imag(z), bit for bit."""
+    if not _is_complex(z):
+        raise TypeError("complex_split expects a ComplexF32 / ComplexF64 device tensor")
+    if z.device.type != "cuda" or z.dtype not in _COMPLEX:
+        raise TypeError("complex_split expects a ComplexF32 / ComplexF64 device tensor")
+    z = julia_layout(z)
+    code, real_dtype = _COMPLEX[z.dtype]
+    shape = tuple(int(v) for v in z.shape) + (2,)
+    planes = torch.empty(tuple(reversed(shape)), dtype=real_dtype, device=z.device).permute(*reversed(range(len(shape))))
+    n = int(z.numel())
+    if n:
+        h, st = _context(z.device)
+        _check(_lib.load().wl_complex_split(h, code, C.c_void_p(planes.data_ptr()), n, C.c_void_p(z.data_ptr()), n, 1, n, st), h)
+    return planes
+
+
+def complex_merge(planes: torch.Tensor) -> torch.Tensor:
+    """The inverse of complex_split: a real array of shape (..., 2) -> the complex array of shape (...) (wl_complex_merge)."""
+    if not isinstance(planes, torch.Tensor) or planes.dtype not in (torch.float32, torch.float64):
+        raise TypeError("complex_merge expects a Float32 / Float64 device tensor of shape (..., 2)")
+    if planes.dim() < 2 or int(planes.shape[-1]) != 2:
+        raise DimensionMismatch("complex_merge expects the two components along the last dimension")
+    planes = _prep_in(planes, maxdim=5)
+    cdtype = torch.complex64 if planes.dtype == torch.float32 else torch.complex128
+    shape = tuple(int(v) for v in planes.shape[:-1])
+    z = torch.empty(tuple(reversed(shape)), dtype=cdtype, device=planes.device)
+    z = z.permute(*reversed(range(len(shape)))) if len(shape) > 1 else z
+    n = int(z.numel())
+    if n:
+        h, st = _context(planes.device)
+        _check(_lib.load().wl_complex_merge(h, _dtype_code(planes), C.c_void_p(z.data_ptr()), C.c_void_p(planes.data_ptr()), n, n, 1, n, st), h)
+    return z
