@@ -480,13 +480,13 @@ WL_API int wl_dwt_lifting_complex(wl_ctx *ctx, int dtype, void *y, const void *x
                                   int64_t unit_stride, int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
                                   const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2, int L, int fw,
                                   void *stream);
-/* y = wpt(x, filter, tree) / iwpt of ONE complex signal of n values (the packet transform has no batch form): split, the packet
- * transform of wl_wpt_filter on each of the two planes, merge.  tree == NULL: the full tree of depth L (wl_wpt_filter_full;
+/* y = wpt(x, filter, tree) / iwpt of ONE complex signal of n values: split, the packet transform of wl_wpt_filter on the two
+ * planes as one batch of two units of stride ps (the level loop of wl_wpt_filter_batch), merge.  tree == NULL: the full tree of depth L (wl_wpt_filter_full;
  * 0 <= L <= maxtransformlevels(n), else WL_EINVAL_L; capturable in a hipGraph).  Otherwise tree / ntree as wl_wpt_filter (HOST
  * pointer, copied before the call returns; not capturable for a partially split tree) and L is ignored.  y must not alias x.
  * Status codes in this order: WL_EINVAL_ARG, WL_EINVAL_DTYPE, WL_EINVAL_FILTER, WL_EDIMS, WL_EALIAS, WL_EINVAL_L / WL_EINVAL_TREE.
- * Workspace: the packet region of one plane (wl_workspace_bytes_full(dtype, 1, {n}, L)) rounded up to 256 bytes + the planes P
- * and Q, 2 * (2 ps) elements.                                                                                                   */
+ * Workspace: the packet region of the two planes (wl_workspace_bytes_full(dtype, 1, {2 ps}, L)) rounded up to 256 bytes + the
+ * planes P and Q, 2 * (2 ps) elements.                                                                                          */
 WL_API int wl_wpt_filter_complex(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, const double *qmf, int flen,
                                  const uint8_t *tree, int64_t ntree, int L, int fw, void *stream);
 /* The same for a GLS: wpt!(y, scheme, tree) of the copy of x (y == x allowed), the packet transform of wl_wpt_lifting in place on
@@ -495,6 +495,40 @@ WL_API int wl_wpt_lifting_complex(wl_ctx *ctx, int dtype, void *y, const void *x
                                   const int32_t *step_is_update, const int32_t *step_ncoef, const int32_t *step_shift,
                                   const double *coefs_flat, double norm1, double norm2, const uint8_t *tree, int64_t ntree, int L,
                                   int fw, void *stream);
+
+/* ---- batched wavelet packet transforms ----------------------------------------------------------------------------------------- */
+/* y_i = wpt(x_i, filter, tree) (fw = 0: iwpt) of nunits independent signals of n values that share ONE tree: unit i is the n
+ * elements at element offset i * unit_stride (>= n) of x and of y.  The reference has no batched form; the result is BIT FOR BIT
+ * what nunits calls of wl_wpt_filter / wl_wpt_filter_full on the units give, in one chain of launches over all units (the launch
+ * plan is the one of a single unit of length n).  tree == NULL: the full tree of depth L (0 <= L <= maxtransformlevels(n), else
+ * WL_EINVAL_L; capturable in a hipGraph once the workspace is held).  Otherwise tree is the HOST byte-per-node vector of
+ * ntree = 2^maxtransformlevels(n) - 1 nodes, validated and staged as wl_wpt_filter does it (copied before the call returns; a
+ * partially split tree is not capturable) and L is ignored.  Depth 0, an empty tree or an unset root copies the units.  The padding
+ * between units of y is never written.  The call only enqueues on `stream`.
+ * The packet kernels take a batch whose unit bases of x, y and the work buffer are all 16-byte aligned (x and y aligned and, for
+ * nunits > 1, unit_stride * sizeof(T) a multiple of 16); any other batch, odd or > 10-tap filters, segments that are no power of
+ * two and wl_ctx_set_path(ctx, 1) take the per-depth kernels with the unit as a third extent -- one launch per depth over all units
+ * either way, never a loop over the units.  wl_last_kernel reports the kernel name of the single-unit transform: the batch runs
+ * the same kernel instances (the single transform is their batch of one), in the fused library too.
+ * Status codes in this order: WL_EINVAL_ARG (NULL ctx / y / x / qmf), WL_EINVAL_DTYPE,
+ * WL_EINVAL_FILTER, WL_EDIMS (n < 1, nunits < 1, unit_stride < n, nunits * unit_stride >= 2^61), WL_EALIAS (y == x), WL_EINVAL_L
+ * (tree == NULL), WL_EINVAL_TREE.
+ * Workspace: units are taken in groups of G -- all of them, at most 65535 (context option WL_WPT_BATCH_GROUP lowers it), halved
+ * until the work buffer G * unit_stride * sizeof(T) is below the context's cap (option WL_TI_WS_CAP_MB, default 8192); groups
+ * change no bit.  With N = G * unit_stride the call holds 2 * (N / 2 + 64) + 3 N + 64 elements + the staged node bits (< n bytes,
+ * partially split trees only) + 256 bytes: nothing is allocated once wl_workspace_bytes_full(dtype, 1, {nunits * unit_stride}, L)
+ * bytes are reserved.                                                                                                            */
+WL_API int wl_wpt_filter_batch(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int64_t nunits, int64_t unit_stride,
+                               const double *qmf, int flen, const uint8_t *tree, int64_t ntree, int L, int fw, void *stream);
+/* The same for a GLS (scheme arguments as wl_dwt_lifting): y == x is the in-place wpt!(y, scheme, tree) of every unit, y != x
+ * leaves x untouched (the first pass reads x and writes y).  Bit for bit nunits calls of wl_wpt_lifting / wl_wpt_lifting_full.
+ * Fully split depths of a dense batch (unit_stride == n) are one launch of the fused line kernels over all segments of all units;
+ * partially split depths and padded batches take the per-depth lifting passes with the unit as a third extent.  Status codes in
+ * this order: WL_EINVAL_ARG, WL_EINVAL_DTYPE, WL_EINVAL_SCHEME, WL_EDIMS, WL_EINVAL_L, WL_EINVAL_TREE.  Workspace as above.       */
+WL_API int wl_wpt_lifting_batch(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int64_t nunits, int64_t unit_stride,
+                                int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef, const int32_t *step_shift,
+                                const double *coefs_flat, double norm1, double norm2, const uint8_t *tree, int64_t ntree, int L,
+                                int fw, void *stream);
 
 /* ---- introspection (tests / bench) ---------------------------------------------------- */
 /* Select the kernel family: 0 = auto (fast paths where they apply), 1 = generic kernels

@@ -16,7 +16,7 @@ from .util import (maxtransformlevels, sufficientpoweroftwo, detailindex, detail
                    ndyadicscales, maketree, isvalidtree, iscube, isdyadic,
                    dyadicdetailindex, dyadicdetailrange, dyadicscalingrange, dyadicdetailn, maxdyadiclevel, tl2dyadiclevel,
                    dyadiclevel2tl, mirror, upsample, downsample, wcount, testfunction)
-from .transforms import (dwt, idwt, dwt_, idwt_, dwt_oop_, idwt_oop_, dwtc, idwtc, dwtc_, idwtc_, wpt, iwpt, wpt_, iwpt_, dwt_batch, idwt_batch,
+from .transforms import (dwt, idwt, dwt_, idwt_, dwt_oop_, idwt_oop_, dwtc, idwtc, dwtc_, idwtc_, wpt, iwpt, wpt_, iwpt_, dwt_batch, idwt_batch, wpt_batch, iwpt_batch,
                          to_device, to_host, similar, julia_layout, is_julia_layout, complex_split, complex_merge, set_complex_arrays, get_complex_arrays, complex_arrays,
                          reserve_workspace, workspace_held, set_kernel_path, last_kernel, destroy_contexts, set_option, clear_options, options, set_arithmetic, get_arithmetic, arithmetic,
                          DimensionMismatch, ArgumentError, HIPError)
@@ -29,7 +29,7 @@ from . import _lib
 
 __all__ = [
     "WT", "Util", "wavelet", "OrthoFilter", "GLS",
-    "dwt", "idwt", "dwt_", "idwt_", "dwt_oop_", "idwt_oop_", "dwtc", "idwtc", "dwtc_", "idwtc_", "wpt", "iwpt", "wpt_", "iwpt_", "dwt_batch", "idwt_batch",
+    "dwt", "idwt", "dwt_", "idwt_", "dwt_oop_", "idwt_oop_", "dwtc", "idwtc", "dwtc_", "idwtc_", "wpt", "iwpt", "wpt_", "iwpt_", "dwt_batch", "idwt_batch", "wpt_batch", "iwpt_batch",
     "maxtransformlevels", "sufficientpoweroftwo", "detailindex", "detailrange", "detailn",
     "ndyadicscales", "maketree", "isvalidtree", "iscube", "isdyadic",
     "dyadicdetailindex", "dyadicdetailrange", "dyadicscalingrange", "dyadicdetailn", "maxdyadiclevel", "tl2dyadiclevel",

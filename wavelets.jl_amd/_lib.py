@@ -103,6 +103,10 @@ SIGNATURES = {
     "wl_wpt_filter_complex": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, _f64p, C.c_int, _u8p, C.c_int64, C.c_int, C.c_int, _vp]),
     "wl_wpt_lifting_complex": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, C.c_int, _i32p, _i32p, _i32p, _f64p, C.c_double, C.c_double,
                                          _u8p, C.c_int64, C.c_int, C.c_int, _vp]),
+    "wl_wpt_filter_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _f64p, C.c_int, _u8p, C.c_int64, C.c_int,
+                                      C.c_int, _vp]),
+    "wl_wpt_lifting_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, _i32p, _i32p, _i32p, _f64p,
+                                       C.c_double, C.c_double, _u8p, C.c_int64, C.c_int, C.c_int, _vp]),
     "wl_circshift": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i64p, _i64p, _vp]),
     "wl_arrayadd": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, _vp]),
     "wl_rmul": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_double, _vp]),

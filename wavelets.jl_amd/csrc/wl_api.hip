@@ -775,13 +775,20 @@ static bool isvalidtree(int64_t n, const uint8_t *b, int64_t nb, int64_t *last_s
 template <typename T>
 static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
                     const Taps<T> *taps, const LiftScheme<T> *sc,
-                    const uint8_t *tree, int64_t ntree, int64_t last_set, int fw, int full_depth = -1, int first_depth = 0)
+                    const uint8_t *tree, int64_t ntree, int64_t last_set, int fw, int full_depth = -1, int first_depth = 0,
+                    int64_t nunits = 1, int64_t ustride = 0)
 {
     // full_depth >= 0: the full tree of that depth, no tree vector (tree == nullptr); only its depths >= first_depth are applied
     // (x already holds the depth-first_depth content: the best-basis search steps one depth at a time)
+    // nunits > 1 (wl_wpt_*_batch): nunits signals of length n that share the tree, unit u at element offset u * ustride of x, of y and
+    // of the work buffers.  The plan below is made for ONE unit of length n -- the batch takes the same kernels, every launch over all
+    // units, the packet kernels being the very instances the single unit runs -- and lifting may then run out of place (x != y: the
+    // first pass reads x, x stays untouched).
     const bool lifting = (sc != nullptr);
-    Extent3 full = {{n, 1, 1}};
-    Strides3 fst = {{1, n, n}};
+    if (nunits == 1) ustride = n;
+    const bool dense = (ustride == n);
+    Extent3 full = {{n, 1, nunits}};
+    Strides3 fst = {{1, n, ustride}};
     if (full_depth >= 0 ? full_depth == 0 : (ntree == 0 || !tree[0])) {
         if (y != x) WL_HIP(ctx, generic_copy_box<T>(st, x, fst, y, fst, full));
         ctx->last_kernel = "copy";
@@ -812,10 +819,11 @@ static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
     while (ncopy - 1 <= last_set && ncopy - 1 < ntree) ncopy <<= 1;
     ncopy = (ncopy - 1 < ntree) ? ncopy - 1 : ntree;
     if (full_depth >= 0) ncopy = 0;
-    int rc = ensure_ws(ctx, ws_elems(n) * sizeof(T) + (size_t)(any_partial ? ncopy : 0) + 256, st);
+    const int64_t NW = nunits * ustride;                // the work buffers mirror the layout of x and y
+    int rc = ensure_ws(ctx, ws_elems(NW) * sizeof(T) + (size_t)(any_partial ? ncopy : 0) + 256, st);
     if (rc) return rc;
-    Work<T> w = carve<T>(ctx->ws, n);
-    uint8_t *dtree = (uint8_t *)ctx->ws + ws_elems(n) * sizeof(T);
+    Work<T> w = carve<T>(ctx->ws, NW);
+    uint8_t *dtree = (uint8_t *)ctx->ws + ws_elems(NW) * sizeof(T);
     if (any_partial) {
         rc = wl_stage_to_device(ctx, dtree, tree, (size_t)ncopy, st);
         if (rc) return rc;
@@ -824,30 +832,31 @@ static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
     // starts 4 or 8 bytes off the grid (buf[1:1+n]) takes the per-depth kernels, which gate on alignment themselves
     auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     const bool fast_any = (ctx->path == 0) && opt("WL_WPT_FAST", 1) != 0;          // the lifting line kernels check alignment themselves
-    const bool fast = fast_any && al16(x) && al16(y) && al16(w.T0);              // the filter-bank packet kernels
+    // (a batch: every unit base, that is the stride too -- NW is then a multiple of 16 bytes and so is T0's offset in the workspace)
+    const bool fast = fast_any && al16(x) && al16(y) && al16(w.T0) && (nunits == 1 || (ustride * sizeof(T)) % 16 == 0);   // the filter-bank packet kernels
 
     if (lifting) {
         // wpt!(y, scheme, ...) is in place for the caller.  A fused lifting level cannot run in place (its [s ; d] outputs land
         // where other waves still read interleaved input; lifting_lines_fast would stage and copy back: three launches), so fully
         // split depths ping-pong between y and a work buffer -- one launch per depth -- and an odd count ends with one copy.
         const char *name = "k_generic_lift_wpt";
-        T *cur = y;
+        const T *cur = x;
         for (int i = 0; i < K; ++i) {
             const int d = depths[i];
             const int64_t nj = n >> d, nseg = (int64_t)1 << d;
-            // fully split depth: one lifting level (all steps fused) of nseg lines of length nj
-            if (kind[i] == 2 && fast_any) {
+            // fully split depth: one lifting level (all steps fused) of nseg lines of length nj (a dense batch: nseg * nunits lines)
+            if (kind[i] == 2 && fast_any && dense) {
                 int handled = 0, herr = 0;
                 const char *kn = nullptr;
                 T *out = (cur == y) ? w.T0 : y;
-                rc = lifting_lines_fast<T>(ctx->ws, ctx->cu_count, st, nj, nseg, nj, out, cur, *sc, 1, fw, &handled, &kn, &herr);
+                rc = lifting_lines_fast<T>(ctx->ws, ctx->cu_count, st, nj, nseg * nunits, nj, out, cur, *sc, 1, fw, &handled, &kn, &herr);
                 if (rc) { ctx->last_hip = herr; return rc; }
                 if (handled) { name = kn ? kn : "k_lift1d_stream"; cur = out; continue; }
             }
             if (cur != y) { WL_HIP(ctx, generic_copy_box<T>(st, cur, fst, y, fst, full)); cur = y; }
-            Extent3 ext = {{nj, nseg, 1}};
-            Strides3 bst = {{1, nj, n}};
-            Extent3 lo = {{nj >> 1, nseg, 1}};
+            Extent3 ext = {{nj, nseg, nunits}};
+            Strides3 bst = {{1, nj, ustride}};
+            Extent3 lo = {{nj >> 1, nseg, nunits}};
             const uint8_t *mask = (kind[i] == 2) ? nullptr : dtree + (((int64_t)1 << d) - 1);
             // reads of y all happen in the first kernel, so in place is safe
             if (fw) {
@@ -915,27 +924,27 @@ static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
         const int d = sp.d;
         T *out = ((P - 1 - i) % 2 == 0) ? y : w.T0;
         if (sp.kindk == 1) {
-            WL_HIP(ctx, wpt_fwd_multi_launch<T>(st, *taps, cur, out, n, n >> d, sp.nd, pmask));
+            WL_HIP(ctx, wpt_fwd_multi_launch<T>(st, *taps, cur, out, n, n >> d, sp.nd, pmask, nunits, ustride));
             name = "k_wpt_fwd_multi";
         } else if (sp.kindk == 3) {
-            WL_HIP(ctx, wpt_inv_multi_launch<T>(st, *taps, cur, out, n, n >> d, sp.nd, pmask));
+            WL_HIP(ctx, wpt_inv_multi_launch<T>(st, *taps, cur, out, n, n >> d, sp.nd, pmask, nunits, ustride));
             name = "k_wpt_inv_multi";
         } else if (sp.kindk == 2) {
-            WL_HIP(ctx, wpt_tail_launch<T>(st, *taps, fw, cur, out, n, n >> d, sp.nd, pmask));
+            WL_HIP(ctx, wpt_tail_launch<T>(st, *taps, fw, cur, out, n, n >> d, sp.nd, pmask, nunits, ustride));
             if (std::strncmp(name, "k_wpt", 5) != 0) name = fw ? "k_wpt_fwd_tail" : "k_wpt_inv_tail";
         } else {
             const int64_t nj = n >> d, nseg = (int64_t)1 << d;
-            Extent3 ext = {{nj, nseg, 1}};
-            Strides3 bst = {{1, nj, n}};
-            Extent3 lo = {{nj >> 1, nseg, 1}};
+            Extent3 ext = {{nj, nseg, nunits}};
+            Strides3 bst = {{1, nj, ustride}};
+            Extent3 lo = {{nj >> 1, nseg, nunits}};
             int ki = 0;
             while (depths[ki] != d) ++ki;
             const bool all_set = kind[ki] == 2;
             bool done = false;
-            if (all_set && ctx->path == 0) {             // fully split depth: every segment is a line of the streaming kernels
+            if (all_set && ctx->path == 0 && dense) {    // fully split depth: every segment (of every unit of a dense batch) is a line of the streaming kernels
                 hipError_t he = hipSuccess;
-                done = fw ? fast_lines_fwd_level<T>(st, *taps, cur, nj, out, nj, out + (nj >> 1), nj, nj, nseg, ctx->cu_count, &he)
-                          : fast_lines_inv_level<T>(st, *taps, cur, nj, cur + (nj >> 1), nj, out, nj, nj, nseg, ctx->cu_count, &he);
+                done = fw ? fast_lines_fwd_level<T>(st, *taps, cur, nj, out, nj, out + (nj >> 1), nj, nj, nseg * nunits, ctx->cu_count, &he)
+                          : fast_lines_inv_level<T>(st, *taps, cur, nj, cur + (nj >> 1), nj, out, nj, nj, nseg * nunits, ctx->cu_count, &he);
                 if (he != hipSuccess) return hip_fail(ctx, he);
                 if (done && std::strncmp(name, "k_wpt", 5) != 0) name = fw ? "k_fwd1d_stream" : "k_inv1d_stream";
             }
@@ -1211,6 +1220,95 @@ int wl_wpt_lifting_full(wl_ctx *ctx, int dtype, void *y, int64_t n,
 
 }  // extern "C"
 
+// ---- batched packet transforms (wl_wpt_*_batch) --------------------------------------------------------------------------------
+// nunits signals that share one tree, in groups of G units: all of them, at most 65535 (option WL_WPT_BATCH_GROUP lowers it: tests
+// reach the group boundary with a handful of units), halved while the work buffer of a group exceeds the context's cap
+// (WL_TI_WS_CAP_MB).  65535 is what the second grid dimension of the packet kernels takes.  A group is ONE wpt_impl call over all its units.
+template <typename T>
+static int wpt_batch_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n, int64_t nunits, int64_t ustride, const Taps<T> *taps,
+                          const LiftScheme<T> *sc, const uint8_t *tree, int64_t ntree, int64_t last_set, int fw, int full_depth)
+{
+    int64_t G = nunits < 65535 ? nunits : 65535;
+    const long long og = opt("WL_WPT_BATCH_GROUP", 0);
+    if (og >= 1 && og < G) G = og;
+    const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
+    while (G > 1 && (size_t)G * (size_t)ustride * sizeof(T) > cap) G = (G + 1) / 2;
+    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
+        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
+        int rc = wpt_impl<T>(ctx, st, y + u0 * ustride, x + u0 * ustride, n, taps, sc, tree, ntree, last_set, fw, full_depth, 0, nb, ustride);
+        if (rc != WL_OK) return rc;
+    }
+    return WL_OK;
+}
+
+// what the two entry points share after their pointer / dtype / wavelet rules
+static int wpt_batch_check(int64_t n, int64_t nunits, int64_t unit_stride, const void *y, const void *x, bool alias_ok, const uint8_t *tree,
+                           int64_t ntree, int L, int64_t *last_set)
+{
+    if (n < 1 || nunits < 1 || unit_stride < n || unit_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
+    if (!alias_ok && y == x) return WL_EALIAS;
+    *last_set = -1;
+    if (!tree) {
+        if (L < 0 || L > wl_maxtransformlevels(n)) return WL_EINVAL_L;
+    } else if (!isvalidtree(n, tree, ntree, last_set)) {
+        return WL_EINVAL_TREE;
+    }
+    return WL_OK;
+}
+
+extern "C" {
+
+int wl_wpt_filter_batch(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int64_t nunits, int64_t unit_stride,
+                        const double *qmf, int flen, const uint8_t *tree, int64_t ntree, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !qmf) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
+    int64_t last_set = -1;
+    int rc = wpt_batch_check(n, nunits, unit_stride, y, x, false, tree, ntree, L, &last_set);
+    if (rc) return rc;
+    const int full_depth = tree ? -1 : L;
+    WL_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == WL_F32) {
+        Taps<float> t; make_taps<float>(qmf, flen, t);
+        return wpt_batch_impl<float>(ctx, st, (float *)y, (const float *)x, n, nunits, unit_stride, &t, nullptr, tree, tree ? ntree : 0, last_set, fw,
+                                     full_depth);
+    }
+    Taps<double> t; make_taps<double>(qmf, flen, t);
+    return wpt_batch_impl<double>(ctx, st, (double *)y, (const double *)x, n, nunits, unit_stride, &t, nullptr, tree, tree ? ntree : 0, last_set, fw,
+                                  full_depth);
+}
+
+int wl_wpt_lifting_batch(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int64_t nunits, int64_t unit_stride, int nsteps,
+                         const int32_t *step_is_update, const int32_t *step_ncoef, const int32_t *step_shift, const double *coefs_flat,
+                         double norm1, double norm2, const uint8_t *tree, int64_t ntree, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    int64_t last_set = -1;
+    const int full_depth = tree ? -1 : L;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == WL_F32) {
+        LiftScheme<float> sc;
+        int rc = make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
+        if (rc == WL_OK) rc = wpt_batch_check(n, nunits, unit_stride, y, x, true, tree, ntree, L, &last_set);
+        if (rc) return rc;
+        WL_SCOPE(ctx);
+        return wpt_batch_impl<float>(ctx, st, (float *)y, (const float *)x, n, nunits, unit_stride, nullptr, &sc, tree, tree ? ntree : 0, last_set, fw,
+                                     full_depth);
+    }
+    LiftScheme<double> sc;
+    int rc = make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
+    if (rc == WL_OK) rc = wpt_batch_check(n, nunits, unit_stride, y, x, true, tree, ntree, L, &last_set);
+    if (rc) return rc;
+    WL_SCOPE(ctx);
+    return wpt_batch_impl<double>(ctx, st, (double *)y, (const double *)x, n, nunits, unit_stride, nullptr, &sc, tree, tree ? ntree : 0, last_set, fw,
+                                  full_depth);
+}
+
+}  // extern "C"
+
 // ---- complex-valued transforms (wl_*_complex) ----------------------------------------------------------------------------------
 // Complex{T} data is (re, im) interleaved and the taps are real: re(y) = transform(re(x)), im(y) = transform(im(x)).  A group of G
 // complex units is split into 2 G planar real planes P (k_cplx_split, wl_complex.hip), the batched level loops of the real entry
@@ -1359,23 +1457,22 @@ int complex_check(int ndims, const int64_t *dims, int64_t nunits, int64_t unit_s
     return WL_OK;
 }
 
-// one complex signal through the packet transform: split, wpt_impl on each plane (filters: P -> Q; lifting: in place on P), merge
+// one complex signal through the packet transform: split, wpt_impl on the two planes as one batch of two units of stride ps
+// (filters: P -> Q; lifting: in place on P), merge
 template <typename T>
 int wpt_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n, const Taps<T> *taps, const LiftScheme<T> *sc,
                      const uint8_t *tree, int64_t ntree, int64_t last_set, int fw, int full_depth)
 {
     const int64_t ps = plane_stride_of<T>(n);
-    const size_t inner = up256(ws_elems(n) * sizeof(T) + (size_t)(tree ? ntree : 0) + 256), pl = up256((size_t)(2 * ps) * sizeof(T));
+    const size_t inner = up256(ws_elems(2 * ps) * sizeof(T) + (size_t)(tree ? ntree : 0) + 256), pl = up256((size_t)(2 * ps) * sizeof(T));
     int rc = ensure_ws(ctx, inner + (taps ? 2 : 1) * pl, st);
     if (rc != WL_OK) return rc;
     const void *held = ctx->ws;
     T *P = (T *)((char *)ctx->ws + inner), *Q = taps ? (T *)((char *)ctx->ws + inner + pl) : P;
     WL_HIP(ctx, complex_split<T>(st, ctx->cu_count, P, ps, x, n, 1, n));
-    for (int c = 0; c < 2; ++c) {
-        rc = wpt_impl<T>(ctx, st, Q + c * ps, P + c * ps, n, taps, sc, tree, ntree, last_set, fw, full_depth);
-        if (rc != WL_OK) return rc;
-        if (ctx->ws != held) return WL_ENOMEM;               // (not reached: wpt_impl asks for no more than `inner`)
-    }
+    rc = wpt_impl<T>(ctx, st, Q, P, n, taps, sc, tree, ntree, last_set, fw, full_depth, 0, 2, ps);
+    if (rc != WL_OK) return rc;
+    if (ctx->ws != held) return WL_ENOMEM;                   // (not reached: wpt_impl asks for no more than `inner`)
     WL_HIP(ctx, complex_merge<T>(st, ctx->cu_count, y, Q, ps, n, 1, n));
     return WL_OK;
 }

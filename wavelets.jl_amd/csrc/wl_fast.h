@@ -257,13 +257,16 @@ hipError_t inv2d_long_launch(hipStream_t st, const Taps<T> &taps, const T *x, in
                              T *dst, int64_t ldd, int64_t n0, int64_t n1, int cu_count, const InvLongBatch &bt = InvLongBatch{1, 0, 0, 0, 1});
 
 // ---- fully split depths of the packet transform (wl_wpt.hip) ----
+// n, nj: the length of ONE unit and its segment length.  nunits > 1: a batch of units that share the tree, unit u at element offset
+// u * stride of src and of dst (every unit base 16-byte aligned), all units in the one launch of the same kernel instances;
+// at most 65535 units per launch (the unit is the second grid dimension; the caller forms groups).
 template <typename T> int wpt_tile_samples();
 template <typename T> bool wpt_fwd_multi_ok(int F, int64_t n, int64_t nj, int NL);
-template <typename T> hipError_t wpt_fwd_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask = nullptr);
+template <typename T> hipError_t wpt_fwd_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask = nullptr, int64_t nunits = 1, int64_t stride = 0);
 template <typename T> bool wpt_inv_multi_ok(int F, int64_t n, int64_t nj, int NL);
-template <typename T> hipError_t wpt_inv_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask = nullptr);
+template <typename T> hipError_t wpt_inv_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask = nullptr, int64_t nunits = 1, int64_t stride = 0);
 template <typename T> bool wpt_tail_ok(int F, int64_t n, int64_t nj, int ndepth);
-template <typename T> hipError_t wpt_tail_launch(hipStream_t st, const Taps<T> &taps, int fw, const T *src, T *dst, int64_t n, int64_t nj, int ndepth, const uint8_t *mask = nullptr);
+template <typename T> hipError_t wpt_tail_launch(hipStream_t st, const Taps<T> &taps, int fw, const T *src, T *dst, int64_t n, int64_t nj, int ndepth, const uint8_t *mask = nullptr, int64_t nunits = 1, int64_t stride = 0);
 
 // ---- a batch of independent volumes (wl_batch3d.hip) ----
 // All L levels of the 3-D transform of nvol (<= 65535) dense boxes dims[0] x dims[1] x dims[2], volume i at element offset i * xs of x

@@ -15,6 +15,10 @@
 //                     indexing (bit mask), down to segments of two samples; one launch instead of one per depth.
 //   k_wpt_inv_tail    the mirror for iwpt: the deepest depths first, [s ; d] halves of a segment -> the segment.
 //
+// Batches (wl_wpt_*_batch): every kernel takes nunits signals that share the tree, unit u at element offset
+// u * stride; blockIdx.y is the unit (the tail packs several whole units of fewer than TS samples into one workgroup instead) and
+// segments and node bits are relative to the unit.  The single transform is the batch of one unit of the same instances.
+//
 // Arithmetic: the closed forms of wl_internal.h in the reference's summation order, no FMA -- bit-identical to the per-depth
 // kernels (tests/test_gpu_parity.py::test_wpt_bitexact pins both against the oracle).
 #include "wl_fast.h"
@@ -33,6 +37,10 @@ struct WptMultiArgs {
     // of depth D; nullptr: every segment of every fused depth splits) and the depth of the first fused level.  A valid tree has no
     // set node below an unset one, so "bit clear" means "this region is (part of) a leaf: pass it through".
     const uint8_t *mask; int depth;
+    // A batch of independent units that share the tree (wl_wpt_*_batch; one unit: the plain transform): unit u is the n elements at
+    // element offset u * stride of src and of dst; blockIdx.y is the unit (at most 65535 per launch), blockIdx.x its tile.
+    // Positions, segments and node bits are all relative to the unit.
+    int64_t stride;
     TapsF<T, F> tp;
 };
 
@@ -48,10 +56,13 @@ __global__ void __launch_bounds__(256) k_wpt_fwd_multi(WptMultiArgs<T, F> a)
     int H[4];
     H[NL] = 0;
     for (int t = NL; t >= 1; --t) H[t - 1] = 2 * H[t] + (F - 2);
-    const int64_t own0 = (int64_t)blockIdx.x * TS;                        // position in the vector
+    const unsigned tile = blockIdx.x;
+    const T *usrc = a.src + (int64_t)blockIdx.y * a.stride;
+    T *udst = a.dst + (int64_t)blockIdx.y * a.stride;
+    const int64_t own0 = (int64_t)tile * TS;                                       // position in the vector (batch: in the unit)
     const int64_t root = own0 / a.nj;                                     // segment of the first fused depth
     const int64_t r0 = own0 - root * a.nj;                                // ... and the tile's offset inside it
-    const T *seg = a.src + root * a.nj;
+    const T *seg = usrc + root * a.nj;
     T *bufA = reinterpret_cast<T *>(smem_raw);
     T *bufB = bufA + a.buf_elems;
     auto gq = [&](const int m) __attribute__((always_inline)) { return (m & 1) ? -a.tp.h[m] : a.tp.h[m]; };
@@ -107,7 +118,7 @@ __global__ void __launch_bounds__(256) k_wpt_fwd_multi(WptMultiArgs<T, F> a)
         const bool lastlev = (t == NL);
         // leaves: band b of the root segment lives at root * nj + b * (nj >> NL), this tile's piece at (r0 >> NL)
         const int64_t leaf = a.nj >> NL;
-        T *out0 = a.dst + root * a.nj + (r0 >> NL);
+        T *out0 = udst + root * a.nj + (r0 >> NL);
         const int64_t segb = root << (t - 1);                             // first segment of depth a.depth + t - 1 under this root
         for (int g = tid; g < total; g += 256) {
             const int b = g / gpb;
@@ -121,7 +132,7 @@ __global__ void __launch_bounds__(256) k_wpt_fwd_multi(WptMultiArgs<T, F> a)
                 if (a.mask[(((int64_t)1 << (a.depth + t - 1)) - 1) + segb + b] == 0) {
                     // a leaf of the tree: its owned samples (parent-band local index 2 (i + q) + F - 2 <-> owned pair i + q - H[t]) go out as they are
                     typedef typename VecOf<T, 2>::type P2;
-                    T *lo = a.dst + root * a.nj + (int64_t)b * (a.nj >> (t - 1)) + (r0 >> (t - 1));
+                    T *lo = udst + root * a.nj + (int64_t)b * (a.nj >> (t - 1)) + (r0 >> (t - 1));
 #pragma unroll
                     for (int q = 0; q < PPT; ++q) {
                         const int io = i + q - H[t];
@@ -173,6 +184,7 @@ struct WptInvMultiArgs {
     int bs[4];                      // band stride in LDS at fused level t
     int buf_elems;
     const uint8_t *mask; int depth; // as WptMultiArgs; depth = the SHALLOWEST fused depth
+    int64_t stride;                 // units of a batch, as WptMultiArgs
     TapsF<T, F> tp;
 };
 
@@ -185,7 +197,10 @@ __global__ void __launch_bounds__(256) k_wpt_inv_multi(WptInvMultiArgs<T, F> a)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x;
     const int NL = a.NL, TS = a.TS;
-    const int64_t own0 = (int64_t)blockIdx.x * TS;
+    const unsigned tile = blockIdx.x;
+    const T *usrc = a.src + (int64_t)blockIdx.y * a.stride;
+    T *udst = a.dst + (int64_t)blockIdx.y * a.stride;
+    const int64_t own0 = (int64_t)tile * TS;
     const int64_t root = own0 / a.nj;
     const int64_t r0 = own0 - root * a.nj;
     T *bufA = reinterpret_cast<T *>(smem_raw);
@@ -196,7 +211,7 @@ __global__ void __launch_bounds__(256) k_wpt_inv_multi(WptInvMultiArgs<T, F> a)
         const int Lt = (TS >> NL) + 2 * a.G[NL];
         const int hp = Lt >> 1;                                           // pairs per band (Lt is even)
         const int total = hp << NL;
-        const T *seg = a.src + root * a.nj;
+        const T *seg = usrc + root * a.nj;
         const int64_t start = (r0 >> NL) - a.G[NL];
         for (int it = tid; it < total; it += 256) {
             const int b = it / hp, jp = it - b * hp;
@@ -219,7 +234,7 @@ __global__ void __launch_bounds__(256) k_wpt_inv_multi(WptInvMultiArgs<T, F> a)
         const bool last = (t == 1);
         // parent pair q of a band is pair q + G[t] - G[t-1] / 2 of its children: SH, or SH + 1 where G[t] was rounded up to even
         const int eps = a.G[t] - a.G[t - 1] / 2 - SH;
-        T *out0 = a.dst + root * a.nj + r0;
+        T *out0 = udst + root * a.nj + r0;
         for (int g = tid; g < total; g += 256) {
             const int b = g / gpb;
             const int q0 = (g - b * gpb) * PPT;
@@ -227,7 +242,7 @@ __global__ void __launch_bounds__(256) k_wpt_inv_multi(WptInvMultiArgs<T, F> a)
                 // parent band b is (part of) a leaf: its samples are taken from the source as they are -- local pair q <-> element
                 // (r0 >> (t-1)) - G[t-1] + 2 q of the band (mod its length).  (If an ancestor is a leaf too nobody reads this band.)
                 const int64_t plen = a.nj >> (t - 1);
-                const T *pb = a.src + root * a.nj + (int64_t)b * plen;
+                const T *pb = usrc + root * a.nj + (int64_t)b * plen;
                 const int64_t start = (r0 >> (t - 1)) - a.G[t - 1];
 #pragma unroll
                 for (int p = 0; p < PPT; ++p) {
@@ -280,8 +295,67 @@ struct WptTailArgs {
     int lgm;                        // segment length 2^lgm at the SHALLOWEST depth handled here (<= chunk)
     int ndepth;                     // depths handled (segments shrink / grow by 2 per depth), 1 <= ndepth <= lgm
     const uint8_t *mask; int depth; // as WptMultiArgs; depth = the shallowest depth handled (segments of 2^lgm)
+    // A batch of units (as WptMultiArgs; one unit: the plain transform).  n >= chunk: blockIdx.y is the unit, blockIdx.x its chunk.
+    // n < chunk (lgn >= 0, n = 2^lgn): a workgroup takes chunk / n WHOLE units, each gathered from and scattered to its own stride
+    // (a dense batch, stride == n, is one contiguous run: staged like a chunk); the last workgroup takes the units that are left and
+    // touches nothing beyond the last one.
+    int64_t stride, nunits;
+    int lgn;                        // log2(n) when a workgroup holds whole units, else -1
     TapsF<T, F> tp;
 };
+// where a workgroup of the tail stands: its source / destination base, the samples it holds and, for the node bits, the
+// first segment of its chunk inside the unit (in chunks) and the bits of a chunk-local segment index that stay inside a unit
+template <typename T>
+struct WptTailPos { const T *src; T *dst; int count; int64_t cblk; int lgn; bool contig; };
+template <typename T, typename A>
+__device__ __forceinline__ WptTailPos<T> wpt_tail_pos(const A &a, int TS)
+{
+    WptTailPos<T> p;
+    if (a.lgn < 0) {
+        const unsigned c = blockIdx.x;
+        p.src = a.src + (int64_t)blockIdx.y * a.stride + (int64_t)c * TS;
+        p.dst = a.dst + (int64_t)blockIdx.y * a.stride + (int64_t)c * TS;
+        p.count = TS; p.cblk = c; p.lgn = -1; p.contig = true;
+    } else {
+        const int64_t u0 = (int64_t)blockIdx.x << (a.lgts - a.lgn);
+        const int64_t left = a.nunits - u0, cap = (int64_t)1 << (a.lgts - a.lgn);
+        p.src = a.src + u0 * a.stride;
+        p.dst = a.dst + u0 * a.stride;
+        p.count = (int)((left < cap ? left : cap) << a.lgn);
+        p.cblk = 0; p.lgn = a.lgn; p.contig = (a.stride == ((int64_t)1 << a.lgn));
+    }
+    return p;
+}
+// count samples = whole units of 2^lgn samples (a multiple of 16 bytes each), unit j of the workgroup at base + j * stride
+template <typename T>
+__device__ __forceinline__ void wpt_units_in(const T *base, int64_t stride, int lgn, T *A, int count, int tid, int nthr)
+{
+    constexpr int VEC = 16 / sizeof(T);
+    for (int c = tid; c < count / VEC; c += nthr) {
+        const int e = c * VEC;
+        T v[VEC];
+        vload<T, VEC>(base + (int64_t)(e >> lgn) * stride + (e & ((1 << lgn) - 1)), v);
+        vstore16<T, VEC>(A + e, v);
+    }
+}
+template <typename T>
+__device__ __forceinline__ void wpt_units_out(T *base, int64_t stride, int lgn, const T *A, int count, int tid, int nthr)
+{
+    constexpr int VEC = 16 / sizeof(T);
+    for (int c = tid; c < count / VEC; c += nthr) {
+        const int e = c * VEC;
+        T v[VEC];
+        vload16<T, VEC>(A + e, v);
+        vstore<T, VEC>(base + (int64_t)(e >> lgn) * stride + (e & ((1 << lgn) - 1)), v);
+    }
+}
+
+// index (inside the unit) of chunk-local segment sg of length 2^lgm: the node bit it reads
+template <typename P>
+__device__ __forceinline__ int64_t wpt_tail_seg(const P &pos, int lgts, int lgm, int sg)
+{
+    return (pos.cblk << (lgts - lgm)) + (pos.lgn < 0 ? sg : (sg & ((1 << (pos.lgn - lgm)) - 1)));
+}
 
 template <typename T>
 __device__ __forceinline__ void wpt_chunk_in(const T *src, T *A, int total, int tid, int nthr)
@@ -318,14 +392,17 @@ __global__ void __launch_bounds__(512) k_wpt_fwd_tail(WptTailArgs<T, F> a)
     const int TS = 1 << a.lgts;
     T *A = reinterpret_cast<T *>(smem_raw);
     T *B = A + TS;
-    wpt_chunk_in<T>(a.src + (int64_t)blockIdx.x * TS, A, TS, tid, nthr);
+    const WptTailPos<T> pos = wpt_tail_pos<T>(a, TS);
+    const int half = pos.count >> 1;                                      // pairs held (the last workgroup of a batch may hold fewer units)
+    if (pos.contig) wpt_chunk_in<T>(pos.src, A, pos.count, tid, nthr);
+    else wpt_units_in<T>(pos.src, a.stride, pos.lgn, A, pos.count, tid, nthr);
     lds_barrier_vm();
     for (int dep = 0; dep < a.ndepth; ++dep) {
         const int lgm = a.lgm - dep, m = 1 << lgm, hm = m >> 1;
-        for (int p = tid; p < (TS >> 1); p += nthr) {
+        for (int p = tid; p < half; p += nthr) {
             const int sg = p >> (lgm - 1), k = p & (hm - 1);
             const T *sb = A + (sg << lgm);
-            if (a.mask && a.mask[(((int64_t)1 << (a.depth + dep)) - 1) + ((int64_t)blockIdx.x << (a.lgts - lgm)) + sg] == 0) {
+            if (a.mask && a.mask[(((int64_t)1 << (a.depth + dep)) - 1) + wpt_tail_seg(pos, a.lgts, lgm, sg)] == 0) {
                 T *ob = B + (sg << lgm);               // (part of) a leaf: passed through
                 ob[k] = sb[k];
                 ob[hm + k] = sb[hm + k];
@@ -351,7 +428,8 @@ __global__ void __launch_bounds__(512) k_wpt_fwd_tail(WptTailArgs<T, F> a)
         lds_barrier();
         T *t = A; A = B; B = t;
     }
-    wpt_chunk_out<T>(a.dst + (int64_t)blockIdx.x * TS, A, TS, tid, nthr);
+    if (pos.contig) wpt_chunk_out<T>(pos.dst, A, pos.count, tid, nthr);
+    else wpt_units_out<T>(pos.dst, a.stride, pos.lgn, A, pos.count, tid, nthr);
 }
 
 // iwpt: depths from the deepest (segments of 2^(lgm - ndepth + 1)) up to segments of 2^lgm
@@ -365,14 +443,17 @@ __global__ void __launch_bounds__(512) k_wpt_inv_tail(WptTailArgs<T, F> a)
     const int TS = 1 << a.lgts;
     T *A = reinterpret_cast<T *>(smem_raw);
     T *B = A + TS;
-    wpt_chunk_in<T>(a.src + (int64_t)blockIdx.x * TS, A, TS, tid, nthr);
+    const WptTailPos<T> pos = wpt_tail_pos<T>(a, TS);
+    const int half = pos.count >> 1;                                      // pairs held (the last workgroup of a batch may hold fewer units)
+    if (pos.contig) wpt_chunk_in<T>(pos.src, A, pos.count, tid, nthr);
+    else wpt_units_in<T>(pos.src, a.stride, pos.lgn, A, pos.count, tid, nthr);
     lds_barrier_vm();
     for (int dep = a.ndepth - 1; dep >= 0; --dep) {
         const int lgm = a.lgm - dep, m = 1 << lgm, hm = m >> 1;
-        for (int p = tid; p < (TS >> 1); p += nthr) {
+        for (int p = tid; p < half; p += nthr) {
             const int sg = p >> (lgm - 1), pp = p & (hm - 1);
             const T *sb = A + (sg << lgm);
-            if (a.mask && a.mask[(((int64_t)1 << (a.depth + dep)) - 1) + ((int64_t)blockIdx.x << (a.lgts - lgm)) + sg] == 0) {
+            if (a.mask && a.mask[(((int64_t)1 << (a.depth + dep)) - 1) + wpt_tail_seg(pos, a.lgts, lgm, sg)] == 0) {
                 *reinterpret_cast<T2 *>(B + (sg << lgm) + 2 * pp) = *reinterpret_cast<const T2 *>(sb + 2 * pp);
                 continue;
             }
@@ -389,7 +470,8 @@ __global__ void __launch_bounds__(512) k_wpt_inv_tail(WptTailArgs<T, F> a)
         lds_barrier();
         T *t = A; A = B; B = t;
     }
-    wpt_chunk_out<T>(a.dst + (int64_t)blockIdx.x * TS, A, TS, tid, nthr);
+    if (pos.contig) wpt_chunk_out<T>(pos.dst, A, pos.count, tid, nthr);
+    else wpt_units_out<T>(pos.dst, a.stride, pos.lgn, A, pos.count, tid, nthr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -414,12 +496,14 @@ bool wpt_fwd_multi_ok(int F, int64_t n, int64_t nj, int NL)
 }
 
 template <typename T, int F>
-static hipError_t launch_wpt_multi_f(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask)
+static hipError_t launch_wpt_multi_f(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask,
+                                     int64_t nunits, int64_t stride)
 {
     constexpr int VEC = 16 / sizeof(T);
     WptMultiArgs<T, F> a;
     a.src = src; a.dst = dst; a.nj = nj; a.NL = NL; a.TS = wpt_tile_samples<T>();
     a.mask = mask; a.depth = ilog2(n / nj);
+    a.stride = stride;
     int H[4];
     H[NL] = 0;
     for (int t = NL; t >= 1; --t) H[t - 1] = 2 * H[t] + (F - 2);
@@ -435,19 +519,20 @@ static hipError_t launch_wpt_multi_f(hipStream_t st, const Taps<T> &taps, const 
     a.buf_elems = (maxlen + 15) & ~15;
     a.tp = shrink<T, F>(taps);
     const size_t shmem = 2 * (size_t)a.buf_elems * sizeof(T);
-    hipLaunchKernelGGL((k_wpt_fwd_multi<T, F>), dim3((unsigned)(n / a.TS)), dim3(256), shmem, st, a);
+    hipLaunchKernelGGL((k_wpt_fwd_multi<T, F>), dim3((unsigned)(n / a.TS), (unsigned)nunits), dim3(256), shmem, st, a);
     return hipGetLastError();
 }
 
 template <typename T>
-hipError_t wpt_fwd_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask)
+hipError_t wpt_fwd_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask,
+                                int64_t nunits, int64_t stride)
 {
     switch (taps.F) {
-    case 2: return launch_wpt_multi_f<T, 2>(st, taps, src, dst, n, nj, NL, mask);
-    case 4: return launch_wpt_multi_f<T, 4>(st, taps, src, dst, n, nj, NL, mask);
-    case 6: return launch_wpt_multi_f<T, 6>(st, taps, src, dst, n, nj, NL, mask);
-    case 8: return launch_wpt_multi_f<T, 8>(st, taps, src, dst, n, nj, NL, mask);
-    case 10: return launch_wpt_multi_f<T, 10>(st, taps, src, dst, n, nj, NL, mask);
+    case 2: return launch_wpt_multi_f<T, 2>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
+    case 4: return launch_wpt_multi_f<T, 4>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
+    case 6: return launch_wpt_multi_f<T, 6>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
+    case 8: return launch_wpt_multi_f<T, 8>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
+    case 10: return launch_wpt_multi_f<T, 10>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
     default: return hipErrorInvalidValue;
     }
 }
@@ -471,12 +556,14 @@ bool wpt_inv_multi_ok(int F, int64_t n, int64_t nj, int NL)
 }
 
 template <typename T, int F>
-static hipError_t launch_wpt_inv_multi_f(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask)
+static hipError_t launch_wpt_inv_multi_f(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask,
+                                         int64_t nunits, int64_t stride)
 {
     constexpr int VEC = 16 / sizeof(T);
     WptInvMultiArgs<T, F> a;
     a.src = src; a.dst = dst; a.nj = nj; a.NL = NL; a.TS = wpt_tile_samples<T>();
     a.mask = mask; a.depth = ilog2(n / nj);
+    a.stride = stride;
     wpt_inv_halos<T>(F, NL, a.G);
     int maxlen = 0;
     for (int t = 0; t <= 3; ++t) a.bs[t] = 0;
@@ -490,19 +577,20 @@ static hipError_t launch_wpt_inv_multi_f(hipStream_t st, const Taps<T> &taps, co
     a.buf_elems = (maxlen + 15) & ~15;
     a.tp = shrink<T, F>(taps);
     const size_t shmem = 2 * (size_t)a.buf_elems * sizeof(T);
-    hipLaunchKernelGGL((k_wpt_inv_multi<T, F>), dim3((unsigned)(n / a.TS)), dim3(256), shmem, st, a);
+    hipLaunchKernelGGL((k_wpt_inv_multi<T, F>), dim3((unsigned)(n / a.TS), (unsigned)nunits), dim3(256), shmem, st, a);
     return hipGetLastError();
 }
 
 template <typename T>
-hipError_t wpt_inv_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask)
+hipError_t wpt_inv_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask,
+                                int64_t nunits, int64_t stride)
 {
     switch (taps.F) {
-    case 2: return launch_wpt_inv_multi_f<T, 2>(st, taps, src, dst, n, nj, NL, mask);
-    case 4: return launch_wpt_inv_multi_f<T, 4>(st, taps, src, dst, n, nj, NL, mask);
-    case 6: return launch_wpt_inv_multi_f<T, 6>(st, taps, src, dst, n, nj, NL, mask);
-    case 8: return launch_wpt_inv_multi_f<T, 8>(st, taps, src, dst, n, nj, NL, mask);
-    case 10: return launch_wpt_inv_multi_f<T, 10>(st, taps, src, dst, n, nj, NL, mask);
+    case 2: return launch_wpt_inv_multi_f<T, 2>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
+    case 4: return launch_wpt_inv_multi_f<T, 4>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
+    case 6: return launch_wpt_inv_multi_f<T, 6>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
+    case 8: return launch_wpt_inv_multi_f<T, 8>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
+    case 10: return launch_wpt_inv_multi_f<T, 10>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
     default: return hipErrorInvalidValue;
     }
 }
@@ -521,30 +609,45 @@ bool wpt_tail_ok(int F, int64_t n, int64_t nj, int ndepth)
 }
 
 template <typename T, int F>
-static hipError_t launch_wpt_tail_f(hipStream_t st, const Taps<T> &taps, int fw, const T *src, T *dst, int64_t n, int64_t nj, int ndepth, const uint8_t *mask)
+static hipError_t launch_wpt_tail_f(hipStream_t st, const Taps<T> &taps, int fw, const T *src, T *dst, int64_t n, int64_t nj, int ndepth, const uint8_t *mask,
+                                    int64_t nunits, int64_t stride)
 {
-    WptTailArgs<T, F> a;
+    // n >= TS: the unit's chunks of TS.  n < TS: a workgroup of upw whole units -- TS / n of them, or with fewer than that in the
+    // batch the next power of two >= nunits (one workgroup; one unit: a chunk of n, the plain transform)
     const int TS = wpt_tile_samples<T>();
-    const int64_t chunk = (n < TS) ? n : TS;
+    WptTailArgs<T, F> a;
+    int64_t chunk = TS;
+    dim3 grid((unsigned)(n / TS), (unsigned)nunits);
+    if (n >= TS) {
+        a.lgn = -1;
+    } else {
+        int64_t upw = TS / n;
+        while (upw / 2 >= nunits) upw /= 2;
+        chunk = upw * n;
+        a.lgn = ilog2(n);
+        grid = dim3((unsigned)((nunits + upw - 1) / upw));
+    }
     a.src = src; a.dst = dst; a.lgts = ilog2(chunk); a.lgm = ilog2(nj); a.ndepth = ndepth;
     a.mask = mask; a.depth = ilog2(n / nj);
+    a.stride = stride; a.nunits = nunits;
     a.tp = shrink<T, F>(taps);
     const size_t shmem = 2 * (size_t)chunk * sizeof(T);
     const int threads = chunk >= 2048 ? 512 : (chunk >= 512 ? 256 : 64);
-    if (fw) hipLaunchKernelGGL((k_wpt_fwd_tail<T, F>), dim3((unsigned)(n / chunk)), dim3(threads), shmem, st, a);
-    else hipLaunchKernelGGL((k_wpt_inv_tail<T, F>), dim3((unsigned)(n / chunk)), dim3(threads), shmem, st, a);
+    if (fw) hipLaunchKernelGGL((k_wpt_fwd_tail<T, F>), grid, dim3(threads), shmem, st, a);
+    else hipLaunchKernelGGL((k_wpt_inv_tail<T, F>), grid, dim3(threads), shmem, st, a);
     return hipGetLastError();
 }
 
 template <typename T>
-hipError_t wpt_tail_launch(hipStream_t st, const Taps<T> &taps, int fw, const T *src, T *dst, int64_t n, int64_t nj, int ndepth, const uint8_t *mask)
+hipError_t wpt_tail_launch(hipStream_t st, const Taps<T> &taps, int fw, const T *src, T *dst, int64_t n, int64_t nj, int ndepth, const uint8_t *mask,
+                           int64_t nunits, int64_t stride)
 {
     switch (taps.F) {
-    case 2: return launch_wpt_tail_f<T, 2>(st, taps, fw, src, dst, n, nj, ndepth, mask);
-    case 4: return launch_wpt_tail_f<T, 4>(st, taps, fw, src, dst, n, nj, ndepth, mask);
-    case 6: return launch_wpt_tail_f<T, 6>(st, taps, fw, src, dst, n, nj, ndepth, mask);
-    case 8: return launch_wpt_tail_f<T, 8>(st, taps, fw, src, dst, n, nj, ndepth, mask);
-    case 10: return launch_wpt_tail_f<T, 10>(st, taps, fw, src, dst, n, nj, ndepth, mask);
+    case 2: return launch_wpt_tail_f<T, 2>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride);
+    case 4: return launch_wpt_tail_f<T, 4>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride);
+    case 6: return launch_wpt_tail_f<T, 6>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride);
+    case 8: return launch_wpt_tail_f<T, 8>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride);
+    case 10: return launch_wpt_tail_f<T, 10>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride);
     default: return hipErrorInvalidValue;
     }
 }
@@ -553,15 +656,15 @@ template int wpt_tile_samples<float>();
 template int wpt_tile_samples<double>();
 template bool wpt_fwd_multi_ok<float>(int, int64_t, int64_t, int);
 template bool wpt_fwd_multi_ok<double>(int, int64_t, int64_t, int);
-template hipError_t wpt_fwd_multi_launch<float>(hipStream_t, const Taps<float> &, const float *, float *, int64_t, int64_t, int, const uint8_t *);
-template hipError_t wpt_fwd_multi_launch<double>(hipStream_t, const Taps<double> &, const double *, double *, int64_t, int64_t, int, const uint8_t *);
+template hipError_t wpt_fwd_multi_launch<float>(hipStream_t, const Taps<float> &, const float *, float *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t);
+template hipError_t wpt_fwd_multi_launch<double>(hipStream_t, const Taps<double> &, const double *, double *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t);
 template bool wpt_inv_multi_ok<float>(int, int64_t, int64_t, int);
 template bool wpt_inv_multi_ok<double>(int, int64_t, int64_t, int);
-template hipError_t wpt_inv_multi_launch<float>(hipStream_t, const Taps<float> &, const float *, float *, int64_t, int64_t, int, const uint8_t *);
-template hipError_t wpt_inv_multi_launch<double>(hipStream_t, const Taps<double> &, const double *, double *, int64_t, int64_t, int, const uint8_t *);
+template hipError_t wpt_inv_multi_launch<float>(hipStream_t, const Taps<float> &, const float *, float *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t);
+template hipError_t wpt_inv_multi_launch<double>(hipStream_t, const Taps<double> &, const double *, double *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t);
 template bool wpt_tail_ok<float>(int, int64_t, int64_t, int);
 template bool wpt_tail_ok<double>(int, int64_t, int64_t, int);
-template hipError_t wpt_tail_launch<float>(hipStream_t, const Taps<float> &, int, const float *, float *, int64_t, int64_t, int, const uint8_t *);
-template hipError_t wpt_tail_launch<double>(hipStream_t, const Taps<double> &, int, const double *, double *, int64_t, int64_t, int, const uint8_t *);
+template hipError_t wpt_tail_launch<float>(hipStream_t, const Taps<float> &, int, const float *, float *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t);
+template hipError_t wpt_tail_launch<double>(hipStream_t, const Taps<double> &, int, const double *, double *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t);
 
 }  // namespace wl

@@ -760,6 +760,52 @@ def iwpt_(*args) -> torch.Tensor:
     return _xwpt_inplace(args, False)
 
 
+# ---- a batch of signals through one packet tree ---------------------------------------------------
+def _xwpt_batch(x, wt, tree_or_L, fw, y, fname):
+    """x: len x B (column-major: unit i = x[:, i]); every column gets the packet transform of the one shared tree, all columns in
+    one chain of launches (wl_wpt_filter_batch / wl_wpt_lifting_batch).  Equals `stack(wpt(x[:, i], wt, tree) for i)` bit for bit."""
+    if not isinstance(wt, (OrthoFilter, GLS)):
+        raise TypeError(f"{fname} is defined for orthogonal filters and lifting schemes")
+    _reject_complex(x, fname)
+    _reject_complex(y, fname)
+    if isinstance(x, torch.Tensor) and x.dim() != 2:
+        raise TypeError(f"{fname} expects a len x B array (unit i = x[:, i])")
+    if isinstance(x, torch.Tensor):
+        tree = _tree_arg(int(x.shape[0]), tree_or_L)         # (wpt's assertion on a bad depth, before anything touches the device)
+    x = _prep_in(x, maxdim=2)
+    n, nb = (int(v) for v in x.shape)
+    y = similar(x) if y is None else y
+    _check_pair(y, x)
+    if isinstance(wt, OrthoFilter) and (y is x or y.data_ptr() == x.data_ptr()):
+        raise ArgumentError("in array is out array")
+    lib = _lib.load()
+    h, st = _context(x.device)
+    if isinstance(tree, _FullTree) or len(tree) == 0:        # (an odd length has an empty tree: the full tree of depth 0)
+        tp, nt, L = None, 0, int(tree) if isinstance(tree, _FullTree) else 0
+    else:
+        tp, nt, L = tree.ctypes.data_as(C.POINTER(C.c_uint8)), len(tree), 0
+    if isinstance(wt, OrthoFilter):
+        q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
+        rc = lib.wl_wpt_filter_batch(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), n, nb, n,
+                                     _f64p(q), len(q), tp, nt, L, 1 if fw else 0, st)
+    else:
+        iu, nc, sh, cf = wt.flatten()
+        # (y may be x: the in-place wpt! of every column)
+        rc = lib.wl_wpt_lifting_batch(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), n, nb, n, len(iu),
+                                      _i32p(iu), _i32p(nc), _i32p(sh), _f64p(cf), wt.norm1, wt.norm2, tp, nt, L, 1 if fw else 0, st)
+    _check(rc, h)
+    return y
+
+
+def wpt_batch(x, wt, tree_or_L=None, y=None) -> torch.Tensor:
+    """wpt of every column of a len x B array with one shared tree (or the full tree of depth L)"""
+    return _xwpt_batch(x, wt, tree_or_L, True, y, "wpt_batch")
+
+
+def iwpt_batch(x, wt, tree_or_L=None, y=None) -> torch.Tensor:
+    return _xwpt_batch(x, wt, tree_or_L, False, y, "iwpt_batch")
+
+
 # ---- complex staging, for direct use ---------------------------------------------------------------
 def complex_split(z: torch.Tensor) -> torch.Tensor:
     """Planar components of a dense complex array (wl_complex_split): a real array of shape (*z.shape, 2), column-major, with
