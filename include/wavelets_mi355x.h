@@ -121,7 +121,10 @@ WL_API size_t wl_workspace_bytes_full(int dtype, int ndims, const int64_t *dims,
  * {n}, L), rounded up to 256 bytes, then two packet buffers of n elements (each rounded up to 256 bytes), the node entropies
  * (ntree + 2^(Lmax-1) doubles, unless the caller passes node_entropy), the best-subtree values (ntree doubles), the reduction
  * partials (n / 1024 + 64 doubles), the norm (256 bytes) and three node byte vectors (3 ntree bytes, each rounded up to 256):
- * about (ws_elems + 2) n elements + 2.1 n doubles + 3 n bytes.  wl_coefentropy holds (n / 1024 + 72) doubles.           */
+ * about (ws_elems + 2) n elements + 2.1 n doubles + 3 n bytes.  wl_coefentropy holds (n / 1024 + 72) doubles.
+ * wl_bestbasistree_filter_batch holds that per group of G units, with N = G * n in place of n in the packet region and
+ * the two packet buffers and G times the entropies, best-subtree values, partials and split bytes: the exact formula is in the
+ * comment of that entry point.                                                                                             */
 WL_API int wl_ctx_reserve(wl_ctx *ctx, size_t bytes);
 WL_API size_t wl_ctx_workspace_held(const wl_ctx *ctx);
 /* hipStreamSynchronize for hosts without their own HIP binding.                        */
@@ -529,6 +532,50 @@ WL_API int wl_wpt_lifting_batch(wl_ctx *ctx, int dtype, void *y, const void *x, 
                                 int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef, const int32_t *step_shift,
                                 const double *coefs_flat, double norm1, double norm2, const uint8_t *tree, int64_t ntree, int L,
                                 int fw, void *stream);
+
+/* ---- per-unit trees: the batched best-basis search and the packet transforms of its result -------------- */
+/* trees_out_u = bestbasistree(x_u, filter, tree, et) of nunits independent signals: unit u is the n elements at element offset
+ * u * unit_stride (>= n) of x, its result the ntree = 2^maxtransformlevels(n) - 1 bytes at trees_out + u * tree_stride
+ * (tree_stride >= ntree) in DEVICE memory; with node_entropy (DEVICE, or NULL) its [entr_bf ; entr_af] doubles (ntree + 2^(Lmax-1))
+ * go to node_entropy + u * entropy_stride.  Padding between units of trees_out and node_entropy is never written.
+ * Input tree: tree == NULL is maketree(n, L, :full) with 0 <= L <= Lmax (else WL_EINVAL_L; ntree is ignored, nothing is staged,
+ * and the call is capturable in a hipGraph once the workspace is held); otherwise ONE HOST tree of ntree nodes shared by all
+ * units, validated and staged as wl_wpt_filter_batch does it (L is ignored).  Per-unit input trees are not supported.
+ * The result IS the loop of wl_bestbasistree_filter over the units, bit for bit -- tree bytes and node-entropy bits, in the exact and
+ * in the fused library (a padded batch, unit_stride > n, is first copied into a dense work buffer, so that every depth runs the
+ * kernels the single search runs) -- in one chain of launches over all units: per depth one packet
+ * launch plus the reductions, then ceil(Lmax / 9) + 1 launches for the decision.  The accuracy contract of wl_bestbasistree_filter
+ * applies unchanged.  The call only enqueues on `stream`; it never synchronises.
+ * Status codes in this order: WL_EINVAL_ARG (NULL ctx / x / qmf / trees_out, unknown et), WL_EINVAL_DTYPE, WL_EINVAL_FILTER,
+ * WL_EDIMS (n < 1, nunits < 1, unit_stride < n, tree_stride < ntree, entropy_stride < ntree + 2^(Lmax-1), products >= 2^61),
+ * WL_EINVAL_SIZE (odd n), WL_EINVAL_L (tree == NULL), WL_EINVAL_TREE.
+ * Workspace: units are taken in groups of G -- all of them, at most 65535 (context option WL_WPT_BATCH_GROUP lowers it), halved
+ * until the group's workspace is below the context's cap (option WL_TI_WS_CAP_MB); groups change no bit.  With N = G * n,
+ * up256(b) = b rounded up to 256 and P = (2 (N / 2 + 64) + 3 N + 64) sizeof(T) the packet region, a group holds
+ *   up256(P + 256) + 2 up256(N sizeof(T)) + up256(G (ntree + 2^(Lmax-1)) 8) [absent with node_entropy] + up256(G ntree 8)
+ *   + up256(G (n / 1024 + 64) 8) + up256(8 G) + up256(G ntree) + 2 up256(ntree)   bytes;
+ * wl_bestbasistree_filter is G = 1 of the same formula.                                                                           */
+WL_API int wl_bestbasistree_filter_batch(wl_ctx *ctx, int dtype, const void *x, int64_t n, int64_t nunits, int64_t unit_stride,
+                                         const double *qmf, int flen, const uint8_t *tree, int64_t ntree, int L, int et,
+                                         uint8_t *trees_out, int64_t tree_stride, double *node_entropy, int64_t entropy_stride,
+                                         void *stream);
+/* y_u = wpt(x_u, filter, trees_u) (fw = 0: iwpt) with ONE TREE PER UNIT in DEVICE memory: unit u's byte-per-node tree is at
+ * trees + u * tree_stride (tree_stride >= 2^maxtransformlevels(n) - 1) -- what wl_bestbasistree_filter_batch leaves behind.  Layout
+ * and aliasing rules of x and y are those of wl_wpt_filter_batch.  Nodes at depth >= L are ignored (0 <= L <= Lmax, else
+ * WL_EINVAL_L; callers default to Lmax).  A device tree cannot be validated on the host: one launch closes every tree into the
+ * workspace first -- a node counts iff it and every ancestor is set -- so an INVALID tree means its largest valid subtree.
+ * Per unit the result equals wl_wpt_filter with that unit's (closed) tree bit for bit.  The launch plan is the one of a single
+ * unit whose every depth < L is partially split; leaves pass through inside the launches.  The call only enqueues and is
+ * capturable in a hipGraph once the workspace is held.
+ * Status codes in this order: WL_EINVAL_ARG (NULL ctx / y / x / qmf / trees), WL_EINVAL_DTYPE, WL_EINVAL_FILTER, WL_EDIMS (as
+ * wl_wpt_filter_batch, and tree_stride too small), WL_EALIAS, WL_EINVAL_L.
+ * Workspace: units are taken in groups of G as wl_wpt_filter_batch takes them -- halved until the work buffer plus the closed trees,
+ * G * (unit_stride * sizeof(T) + 2^L - 1) bytes, is below the cap, not the whole workspace -- and a group holds that call's bytes
+ * (2 * (N / 2 + 64) + 3 N + 64 elements, N = G * unit_stride, + 256 bytes) with G (2^L - 1) bytes of closed trees in place of the
+ * staged node bits.                                                                                                               */
+WL_API int wl_wpt_filter_batch_trees(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int64_t nunits, int64_t unit_stride,
+                                     const double *qmf, int flen, const uint8_t *trees, int64_t tree_stride, int L, int fw,
+                                     void *stream);
 
 /* ---- introspection (tests / bench) ---------------------------------------------------- */
 /* Select the kernel family: 0 = auto (fast paths where they apply), 1 = generic kernels

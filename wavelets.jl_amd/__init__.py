@@ -24,7 +24,7 @@ from .modwt import modwt, imodwt, maxmodwttransformlevels
 from .threshold import (THType, HardTH, SoftTH, SemiSoftTH, SteinTH, BiggestTH, PosTH, NegTH, DEFAULT_TH, threshold, threshold_,
                         DNFT, VisuShrink, denoise, noisest, mad_, median, nspin2circ, circshift, DEFAULT_WAVELET,
                         denoise_batch, noisest_batch, mad_batch_)
-from .entropy import Entropy, ShannonEntropy, LogEnergyEntropy, coefentropy, bestbasistree
+from .entropy import Entropy, ShannonEntropy, LogEnergyEntropy, coefentropy, bestbasistree, bestbasistree_batch
 from . import _lib
 
 __all__ = [
@@ -41,5 +41,5 @@ __all__ = [
     "THType", "HardTH", "SoftTH", "SemiSoftTH", "SteinTH", "BiggestTH", "PosTH", "NegTH", "DEFAULT_TH", "threshold", "threshold_",
     "DNFT", "VisuShrink", "denoise", "noisest", "mad_", "median", "nspin2circ", "circshift", "DEFAULT_WAVELET",
     "denoise_batch", "noisest_batch", "mad_batch_",
-    "Entropy", "ShannonEntropy", "LogEnergyEntropy", "coefentropy", "bestbasistree",
+    "Entropy", "ShannonEntropy", "LogEnergyEntropy", "coefentropy", "bestbasistree", "bestbasistree_batch",
 ]

@@ -112,6 +112,11 @@ SIGNATURES = {
     "wl_rmul": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_double, _vp]),
     "wl_coefentropy": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int, C.c_int, C.c_double, _f64p, _vp]),
     "wl_bestbasistree_filter": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _f64p, C.c_int, _u8p, C.c_int64, C.c_int, _u8p, _f64p, _vp]),
+    # (trees_out / node_entropy / trees are DEVICE pointers: passed as addresses)
+    "wl_bestbasistree_filter_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int64, C.c_int64, _f64p, C.c_int, _u8p, C.c_int64, C.c_int,
+                                                C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "wl_wpt_filter_batch_trees": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _f64p, C.c_int, _vp, C.c_int64, C.c_int,
+                                            C.c_int, _vp]),
 }
 
 

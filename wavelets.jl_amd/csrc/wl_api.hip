@@ -776,7 +776,7 @@ template <typename T>
 static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
                     const Taps<T> *taps, const LiftScheme<T> *sc,
                     const uint8_t *tree, int64_t ntree, int64_t last_set, int fw, int full_depth = -1, int first_depth = 0,
-                    int64_t nunits = 1, int64_t ustride = 0)
+                    int64_t nunits = 1, int64_t ustride = 0, const uint8_t *utrees = nullptr, int64_t utstride = 0, int utL = 0)
 {
     // full_depth >= 0: the full tree of that depth, no tree vector (tree == nullptr); only its depths >= first_depth are applied
     // (x already holds the depth-first_depth content: the best-basis search steps one depth at a time)
@@ -784,12 +784,17 @@ static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
     // of the work buffers.  The plan below is made for ONE unit of length n -- the batch takes the same kernels, every launch over all
     // units, the packet kernels being the very instances the single unit runs -- and lifting may then run out of place (x != y: the
     // first pass reads x, x stays untouched).
+    // utrees != nullptr (wl_wpt_filter_batch_trees; filter banks only): one DEVICE tree per unit, unit u's node bits at utrees +
+    // u * utstride, depths < utL.  Nothing of them is known here, so the plan is the partial-tree plan of one unit with every depth
+    // < utL present; one launch closes the trees into the workspace (a node counts iff it and every ancestor is set) and the kernels
+    // read those bits with a per-unit stride.  Leaves pass through inside the launches.
     const bool lifting = (sc != nullptr);
+    if (utrees) full_depth = -1;
     if (nunits == 1) ustride = n;
     const bool dense = (ustride == n);
     Extent3 full = {{n, 1, nunits}};
     Strides3 fst = {{1, n, ustride}};
-    if (full_depth >= 0 ? full_depth == 0 : (ntree == 0 || !tree[0])) {
+    if (utrees ? utL == 0 : full_depth >= 0 ? full_depth == 0 : (ntree == 0 || !tree[0])) {
         if (y != x) WL_HIP(ctx, generic_copy_box<T>(st, x, fst, y, fst, full));
         ctx->last_kernel = "copy";
         return WL_OK;
@@ -800,6 +805,10 @@ static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
     bool any_partial = false;
     for (int L = Lmax; L > 0; --L) {
         int d = fw ? Lmax - L : L - 1;
+        if (utrees) {
+            if (d < utL) { depths.push_back(d); kind.push_back(1); any_partial = true; }
+            continue;
+        }
         if (full_depth >= 0) {
             if (d >= first_depth && d < full_depth) { depths.push_back(d); kind.push_back(2); }
             continue;
@@ -819,12 +828,16 @@ static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
     while (ncopy - 1 <= last_set && ncopy - 1 < ntree) ncopy <<= 1;
     ncopy = (ncopy - 1 < ntree) ? ncopy - 1 : ntree;
     if (full_depth >= 0) ncopy = 0;
+    const int64_t mstride = utrees ? ((int64_t)1 << utL) - 1 : 0;       // closed per-unit trees: the nodes of the depths < utL, dense
+    if (utrees) ncopy = nunits * mstride;
     const int64_t NW = nunits * ustride;                // the work buffers mirror the layout of x and y
     int rc = ensure_ws(ctx, ws_elems(NW) * sizeof(T) + (size_t)(any_partial ? ncopy : 0) + 256, st);
     if (rc) return rc;
     Work<T> w = carve<T>(ctx->ws, NW);
     uint8_t *dtree = (uint8_t *)ctx->ws + ws_elems(NW) * sizeof(T);
-    if (any_partial) {
+    if (utrees) {
+        WL_HIP(ctx, tree_close(st, utrees, utstride, mstride, dtree, mstride, nunits));
+    } else if (any_partial) {
         rc = wl_stage_to_device(ctx, dtree, tree, (size_t)ncopy, st);
         if (rc) return rc;
     }
@@ -924,13 +937,13 @@ static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
         const int d = sp.d;
         T *out = ((P - 1 - i) % 2 == 0) ? y : w.T0;
         if (sp.kindk == 1) {
-            WL_HIP(ctx, wpt_fwd_multi_launch<T>(st, *taps, cur, out, n, n >> d, sp.nd, pmask, nunits, ustride));
+            WL_HIP(ctx, wpt_fwd_multi_launch<T>(st, *taps, cur, out, n, n >> d, sp.nd, pmask, nunits, ustride, mstride));
             name = "k_wpt_fwd_multi";
         } else if (sp.kindk == 3) {
-            WL_HIP(ctx, wpt_inv_multi_launch<T>(st, *taps, cur, out, n, n >> d, sp.nd, pmask, nunits, ustride));
+            WL_HIP(ctx, wpt_inv_multi_launch<T>(st, *taps, cur, out, n, n >> d, sp.nd, pmask, nunits, ustride, mstride));
             name = "k_wpt_inv_multi";
         } else if (sp.kindk == 2) {
-            WL_HIP(ctx, wpt_tail_launch<T>(st, *taps, fw, cur, out, n, n >> d, sp.nd, pmask, nunits, ustride));
+            WL_HIP(ctx, wpt_tail_launch<T>(st, *taps, fw, cur, out, n, n >> d, sp.nd, pmask, nunits, ustride, mstride));
             if (std::strncmp(name, "k_wpt", 5) != 0) name = fw ? "k_wpt_fwd_tail" : "k_wpt_inv_tail";
         } else {
             const int64_t nj = n >> d, nseg = (int64_t)1 << d;
@@ -951,9 +964,9 @@ static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
             if (!done) {
                 const uint8_t *mask = all_set ? nullptr : dtree + (((int64_t)1 << d) - 1);
                 if (fw)
-                    WL_HIP(ctx, generic_fwd_filter_pass<T>(st, *taps, cur, bst, out, bst, (T *)nullptr, bst, ext, 0, lo, mask));
+                    WL_HIP(ctx, generic_fwd_filter_pass<T>(st, *taps, cur, bst, out, bst, (T *)nullptr, bst, ext, 0, lo, mask, mstride));
                 else
-                    WL_HIP(ctx, generic_inv_filter_pass<T>(st, *taps, cur, bst, (const T *)nullptr, bst, out, bst, ext, 0, lo, mask));
+                    WL_HIP(ctx, generic_inv_filter_pass<T>(st, *taps, cur, bst, (const T *)nullptr, bst, out, bst, ext, 0, lo, mask, mstride));
             }
         }
         cur = out;
@@ -966,50 +979,120 @@ static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
 // The reference decomposes the signal to the full depth Lmax one dwt! level per node and takes each node's entropy before its split.
 // Here depth d + 1 comes from depth d by one full-depth packet step (wpt_impl, first_depth = d: the packet kernels, bit-identical to
 // wpt), ping-ponging between two buffers, and every depth is reduced to its node entropies by the segmented kernel (wl_entropy.hip);
-// depth Lmax is reduced over the pairs of siblings only (entr_af).  The decision runs on the device; the tree comes back in one copy.
+// depth Lmax is reduced over the pairs of siblings only (entr_af).  The decision runs on the device.
+//
+// A group of G units (wl_bestbasistree_filter_batch; the single search is the group of one): every launch
+// above goes over all units of the group -- unit u at x + u * S -- and the trees are written to device memory, unit u's at
+// tree_out + u * tstride.  The packet buffers are DENSE (unit u at u * n): a padded batch (S > n) is copied into one first, so that
+// every depth runs the plan of a dense batch -- the kernels the single search runs, which is what makes batch = loop hold in the
+// fused library too (a padded batch would take the per-depth kernels where a single unit takes the streaming line kernels).
+// Workspace layout of a group (bytes, every part rounded up to 256):
+//   [wpt_impl's region of G n elements + 256 | A, B: G n elements each | entropies G (ntree + naf) doubles, unless the caller's |
+//    best G ntree doubles | partials G (n / 1024 + 64) doubles | norms G doubles | split G ntree bytes | tree ntree | out ntree]
+// (tree: the staged input tree, when there is one; out: the single search's result before its one copy to the host)
+struct BBLayout { size_t oA, oB, oE, oBest, oP, oN, oS, oT, oO, total; };
+static BBLayout bb_layout(int64_t n, int64_t G, size_t es, bool own_ent)
+{
+    const int Lmax = wl_maxtransformlevels(n);
+    const int64_t ntree = ((int64_t)1 << Lmax) - 1, naf = (int64_t)1 << (Lmax - 1);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const int64_t NW = G * n;
+    BBLayout l;
+    size_t off = up(ws_elems(NW) * es + 256);
+    l.oA = off; off += up((size_t)NW * es);
+    l.oB = off; off += up((size_t)NW * es);
+    l.oE = off; off += own_ent ? up((size_t)G * (size_t)(ntree + naf) * sizeof(double)) : 0;
+    l.oBest = off; off += up((size_t)G * (size_t)ntree * sizeof(double));
+    l.oP = off; off += up((size_t)G * entropy_partials(n) * sizeof(double));
+    l.oN = off; off += up((size_t)G * sizeof(double));
+    l.oS = off; off += up((size_t)G * (size_t)ntree);
+    l.oT = off; off += up((size_t)ntree);
+    l.oO = off; off += up((size_t)ntree);
+    l.total = off;
+    return l;
+}
+
+// tree: the HOST input tree (staged here) or nullptr for the full tree of depth Lfull.  tree_out: DEVICE, or nullptr for the `out`
+// part of the workspace (the single search copies it to the host itself).
+template <typename T>
+static int bestbasis_group(wl_ctx *ctx, hipStream_t st, const T *x, int64_t n, int64_t G, int64_t S, const Taps<T> &taps, const uint8_t *tree,
+                           int Lfull, int et, uint8_t *tree_out, int64_t tstride, double *node_entropy, int64_t estride, uint8_t **ws_out)
+{
+    const int Lmax = wl_maxtransformlevels(n);
+    const int64_t ntree = ((int64_t)1 << Lmax) - 1, naf = (int64_t)1 << (Lmax - 1);
+    if (G == 1) S = n;
+    const BBLayout l = bb_layout(n, G, sizeof(T), node_entropy == nullptr);
+    int rc = ensure_ws(ctx, l.total, st);
+    if (rc) return rc;
+    char *ws = (char *)ctx->ws;
+    T *A = (T *)(ws + l.oA), *B = (T *)(ws + l.oB);
+    double *ent = node_entropy ? node_entropy : (double *)(ws + l.oE);
+    const int64_t uent = node_entropy ? estride : ntree + naf;
+    double *best = (double *)(ws + l.oBest), *part = (double *)(ws + l.oP), *nrm = (double *)(ws + l.oN);
+    uint8_t *split = (uint8_t *)(ws + l.oS), *dtree = (uint8_t *)(ws + l.oT), *dout = (uint8_t *)(ws + l.oO);
+    if (tree) {
+        rc = wl_stage_to_device(ctx, dtree, tree, (size_t)ntree, st);
+        if (rc) return rc;
+    }
+    const int64_t np = (int64_t)entropy_partials(n);
+    const T *cur = x;
+    if (S != n) {                                        // a padded batch: from here on a dense one
+        Extent3 full = {{n, 1, G}};
+        Strides3 sst = {{1, n, S}}, dst = {{1, n, n}};
+        WL_HIP(ctx, generic_copy_box<T>(st, x, sst, A, dst, full));
+        cur = A;
+        S = n;
+    }
+    EntBatch bu = {G, S, np, uent};
+    WL_HIP(ctx, entropy_norm<T>(st, cur, n, part, nrm, bu));
+    for (int d = 0; d <= Lmax; ++d) {
+        if (d > 0) {
+            T *out = (cur == A) ? B : A;
+            rc = wpt_impl<T>(ctx, st, out, cur, n, &taps, nullptr, nullptr, 0, -1, 1, d, d - 1, G, S);
+            if (rc) return rc;
+            cur = out;
+        }
+        if (d < Lmax) WL_HIP(ctx, entropy_segments<T>(st, et, cur, n >> d, (int64_t)1 << d, nrm, 0.0, part, ent + ((int64_t)1 << d) - 1, bu));
+        else WL_HIP(ctx, entropy_segments<T>(st, et, cur, n >> (Lmax - 1), naf, nrm, 0.0, part, ent + ntree, bu));
+    }
+    WL_HIP(ctx, bestbasis_decide(st, ent, ntree, Lmax, best, split, tree ? dtree : nullptr, Lfull, tree_out ? tree_out : dout, G, uent,
+                                 tree_out ? tstride : ntree));
+    if (ws_out) *ws_out = dout;
+    ctx->last_kernel = "k_entropy_seg";
+    return WL_OK;
+}
+
 template <typename T>
 static int bestbasis_impl(wl_ctx *ctx, hipStream_t st, const T *x, int64_t n, const Taps<T> &taps, const uint8_t *tree, int64_t ntree,
                           int et, uint8_t *tree_out, double *node_entropy)
 {
-    const int Lmax = wl_maxtransformlevels(n);
-    const int64_t naf = (int64_t)1 << (Lmax - 1);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // layout (bytes): [wpt_impl's region | A | B | entropies | best | partials | nrm | split | tree | tree_out]
-    size_t off = up(ws_elems(n) * sizeof(T) + 256);
-    const size_t oA = off; off += up((size_t)n * sizeof(T));
-    const size_t oB = off; off += up((size_t)n * sizeof(T));
-    const size_t oE = off; off += node_entropy ? 0 : up((size_t)(ntree + naf) * sizeof(double));
-    const size_t oBest = off; off += up((size_t)ntree * sizeof(double));
-    const size_t oP = off; off += up(entropy_partials(n) * sizeof(double));
-    const size_t oN = off; off += 256;
-    const size_t oS = off; off += up((size_t)ntree);
-    const size_t oT = off; off += up((size_t)ntree);
-    const size_t oO = off; off += up((size_t)ntree);
-    int rc = ensure_ws(ctx, off, st);
+    uint8_t *dout = nullptr;
+    int rc = bestbasis_group<T>(ctx, st, x, n, 1, n, taps, tree, 0, et, nullptr, ntree, node_entropy, 0, &dout);
     if (rc) return rc;
-    char *ws = (char *)ctx->ws;
-    T *A = (T *)(ws + oA), *B = (T *)(ws + oB);
-    double *ent = node_entropy ? node_entropy : (double *)(ws + oE);
-    double *best = (double *)(ws + oBest), *part = (double *)(ws + oP), *nrm = (double *)(ws + oN);
-    uint8_t *split = (uint8_t *)(ws + oS), *dtree = (uint8_t *)(ws + oT), *dout = (uint8_t *)(ws + oO);
-    rc = wl_stage_to_device(ctx, dtree, tree, (size_t)ntree, st);
-    if (rc) return rc;
-    WL_HIP(ctx, entropy_norm<T>(st, x, n, part, nrm));
-    const T *cur = x;
-    for (int d = 0; d <= Lmax; ++d) {
-        if (d > 0) {
-            T *out = (cur == A) ? B : A;
-            rc = wpt_impl<T>(ctx, st, out, cur, n, &taps, nullptr, nullptr, 0, -1, 1, d, d - 1);
-            if (rc) return rc;
-            cur = out;
-        }
-        if (d < Lmax) WL_HIP(ctx, entropy_segments<T>(st, et, cur, n >> d, (int64_t)1 << d, nrm, 0.0, part, ent + ((int64_t)1 << d) - 1));
-        else WL_HIP(ctx, entropy_segments<T>(st, et, cur, n >> (Lmax - 1), naf, nrm, 0.0, part, ent + ntree));
-    }
-    WL_HIP(ctx, bestbasis_decide(st, ent, ntree, Lmax, best, split, dtree, dout));
     WL_HIP(ctx, hipMemcpyAsync(tree_out, dout, (size_t)ntree, hipMemcpyDeviceToHost, st));
     WL_HIP(ctx, hipStreamSynchronize(st));
-    ctx->last_kernel = "k_entropy_seg";
+    return WL_OK;
+}
+
+// units in groups of G, as wpt_batch_impl: at most 65535 (WL_WPT_BATCH_GROUP lowers it), halved until the group's workspace fits the cap
+template <typename T>
+static int bestbasis_batch_impl(wl_ctx *ctx, hipStream_t st, const T *x, int64_t n, int64_t nunits, int64_t S, const Taps<T> &taps,
+                                const uint8_t *tree, int Lfull, int et, uint8_t *trees_out, int64_t tstride, double *node_entropy, int64_t estride)
+{
+    int64_t G = nunits < 65535 ? nunits : 65535;
+    const long long og = opt("WL_WPT_BATCH_GROUP", 0);
+    if (og >= 1 && og < G) G = og;
+    const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
+    while (G > 1 && bb_layout(n, G, sizeof(T), node_entropy == nullptr).total > cap) G = (G + 1) / 2;
+    // one workspace size for every group (the last one may be shorter): nothing grows between groups
+    int rc = ensure_ws(ctx, bb_layout(n, G, sizeof(T), node_entropy == nullptr).total, st);
+    if (rc) return rc;
+    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
+        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
+        rc = bestbasis_group<T>(ctx, st, x + u0 * S, n, nb, S, taps, tree, Lfull, et, trees_out + u0 * tstride, tstride,
+                                node_entropy ? node_entropy + u0 * estride : nullptr, estride, nullptr);
+        if (rc != WL_OK) return rc;
+    }
     return WL_OK;
 }
 
@@ -1305,6 +1388,82 @@ int wl_wpt_lifting_batch(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t
     WL_SCOPE(ctx);
     return wpt_batch_impl<double>(ctx, st, (double *)y, (const double *)x, n, nunits, unit_stride, nullptr, &sc, tree, tree ? ntree : 0, last_set, fw,
                                   full_depth);
+}
+
+}  // extern "C"
+
+// ---- per-unit trees: the batched best-basis search and the packet transforms that take its result --------
+extern "C" {
+
+int wl_bestbasistree_filter_batch(wl_ctx *ctx, int dtype, const void *x, int64_t n, int64_t nunits, int64_t unit_stride, const double *qmf,
+                                  int flen, const uint8_t *tree, int64_t ntree, int L, int et, uint8_t *trees_out, int64_t tree_stride,
+                                  double *node_entropy, int64_t entropy_stride, void *stream)
+{
+    if (!ctx || !x || !qmf || !trees_out) return WL_EINVAL_ARG;
+    if (et != WL_ENTROPY_SHANNON && et != WL_ENTROPY_LOGENERGY) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
+    if (n < 1 || nunits < 1 || unit_stride < n || unit_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
+    const int Lmax = wl_maxtransformlevels(n);
+    const int64_t nt = ((int64_t)1 << Lmax) - 1;
+    if (tree_stride < nt || tree_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
+    if (node_entropy && Lmax > 0 && (entropy_stride < nt + ((int64_t)1 << (Lmax - 1)) || entropy_stride >= ((int64_t)1 << 58) / nunits))
+        return WL_EDIMS;
+    if (Lmax == 0) return WL_EINVAL_SIZE;                                // the reference fails on 2^(Lmax - 1) (entropy.jl:85)
+    int64_t last_set = -1;
+    if (!tree) {
+        if (L < 0 || L > Lmax) return WL_EINVAL_L;
+    } else if (!isvalidtree(n, tree, ntree, &last_set)) {
+        return WL_EINVAL_TREE;
+    }
+    WL_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == WL_F32) {
+        Taps<float> t; make_taps<float>(qmf, flen, t);
+        return bestbasis_batch_impl<float>(ctx, st, (const float *)x, n, nunits, unit_stride, t, tree, L, et, trees_out, tree_stride, node_entropy,
+                                           entropy_stride);
+    }
+    Taps<double> t; make_taps<double>(qmf, flen, t);
+    return bestbasis_batch_impl<double>(ctx, st, (const double *)x, n, nunits, unit_stride, t, tree, L, et, trees_out, tree_stride, node_entropy,
+                                        entropy_stride);
+}
+
+int wl_wpt_filter_batch_trees(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int64_t nunits, int64_t unit_stride, const double *qmf,
+                              int flen, const uint8_t *trees, int64_t tree_stride, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !qmf || !trees) return WL_EINVAL_ARG;
+    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
+    if (n < 1 || nunits < 1 || unit_stride < n || unit_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
+    const int Lmax = wl_maxtransformlevels(n);
+    if (tree_stride < ((int64_t)1 << Lmax) - 1 || tree_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
+    if (y == x) return WL_EALIAS;
+    if (L < 0 || L > Lmax) return WL_EINVAL_L;
+    WL_SCOPE(ctx);
+    hipStream_t st = (hipStream_t)stream;
+    // groups as wpt_batch_impl; the closed trees of a group (G (2^L - 1) bytes) ride on top of its work buffer
+    int64_t G = nunits < 65535 ? nunits : 65535;
+    const long long og = opt("WL_WPT_BATCH_GROUP", 0);
+    if (og >= 1 && og < G) G = og;
+    const size_t es = dtype == WL_F32 ? 4 : 8;
+    const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
+    while (G > 1 && (size_t)G * ((size_t)unit_stride * es + (((size_t)1 << L) - 1)) > cap) G = (G + 1) / 2;
+    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
+        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
+        const uint8_t *tr = trees + u0 * tree_stride;
+        int rc;
+        if (dtype == WL_F32) {
+            Taps<float> t; make_taps<float>(qmf, flen, t);
+            rc = wpt_impl<float>(ctx, st, (float *)y + u0 * unit_stride, (const float *)x + u0 * unit_stride, n, &t, nullptr, nullptr, 0, -1, fw, -1, 0,
+                                 nb, unit_stride, tr, tree_stride, L);
+        } else {
+            Taps<double> t; make_taps<double>(qmf, flen, t);
+            rc = wpt_impl<double>(ctx, st, (double *)y + u0 * unit_stride, (const double *)x + u0 * unit_stride, n, &t, nullptr, nullptr, 0, -1, fw, -1,
+                                  0, nb, unit_stride, tr, tree_stride, L);
+        }
+        if (rc != WL_OK) return rc;
+    }
+    return WL_OK;
 }
 
 }  // extern "C"

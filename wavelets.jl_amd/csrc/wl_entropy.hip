@@ -12,6 +12,11 @@
 // giving |entropy - exact entropy of the same T coefficients| <= 1e-12 * sum|term| (Float64) / 4e-7 * sum|term| (Float32); the
 // reference itself is off by ~n eps(T).  The decision runs in Float64 on these
 // values with Julia's `min` (NaN propagates) and the reference's `entr_bf[i] <= best(i)` test.
+//
+// Batches (wl_bestbasistree_filter_batch): every kernel takes blockIdx.y as the unit and per-unit bases of its
+// operands (EntUnits / BBUnits: element strides from one unit to the next).  What a segment's sum is made of -- the lane group,
+// the piece size, the fold order -- depends on its length only, so a unit's values do not depend on the batch around it; the single
+// search is the batch of one unit of the same instances.
 #include "wl_ctx.h"
 
 #include <cmath>
@@ -36,14 +41,21 @@ __device__ __forceinline__ double ent_term(T v, T nrm)
     return ET == 0 ? -sd * log(sd) : -log(sd);
 }
 
+// strides from unit u to unit u + 1 (blockIdx.y): samples, norms (one double per unit), partials / outputs
+struct EntUnits { int64_t x, nrm, out; };
+
 // One group of G lanes (G divides 64, or G == 256) per piece; piece p of segment s is [p * chunk, min(nj, (p + 1) * chunk)) of
 // x[s * nj ...].  Lanes sum a fixed lane-strided subset, the group folds them with a fixed butterfly: the same input always gives
 // the same bits.  out[s * npieces + p] = the piece's sum.  nrmp == nullptr: the norm is nrm_val.
 template <typename T, int ET, int G>
 __global__ __launch_bounds__(ENT_THREADS) void k_entropy_seg(const T *__restrict__ x, int64_t nj, int64_t npieces, int64_t ngroups,
                                                              int64_t chunk, const double *__restrict__ nrmp, double nrm_val,
-                                                             double *__restrict__ out)
+                                                             double *__restrict__ out, EntUnits us)
 {
+    const int64_t unit = blockIdx.y;
+    x += unit * us.x;
+    out += unit * us.out;
+    if (nrmp) nrmp += unit * us.nrm;
     const int64_t grp = ((int64_t)blockIdx.x * ENT_THREADS + threadIdx.x) / G;
     const int lane = (int)(threadIdx.x % G);
     const T nrm = (T)(nrmp ? *nrmp : nrm_val);
@@ -72,8 +84,10 @@ __global__ __launch_bounds__(ENT_THREADS) void k_entropy_seg(const T *__restrict
 
 // out[s] = sum of the npieces partials of segment s, one wave per segment (lane-strided, then a fixed butterfly)
 __global__ __launch_bounds__(ENT_THREADS) void k_entropy_fold(const double *__restrict__ part, int64_t npieces, int64_t nseg,
-                                                              double *__restrict__ out)
+                                                              double *__restrict__ out, int64_t upart, int64_t uout)
 {
+    part += (int64_t)blockIdx.y * upart;
+    out += (int64_t)blockIdx.y * uout;
     const int64_t s = ((int64_t)blockIdx.x * ENT_THREADS + threadIdx.x) / 64;
     const int lane = (int)(threadIdx.x % 64);
     double acc = 0.0;
@@ -84,11 +98,12 @@ __global__ __launch_bounds__(ENT_THREADS) void k_entropy_fold(const double *__re
     if (s < nseg && lane == 0) out[s] = acc;
 }
 
-// *nrm = T(sqrt(sum of squares)), kept as a double
+// nrm[u] = T(sqrt(sum of squares of unit u)), kept as a double; unit u's sum is sumsq[u * usum]
 template <typename T>
-__global__ void k_entropy_nrm(const double *__restrict__ sumsq, double *__restrict__ nrm)
+__global__ void k_entropy_nrm(const double *__restrict__ sumsq, double *__restrict__ nrm, int64_t usum, int64_t nunits)
 {
-    if (threadIdx.x == 0 && blockIdx.x == 0) *nrm = (double)(T)sqrt(*sumsq);
+    const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u < nunits) nrm[u] = (double)(T)sqrt(sumsq[u * usum]);
 }
 
 // Julia's min(x, y) for floats: NaN propagates, -0.0 < +0.0
@@ -104,10 +119,15 @@ __device__ __forceinline__ double jl_min(double a, double b)
 //   cs(k)    = the children's best sum (depth Lmax - 1: entr_af of the node), left + right
 //   split[k] = !(entr_bf[k] <= cs(k))        (== !(entr_bf[k] <= min(entr_bf[k], cs(k))), the reference's test)
 //   best[k]  = min(entr_bf[k], cs(k))        stored for the band's top row only (the next band's children)
+// blockIdx.y is the unit: uent / ubest / usplit elements from one unit's vector to the next.
 __global__ __launch_bounds__(ENT_THREADS) void k_bb_up(const double *__restrict__ ent, int64_t ntree, int Lmax, int dbot, int nlev,
-                                                       double *__restrict__ best, uint8_t *__restrict__ split)
+                                                       double *__restrict__ best, uint8_t *__restrict__ split, int64_t uent, int64_t ubest,
+                                                       int64_t usplit)
 {
     __shared__ double sh[ENT_THREADS];
+    ent += (int64_t)blockIdx.y * uent;
+    best += (int64_t)blockIdx.y * ubest;
+    split += (int64_t)blockIdx.y * usplit;
     const int W = 1 << (nlev - 1);
     const int t = (int)threadIdx.x;
     const int64_t j0 = (int64_t)blockIdx.x * W;
@@ -133,13 +153,18 @@ __global__ __launch_bounds__(ENT_THREADS) void k_bb_up(const double *__restrict_
 }
 
 // Top-down: node k stays split iff the input tree has it and it and every ancestor split (a valid tree has every ancestor of a set
-// node set, so tree[k] covers the input tree's ancestors)
-__global__ __launch_bounds__(ENT_THREADS) void k_bb_down(const uint8_t *__restrict__ tree, const uint8_t *__restrict__ split, int64_t ntree,
-                                                         uint8_t *__restrict__ out)
+// node set, so tree[k] covers the input tree's ancestors).  tree == nullptr: the input tree is the full tree of depth Lfull, node k
+// is in it iff k < 2^Lfull - 1.  blockIdx.y is the unit (utree == 0: one input tree for all).  With split == tree this is the
+// closure of a tree nobody validated: a node counts iff it and every ancestor is set (tree_close).
+__global__ __launch_bounds__(ENT_THREADS) void k_bb_down(const uint8_t *tree, int Lfull, const uint8_t *split, int64_t ntree, uint8_t *__restrict__ out,
+                                                         int64_t utree, int64_t usplit, int64_t uout)
 {
     const int64_t k = (int64_t)blockIdx.x * ENT_THREADS + threadIdx.x;
     if (k >= ntree) return;
-    bool v = tree[k] != 0 && split[k] != 0;
+    split += (int64_t)blockIdx.y * usplit;
+    out += (int64_t)blockIdx.y * uout;
+    const bool in_tree = tree ? tree[(int64_t)blockIdx.y * utree + k] != 0 : k < (((int64_t)1 << Lfull) - 1);
+    bool v = in_tree && split[k] != 0;
     for (int64_t j = k; v && j > 0;) {
         j = (j - 1) >> 1;
         v = split[j] != 0;
@@ -149,23 +174,29 @@ __global__ __launch_bounds__(ENT_THREADS) void k_bb_down(const uint8_t *__restri
 
 inline unsigned nblocks(int64_t threads) { return (unsigned)((threads + ENT_THREADS - 1) / ENT_THREADS); }
 
+// bu: the units of the launch (grid y) and the strides of x, the norms, the partials and the outputs between them
 template <typename T, int ET>
-hipError_t seg_launch(hipStream_t st, const T *x, int64_t nj, int64_t nseg, const double *nrmp, double nrm_val, double *part, double *out)
+hipError_t seg_launch(hipStream_t st, const T *x, int64_t nj, int64_t nseg, const double *nrmp, double nrm_val, double *part, double *out,
+                      const EntBatch &bu)
 {
+    const unsigned nu = (unsigned)bu.nunits;
     if (nj > 2048) {
         const int64_t npieces = (nj + ENT_CHUNK - 1) / ENT_CHUNK, ng = nseg * npieces;
         double *dst = npieces == 1 ? out : part;
-        hipLaunchKernelGGL((k_entropy_seg<T, ET, 256>), dim3(nblocks(ng * 256)), dim3(ENT_THREADS), 0, st, x, nj, npieces, ng, ENT_CHUNK,
-                           nrmp, nrm_val, dst);
+        const EntUnits us = {bu.x, 1, npieces == 1 ? bu.out : bu.part};
+        hipLaunchKernelGGL((k_entropy_seg<T, ET, 256>), dim3(nblocks(ng * 256), nu), dim3(ENT_THREADS), 0, st, x, nj, npieces, ng, ENT_CHUNK,
+                           nrmp, nrm_val, dst, us);
         if (npieces > 1)
-            hipLaunchKernelGGL(k_entropy_fold, dim3(nblocks(nseg * 64)), dim3(ENT_THREADS), 0, st, (const double *)part, npieces, nseg, out);
+            hipLaunchKernelGGL(k_entropy_fold, dim3(nblocks(nseg * 64), nu), dim3(ENT_THREADS), 0, st, (const double *)part, npieces, nseg, out,
+                               bu.part, bu.out);
         return hipGetLastError();
     }
     // one group per segment, about 8 samples per lane
     const int64_t want = (nj + 7) / 8;
+    const EntUnits us = {bu.x, 1, bu.out};
 #define WL_ENT_SEG(G_)                                                                                                       \
-    hipLaunchKernelGGL((k_entropy_seg<T, ET, G_>), dim3(nblocks(nseg * (G_))), dim3(ENT_THREADS), 0, st, x, nj, (int64_t)1, nseg, \
-                       nj, nrmp, nrm_val, out)
+    hipLaunchKernelGGL((k_entropy_seg<T, ET, G_>), dim3(nblocks(nseg * (G_)), nu), dim3(ENT_THREADS), 0, st, x, nj, (int64_t)1, nseg, \
+                       nj, nrmp, nrm_val, out, us)
     if (want > 64) WL_ENT_SEG(256);
     else if (want > 32) WL_ENT_SEG(64);
     else if (want > 16) WL_ENT_SEG(32);
@@ -184,41 +215,55 @@ size_t entropy_partials(int64_t n) { return (size_t)(n / 1024 + 64); }
 
 template <typename T>
 hipError_t entropy_segments(hipStream_t st, int et, const T *x, int64_t nj, int64_t nseg, const double *nrmp, double nrm_val, double *part,
-                            double *out)
+                            double *out, const EntBatch &bu)
 {
-    return et == WL_ENTROPY_SHANNON ? seg_launch<T, 0>(st, x, nj, nseg, nrmp, nrm_val, part, out)
-                                    : seg_launch<T, 1>(st, x, nj, nseg, nrmp, nrm_val, part, out);
+    return et == WL_ENTROPY_SHANNON ? seg_launch<T, 0>(st, x, nj, nseg, nrmp, nrm_val, part, out, bu)
+                                    : seg_launch<T, 1>(st, x, nj, nseg, nrmp, nrm_val, part, out, bu);
 }
 
 template <typename T>
-hipError_t entropy_norm(hipStream_t st, const T *x, int64_t n, double *part, double *nrm_out)
+hipError_t entropy_norm(hipStream_t st, const T *x, int64_t n, double *part, double *nrm_out, const EntBatch &bu)
 {
-    // the sum of squares lands in part[entropy_partials(n) - 1], past every partial a one-segment reduction writes
+    // the sum of squares of a unit lands in the last of its entropy_partials(n) partials, past every partial a one-segment reduction
+    // writes (bu.out is not used: the sums stay with the partials)
     double *sumsq = part + entropy_partials(n) - 1;
-    hipError_t e = seg_launch<T, 2>(st, x, n, 1, nullptr, 0.0, part, sumsq);
+    EntBatch b = bu;
+    b.out = bu.part;
+    hipError_t e = seg_launch<T, 2>(st, x, n, 1, nullptr, 0.0, part, sumsq, b);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_entropy_nrm<T>), dim3(1), dim3(64), 0, st, (const double *)sumsq, nrm_out);
+    hipLaunchKernelGGL((k_entropy_nrm<T>), dim3(nblocks(bu.nunits)), dim3(ENT_THREADS), 0, st, (const double *)sumsq, nrm_out, bu.part, bu.nunits);
     return hipGetLastError();
 }
 
 hipError_t bestbasis_decide(hipStream_t st, const double *ent, int64_t ntree, int Lmax, double *best, uint8_t *split, const uint8_t *tree,
-                            uint8_t *tree_out)
+                            int Lfull, uint8_t *tree_out, int64_t nunits, int64_t uent, int64_t uout)
 {
+    const unsigned nu = (unsigned)nunits;
     for (int d = Lmax - 1; d >= 0;) {
         const int nlev = d + 1 < BB_LEVELS ? d + 1 : BB_LEVELS;
         const int64_t nwg = (int64_t)1 << (d - nlev + 1);
         const int W = 1 << (nlev - 1);
-        hipLaunchKernelGGL(k_bb_up, dim3((unsigned)nwg), dim3(W < 64 ? 64 : W), 0, st, ent, ntree, Lmax, d, nlev, best, split);
+        hipLaunchKernelGGL(k_bb_up, dim3((unsigned)nwg, nu), dim3(W < 64 ? 64 : W), 0, st, ent, ntree, Lmax, d, nlev, best, split, uent, ntree, ntree);
         d -= nlev;
     }
-    hipLaunchKernelGGL(k_bb_down, dim3(nblocks(ntree)), dim3(ENT_THREADS), 0, st, tree, (const uint8_t *)split, ntree, tree_out);
+    hipLaunchKernelGGL(k_bb_down, dim3(nblocks(ntree), nu), dim3(ENT_THREADS), 0, st, tree, Lfull, (const uint8_t *)split, ntree, tree_out,
+                       (int64_t)0, ntree, uout);
     return hipGetLastError();
 }
 
-template hipError_t entropy_segments<float>(hipStream_t, int, const float *, int64_t, int64_t, const double *, double, double *, double *);
-template hipError_t entropy_segments<double>(hipStream_t, int, const double *, int64_t, int64_t, const double *, double, double *, double *);
-template hipError_t entropy_norm<float>(hipStream_t, const float *, int64_t, double *, double *);
-template hipError_t entropy_norm<double>(hipStream_t, const double *, int64_t, double *, double *);
+hipError_t tree_close(hipStream_t st, const uint8_t *trees, int64_t utrees, int64_t nnodes, uint8_t *out, int64_t uout, int64_t nunits)
+{
+    hipLaunchKernelGGL(k_bb_down, dim3(nblocks(nnodes), (unsigned)nunits), dim3(ENT_THREADS), 0, st, trees, 0, trees, nnodes, out, utrees, utrees,
+                       uout);
+    return hipGetLastError();
+}
+
+template hipError_t entropy_segments<float>(hipStream_t, int, const float *, int64_t, int64_t, const double *, double, double *, double *,
+                                            const EntBatch &);
+template hipError_t entropy_segments<double>(hipStream_t, int, const double *, int64_t, int64_t, const double *, double, double *, double *,
+                                             const EntBatch &);
+template hipError_t entropy_norm<float>(hipStream_t, const float *, int64_t, double *, double *, const EntBatch &);
+template hipError_t entropy_norm<double>(hipStream_t, const double *, int64_t, double *, double *, const EntBatch &);
 
 }  // namespace wl
 
@@ -235,8 +280,9 @@ int coefentropy_impl(wl_ctx *ctx, hipStream_t st, const T *x, int64_t n, int et,
     if (rc) return rc;
     double *part = (double *)ctx->ws;
     double *nrmd = part + np, *res = nrmd + 1;
-    if (!have_nrm) WL_HIP(ctx, entropy_norm<T>(st, x, n, part, nrmd));
-    WL_HIP(ctx, entropy_segments<T>(st, et, x, n, 1, have_nrm ? nullptr : nrmd, (double)(T)nrm, part, res));
+    const EntBatch one = {1, 0, 0, 0};
+    if (!have_nrm) WL_HIP(ctx, entropy_norm<T>(st, x, n, part, nrmd, one));
+    WL_HIP(ctx, entropy_segments<T>(st, et, x, n, 1, have_nrm ? nullptr : nrmd, (double)(T)nrm, part, res, one));
     double h = 0.0;
     WL_HIP(ctx, hipMemcpyAsync(&h, res, sizeof(double), hipMemcpyDeviceToHost, st));
     WL_HIP(ctx, hipStreamSynchronize(st));

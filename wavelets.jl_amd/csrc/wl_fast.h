@@ -262,11 +262,11 @@ hipError_t inv2d_long_launch(hipStream_t st, const Taps<T> &taps, const T *x, in
 // at most 65535 units per launch (the unit is the second grid dimension; the caller forms groups).
 template <typename T> int wpt_tile_samples();
 template <typename T> bool wpt_fwd_multi_ok(int F, int64_t n, int64_t nj, int NL);
-template <typename T> hipError_t wpt_fwd_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask = nullptr, int64_t nunits = 1, int64_t stride = 0);
+template <typename T> hipError_t wpt_fwd_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask = nullptr, int64_t nunits = 1, int64_t stride = 0, int64_t mstride = 0);
 template <typename T> bool wpt_inv_multi_ok(int F, int64_t n, int64_t nj, int NL);
-template <typename T> hipError_t wpt_inv_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask = nullptr, int64_t nunits = 1, int64_t stride = 0);
+template <typename T> hipError_t wpt_inv_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask = nullptr, int64_t nunits = 1, int64_t stride = 0, int64_t mstride = 0);
 template <typename T> bool wpt_tail_ok(int F, int64_t n, int64_t nj, int ndepth);
-template <typename T> hipError_t wpt_tail_launch(hipStream_t st, const Taps<T> &taps, int fw, const T *src, T *dst, int64_t n, int64_t nj, int ndepth, const uint8_t *mask = nullptr, int64_t nunits = 1, int64_t stride = 0);
+template <typename T> hipError_t wpt_tail_launch(hipStream_t st, const Taps<T> &taps, int fw, const T *src, T *dst, int64_t n, int64_t nj, int ndepth, const uint8_t *mask = nullptr, int64_t nunits = 1, int64_t stride = 0, int64_t mstride = 0);
 
 // ---- a batch of independent volumes (wl_batch3d.hip) ----
 // All L levels of the 3-D transform of nvol (<= 65535) dense boxes dims[0] x dims[1] x dims[2], volume i at element offset i * xs of x

@@ -47,7 +47,7 @@ template <typename T>
 __global__ void __launch_bounds__(kBlock)
 k_generic_fwd_filter(Taps<T> taps, const T *__restrict__ src, Strides3 sst,
                      T *__restrict__ dst, Strides3 dst_st, T *__restrict__ ll, Strides3 ll_st,
-                     Extent3 n, int axis, Extent3 lo, const uint8_t *__restrict__ mask)
+                     Extent3 n, int axis, Extent3 lo, const uint8_t *__restrict__ mask, int64_t mstride)
 {
     const int F = taps.F;
     const int64_t nax = n.n[axis], nx = nax >> 1, sa = sst.s[axis];
@@ -62,7 +62,7 @@ k_generic_fwd_filter(Taps<T> taps, const T *__restrict__ src, Strides3 sst,
         for (int d = 0; d < 3; ++d)
             if (d != axis) base += c.i[d] * sst.s[d];
         const T *p = src + base;
-        if (mask != nullptr && !mask[c.i[1]]) {      // WPT: node not split -> copy the segment through
+        if (mask != nullptr && !mask[c.i[1] + c.i[2] * mstride]) {      // WPT: node not split -> copy the segment through (mstride: per-unit trees)
             int64_t o0 = 0;
 #pragma unroll
             for (int d = 0; d < 3; ++d) o0 += (d == axis ? 0 : c.i[d]) * dst_st.s[d];
@@ -128,7 +128,7 @@ __global__ void __launch_bounds__(kBlock)
 k_generic_inv_filter(Taps<T> taps, const T *__restrict__ src, Strides3 sst,
                      const T *__restrict__ ll, Strides3 ll_st,
                      T *__restrict__ dst, Strides3 dst_st, Extent3 n, int axis, Extent3 lo,
-                     const uint8_t *__restrict__ mask)
+                     const uint8_t *__restrict__ mask, int64_t mstride)
 {
     const int F = taps.F;
     const int64_t nax = n.n[axis], nx = nax >> 1;
@@ -140,7 +140,7 @@ k_generic_inv_filter(Taps<T> taps, const T *__restrict__ src, Strides3 sst,
 #pragma unroll
         for (int d = 0; d < 3; ++d)
             if (d != axis) { base += c.i[d] * sst.s[d]; lbase += c.i[d] * ll_st.s[d]; }
-        if (mask != nullptr && !mask[c.i[1]]) {
+        if (mask != nullptr && !mask[c.i[1] + c.i[2] * mstride]) {
             int64_t off = 0;
 #pragma unroll
             for (int d = 0; d < 3; ++d) off += c.i[d] * dst_st.s[d];
@@ -413,21 +413,21 @@ k_copy_lines(const T *__restrict__ src, Strides3 sst, T *__restrict__ dst, Strid
 template <typename T>
 hipError_t generic_fwd_filter_pass(hipStream_t st, const Taps<T> &taps, const T *src, Strides3 sst,
                                    T *dst, Strides3 dst_st, T *ll, Strides3 ll_st,
-                                   Extent3 n, int axis, Extent3 lo, const uint8_t *mask)
+                                   Extent3 n, int axis, Extent3 lo, const uint8_t *mask, int64_t mstride)
 {
     int64_t total = n.n[0] * n.n[1] * n.n[2] / 2;
     hipLaunchKernelGGL(k_generic_fwd_filter<T>, grid_for(total), dim3(kBlock), 0, st,
-                       taps, src, sst, dst, dst_st, ll, ll_st, n, axis, lo, mask);
+                       taps, src, sst, dst, dst_st, ll, ll_st, n, axis, lo, mask, mstride);
     return hipGetLastError();
 }
 template <typename T>
 hipError_t generic_inv_filter_pass(hipStream_t st, const Taps<T> &taps, const T *src, Strides3 sst,
                                    const T *ll, Strides3 ll_st, T *dst, Strides3 dst_st,
-                                   Extent3 n, int axis, Extent3 lo, const uint8_t *mask)
+                                   Extent3 n, int axis, Extent3 lo, const uint8_t *mask, int64_t mstride)
 {
     int64_t total = n.n[0] * n.n[1] * n.n[2];
     hipLaunchKernelGGL(k_generic_inv_filter<T>, grid_for(total), dim3(kBlock), 0, st,
-                       taps, src, sst, ll, ll_st, dst, dst_st, n, axis, lo, mask);
+                       taps, src, sst, ll, ll_st, dst, dst_st, n, axis, lo, mask, mstride);
     return hipGetLastError();
 }
 template <typename T>
@@ -497,9 +497,9 @@ hipError_t generic_copy_box(hipStream_t st, const T *src, Strides3 sst, T *dst, 
 
 #define WL_INSTANTIATE(T)                                                                                              \
     template hipError_t generic_fwd_filter_pass<T>(hipStream_t, const Taps<T> &, const T *, Strides3, T *, Strides3,  \
-                                                   T *, Strides3, Extent3, int, Extent3, const uint8_t *);             \
+                                                   T *, Strides3, Extent3, int, Extent3, const uint8_t *, int64_t);    \
     template hipError_t generic_inv_filter_pass<T>(hipStream_t, const Taps<T> &, const T *, Strides3, const T *,       \
-                                                   Strides3, T *, Strides3, Extent3, int, Extent3, const uint8_t *);   \
+                                                   Strides3, T *, Strides3, Extent3, int, Extent3, const uint8_t *, int64_t); \
     template hipError_t generic_lift_split<T>(hipStream_t, const T *, Strides3, T *, Strides3, Extent3, int,           \
                                               const uint8_t *);                                                        \
     template hipError_t generic_lift_step<T>(hipStream_t, const LiftStep<T> &, T *, Strides3, Extent3, int,            \

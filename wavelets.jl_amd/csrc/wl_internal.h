@@ -94,13 +94,13 @@ hipError_t generic_fwd_filter_pass(hipStream_t st, const Taps<T> &taps,
                                    const T *src, Strides3 sst,
                                    T *dst, Strides3 dst_st,
                                    T *ll, Strides3 ll_st,
-                                   Extent3 n, int axis, Extent3 lo, const uint8_t *mask = nullptr);
+                                   Extent3 n, int axis, Extent3 lo, const uint8_t *mask = nullptr, int64_t mstride = 0);
 template <typename T>
 hipError_t generic_inv_filter_pass(hipStream_t st, const Taps<T> &taps,
                                    const T *src, Strides3 sst,
                                    const T *ll, Strides3 ll_st,
                                    T *dst, Strides3 dst_st,
-                                   Extent3 n, int axis, Extent3 lo, const uint8_t *mask = nullptr);
+                                   Extent3 n, int axis, Extent3 lo, const uint8_t *mask = nullptr, int64_t mstride = 0);
 // lifting building blocks (box n, [s;d] layout along `axis` in the dense work buffer w)
 template <typename T>
 hipError_t generic_lift_split(hipStream_t st, const T *src, Strides3 sst, T *w, Strides3 wst,
@@ -177,18 +177,24 @@ inline Extent3 low_corner(const BoxSpec &b, const int64_t n[3])
 // ---- best-basis search (wl_entropy.hip) ----
 // doubles of scratch a reduction over a vector of n samples needs (entropy_segments / entropy_norm)
 size_t entropy_partials(int64_t n);
+// a batch of units for the reductions: nunits of them (<= 65535: the second grid dimension), unit u at x + u * x of the samples,
+// part + u * part of the partials and out + u * out of the outputs; the norm of unit u is nrmp[u].  One unit: {1, 0, 0, 0}.
+struct EntBatch { int64_t nunits, x, part, out; };
 // out[s] = coefentropy(x[s * nj : (s + 1) * nj], et, nrm) for s < nseg, in Float64 (accuracy contract: wl_entropy.hip); the norm is
 // *nrmp (a T value held as a double) or, when nrmp == nullptr, nrm_val
 template <typename T>
 hipError_t entropy_segments(hipStream_t st, int et, const T *x, int64_t nj, int64_t nseg, const double *nrmp, double nrm_val, double *part,
-                            double *out);
-// *nrm_out = T(sqrt(Float64 sum of x^2)), held as a double
+                            double *out, const EntBatch &bu);
+// nrm_out[u] = T(sqrt(Float64 sum of x_u^2)), held as a double
 template <typename T>
-hipError_t entropy_norm(hipStream_t st, const T *x, int64_t n, double *part, double *nrm_out);
-// bestbasistree's decision from ent = [entr_bf (ntree) ; entr_af (2^(Lmax - 1))]: best (ntree doubles) and split (ntree bytes) are
-// scratch, tree / tree_out device byte vectors of ntree nodes
+hipError_t entropy_norm(hipStream_t st, const T *x, int64_t n, double *part, double *nrm_out, const EntBatch &bu);
+// bestbasistree's decision from ent = [entr_bf (ntree) ; entr_af (2^(Lmax - 1))]: best (ntree doubles per unit) and split (ntree bytes
+// per unit) are scratch, tree the one device input tree of ntree nodes (nullptr: the full tree of depth Lfull), tree_out device byte
+// vectors; unit u reads ent + u * uent and writes tree_out + u * uout
 hipError_t bestbasis_decide(hipStream_t st, const double *ent, int64_t ntree, int Lmax, double *best, uint8_t *split, const uint8_t *tree,
-                            uint8_t *tree_out);
+                            int Lfull, uint8_t *tree_out, int64_t nunits, int64_t uent, int64_t uout);
+// out_u[k] = trees_u[k] and every ancestor of k set, k < nnodes: the largest valid subtree of a tree nobody validated
+hipError_t tree_close(hipStream_t st, const uint8_t *trees, int64_t utrees, int64_t nnodes, uint8_t *out, int64_t uout, int64_t nunits);
 
 // ---- complex staging (wl_complex.hip) ----
 // planes[(2u + c) * plane_stride + i] = component c (0 re, 1 im) of the complex value z[u * unit_stride + i] (z: interleaved reals,

@@ -18,6 +18,9 @@
 // Batches (wl_wpt_*_batch): every kernel takes nunits signals that share the tree, unit u at element offset
 // u * stride; blockIdx.y is the unit (the tail packs several whole units of fewer than TS samples into one workgroup instead) and
 // segments and node bits are relative to the unit.  The single transform is the batch of one unit of the same instances.
+// Per-unit trees (wl_wpt_filter_batch_trees): the node bits of unit u start mstride bytes after those of
+// unit u - 1 (mstride == 0: the one shared tree); a workgroup of the tail that holds several whole units picks the bits of the
+// unit a chunk-local segment belongs to.
 //
 // Arithmetic: the closed forms of wl_internal.h in the reference's summation order, no FMA -- bit-identical to the per-depth
 // kernels (tests/test_gpu_parity.py::test_wpt_bitexact pins both against the oracle).
@@ -41,6 +44,7 @@ struct WptMultiArgs {
     // element offset u * stride of src and of dst; blockIdx.y is the unit (at most 65535 per launch), blockIdx.x its tile.
     // Positions, segments and node bits are all relative to the unit.
     int64_t stride;
+    int64_t mstride;                // bytes between the node bits of consecutive units (0: every unit reads the same tree)
     TapsF<T, F> tp;
 };
 
@@ -59,6 +63,7 @@ __global__ void __launch_bounds__(256) k_wpt_fwd_multi(WptMultiArgs<T, F> a)
     const unsigned tile = blockIdx.x;
     const T *usrc = a.src + (int64_t)blockIdx.y * a.stride;
     T *udst = a.dst + (int64_t)blockIdx.y * a.stride;
+    const uint8_t *mask = a.mask ? a.mask + (int64_t)blockIdx.y * a.mstride : nullptr;
     const int64_t own0 = (int64_t)tile * TS;                                       // position in the vector (batch: in the unit)
     const int64_t root = own0 / a.nj;                                     // segment of the first fused depth
     const int64_t r0 = own0 - root * a.nj;                                // ... and the tile's offset inside it
@@ -123,13 +128,13 @@ __global__ void __launch_bounds__(256) k_wpt_fwd_multi(WptMultiArgs<T, F> a)
         for (int g = tid; g < total; g += 256) {
             const int b = g / gpb;
             const int i = (g - b * gpb) * PPT;
-            if (a.mask) {
+            if (mask) {
                 // live: every ancestor of parent band b inside this launch splits; bit: the band itself splits
                 bool live = true;
                 for (int u = 1; u < t; ++u)
-                    live = live && a.mask[(((int64_t)1 << (a.depth + u - 1)) - 1) + (root << (u - 1)) + (b >> (t - u))] != 0;
+                    live = live && mask[(((int64_t)1 << (a.depth + u - 1)) - 1) + (root << (u - 1)) + (b >> (t - u))] != 0;
                 if (!live) continue;
-                if (a.mask[(((int64_t)1 << (a.depth + t - 1)) - 1) + segb + b] == 0) {
+                if (mask[(((int64_t)1 << (a.depth + t - 1)) - 1) + segb + b] == 0) {
                     // a leaf of the tree: its owned samples (parent-band local index 2 (i + q) + F - 2 <-> owned pair i + q - H[t]) go out as they are
                     typedef typename VecOf<T, 2>::type P2;
                     T *lo = udst + root * a.nj + (int64_t)b * (a.nj >> (t - 1)) + (r0 >> (t - 1));
@@ -184,7 +189,7 @@ struct WptInvMultiArgs {
     int bs[4];                      // band stride in LDS at fused level t
     int buf_elems;
     const uint8_t *mask; int depth; // as WptMultiArgs; depth = the SHALLOWEST fused depth
-    int64_t stride;                 // units of a batch, as WptMultiArgs
+    int64_t stride, mstride;        // units of a batch and their node bits, as WptMultiArgs
     TapsF<T, F> tp;
 };
 
@@ -200,6 +205,7 @@ __global__ void __launch_bounds__(256) k_wpt_inv_multi(WptInvMultiArgs<T, F> a)
     const unsigned tile = blockIdx.x;
     const T *usrc = a.src + (int64_t)blockIdx.y * a.stride;
     T *udst = a.dst + (int64_t)blockIdx.y * a.stride;
+    const uint8_t *mask = a.mask ? a.mask + (int64_t)blockIdx.y * a.mstride : nullptr;
     const int64_t own0 = (int64_t)tile * TS;
     const int64_t root = own0 / a.nj;
     const int64_t r0 = own0 - root * a.nj;
@@ -238,7 +244,7 @@ __global__ void __launch_bounds__(256) k_wpt_inv_multi(WptInvMultiArgs<T, F> a)
         for (int g = tid; g < total; g += 256) {
             const int b = g / gpb;
             const int q0 = (g - b * gpb) * PPT;
-            if (a.mask && a.mask[(((int64_t)1 << (a.depth + t - 1)) - 1) + (root << (t - 1)) + b] == 0) {
+            if (mask && mask[(((int64_t)1 << (a.depth + t - 1)) - 1) + (root << (t - 1)) + b] == 0) {
                 // parent band b is (part of) a leaf: its samples are taken from the source as they are -- local pair q <-> element
                 // (r0 >> (t-1)) - G[t-1] + 2 q of the band (mod its length).  (If an ancestor is a leaf too nobody reads this band.)
                 const int64_t plen = a.nj >> (t - 1);
@@ -301,12 +307,14 @@ struct WptTailArgs {
     // touches nothing beyond the last one.
     int64_t stride, nunits;
     int lgn;                        // log2(n) when a workgroup holds whole units, else -1
+    int64_t mstride;                // node bits of consecutive units, as WptMultiArgs
     TapsF<T, F> tp;
 };
 // where a workgroup of the tail stands: its source / destination base, the samples it holds and, for the node bits, the
-// first segment of its chunk inside the unit (in chunks) and the bits of a chunk-local segment index that stay inside a unit
+// first segment of its chunk inside the unit (in chunks) and the bits of a chunk-local segment index that stay inside a unit;
+// mbase: where the node bits of its first (or only) unit start, mstride: the step to the next unit it holds
 template <typename T>
-struct WptTailPos { const T *src; T *dst; int count; int64_t cblk; int lgn; bool contig; };
+struct WptTailPos { const T *src; T *dst; int count; int64_t cblk; int lgn; bool contig; int64_t mbase, mstride; };
 template <typename T, typename A>
 __device__ __forceinline__ WptTailPos<T> wpt_tail_pos(const A &a, int TS)
 {
@@ -316,6 +324,7 @@ __device__ __forceinline__ WptTailPos<T> wpt_tail_pos(const A &a, int TS)
         p.src = a.src + (int64_t)blockIdx.y * a.stride + (int64_t)c * TS;
         p.dst = a.dst + (int64_t)blockIdx.y * a.stride + (int64_t)c * TS;
         p.count = TS; p.cblk = c; p.lgn = -1; p.contig = true;
+        p.mbase = (int64_t)blockIdx.y * a.mstride;
     } else {
         const int64_t u0 = (int64_t)blockIdx.x << (a.lgts - a.lgn);
         const int64_t left = a.nunits - u0, cap = (int64_t)1 << (a.lgts - a.lgn);
@@ -323,7 +332,9 @@ __device__ __forceinline__ WptTailPos<T> wpt_tail_pos(const A &a, int TS)
         p.dst = a.dst + u0 * a.stride;
         p.count = (int)((left < cap ? left : cap) << a.lgn);
         p.cblk = 0; p.lgn = a.lgn; p.contig = (a.stride == ((int64_t)1 << a.lgn));
+        p.mbase = u0 * a.mstride;
     }
+    p.mstride = a.mstride;
     return p;
 }
 // count samples = whole units of 2^lgn samples (a multiple of 16 bytes each), unit j of the workgroup at base + j * stride
@@ -350,11 +361,14 @@ __device__ __forceinline__ void wpt_units_out(T *base, int64_t stride, int lgn, 
     }
 }
 
-// index (inside the unit) of chunk-local segment sg of length 2^lgm: the node bit it reads
+// index of chunk-local segment sg of length 2^lgm among the segments of its depth: the node bit it reads -- inside the unit, plus
+// the offset of that unit's tree (a workgroup of whole units: unit sg >> (lgn - lgm) of those it holds; the last workgroup of a
+// batch holds fewer units and its pairs p < half never name a segment beyond them)
 template <typename P>
 __device__ __forceinline__ int64_t wpt_tail_seg(const P &pos, int lgts, int lgm, int sg)
 {
-    return (pos.cblk << (lgts - lgm)) + (pos.lgn < 0 ? sg : (sg & ((1 << (pos.lgn - lgm)) - 1)));
+    if (pos.lgn < 0) return pos.mbase + (pos.cblk << (lgts - lgm)) + sg;
+    return pos.mbase + (int64_t)(sg >> (pos.lgn - lgm)) * pos.mstride + (sg & ((1 << (pos.lgn - lgm)) - 1));
 }
 
 template <typename T>
@@ -497,13 +511,13 @@ bool wpt_fwd_multi_ok(int F, int64_t n, int64_t nj, int NL)
 
 template <typename T, int F>
 static hipError_t launch_wpt_multi_f(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask,
-                                     int64_t nunits, int64_t stride)
+                                     int64_t nunits, int64_t stride, int64_t mstride)
 {
     constexpr int VEC = 16 / sizeof(T);
     WptMultiArgs<T, F> a;
     a.src = src; a.dst = dst; a.nj = nj; a.NL = NL; a.TS = wpt_tile_samples<T>();
     a.mask = mask; a.depth = ilog2(n / nj);
-    a.stride = stride;
+    a.stride = stride; a.mstride = mstride;
     int H[4];
     H[NL] = 0;
     for (int t = NL; t >= 1; --t) H[t - 1] = 2 * H[t] + (F - 2);
@@ -525,14 +539,14 @@ static hipError_t launch_wpt_multi_f(hipStream_t st, const Taps<T> &taps, const 
 
 template <typename T>
 hipError_t wpt_fwd_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask,
-                                int64_t nunits, int64_t stride)
+                                int64_t nunits, int64_t stride, int64_t mstride)
 {
     switch (taps.F) {
-    case 2: return launch_wpt_multi_f<T, 2>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
-    case 4: return launch_wpt_multi_f<T, 4>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
-    case 6: return launch_wpt_multi_f<T, 6>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
-    case 8: return launch_wpt_multi_f<T, 8>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
-    case 10: return launch_wpt_multi_f<T, 10>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
+    case 2: return launch_wpt_multi_f<T, 2>(st, taps, src, dst, n, nj, NL, mask, nunits, stride, mstride);
+    case 4: return launch_wpt_multi_f<T, 4>(st, taps, src, dst, n, nj, NL, mask, nunits, stride, mstride);
+    case 6: return launch_wpt_multi_f<T, 6>(st, taps, src, dst, n, nj, NL, mask, nunits, stride, mstride);
+    case 8: return launch_wpt_multi_f<T, 8>(st, taps, src, dst, n, nj, NL, mask, nunits, stride, mstride);
+    case 10: return launch_wpt_multi_f<T, 10>(st, taps, src, dst, n, nj, NL, mask, nunits, stride, mstride);
     default: return hipErrorInvalidValue;
     }
 }
@@ -557,13 +571,13 @@ bool wpt_inv_multi_ok(int F, int64_t n, int64_t nj, int NL)
 
 template <typename T, int F>
 static hipError_t launch_wpt_inv_multi_f(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask,
-                                         int64_t nunits, int64_t stride)
+                                         int64_t nunits, int64_t stride, int64_t mstride)
 {
     constexpr int VEC = 16 / sizeof(T);
     WptInvMultiArgs<T, F> a;
     a.src = src; a.dst = dst; a.nj = nj; a.NL = NL; a.TS = wpt_tile_samples<T>();
     a.mask = mask; a.depth = ilog2(n / nj);
-    a.stride = stride;
+    a.stride = stride; a.mstride = mstride;
     wpt_inv_halos<T>(F, NL, a.G);
     int maxlen = 0;
     for (int t = 0; t <= 3; ++t) a.bs[t] = 0;
@@ -583,14 +597,14 @@ static hipError_t launch_wpt_inv_multi_f(hipStream_t st, const Taps<T> &taps, co
 
 template <typename T>
 hipError_t wpt_inv_multi_launch(hipStream_t st, const Taps<T> &taps, const T *src, T *dst, int64_t n, int64_t nj, int NL, const uint8_t *mask,
-                                int64_t nunits, int64_t stride)
+                                int64_t nunits, int64_t stride, int64_t mstride)
 {
     switch (taps.F) {
-    case 2: return launch_wpt_inv_multi_f<T, 2>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
-    case 4: return launch_wpt_inv_multi_f<T, 4>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
-    case 6: return launch_wpt_inv_multi_f<T, 6>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
-    case 8: return launch_wpt_inv_multi_f<T, 8>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
-    case 10: return launch_wpt_inv_multi_f<T, 10>(st, taps, src, dst, n, nj, NL, mask, nunits, stride);
+    case 2: return launch_wpt_inv_multi_f<T, 2>(st, taps, src, dst, n, nj, NL, mask, nunits, stride, mstride);
+    case 4: return launch_wpt_inv_multi_f<T, 4>(st, taps, src, dst, n, nj, NL, mask, nunits, stride, mstride);
+    case 6: return launch_wpt_inv_multi_f<T, 6>(st, taps, src, dst, n, nj, NL, mask, nunits, stride, mstride);
+    case 8: return launch_wpt_inv_multi_f<T, 8>(st, taps, src, dst, n, nj, NL, mask, nunits, stride, mstride);
+    case 10: return launch_wpt_inv_multi_f<T, 10>(st, taps, src, dst, n, nj, NL, mask, nunits, stride, mstride);
     default: return hipErrorInvalidValue;
     }
 }
@@ -610,7 +624,7 @@ bool wpt_tail_ok(int F, int64_t n, int64_t nj, int ndepth)
 
 template <typename T, int F>
 static hipError_t launch_wpt_tail_f(hipStream_t st, const Taps<T> &taps, int fw, const T *src, T *dst, int64_t n, int64_t nj, int ndepth, const uint8_t *mask,
-                                    int64_t nunits, int64_t stride)
+                                    int64_t nunits, int64_t stride, int64_t mstride)
 {
     // n >= TS: the unit's chunks of TS.  n < TS: a workgroup of upw whole units -- TS / n of them, or with fewer than that in the
     // batch the next power of two >= nunits (one workgroup; one unit: a chunk of n, the plain transform)
@@ -629,7 +643,7 @@ static hipError_t launch_wpt_tail_f(hipStream_t st, const Taps<T> &taps, int fw,
     }
     a.src = src; a.dst = dst; a.lgts = ilog2(chunk); a.lgm = ilog2(nj); a.ndepth = ndepth;
     a.mask = mask; a.depth = ilog2(n / nj);
-    a.stride = stride; a.nunits = nunits;
+    a.stride = stride; a.nunits = nunits; a.mstride = mstride;
     a.tp = shrink<T, F>(taps);
     const size_t shmem = 2 * (size_t)chunk * sizeof(T);
     const int threads = chunk >= 2048 ? 512 : (chunk >= 512 ? 256 : 64);
@@ -640,14 +654,14 @@ static hipError_t launch_wpt_tail_f(hipStream_t st, const Taps<T> &taps, int fw,
 
 template <typename T>
 hipError_t wpt_tail_launch(hipStream_t st, const Taps<T> &taps, int fw, const T *src, T *dst, int64_t n, int64_t nj, int ndepth, const uint8_t *mask,
-                           int64_t nunits, int64_t stride)
+                           int64_t nunits, int64_t stride, int64_t mstride)
 {
     switch (taps.F) {
-    case 2: return launch_wpt_tail_f<T, 2>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride);
-    case 4: return launch_wpt_tail_f<T, 4>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride);
-    case 6: return launch_wpt_tail_f<T, 6>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride);
-    case 8: return launch_wpt_tail_f<T, 8>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride);
-    case 10: return launch_wpt_tail_f<T, 10>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride);
+    case 2: return launch_wpt_tail_f<T, 2>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride, mstride);
+    case 4: return launch_wpt_tail_f<T, 4>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride, mstride);
+    case 6: return launch_wpt_tail_f<T, 6>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride, mstride);
+    case 8: return launch_wpt_tail_f<T, 8>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride, mstride);
+    case 10: return launch_wpt_tail_f<T, 10>(st, taps, fw, src, dst, n, nj, ndepth, mask, nunits, stride, mstride);
     default: return hipErrorInvalidValue;
     }
 }
@@ -656,15 +670,15 @@ template int wpt_tile_samples<float>();
 template int wpt_tile_samples<double>();
 template bool wpt_fwd_multi_ok<float>(int, int64_t, int64_t, int);
 template bool wpt_fwd_multi_ok<double>(int, int64_t, int64_t, int);
-template hipError_t wpt_fwd_multi_launch<float>(hipStream_t, const Taps<float> &, const float *, float *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t);
-template hipError_t wpt_fwd_multi_launch<double>(hipStream_t, const Taps<double> &, const double *, double *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t);
+template hipError_t wpt_fwd_multi_launch<float>(hipStream_t, const Taps<float> &, const float *, float *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t, int64_t);
+template hipError_t wpt_fwd_multi_launch<double>(hipStream_t, const Taps<double> &, const double *, double *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t, int64_t);
 template bool wpt_inv_multi_ok<float>(int, int64_t, int64_t, int);
 template bool wpt_inv_multi_ok<double>(int, int64_t, int64_t, int);
-template hipError_t wpt_inv_multi_launch<float>(hipStream_t, const Taps<float> &, const float *, float *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t);
-template hipError_t wpt_inv_multi_launch<double>(hipStream_t, const Taps<double> &, const double *, double *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t);
+template hipError_t wpt_inv_multi_launch<float>(hipStream_t, const Taps<float> &, const float *, float *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t, int64_t);
+template hipError_t wpt_inv_multi_launch<double>(hipStream_t, const Taps<double> &, const double *, double *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t, int64_t);
 template bool wpt_tail_ok<float>(int, int64_t, int64_t, int);
 template bool wpt_tail_ok<double>(int, int64_t, int64_t, int);
-template hipError_t wpt_tail_launch<float>(hipStream_t, const Taps<float> &, int, const float *, float *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t);
-template hipError_t wpt_tail_launch<double>(hipStream_t, const Taps<double> &, int, const double *, double *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t);
+template hipError_t wpt_tail_launch<float>(hipStream_t, const Taps<float> &, int, const float *, float *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t, int64_t);
+template hipError_t wpt_tail_launch<double>(hipStream_t, const Taps<double> &, int, const double *, double *, int64_t, int64_t, int, const uint8_t *, int64_t, int64_t, int64_t);
 
 }  // namespace wl

@@ -1,7 +1,8 @@
 """Entropy -- host-side mirror of src/Threshold/entropy.jl: the entropy measures, coefentropy and bestbasistree, the best-basis
 search of a wavelet packet tree (`tree = bestbasistree(x, wt); y = wpt(x, wt, tree)`).
 
-On a device tensor both run on the device (wl_coefentropy, wl_bestbasistree_filter); the packet content of every node is
+On a device tensor both run on the device (wl_coefentropy, wl_bestbasistree_filter; bestbasistree_batch: every column of a
+len x B array in one chain of launches, the trees staying on the device for wpt_batch -- wl_bestbasistree_filter_batch); the packet content of every node is
 bit-identical to wpt's, the entropies follow the accuracy contract of DESIGN.md section 11 (Float64 log and sums, deterministic).
 coefentropy of a single coefficient is host arithmetic in the coefficient's type, as in the reference (entropy.jl:15-30).
 """
@@ -105,5 +106,42 @@ def bestbasistree(y, wt, L_or_tree=None, et=ShannonEntropy(), *, return_entropy=
     rc = _lib.load().wl_bestbasistree_filter(h, _dtype_code(y), C.c_void_p(y.data_ptr()), n, _f64p(q), len(q),
                                              tree.ctypes.data_as(u8), len(tree), code, out.ctypes.data_as(u8),
                                              C.cast(C.c_void_p(ent.data_ptr()), C.POINTER(C.c_double)) if ent is not None else None, st)
+    _check(rc, h)
+    return (out, ent) if return_entropy else out
+
+
+def bestbasistree_batch(x, wt, L_or_tree=None, et=ShannonEntropy(), *, return_entropy=False):
+    """bestbasistree of every column of a len x B device array (unit u = x[:, u]) in one chain of launches over all columns
+    (wl_bestbasistree_filter_batch): a torch.uint8 DEVICE tensor of shape (ntree, B), column u being unit u's tree -- bit for bit
+    `bestbasistree(x[:, u], wt, L_or_tree, et)` -- which wpt_batch / iwpt_batch take as their tree argument.  Nothing synchronises.
+    L_or_tree: None / an integer L (maketree(n, L, :full)) or ONE host tree shared by all columns.  return_entropy=True also returns
+    the Float64 device tensor (ntree + 2^(Lmax-1), B) of the node entropies [entr_bf ; entr_af] of every column."""
+    _reject_complex(x, "bestbasistree_batch")
+    if not isinstance(wt, OrthoFilter):
+        raise TypeError("bestbasistree_batch is defined for OrthoFilter wavelets only (the reference has no method for %s)" % type(wt).__name__)
+    code = _et_code(et)
+    if isinstance(x, torch.Tensor) and x.dim() != 2:
+        raise TypeError("bestbasistree_batch expects a len x B array (unit u = x[:, u])")
+    if isinstance(x, torch.Tensor):
+        tree = _tree_arg(int(x.shape[0]), L_or_tree)         # (maketree's assertion on a bad depth, before anything touches the device)
+    x = _prep_in(x, maxdim=2)
+    n, nb = (int(v) for v in x.shape)
+    Lmax = Util.maxtransformlevels(n)
+    ntree = (1 << Lmax) - 1
+    if isinstance(tree, np.ndarray):
+        tp, nt, L = tree.ctypes.data_as(C.POINTER(C.c_uint8)), len(tree), 0
+    else:
+        tp, nt, L = None, ntree, int(tree)
+    # (column-major like x: column u is contiguous, ntree bytes from column u - 1)
+    out = torch.empty((nb, ntree), dtype=torch.uint8, device=x.device).t()
+    ent = None
+    nent = ntree + (1 << (Lmax - 1)) if Lmax > 0 else 0
+    if return_entropy:
+        ent = torch.empty((nb, nent), dtype=torch.float64, device=x.device).t()
+    h, st = _context(x.device)
+    q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
+    rc = _lib.load().wl_bestbasistree_filter_batch(h, _dtype_code(x), C.c_void_p(x.data_ptr()), n, nb, n, _f64p(q), len(q), tp, nt, L, code,
+                                                   C.c_void_p(out.data_ptr()), ntree,
+                                                   C.c_void_p(ent.data_ptr()) if ent is not None and nent else None, nent, st)
     _check(rc, h)
     return (out, ent) if return_entropy else out

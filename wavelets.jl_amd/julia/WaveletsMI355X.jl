@@ -445,5 +445,6 @@ include("WaveletsMI355X_bestbasis.jl")
 include("WaveletsMI355X_denoise_batch.jl")
 include("WaveletsMI355X_wpt_batch.jl")
 include("WaveletsMI355X_complex.jl")
+include("WaveletsMI355X_bestbasis_batch.jl")
 
 end # module

@@ -761,7 +761,7 @@ def iwpt_(*args) -> torch.Tensor:
 
 
 # ---- a batch of signals through one packet tree ---------------------------------------------------
-def _xwpt_batch(x, wt, tree_or_L, fw, y, fname):
+def _xwpt_batch(x, wt, tree_or_L, fw, y, fname, L=None):
     """x: len x B (column-major: unit i = x[:, i]); every column gets the packet transform of the one shared tree, all columns in
     one chain of launches (wl_wpt_filter_batch / wl_wpt_lifting_batch).  Equals `stack(wpt(x[:, i], wt, tree) for i)` bit for bit."""
     if not isinstance(wt, (OrthoFilter, GLS)):
@@ -770,6 +770,10 @@ def _xwpt_batch(x, wt, tree_or_L, fw, y, fname):
     _reject_complex(y, fname)
     if isinstance(x, torch.Tensor) and x.dim() != 2:
         raise TypeError(f"{fname} expects a len x B array (unit i = x[:, i])")
+    if isinstance(tree_or_L, torch.Tensor):
+        return _xwpt_batch_trees(x, wt, tree_or_L, fw, y, fname, L)
+    if L is not None:
+        raise TypeError(f"{fname}: L bounds a tensor of per-unit trees only (pass the depth of a full tree as tree_or_L)")
     if isinstance(x, torch.Tensor):
         tree = _tree_arg(int(x.shape[0]), tree_or_L)         # (wpt's assertion on a bad depth, before anything touches the device)
     x = _prep_in(x, maxdim=2)
@@ -797,13 +801,51 @@ def _xwpt_batch(x, wt, tree_or_L, fw, y, fname):
     return y
 
 
-def wpt_batch(x, wt, tree_or_L=None, y=None) -> torch.Tensor:
-    """wpt of every column of a len x B array with one shared tree (or the full tree of depth L)"""
-    return _xwpt_batch(x, wt, tree_or_L, True, y, "wpt_batch")
+def _xwpt_batch_trees(x, wt, trees, fw, y, fname, L=None):
+    """one DEVICE tree per column (what bestbasistree_batch returns): trees is a uint8 / bool tensor of shape (ntree, B), column u
+    the tree of x[:, u] (wl_wpt_filter_batch_trees).  A tree that is not valid counts as its largest valid subtree."""
+    if not isinstance(wt, OrthoFilter):
+        raise TypeError(f"{fname} with one tree per unit is defined for orthogonal filters only (not for {type(wt).__name__})")
+    if trees.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f"{fname}: a tensor of trees must be uint8 or bool, got {trees.dtype}")
+    if isinstance(x, torch.Tensor):                          # (the shape rule before anything touches the device)
+        want = ((1 << Util.maxtransformlevels(int(x.shape[0]))) - 1, int(x.shape[1]))
+        if tuple(trees.shape) != want:
+            raise AssertionError(f"{fname}: trees must have shape (2^maxtransformlevels(n) - 1, B) = {want}, got {tuple(trees.shape)}")
+    x = _prep_in(x, maxdim=2)
+    n, nb = (int(v) for v in x.shape)
+    Lmax = Util.maxtransformlevels(n)
+    ntree = (1 << Lmax) - 1
+    if trees.device != x.device:
+        raise ArgumentError(f"{fname}: the trees must be on the device of x")
+    if trees.dtype == torch.bool:
+        trees = trees.view(torch.uint8)
+    if ntree and (trees.stride(0) != 1 or (nb > 1 and trees.stride(1) < ntree)):
+        trees = trees.t().contiguous().t()                   # column-major: column u contiguous, columns apart (not a broadcast view)
+    tstride = int(trees.stride(1)) if nb > 1 and ntree else ntree
+    L = Lmax if L is None else int(L)
+    y = similar(x) if y is None else y
+    _check_pair(y, x)
+    if y is x or y.data_ptr() == x.data_ptr():
+        raise ArgumentError("in array is out array")
+    h, st = _context(x.device)
+    q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
+    # (an odd length has no nodes: any non-NULL address stands for the empty trees)
+    rc = _lib.load().wl_wpt_filter_batch_trees(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), n, nb, n, _f64p(q), len(q),
+                                               C.c_void_p(trees.data_ptr() if ntree else x.data_ptr()), max(tstride, ntree), L, 1 if fw else 0, st)
+    _check(rc, h)
+    return y
 
 
-def iwpt_batch(x, wt, tree_or_L=None, y=None) -> torch.Tensor:
-    return _xwpt_batch(x, wt, tree_or_L, False, y, "iwpt_batch")
+def wpt_batch(x, wt, tree_or_L=None, y=None, *, L=None) -> torch.Tensor:
+    """wpt of every column of a len x B array with one shared tree (or the full tree of depth L), or -- tree_or_L a device uint8 /
+    bool tensor of shape (ntree, B), e.g. from bestbasistree_batch -- with the tree of its own column (L: nodes at depth >= L of
+    those trees are ignored; default maxtransformlevels(n))"""
+    return _xwpt_batch(x, wt, tree_or_L, True, y, "wpt_batch", L)
+
+
+def iwpt_batch(x, wt, tree_or_L=None, y=None, *, L=None) -> torch.Tensor:
+    return _xwpt_batch(x, wt, tree_or_L, False, y, "iwpt_batch", L)
 
 
 # ---- complex staging, for direct use ---------------------------------------------------------------
