@@ -11,7 +11,7 @@
 
 using namespace wl;
 
-#include "wl_ctx.h"
+#include "wl_entry.h"
 
 thread_local const wl::Opts *wl::tl_opts = nullptr;
 thread_local unsigned *wl::tl_sync = nullptr;
@@ -106,36 +106,6 @@ inline bool sufficientpoweroftwo(int64_t n, int L) { return L < 62 && (n % ((int
 inline int ensure_ws(wl_ctx *ctx, size_t bytes) { return wl_ensure_ws(ctx, bytes); }
 inline int ensure_ws(wl_ctx *ctx, size_t bytes, hipStream_t st) { return wl_ensure_ws(ctx, bytes, st, true); }
 
-// makescheme (transforms_lifting.jl:13-25)
-template <typename T>
-int make_scheme(int nsteps, const int32_t *is_update, const int32_t *ncoef, const int32_t *shift,
-                const double *coefs, double norm1, double norm2, int fw, LiftScheme<T> &sc)
-{
-    if (nsteps < 0 || nsteps > WL_MAX_STEPS) return WL_EINVAL_SCHEME;
-    if (nsteps > 0 && (!is_update || !ncoef || !shift || !coefs)) return WL_EINVAL_ARG;
-    int off[WL_MAX_STEPS];
-    int o = 0;
-    for (int i = 0; i < nsteps; ++i) {
-        if (ncoef[i] < 1 || ncoef[i] > WL_MAX_NCOEF) return WL_EINVAL_SCHEME;
-        off[i] = o;
-        o += ncoef[i];
-    }
-    sc.nsteps = nsteps;
-    for (int i = 0; i < nsteps; ++i) {
-        int j = fw ? i : nsteps - 1 - i;
-        LiftStep<T> &st = sc.step[i];
-        st.is_update = is_update[j] ? 1 : 0;
-        st.nc = ncoef[j];
-        st.shift = shift[j];
-        for (int k = 0; k < WL_MAX_NCOEF; ++k) st.c[k] = (T)0;
-        for (int k = 0; k < st.nc; ++k) st.c[k] = (T)(coefs[off[j] + k] * (fw ? -1.0 : 1.0));
-    }
-    sc.norm1 = (T)(fw ? norm1 : 1.0 / norm1);
-    sc.norm2 = (T)(fw ? norm2 : 1.0 / norm2);
-    return WL_OK;
-}
-
-// ---- generic filter level loops ----------------------------------------------------------
 // ---- generic lifting level loops -----------------------------------------------------------
 template <typename T>
 int generic_lifting_fwd(wl_ctx *ctx, hipStream_t st, const BoxSpec &b, T *y, const T *x,
@@ -273,8 +243,7 @@ int dwt_filter_impl(wl_ctx *ctx, hipStream_t st, const BoxSpec &b, T *y, const T
     const bool want_gen = (ctx->path != 0) || (b.nd == 3) || (flen % 2 != 0) || (flen > 10 && b.nt > 1);
     int rc = ensure_ws(ctx, want_gen ? full_bytes : ab_bytes, st);
     if (rc) return rc;
-    Taps<T> taps;
-    make_taps<T>(qmf, flen, taps);
+    const Taps<T> taps = taps_of<T>(qmf, flen);
     for (int attempt = 0; attempt < 2; ++attempt) {
         const bool have_gen = ctx->ws_bytes >= full_bytes;
         rc = fw ? filter_fwd_levels<T>(ctx->ws, have_gen, ctx->cu_count, ctx->path, st, b, y, x, taps, L, &ctx->last_kernel, &ctx->last_hip)
@@ -288,13 +257,24 @@ int dwt_filter_impl(wl_ctx *ctx, hipStream_t st, const BoxSpec &b, T *y, const T
 
 template <typename T>
 int dwt_lifting_impl(wl_ctx *ctx, hipStream_t st, const BoxSpec &b, T *y, const T *x,
-                     int nsteps, const int32_t *is_update, const int32_t *ncoef, const int32_t *shift,
-                     const double *coefs, double norm1, double norm2, int L, int fw)
+                     const SchemeArgs &s, int L, int fw)
 {
-    LiftScheme<T> sc;
-    int rc = make_scheme<T>(nsteps, is_update, ncoef, shift, coefs, norm1, norm2, fw, sc);
-    if (rc) return rc;
-    return wl_lifting_box<T>(ctx, st, b, y, x, sc, L, fw);
+    WL_TRY(s.check());
+    return wl_lifting_box<T>(ctx, st, b, y, x, s.build<T>(fw), L, fw);
+}
+
+// nunits dense units of N elements, unit i at element offset i * stride of x and of y: one copy of an N x nunits matrix with leading
+// dimension stride per 65535 units (the padding is not touched)
+template <typename T>
+int copy_units(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t N, int64_t nunits, int64_t stride)
+{
+    const Strides3 s = {{1, stride, 0}};
+    ctx->last_kernel = "copy";
+    return for_groups(nunits, 65535, [&](int64_t i0, int64_t nu) -> int {
+        const Extent3 ext = {{N, nu, 1}};
+        WL_HIP(ctx, generic_copy_box<T>(st, x + i0 * stride, s, y + i0 * stride, s, ext));
+        return WL_OK;
+    });
 }
 
 // a batch of square images: the box of wl_dwt_filter_batch (third extent = images), images in groups of at most 65535
@@ -307,12 +287,10 @@ int lifting_batch_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
     b.dims[0] = n; b.dims[1] = n;
     b.full.s[0] = 1; b.full.s[1] = n; b.full.s[2] = image_stride;
     // images in groups of at most 65535 (one grid plane / workgroup per image in the batched kernels)
-    for (int64_t i0 = 0; i0 < nimages; i0 += 65535) {
-        b.dims[2] = (nimages - i0 < 65535) ? (nimages - i0) : 65535;
-        int rc = wl_lifting_box<T>(ctx, st, b, y + i0 * image_stride, x + i0 * image_stride, sc, L, fw);
-        if (rc) return rc;
-    }
-    return WL_OK;
+    return for_groups(nimages, 65535, [&](int64_t i0, int64_t ni) {
+        b.dims[2] = ni;
+        return wl_lifting_box<T>(ctx, st, b, y + i0 * image_stride, x + i0 * image_stride, sc, L, fw);
+    });
 }
 
 // a batch of volumes (wl_dwt_filter_batch3): volumes in groups of at most 65535, the level loops of wl_batch3d.hip
@@ -321,45 +299,23 @@ int dwt_filter_batch3_impl(wl_ctx *ctx, hipStream_t st, const int64_t dims[3], i
                            int flen, int L, int fw)
 {
     const int64_t N = dims[0] * dims[1] * dims[2];
-    if (L == 0) {
-        // every volume is dense: one copy of an N x nvol matrix with leading dimension vs (the padding is not touched)
-        const Strides3 s = {{1, vs, 0}};
-        for (int64_t i0 = 0; i0 < nvol; i0 += 65535) {
-            const Extent3 ext = {{N, (nvol - i0 < 65535) ? (nvol - i0) : 65535, 1}};
-            WL_HIP(ctx, generic_copy_box<T>(st, x + i0 * vs, s, y + i0 * vs, s, ext));
-        }
-        ctx->last_kernel = "copy";
-        return WL_OK;
-    }
-    Taps<T> taps;
-    make_taps<T>(qmf, flen, taps);
+    if (L == 0) return copy_units<T>(ctx, st, y, x, N, nvol, vs);              // (every volume is dense)
+    const Taps<T> taps = taps_of<T>(qmf, flen);
     const int64_t gmax = nvol < 65535 ? nvol : 65535;
     // 3-D levels outside the tail want one volume's T0 / T1 (as dwt_filter_impl does for a 3-D box): ask for them up front
     const size_t full_bytes = ws_vols_elems(N, gmax) * sizeof(T);
     int rc = ensure_ws(ctx, full_bytes, st);
     if (rc) return rc;
-    for (int64_t i0 = 0; i0 < nvol; i0 += 65535) {
-        const int64_t nv = (nvol - i0 < 65535) ? (nvol - i0) : 65535;
+    return for_groups(nvol, 65535, [&](int64_t i0, int64_t nv) {
         rc = fw ? filter_fwd_levels_vols<T>(ctx->ws, true, ctx->cu_count, ctx->path, st, dims, nv, vs, vs, y + i0 * vs, x + i0 * vs, taps, L,
                                             &ctx->last_kernel, &ctx->last_hip)
                 : filter_inv_levels_vols<T>(ctx->ws, true, ctx->cu_count, ctx->path, st, dims, nv, vs, vs, y + i0 * vs, x + i0 * vs, taps, L,
                                             &ctx->last_kernel, &ctx->last_hip);
-        if (rc == WL_RETRY_GEN) return WL_EINVAL_ARG;          // (the full workspace is held: no level can ask for more)
-        if (rc) return rc;
-    }
-    return WL_OK;
+        return rc == WL_RETRY_GEN ? WL_EINVAL_ARG : rc;        // (the full workspace is held: no level can ask for more)
+    });
 }
 
 }  // namespace
-
-template <typename T>
-int wl_make_scheme(int nsteps, const int32_t *is_update, const int32_t *ncoef, const int32_t *shift, const double *coefs, double norm1,
-                   double norm2, int fw, wl::LiftScheme<T> &sc)
-{
-    return make_scheme<T>(nsteps, is_update, ncoef, shift, coefs, norm1, norm2, fw, sc);
-}
-template int wl_make_scheme<float>(int, const int32_t *, const int32_t *, const int32_t *, const double *, double, double, int, wl::LiftScheme<float> &);
-template int wl_make_scheme<double>(int, const int32_t *, const int32_t *, const int32_t *, const double *, double, double, int, wl::LiftScheme<double> &);
 
 // the lifting transform of a box with a direction-adjusted scheme (shared with wl_ext.hip: the translation-invariant denoise)
 template <typename T>
@@ -419,30 +375,19 @@ template <typename T>
 int wl_lifting_vols(wl_ctx *ctx, hipStream_t st, int64_t n, int64_t nvol, int64_t vs, T *y, const T *x, const LiftScheme<T> &sc, int L, int fw)
 {
     const int64_t N = n * n * n;
-    if (L == 0) {
-        // every cube is dense: one copy of an N x nvol matrix with leading dimension vs (the padding is not touched)
-        const Strides3 s = {{1, vs, 0}};
-        for (int64_t i0 = 0; i0 < nvol && y != x; i0 += 65535) {
-            const Extent3 ext = {{N, (nvol - i0 < 65535) ? (nvol - i0) : 65535, 1}};
-            WL_HIP(ctx, generic_copy_box<T>(st, x + i0 * vs, s, y + i0 * vs, s, ext));
-        }
-        ctx->last_kernel = "copy";
-        return WL_OK;
-    }
+    if (L == 0) return copy_units<T>(ctx, st, y, x, N, y != x ? nvol : 0, vs);  // (every cube is dense; in place: nothing to copy)
     const int64_t gmax = nvol < 65535 ? nvol : 65535;
     // (every group starts a multiple of vs from x: one answer for all of them; the last, shorter group needs no more than the first)
     const int64_t need = (opt("WL_LIFT_BATCH3_LOOP", 0) != 0 || ctx->path != 0 || nvol == 1) ? -1 : lifting_3d_fast_ws<T>(sc, n, L, fw, x, y, gmax, vs, vs);
     if (need >= 0) {
         int rc = ensure_ws(ctx, (size_t)need * sizeof(T), st);
         if (rc) return rc;
-        for (int64_t i0 = 0; i0 < nvol; i0 += 65535) {
-            const int64_t nv = (nvol - i0 < 65535) ? (nvol - i0) : 65535;
+        WL_TRY(for_groups(nvol, 65535, [&](int64_t i0, int64_t nv) {
             int handled = 0;
             rc = lifting_3d_fast<T>(ctx->ws, ctx->cu_count, st, n, y + i0 * vs, x + i0 * vs, sc, L, fw, &handled, &ctx->last_kernel, &ctx->last_hip,
                                     nv, vs, vs);
-            if (rc) return rc;
-            if (!handled) return WL_EINVAL_ARG;               // (lifting_3d_fast_ws said eligible: not reached)
-        }
+            return (rc || handled) ? rc : WL_EINVAL_ARG;       // (lifting_3d_fast_ws said eligible: not reached)
+        }));
         ctx->last_kernel = "k_lift_axis_stream+k_lift_short_lines_batch";      // (whatever the size of the last group)
         return WL_OK;
     }
@@ -623,36 +568,38 @@ int wl_dwt_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, con
                   const double *qmf, int flen, int L, int fw, void *stream)
 {
     if (!ctx || !y || !x || !qmf) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen));
     BoxSpec b;
-    int rc = check_box(ndims, dims, L, b);
-    if (rc) return rc;
+    WL_TRY(check_box(ndims, dims, L, b));
     if (y == x) return WL_EALIAS;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == WL_F32 ? dwt_filter_impl<float>(ctx, st, b, (float *)y, (const float *)x, qmf, flen, L, fw)
-                           : dwt_filter_impl<double>(ctx, st, b, (double *)y, (const double *)x, qmf, flen, L, fw);
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return dwt_filter_impl<T>(ctx, st, b, (T *)y, (const T *)x, qmf, flen, L, fw);
+    });
 }
 
-static int lifting_common(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims,
-                          int nsteps, const int32_t *is_update, const int32_t *ncoef, const int32_t *shift,
-                          const double *coefs, double norm1, double norm2, int L, int fw, void *stream)
+// the lifting entry points on a box: the scope, then the scheme's rules, then the transform
+static int lifting_scoped(wl_ctx *ctx, int dtype, const BoxSpec &b, void *y, const void *x, const SchemeArgs &s, int L, int fw, void *stream)
+{
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return dwt_lifting_impl<T>(ctx, st, b, (T *)y, (const T *)x, s, L, fw);
+    });
+}
+
+static int lifting_common(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, const SchemeArgs &s, int L, int fw,
+                          void *stream)
 {
     if (!ctx || !y || !x) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    WL_TRY(check_dtype(dtype));
     BoxSpec b;
     // iscube check comes first in the reference (transforms_lifting.jl:131-136)
     if (dims && ndims >= 2 && ndims <= 3)
         for (int d = 1; d < ndims; ++d)
             if (dims[d] != dims[0]) return WL_EINVAL_CUBE;
-    int rc = check_box(ndims, dims, L, b);
-    if (rc) return rc;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == WL_F32
-               ? dwt_lifting_impl<float>(ctx, st, b, (float *)y, (const float *)x, nsteps, is_update, ncoef, shift, coefs, norm1, norm2, L, fw)
-               : dwt_lifting_impl<double>(ctx, st, b, (double *)y, (const double *)x, nsteps, is_update, ncoef, shift, coefs, norm1, norm2, L, fw);
+    WL_TRY(check_box(ndims, dims, L, b));
+    return lifting_scoped(ctx, dtype, b, y, x, s, L, fw, stream);
 }
 
 int wl_dwt_lifting(wl_ctx *ctx, int dtype, void *y, int ndims, const int64_t *dims,
@@ -660,8 +607,8 @@ int wl_dwt_lifting(wl_ctx *ctx, int dtype, void *y, int ndims, const int64_t *di
                    const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2,
                    int L, int fw, void *stream)
 {
-    return lifting_common(ctx, dtype, y, y, ndims, dims, nsteps, step_is_update, step_ncoef, step_shift,
-                          coefs_flat, norm1, norm2, L, fw, stream);
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
+    return lifting_common(ctx, dtype, y, y, ndims, dims, s, L, fw, stream);
 }
 
 int wl_dwt_lifting_oop(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims,
@@ -669,8 +616,8 @@ int wl_dwt_lifting_oop(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims
                        const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2,
                        int L, int fw, void *stream)
 {
-    return lifting_common(ctx, dtype, y, x, ndims, dims, nsteps, step_is_update, step_ncoef, step_shift,
-                          coefs_flat, norm1, norm2, L, fw, stream);
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
+    return lifting_common(ctx, dtype, y, x, ndims, dims, s, L, fw, stream);
 }
 
 // ---- batched column-wise --------------------------------------------------------------------
@@ -689,16 +636,15 @@ int wl_dwtc_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t len, 
                    const double *qmf, int flen, int L, int fw, void *stream)
 {
     if (!ctx || !y || !x || !qmf) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen));
     BoxSpec b;
-    int rc = check_dwtc(len, nsignals, ld, L, b);
-    if (rc) return rc;
+    WL_TRY(check_dwtc(len, nsignals, ld, L, b));
     if (y == x) return WL_EALIAS;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == WL_F32 ? dwt_filter_impl<float>(ctx, st, b, (float *)y, (const float *)x, qmf, flen, L, fw)
-                           : dwt_filter_impl<double>(ctx, st, b, (double *)y, (const double *)x, qmf, flen, L, fw);
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return dwt_filter_impl<T>(ctx, st, b, (T *)y, (const T *)x, qmf, flen, L, fw);
+    });
 }
 
 int wl_dwtc_lifting_oop(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t len, int64_t nsignals, int64_t ld,
@@ -706,16 +652,12 @@ int wl_dwtc_lifting_oop(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t 
                         const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2,
                         int L, int fw, void *stream)
 {
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
     if (!ctx || !y || !x) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    WL_TRY(check_dtype(dtype));
     BoxSpec b;
-    int rc = check_dwtc(len, nsignals, ld, L, b);
-    if (rc) return rc;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == WL_F32
-               ? dwt_lifting_impl<float>(ctx, st, b, (float *)y, (const float *)x, nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, L, fw)
-               : dwt_lifting_impl<double>(ctx, st, b, (double *)y, (const double *)x, nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, L, fw);
+    WL_TRY(check_dwtc(len, nsignals, ld, L, b));
+    return lifting_scoped(ctx, dtype, b, y, x, s, L, fw, stream);
 }
 
 int wl_dwtc_lifting(wl_ctx *ctx, int dtype, void *y, int64_t len, int64_t nsignals, int64_t ld,
@@ -723,16 +665,12 @@ int wl_dwtc_lifting(wl_ctx *ctx, int dtype, void *y, int64_t len, int64_t nsigna
                     const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2,
                     int L, int fw, void *stream)
 {
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
     if (!ctx || !y) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    WL_TRY(check_dtype(dtype));
     BoxSpec b;
-    int rc = check_dwtc(len, nsignals, ld, L, b);
-    if (rc) return rc;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == WL_F32
-               ? dwt_lifting_impl<float>(ctx, st, b, (float *)y, (const float *)y, nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, L, fw)
-               : dwt_lifting_impl<double>(ctx, st, b, (double *)y, (const double *)y, nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, L, fw);
+    WL_TRY(check_dwtc(len, nsignals, ld, L, b));
+    return lifting_scoped(ctx, dtype, b, y, y, s, L, fw, stream);
 }
 
 }  // extern "C"
@@ -772,22 +710,53 @@ static bool isvalidtree(int64_t n, const uint8_t *b, int64_t nb, int64_t *last_s
     return true;
 }
 
-template <typename T>
-static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n,
-                    const Taps<T> *taps, const LiftScheme<T> *sc,
-                    const uint8_t *tree, int64_t ntree, int64_t last_set, int fw, int full_depth = -1, int first_depth = 0,
-                    int64_t nunits = 1, int64_t ustride = 0, const uint8_t *utrees = nullptr, int64_t utstride = 0, int utL = 0)
+// the tree rule of the entry points that take either: tree == NULL is the full tree of depth L
+static int check_tree_or_depth(int64_t n, const uint8_t *tree, int64_t ntree, int L, int64_t *last_set)
 {
+    *last_set = -1;
+    if (!tree) return (L < 0 || L > wl_maxtransformlevels(n)) ? WL_EINVAL_L : WL_OK;
+    return isvalidtree(n, tree, ntree, last_set) ? WL_OK : WL_EINVAL_TREE;
+}
+
+// one packet transform of nunits signals of length n (wpt_impl)
+template <typename T>
+struct WptCall {
+    int64_t n = 0;
+    const Taps<T> *taps = nullptr;      // a filter bank, or
+    const LiftScheme<T> *sc = nullptr;  // a lifting scheme (direction-adjusted)
+    const uint8_t *tree = nullptr;      // HOST node bits (isvalidtree), ntree of them, the last set one at last_set
+    int64_t ntree = 0;
+    int64_t last_set = -1;
+    int fw = 1;
     // full_depth >= 0: the full tree of that depth, no tree vector (tree == nullptr); only its depths >= first_depth are applied
     // (x already holds the depth-first_depth content: the best-basis search steps one depth at a time)
+    int full_depth = -1;
+    int first_depth = 0;
     // nunits > 1 (wl_wpt_*_batch): nunits signals of length n that share the tree, unit u at element offset u * ustride of x, of y and
-    // of the work buffers.  The plan below is made for ONE unit of length n -- the batch takes the same kernels, every launch over all
+    // of the work buffers.  The plan is made for ONE unit of length n -- the batch takes the same kernels, every launch over all
     // units, the packet kernels being the very instances the single unit runs -- and lifting may then run out of place (x != y: the
     // first pass reads x, x stays untouched).
+    int64_t nunits = 1;
+    int64_t ustride = 0;
     // utrees != nullptr (wl_wpt_filter_batch_trees; filter banks only): one DEVICE tree per unit, unit u's node bits at utrees +
-    // u * utstride, depths < utL.  Nothing of them is known here, so the plan is the partial-tree plan of one unit with every depth
-    // < utL present; one launch closes the trees into the workspace (a node counts iff it and every ancestor is set) and the kernels
-    // read those bits with a per-unit stride.  Leaves pass through inside the launches.
+    // u * utstride, depths < utL.  Nothing of them is known on the host, so the plan is the partial-tree plan of one unit with every
+    // depth < utL present; one launch closes the trees into the workspace (a node counts iff it and every ancestor is set) and the
+    // kernels read those bits with a per-unit stride.  Leaves pass through inside the launches.
+    const uint8_t *utrees = nullptr;
+    int64_t utstride = 0;
+    int utL = 0;
+};
+
+template <typename T>
+static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, const WptCall<T> &c)
+{
+    const int64_t n = c.n, ntree = c.ntree, last_set = c.last_set, nunits = c.nunits, utstride = c.utstride;
+    const Taps<T> *taps = c.taps;
+    const LiftScheme<T> *sc = c.sc;
+    const uint8_t *tree = c.tree, *utrees = c.utrees;
+    const int fw = c.fw, first_depth = c.first_depth, utL = c.utL;
+    int full_depth = c.full_depth;
+    int64_t ustride = c.ustride;
     const bool lifting = (sc != nullptr);
     if (utrees) full_depth = -1;
     if (nunits == 1) ustride = n;
@@ -1048,7 +1017,11 @@ static int bestbasis_group(wl_ctx *ctx, hipStream_t st, const T *x, int64_t n, i
     for (int d = 0; d <= Lmax; ++d) {
         if (d > 0) {
             T *out = (cur == A) ? B : A;
-            rc = wpt_impl<T>(ctx, st, out, cur, n, &taps, nullptr, nullptr, 0, -1, 1, d, d - 1, G, S);
+            WptCall<T> c;
+            c.n = n; c.taps = &taps;
+            c.full_depth = d; c.first_depth = d - 1;
+            c.nunits = G; c.ustride = S;
+            rc = wpt_impl<T>(ctx, st, out, cur, c);
             if (rc) return rc;
             cur = out;
         }
@@ -1074,254 +1047,35 @@ static int bestbasis_impl(wl_ctx *ctx, hipStream_t st, const T *x, int64_t n, co
     return WL_OK;
 }
 
-// units in groups of G, as wpt_batch_impl: at most 65535 (WL_WPT_BATCH_GROUP lowers it), halved until the group's workspace fits the cap
+// units in groups of G, as wpt_batch_impl; one workspace size for every group (the last one may be shorter): nothing grows between groups
 template <typename T>
 static int bestbasis_batch_impl(wl_ctx *ctx, hipStream_t st, const T *x, int64_t n, int64_t nunits, int64_t S, const Taps<T> &taps,
                                 const uint8_t *tree, int Lfull, int et, uint8_t *trees_out, int64_t tstride, double *node_entropy, int64_t estride)
 {
-    int64_t G = nunits < 65535 ? nunits : 65535;
-    const long long og = opt("WL_WPT_BATCH_GROUP", 0);
-    if (og >= 1 && og < G) G = og;
-    const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
-    while (G > 1 && bb_layout(n, G, sizeof(T), node_entropy == nullptr).total > cap) G = (G + 1) / 2;
-    // one workspace size for every group (the last one may be shorter): nothing grows between groups
-    int rc = ensure_ws(ctx, bb_layout(n, G, sizeof(T), node_entropy == nullptr).total, st);
-    if (rc) return rc;
-    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
-        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
-        rc = bestbasis_group<T>(ctx, st, x + u0 * S, n, nb, S, taps, tree, Lfull, et, trees_out + u0 * tstride, tstride,
-                                node_entropy ? node_entropy + u0 * estride : nullptr, estride, nullptr);
-        if (rc != WL_OK) return rc;
-    }
-    return WL_OK;
+    auto bytes = [&](int64_t G) { return bb_layout(n, G, sizeof(T), node_entropy == nullptr).total; };
+    const int64_t G = group_size(nunits, 65535, opt("WL_WPT_BATCH_GROUP", 0), true, group_cap(), bytes);
+    WL_TRY(ensure_ws(ctx, bytes(G), st));
+    return for_groups(nunits, G, [&](int64_t u0, int64_t nb) {
+        return bestbasis_group<T>(ctx, st, x + u0 * S, n, nb, S, taps, tree, Lfull, et, trees_out + u0 * tstride, tstride,
+                                  node_entropy ? node_entropy + u0 * estride : nullptr, estride, nullptr);
+    });
 }
-
-extern "C" {
-
-int wl_bestbasistree_filter(wl_ctx *ctx, int dtype, const void *x, int64_t n, const double *qmf, int flen, const uint8_t *tree,
-                            int64_t ntree, int et, uint8_t *tree_out, double *node_entropy, void *stream)
-{
-    if (!ctx || !x || !qmf || !tree || !tree_out) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (et != WL_ENTROPY_SHANNON && et != WL_ENTROPY_LOGENERGY) return WL_EINVAL_ARG;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
-    if (n < 1) return WL_EDIMS;
-    if (wl_maxtransformlevels(n) == 0) return WL_EINVAL_SIZE;        // the reference fails on 2^(Lmax - 1) (entropy.jl:85)
-    int64_t last_set = -1;
-    if (!isvalidtree(n, tree, ntree, &last_set)) return WL_EINVAL_TREE;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        Taps<float> t; make_taps<float>(qmf, flen, t);
-        return bestbasis_impl<float>(ctx, st, (const float *)x, n, t, tree, ntree, et, tree_out, node_entropy);
-    }
-    Taps<double> t; make_taps<double>(qmf, flen, t);
-    return bestbasis_impl<double>(ctx, st, (const double *)x, n, t, tree, ntree, et, tree_out, node_entropy);
-}
-
-int wl_wpt_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, const double *qmf, int flen,
-                  const uint8_t *tree, int64_t ntree, int fw, void *stream)
-{
-    if (!ctx || !y || !x || !qmf || (!tree && ntree > 0)) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
-    if (n < 1) return WL_EDIMS;
-    if (y == x) return WL_EALIAS;
-    int64_t last_set = -1;
-    if (!isvalidtree(n, tree, ntree, &last_set)) return WL_EINVAL_TREE;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        Taps<float> t; make_taps<float>(qmf, flen, t);
-        return wpt_impl<float>(ctx, st, (float *)y, (const float *)x, n, &t, nullptr, tree, ntree, last_set, fw);
-    }
-    Taps<double> t; make_taps<double>(qmf, flen, t);
-    return wpt_impl<double>(ctx, st, (double *)y, (const double *)x, n, &t, nullptr, tree, ntree, last_set, fw);
-}
-
-int wl_wpt_lifting(wl_ctx *ctx, int dtype, void *y, int64_t n,
-                   int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
-                   const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2,
-                   const uint8_t *tree, int64_t ntree, int fw, void *stream)
-{
-    if (!ctx || !y || (!tree && ntree > 0)) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (n < 1) return WL_EDIMS;
-    int64_t last_set = -1;
-    if (!isvalidtree(n, tree, ntree, &last_set)) return WL_EINVAL_TREE;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        LiftScheme<float> sc;
-        int rc = make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-        if (rc) return rc;
-        return wpt_impl<float>(ctx, st, (float *)y, (const float *)y, n, nullptr, &sc, tree, ntree, last_set, fw);
-    }
-    LiftScheme<double> sc;
-    int rc = make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-    if (rc) return rc;
-    return wpt_impl<double>(ctx, st, (double *)y, (const double *)y, n, nullptr, &sc, tree, ntree, last_set, fw);
-}
-
-int wl_dwt_filter_batch(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nimages, int64_t image_stride,
-                        const double *qmf, int flen, int L, int fw, void *stream)
-{
-    if (!ctx || !y || !x || !dims || !qmf) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
-    if (dims[0] < 1 || dims[1] < 1 || nimages < 1 || image_stride < dims[0] * dims[1]) return WL_EDIMS;
-    if (L < 0) return WL_EINVAL_L;
-    if (!sufficientpoweroftwo(dims[0], L) || !sufficientpoweroftwo(dims[1], L)) return WL_EINVAL_SIZE;
-    if (y == x) return WL_EALIAS;
-    BoxSpec b;
-    b.nd = 3; b.nt = 2;
-    b.dims[0] = dims[0]; b.dims[1] = dims[1]; b.dims[2] = nimages;
-    b.full.s[0] = 1; b.full.s[1] = dims[0]; b.full.s[2] = image_stride;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    // images in groups of at most 65535 (one grid row / plane per image in the batched kernels)
-    const size_t es = dtype == WL_F32 ? 4 : 8;
-    for (int64_t i0 = 0; i0 < nimages; i0 += 65535) {
-        b.dims[2] = (nimages - i0 < 65535) ? (nimages - i0) : 65535;
-        char *yy = (char *)y + (size_t)i0 * image_stride * es;
-        const char *xx = (const char *)x + (size_t)i0 * image_stride * es;
-        int rc = dtype == WL_F32 ? dwt_filter_impl<float>(ctx, st, b, (float *)yy, (const float *)xx, qmf, flen, L, fw)
-                                 : dwt_filter_impl<double>(ctx, st, b, (double *)yy, (const double *)xx, qmf, flen, L, fw);
-        if (rc) return rc;
-    }
-    return WL_OK;
-}
-
-int wl_dwt_filter_batch3(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nvolumes, int64_t volume_stride,
-                         const double *qmf, int flen, int L, int fw, void *stream)
-{
-    if (!ctx || !y || !x || !dims || !qmf) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
-    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || nvolumes < 1 || volume_stride < dims[0] * dims[1] * dims[2]) return WL_EDIMS;
-    if (L < 0) return WL_EINVAL_L;
-    if (!sufficientpoweroftwo(dims[0], L) || !sufficientpoweroftwo(dims[1], L) || !sufficientpoweroftwo(dims[2], L)) return WL_EINVAL_SIZE;
-    if (y == x) return WL_EALIAS;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == WL_F32 ? dwt_filter_batch3_impl<float>(ctx, st, dims, nvolumes, volume_stride, (float *)y, (const float *)x, qmf, flen, L, fw)
-                           : dwt_filter_batch3_impl<double>(ctx, st, dims, nvolumes, volume_stride, (double *)y, (const double *)x, qmf, flen, L,
-                                                            fw);
-}
-
-int wl_dwt_lifting_batch(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nimages, int64_t image_stride,
-                         int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef, const int32_t *step_shift,
-                         const double *coefs_flat, double norm1, double norm2, int L, int fw, void *stream)
-{
-    if (!ctx || !y || !x || !dims) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (dims[0] != dims[1]) return WL_EINVAL_CUBE;           // the square rule comes first in the reference (transforms_lifting.jl:131-132)
-    if (dims[0] < 1 || nimages < 1 || image_stride < dims[0] * dims[1]) return WL_EDIMS;
-    if (L < 0) return WL_EINVAL_L;
-    if (!sufficientpoweroftwo(dims[0], L)) return WL_EINVAL_SIZE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        LiftScheme<float> sc;
-        int rc = make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-        if (rc) return rc;
-        WL_SCOPE(ctx);
-        return lifting_batch_impl<float>(ctx, st, (float *)y, (const float *)x, dims[0], nimages, image_stride, sc, L, fw);
-    }
-    LiftScheme<double> sc;
-    int rc = make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-    if (rc) return rc;
-    WL_SCOPE(ctx);
-    return lifting_batch_impl<double>(ctx, st, (double *)y, (const double *)x, dims[0], nimages, image_stride, sc, L, fw);
-}
-
-int wl_dwt_lifting_batch3(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nvolumes, int64_t volume_stride,
-                          int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef, const int32_t *step_shift,
-                          const double *coefs_flat, double norm1, double norm2, int L, int fw, void *stream)
-{
-    if (!ctx || !y || !x || !dims) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (dims[0] != dims[1] || dims[0] != dims[2]) return WL_EINVAL_CUBE;     // the cube rule comes first in the reference (transforms_lifting.jl:203)
-    // (a side of 2^21 or more: the volume has 2^63 elements or more, above every stride an int64 holds)
-    if (dims[0] < 1 || nvolumes < 1 || dims[0] >= ((int64_t)1 << 21) || volume_stride < dims[0] * dims[1] * dims[2]) return WL_EDIMS;
-    if (L < 0) return WL_EINVAL_L;
-    if (!sufficientpoweroftwo(dims[0], L)) return WL_EINVAL_SIZE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        LiftScheme<float> sc;
-        int rc = make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-        if (rc) return rc;
-        WL_SCOPE(ctx);
-        return wl_lifting_vols<float>(ctx, st, dims[0], nvolumes, volume_stride, (float *)y, (const float *)x, sc, L, fw);
-    }
-    LiftScheme<double> sc;
-    int rc = make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-    if (rc) return rc;
-    WL_SCOPE(ctx);
-    return wl_lifting_vols<double>(ctx, st, dims[0], nvolumes, volume_stride, (double *)y, (const double *)x, sc, L, fw);
-}
-
-int wl_wpt_filter_full(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, const double *qmf, int flen, int L, int fw, void *stream)
-{
-    if (!ctx || !y || !x || !qmf) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
-    if (n < 1) return WL_EDIMS;
-    if (y == x) return WL_EALIAS;
-    if (L < 0 || L > wl_maxtransformlevels(n)) return WL_EINVAL_L;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        Taps<float> t; make_taps<float>(qmf, flen, t);
-        return wpt_impl<float>(ctx, st, (float *)y, (const float *)x, n, &t, nullptr, nullptr, 0, -1, fw, L);
-    }
-    Taps<double> t; make_taps<double>(qmf, flen, t);
-    return wpt_impl<double>(ctx, st, (double *)y, (const double *)x, n, &t, nullptr, nullptr, 0, -1, fw, L);
-}
-
-int wl_wpt_lifting_full(wl_ctx *ctx, int dtype, void *y, int64_t n,
-                        int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
-                        const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2,
-                        int L, int fw, void *stream)
-{
-    if (!ctx || !y) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (n < 1) return WL_EDIMS;
-    if (L < 0 || L > wl_maxtransformlevels(n)) return WL_EINVAL_L;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        LiftScheme<float> sc;
-        int rc = make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-        if (rc) return rc;
-        return wpt_impl<float>(ctx, st, (float *)y, (const float *)y, n, nullptr, &sc, nullptr, 0, -1, fw, L);
-    }
-    LiftScheme<double> sc;
-    int rc = make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-    if (rc) return rc;
-    return wpt_impl<double>(ctx, st, (double *)y, (const double *)y, n, nullptr, &sc, nullptr, 0, -1, fw, L);
-}
-
-}  // extern "C"
 
 // ---- batched packet transforms (wl_wpt_*_batch) --------------------------------------------------------------------------------
-// nunits signals that share one tree, in groups of G units: all of them, at most 65535 (option WL_WPT_BATCH_GROUP lowers it: tests
-// reach the group boundary with a handful of units), halved while the work buffer of a group exceeds the context's cap
-// (WL_TI_WS_CAP_MB).  65535 is what the second grid dimension of the packet kernels takes.  A group is ONE wpt_impl call over all its units.
+// c.nunits signals of stride c.ustride in groups of G units: all of them, at most 65535 (option WL_WPT_BATCH_GROUP lowers it),
+// halved while the buffers of a group -- its work buffer and tree_bytes per unit -- exceed the context's cap (group_size).  65535
+// is what the second grid dimension of the packet kernels takes.  A group is ONE wpt_impl call over all its units.
 template <typename T>
-static int wpt_batch_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n, int64_t nunits, int64_t ustride, const Taps<T> *taps,
-                          const LiftScheme<T> *sc, const uint8_t *tree, int64_t ntree, int64_t last_set, int fw, int full_depth)
+static int wpt_batch_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, const WptCall<T> &c, size_t tree_bytes = 0)
 {
-    int64_t G = nunits < 65535 ? nunits : 65535;
-    const long long og = opt("WL_WPT_BATCH_GROUP", 0);
-    if (og >= 1 && og < G) G = og;
-    const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
-    while (G > 1 && (size_t)G * (size_t)ustride * sizeof(T) > cap) G = (G + 1) / 2;
-    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
-        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
-        int rc = wpt_impl<T>(ctx, st, y + u0 * ustride, x + u0 * ustride, n, taps, sc, tree, ntree, last_set, fw, full_depth, 0, nb, ustride);
-        if (rc != WL_OK) return rc;
-    }
-    return WL_OK;
+    const int64_t G = group_size(c.nunits, 65535, opt("WL_WPT_BATCH_GROUP", 0), true, group_cap(),
+                                 [&](int64_t g) { return (size_t)g * ((size_t)c.ustride * sizeof(T) + tree_bytes); });
+    return for_groups(c.nunits, G, [&](int64_t u0, int64_t nb) {
+        WptCall<T> g = c;
+        g.nunits = nb;
+        if (c.utrees) g.utrees = c.utrees + u0 * c.utstride;
+        return wpt_impl<T>(ctx, st, y + u0 * c.ustride, x + u0 * c.ustride, g);
+    });
 }
 
 // what the two entry points share after their pointer / dtype / wavelet rules
@@ -1330,143 +1084,20 @@ static int wpt_batch_check(int64_t n, int64_t nunits, int64_t unit_stride, const
 {
     if (n < 1 || nunits < 1 || unit_stride < n || unit_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
     if (!alias_ok && y == x) return WL_EALIAS;
-    *last_set = -1;
-    if (!tree) {
-        if (L < 0 || L > wl_maxtransformlevels(n)) return WL_EINVAL_L;
-    } else if (!isvalidtree(n, tree, ntree, last_set)) {
-        return WL_EINVAL_TREE;
-    }
-    return WL_OK;
+    return check_tree_or_depth(n, tree, ntree, L, last_set);
 }
 
-extern "C" {
-
-int wl_wpt_filter_batch(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int64_t nunits, int64_t unit_stride,
-                        const double *qmf, int flen, const uint8_t *tree, int64_t ntree, int L, int fw, void *stream)
+// the call of the entry points that take a HOST tree or, with tree == NULL, the full tree of depth L
+template <typename T>
+static WptCall<T> wpt_call(int64_t n, const Taps<T> *taps, const LiftScheme<T> *sc, const uint8_t *tree, int64_t ntree, int64_t last_set, int L,
+                           int fw)
 {
-    if (!ctx || !y || !x || !qmf) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
-    int64_t last_set = -1;
-    int rc = wpt_batch_check(n, nunits, unit_stride, y, x, false, tree, ntree, L, &last_set);
-    if (rc) return rc;
-    const int full_depth = tree ? -1 : L;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        Taps<float> t; make_taps<float>(qmf, flen, t);
-        return wpt_batch_impl<float>(ctx, st, (float *)y, (const float *)x, n, nunits, unit_stride, &t, nullptr, tree, tree ? ntree : 0, last_set, fw,
-                                     full_depth);
-    }
-    Taps<double> t; make_taps<double>(qmf, flen, t);
-    return wpt_batch_impl<double>(ctx, st, (double *)y, (const double *)x, n, nunits, unit_stride, &t, nullptr, tree, tree ? ntree : 0, last_set, fw,
-                                  full_depth);
+    WptCall<T> c;
+    c.n = n; c.taps = taps; c.sc = sc; c.fw = fw;
+    if (tree) { c.tree = tree; c.ntree = ntree; c.last_set = last_set; }
+    else c.full_depth = L;
+    return c;
 }
-
-int wl_wpt_lifting_batch(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int64_t nunits, int64_t unit_stride, int nsteps,
-                         const int32_t *step_is_update, const int32_t *step_ncoef, const int32_t *step_shift, const double *coefs_flat,
-                         double norm1, double norm2, const uint8_t *tree, int64_t ntree, int L, int fw, void *stream)
-{
-    if (!ctx || !y || !x) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    int64_t last_set = -1;
-    const int full_depth = tree ? -1 : L;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        LiftScheme<float> sc;
-        int rc = make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-        if (rc == WL_OK) rc = wpt_batch_check(n, nunits, unit_stride, y, x, true, tree, ntree, L, &last_set);
-        if (rc) return rc;
-        WL_SCOPE(ctx);
-        return wpt_batch_impl<float>(ctx, st, (float *)y, (const float *)x, n, nunits, unit_stride, nullptr, &sc, tree, tree ? ntree : 0, last_set, fw,
-                                     full_depth);
-    }
-    LiftScheme<double> sc;
-    int rc = make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-    if (rc == WL_OK) rc = wpt_batch_check(n, nunits, unit_stride, y, x, true, tree, ntree, L, &last_set);
-    if (rc) return rc;
-    WL_SCOPE(ctx);
-    return wpt_batch_impl<double>(ctx, st, (double *)y, (const double *)x, n, nunits, unit_stride, nullptr, &sc, tree, tree ? ntree : 0, last_set, fw,
-                                  full_depth);
-}
-
-}  // extern "C"
-
-// ---- per-unit trees: the batched best-basis search and the packet transforms that take its result (DESIGN.md section 15) --------
-extern "C" {
-
-int wl_bestbasistree_filter_batch(wl_ctx *ctx, int dtype, const void *x, int64_t n, int64_t nunits, int64_t unit_stride, const double *qmf,
-                                  int flen, const uint8_t *tree, int64_t ntree, int L, int et, uint8_t *trees_out, int64_t tree_stride,
-                                  double *node_entropy, int64_t entropy_stride, void *stream)
-{
-    if (!ctx || !x || !qmf || !trees_out) return WL_EINVAL_ARG;
-    if (et != WL_ENTROPY_SHANNON && et != WL_ENTROPY_LOGENERGY) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
-    if (n < 1 || nunits < 1 || unit_stride < n || unit_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
-    const int Lmax = wl_maxtransformlevels(n);
-    const int64_t nt = ((int64_t)1 << Lmax) - 1;
-    if (tree_stride < nt || tree_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
-    if (node_entropy && Lmax > 0 && (entropy_stride < nt + ((int64_t)1 << (Lmax - 1)) || entropy_stride >= ((int64_t)1 << 58) / nunits))
-        return WL_EDIMS;
-    if (Lmax == 0) return WL_EINVAL_SIZE;                                // the reference fails on 2^(Lmax - 1) (entropy.jl:85)
-    int64_t last_set = -1;
-    if (!tree) {
-        if (L < 0 || L > Lmax) return WL_EINVAL_L;
-    } else if (!isvalidtree(n, tree, ntree, &last_set)) {
-        return WL_EINVAL_TREE;
-    }
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        Taps<float> t; make_taps<float>(qmf, flen, t);
-        return bestbasis_batch_impl<float>(ctx, st, (const float *)x, n, nunits, unit_stride, t, tree, L, et, trees_out, tree_stride, node_entropy,
-                                           entropy_stride);
-    }
-    Taps<double> t; make_taps<double>(qmf, flen, t);
-    return bestbasis_batch_impl<double>(ctx, st, (const double *)x, n, nunits, unit_stride, t, tree, L, et, trees_out, tree_stride, node_entropy,
-                                        entropy_stride);
-}
-
-int wl_wpt_filter_batch_trees(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int64_t nunits, int64_t unit_stride, const double *qmf,
-                              int flen, const uint8_t *trees, int64_t tree_stride, int L, int fw, void *stream)
-{
-    if (!ctx || !y || !x || !qmf || !trees) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
-    if (n < 1 || nunits < 1 || unit_stride < n || unit_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
-    const int Lmax = wl_maxtransformlevels(n);
-    if (tree_stride < ((int64_t)1 << Lmax) - 1 || tree_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
-    if (y == x) return WL_EALIAS;
-    if (L < 0 || L > Lmax) return WL_EINVAL_L;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    // groups as wpt_batch_impl; the closed trees of a group (G (2^L - 1) bytes) ride on top of its work buffer
-    int64_t G = nunits < 65535 ? nunits : 65535;
-    const long long og = opt("WL_WPT_BATCH_GROUP", 0);
-    if (og >= 1 && og < G) G = og;
-    const size_t es = dtype == WL_F32 ? 4 : 8;
-    const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
-    while (G > 1 && (size_t)G * ((size_t)unit_stride * es + (((size_t)1 << L) - 1)) > cap) G = (G + 1) / 2;
-    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
-        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
-        const uint8_t *tr = trees + u0 * tree_stride;
-        int rc;
-        if (dtype == WL_F32) {
-            Taps<float> t; make_taps<float>(qmf, flen, t);
-            rc = wpt_impl<float>(ctx, st, (float *)y + u0 * unit_stride, (const float *)x + u0 * unit_stride, n, &t, nullptr, nullptr, 0, -1, fw, -1, 0,
-                                 nb, unit_stride, tr, tree_stride, L);
-        } else {
-            Taps<double> t; make_taps<double>(qmf, flen, t);
-            rc = wpt_impl<double>(ctx, st, (double *)y + u0 * unit_stride, (const double *)x + u0 * unit_stride, n, &t, nullptr, nullptr, 0, -1, fw, -1,
-                                  0, nb, unit_stride, tr, tree_stride, L);
-        }
-        if (rc != WL_OK) return rc;
-    }
-    return WL_OK;
-}
-
-}  // extern "C"
 
 // ---- complex-valued transforms (wl_*_complex) ----------------------------------------------------------------------------------
 // Complex{T} data is (re, im) interleaved and the taps are real: re(y) = transform(re(x)), im(y) = transform(im(x)).  A group of G
@@ -1485,35 +1116,7 @@ inline int64_t plane_stride_of(int64_t N)
     return (N + E - 1) / E * E;
 }
 
-// units per group: all of them, halved until need(G) fits under the context's cap (the cap of wl_denoise_batch_*), at most 32767
-// (2 G planes: a grid row / plane / workgroup per plane in the batched kernels); then the workspace is grown once
-template <typename F>
-int complex_group(wl_ctx *ctx, hipStream_t st, int64_t nunits, F need, int64_t &G)
-{
-    const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
-    G = nunits;
-    while (G > 1 && need(G) > cap) G = (G + 1) / 2;
-    if (G > 32767) G = 32767;
-    int rc = ensure_ws(ctx, need(G), st);
-    while (rc == WL_ENOMEM && G > 1) {                      // (another allocator may own most of the HBM: smaller groups)
-        G = (G + 1) / 2;
-        rc = ensure_ws(ctx, need(G), st);
-    }
-    return rc;
-}
-
-// L = 0: the units are copied (a 2 N x nunits real matrix with leading dimension 2 S); the padding between units is not touched
-template <typename T>
-int complex_copy_units(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t N, int64_t nunits, int64_t S)
-{
-    const Strides3 s = {{1, 2 * S, 0}};
-    for (int64_t i0 = 0; i0 < nunits && y != x; i0 += 65535) {
-        const Extent3 ext = {{2 * N, (nunits - i0 < 65535) ? (nunits - i0) : 65535, 1}};
-        WL_HIP(ctx, generic_copy_box<T>(st, x + 2 * i0 * S, s, y + 2 * i0 * S, s, ext));
-    }
-    ctx->last_kernel = "copy";
-    return WL_OK;
-}
+// (groups: group_reserve with a limit of 32767 units -- 2 G planes, a grid row / plane / workgroup per plane in the batched kernels)
 
 // the box of np real planes of stride ps as the batched real entry points describe it: lines (wl_dwtc_*) or images (wl_dwt_*_batch)
 inline BoxSpec planes_box(int ndims, const int64_t *dims, int64_t np, int64_t ps)
@@ -1531,21 +1134,19 @@ int dwt_filter_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
 {
     int64_t N = 1;
     for (int d = 0; d < ndims; ++d) N *= dims[d];
-    if (L == 0) return complex_copy_units<T>(ctx, st, y, x, N, nunits, S);
+    if (L == 0) return copy_units<T>(ctx, st, y, x, 2 * N, y != x ? nunits : 0, 2 * S);      // (a unit: 2 N reals)
     const int64_t ps = plane_stride_of<T>(N);
-    Taps<T> taps;
-    make_taps<T>(qmf, flen, taps);
+    const Taps<T> taps = taps_of<T>(qmf, flen);
     auto tw_bytes = [&](int64_t G) { return up256((ndims == 3 ? ws_vols_elems(N, 2 * G) : ws_elems(N * 2 * G, ndims)) * sizeof(T)); };
     auto pl_bytes = [&](int64_t G) { return up256((size_t)(2 * G * ps) * sizeof(T)); };
     auto need = [&](int64_t G) { return tw_bytes(G) + 2 * pl_bytes(G); };
     int64_t G = 1;
-    int rc = complex_group(ctx, st, nunits, need, G);
+    int rc = group_reserve(ctx, st, nunits, 32767, need, G);
     if (rc != WL_OK) return rc;
     char *wsb = (char *)ctx->ws;
     T *P = (T *)(wsb + tw_bytes(G)), *Q = (T *)(wsb + tw_bytes(G) + pl_bytes(G));
     const char *kn = ctx->last_kernel;
-    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
-        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
+    WL_TRY(for_groups(nunits, G, [&](int64_t u0, int64_t nb) -> int {
         WL_HIP(ctx, complex_split<T>(st, ctx->cu_count, P, ps, x + 2 * u0 * S, N, nb, S));
         if (ndims == 3) {
             rc = fw ? filter_fwd_levels_vols<T>(wsb, true, ctx->cu_count, ctx->path, st, dims, 2 * nb, ps, ps, Q, P, taps, L, &kn, &ctx->last_hip)
@@ -1558,7 +1159,8 @@ int dwt_filter_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
         if (rc == WL_RETRY_GEN) rc = WL_EINVAL_ARG;          // (the full workspace is held: no level can ask for more)
         if (rc != WL_OK) return rc;
         WL_HIP(ctx, complex_merge<T>(st, ctx->cu_count, y + 2 * u0 * S, Q, ps, N, nb, S));
-    }
+        return WL_OK;
+    }));
     ctx->last_kernel = kn;
     return WL_OK;
 }
@@ -1569,7 +1171,7 @@ int dwt_lifting_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int 
 {
     int64_t N = 1;
     for (int d = 0; d < ndims; ++d) N *= dims[d];
-    if (L == 0) return complex_copy_units<T>(ctx, st, y, x, N, nunits, S);
+    if (L == 0) return copy_units<T>(ctx, st, y, x, 2 * N, y != x ? nunits : 0, 2 * S);      // (a unit: 2 N reals)
     const int64_t ps = plane_stride_of<T>(N);
     // the lifting workspace of the planes of a group, as wl_denoise_batch_lifting sizes it (the loops below ask for no more)
     auto tw_bytes = [&](int64_t G) -> size_t {
@@ -1579,20 +1181,19 @@ int dwt_lifting_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int 
     };
     auto need = [&](int64_t G) { return tw_bytes(G) + up256((size_t)(2 * G * ps) * sizeof(T)); };
     int64_t G = 1;
-    int rc = complex_group(ctx, st, nunits, need, G);
+    int rc = group_reserve(ctx, st, nunits, 32767, need, G);
     if (rc != WL_OK) return rc;
     const void *held = ctx->ws;
     T *P = (T *)((char *)ctx->ws + tw_bytes(G));
-    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
-        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
+    return for_groups(nunits, G, [&](int64_t u0, int64_t nb) -> int {
         WL_HIP(ctx, complex_split<T>(st, ctx->cu_count, P, ps, x + 2 * u0 * S, N, nb, S));
         rc = ndims == 3 ? wl_lifting_vols<T>(ctx, st, dims[0], 2 * nb, ps, P, P, sc, L, fw)
                         : wl_lifting_box<T>(ctx, st, planes_box(ndims, dims, 2 * nb, ps), P, P, sc, L, fw);
         if (rc != WL_OK) return rc;
         if (ctx->ws != held) return WL_ENOMEM;               // (a loop that outgrew the reservation would have moved P: not reached)
         WL_HIP(ctx, complex_merge<T>(st, ctx->cu_count, y + 2 * u0 * S, P, ps, N, nb, S));
-    }
-    return WL_OK;
+        return WL_OK;
+    });
 }
 
 // the argument contract the two complex dwt entry points share after their pointer / dtype / wavelet rules (the order of the real
@@ -1619,17 +1220,17 @@ int complex_check(int ndims, const int64_t *dims, int64_t nunits, int64_t unit_s
 // one complex signal through the packet transform: split, wpt_impl on the two planes as one batch of two units of stride ps
 // (filters: P -> Q; lifting: in place on P), merge
 template <typename T>
-int wpt_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n, const Taps<T> *taps, const LiftScheme<T> *sc,
-                     const uint8_t *tree, int64_t ntree, int64_t last_set, int fw, int full_depth)
+int wpt_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, WptCall<T> c)
 {
-    const int64_t ps = plane_stride_of<T>(n);
-    const size_t inner = up256(ws_elems(2 * ps) * sizeof(T) + (size_t)(tree ? ntree : 0) + 256), pl = up256((size_t)(2 * ps) * sizeof(T));
-    int rc = ensure_ws(ctx, inner + (taps ? 2 : 1) * pl, st);
+    const int64_t n = c.n, ps = plane_stride_of<T>(n);
+    const size_t inner = up256(ws_elems(2 * ps) * sizeof(T) + (size_t)c.ntree + 256), pl = up256((size_t)(2 * ps) * sizeof(T));
+    int rc = ensure_ws(ctx, inner + (c.taps ? 2 : 1) * pl, st);
     if (rc != WL_OK) return rc;
     const void *held = ctx->ws;
-    T *P = (T *)((char *)ctx->ws + inner), *Q = taps ? (T *)((char *)ctx->ws + inner + pl) : P;
+    T *P = (T *)((char *)ctx->ws + inner), *Q = c.taps ? (T *)((char *)ctx->ws + inner + pl) : P;
     WL_HIP(ctx, complex_split<T>(st, ctx->cu_count, P, ps, x, n, 1, n));
-    rc = wpt_impl<T>(ctx, st, Q, P, n, taps, sc, tree, ntree, last_set, fw, full_depth, 0, 2, ps);
+    c.nunits = 2; c.ustride = ps;
+    rc = wpt_impl<T>(ctx, st, Q, P, c);
     if (rc != WL_OK) return rc;
     if (ctx->ws != held) return WL_ENOMEM;                   // (not reached: wpt_impl asks for no more than `inner`)
     WL_HIP(ctx, complex_merge<T>(st, ctx->cu_count, y, Q, ps, n, 1, n));
@@ -1638,124 +1239,361 @@ int wpt_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int64_t n, c
 
 }  // namespace
 
+// ==========================================================================================
 extern "C" {
 
+int wl_bestbasistree_filter(wl_ctx *ctx, int dtype, const void *x, int64_t n, const double *qmf, int flen, const uint8_t *tree,
+                            int64_t ntree, int et, uint8_t *tree_out, double *node_entropy, void *stream)
+{
+    if (!ctx || !x || !qmf || !tree || !tree_out) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    if (et != WL_ENTROPY_SHANNON && et != WL_ENTROPY_LOGENERGY) return WL_EINVAL_ARG;
+    WL_TRY(check_flen(flen));
+    if (n < 1) return WL_EDIMS;
+    if (wl_maxtransformlevels(n) == 0) return WL_EINVAL_SIZE;        // the reference fails on 2^(Lmax - 1) (entropy.jl:85)
+    int64_t last_set = -1;
+    if (!isvalidtree(n, tree, ntree, &last_set)) return WL_EINVAL_TREE;
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return bestbasis_impl<T>(ctx, st, (const T *)x, n, taps_of<T>(qmf, flen), tree, ntree, et, tree_out, node_entropy);
+    });
+}
+
+int wl_wpt_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, const double *qmf, int flen,
+                  const uint8_t *tree, int64_t ntree, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !qmf || (!tree && ntree > 0)) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen));
+    if (n < 1) return WL_EDIMS;
+    if (y == x) return WL_EALIAS;
+    int64_t last_set = -1;
+    if (!isvalidtree(n, tree, ntree, &last_set)) return WL_EINVAL_TREE;
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        const Taps<T> taps = taps_of<T>(qmf, flen);
+        WptCall<T> c;
+        c.n = n; c.taps = &taps; c.fw = fw;
+        c.tree = tree; c.ntree = ntree; c.last_set = last_set;
+        return wpt_impl<T>(ctx, st, (T *)y, (const T *)x, c);
+    });
+}
+
+int wl_wpt_lifting(wl_ctx *ctx, int dtype, void *y, int64_t n,
+                   int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
+                   const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2,
+                   const uint8_t *tree, int64_t ntree, int fw, void *stream)
+{
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
+    if (!ctx || !y || (!tree && ntree > 0)) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    if (n < 1) return WL_EDIMS;
+    int64_t last_set = -1;
+    if (!isvalidtree(n, tree, ntree, &last_set)) return WL_EINVAL_TREE;
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        WL_TRY(s.check());
+        const LiftScheme<T> sc = s.build<T>(fw);
+        WptCall<T> c;
+        c.n = n; c.sc = &sc; c.fw = fw;
+        c.tree = tree; c.ntree = ntree; c.last_set = last_set;
+        return wpt_impl<T>(ctx, st, (T *)y, (const T *)y, c);
+    });
+}
+
+int wl_dwt_filter_batch(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nimages, int64_t image_stride,
+                        const double *qmf, int flen, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !dims || !qmf) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen));
+    if (dims[0] < 1 || dims[1] < 1 || nimages < 1 || image_stride < dims[0] * dims[1]) return WL_EDIMS;
+    if (L < 0) return WL_EINVAL_L;
+    if (!sufficientpoweroftwo(dims[0], L) || !sufficientpoweroftwo(dims[1], L)) return WL_EINVAL_SIZE;
+    if (y == x) return WL_EALIAS;
+    BoxSpec b;
+    b.nd = 3; b.nt = 2;
+    b.dims[0] = dims[0]; b.dims[1] = dims[1]; b.dims[2] = nimages;
+    b.full.s[0] = 1; b.full.s[1] = dims[0]; b.full.s[2] = image_stride;
+    // images in groups of at most 65535 (one grid row / plane per image in the batched kernels)
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return for_groups(nimages, 65535, [&](int64_t i0, int64_t ni) {
+            b.dims[2] = ni;
+            return dwt_filter_impl<T>(ctx, st, b, (T *)y + i0 * image_stride, (const T *)x + i0 * image_stride, qmf, flen, L, fw);
+        });
+    });
+}
+
+int wl_dwt_filter_batch3(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nvolumes, int64_t volume_stride,
+                         const double *qmf, int flen, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !dims || !qmf) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen));
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || nvolumes < 1 || volume_stride < dims[0] * dims[1] * dims[2]) return WL_EDIMS;
+    if (L < 0) return WL_EINVAL_L;
+    if (!sufficientpoweroftwo(dims[0], L) || !sufficientpoweroftwo(dims[1], L) || !sufficientpoweroftwo(dims[2], L)) return WL_EINVAL_SIZE;
+    if (y == x) return WL_EALIAS;
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return dwt_filter_batch3_impl<T>(ctx, st, dims, nvolumes, volume_stride, (T *)y, (const T *)x, qmf, flen, L, fw);
+    });
+}
+
+int wl_dwt_lifting_batch(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nimages, int64_t image_stride,
+                         int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef, const int32_t *step_shift,
+                         const double *coefs_flat, double norm1, double norm2, int L, int fw, void *stream)
+{
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
+    if (!ctx || !y || !x || !dims) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    if (dims[0] != dims[1]) return WL_EINVAL_CUBE;           // the square rule comes first in the reference (transforms_lifting.jl:131-132)
+    if (dims[0] < 1 || nimages < 1 || image_stride < dims[0] * dims[1]) return WL_EDIMS;
+    if (L < 0) return WL_EINVAL_L;
+    if (!sufficientpoweroftwo(dims[0], L)) return WL_EINVAL_SIZE;
+    WL_TRY(s.check());
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        const LiftScheme<T> sc = s.build<T>(fw);
+        return lifting_batch_impl<T>(ctx, st, (T *)y, (const T *)x, dims[0], nimages, image_stride, sc, L, fw);
+    });
+}
+
+int wl_dwt_lifting_batch3(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims, int64_t nvolumes, int64_t volume_stride,
+                          int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef, const int32_t *step_shift,
+                          const double *coefs_flat, double norm1, double norm2, int L, int fw, void *stream)
+{
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
+    if (!ctx || !y || !x || !dims) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    if (dims[0] != dims[1] || dims[0] != dims[2]) return WL_EINVAL_CUBE;     // the cube rule comes first in the reference (transforms_lifting.jl:203)
+    // (a side of 2^21 or more: the volume has 2^63 elements or more, above every stride an int64 holds)
+    if (dims[0] < 1 || nvolumes < 1 || dims[0] >= ((int64_t)1 << 21) || volume_stride < dims[0] * dims[1] * dims[2]) return WL_EDIMS;
+    if (L < 0) return WL_EINVAL_L;
+    if (!sufficientpoweroftwo(dims[0], L)) return WL_EINVAL_SIZE;
+    WL_TRY(s.check());
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        const LiftScheme<T> sc = s.build<T>(fw);
+        return wl_lifting_vols<T>(ctx, st, dims[0], nvolumes, volume_stride, (T *)y, (const T *)x, sc, L, fw);
+    });
+}
+
+int wl_wpt_filter_full(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, const double *qmf, int flen, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !qmf) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen));
+    if (n < 1) return WL_EDIMS;
+    if (y == x) return WL_EALIAS;
+    if (L < 0 || L > wl_maxtransformlevels(n)) return WL_EINVAL_L;
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        const Taps<T> taps = taps_of<T>(qmf, flen);
+        WptCall<T> c;
+        c.n = n; c.taps = &taps; c.fw = fw;
+        c.full_depth = L;
+        return wpt_impl<T>(ctx, st, (T *)y, (const T *)x, c);
+    });
+}
+
+int wl_wpt_lifting_full(wl_ctx *ctx, int dtype, void *y, int64_t n,
+                        int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
+                        const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2,
+                        int L, int fw, void *stream)
+{
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
+    if (!ctx || !y) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    if (n < 1) return WL_EDIMS;
+    if (L < 0 || L > wl_maxtransformlevels(n)) return WL_EINVAL_L;
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        WL_TRY(s.check());
+        const LiftScheme<T> sc = s.build<T>(fw);
+        WptCall<T> c;
+        c.n = n; c.sc = &sc; c.fw = fw;
+        c.full_depth = L;
+        return wpt_impl<T>(ctx, st, (T *)y, (const T *)y, c);
+    });
+}
+
+// ---- batched packet transforms ---------------------------------------------------------------------------------------------------
+int wl_wpt_filter_batch(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int64_t nunits, int64_t unit_stride,
+                        const double *qmf, int flen, const uint8_t *tree, int64_t ntree, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !qmf) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen));
+    int64_t last_set = -1;
+    WL_TRY(wpt_batch_check(n, nunits, unit_stride, y, x, false, tree, ntree, L, &last_set));
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        const Taps<T> taps = taps_of<T>(qmf, flen);
+        WptCall<T> c = wpt_call<T>(n, &taps, nullptr, tree, ntree, last_set, L, fw);
+        c.nunits = nunits; c.ustride = unit_stride;
+        return wpt_batch_impl<T>(ctx, st, (T *)y, (const T *)x, c);
+    });
+}
+
+int wl_wpt_lifting_batch(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int64_t nunits, int64_t unit_stride, int nsteps,
+                         const int32_t *step_is_update, const int32_t *step_ncoef, const int32_t *step_shift, const double *coefs_flat,
+                         double norm1, double norm2, const uint8_t *tree, int64_t ntree, int L, int fw, void *stream)
+{
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
+    if (!ctx || !y || !x) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(s.check());
+    int64_t last_set = -1;
+    WL_TRY(wpt_batch_check(n, nunits, unit_stride, y, x, true, tree, ntree, L, &last_set));
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        const LiftScheme<T> sc = s.build<T>(fw);
+        WptCall<T> c = wpt_call<T>(n, nullptr, &sc, tree, ntree, last_set, L, fw);
+        c.nunits = nunits; c.ustride = unit_stride;
+        return wpt_batch_impl<T>(ctx, st, (T *)y, (const T *)x, c);
+    });
+}
+
+// ---- per-unit trees: the batched best-basis search and the packet transforms that take its result (DESIGN.md section 15) --------
+int wl_bestbasistree_filter_batch(wl_ctx *ctx, int dtype, const void *x, int64_t n, int64_t nunits, int64_t unit_stride, const double *qmf,
+                                  int flen, const uint8_t *tree, int64_t ntree, int L, int et, uint8_t *trees_out, int64_t tree_stride,
+                                  double *node_entropy, int64_t entropy_stride, void *stream)
+{
+    if (!ctx || !x || !qmf || !trees_out) return WL_EINVAL_ARG;
+    if (et != WL_ENTROPY_SHANNON && et != WL_ENTROPY_LOGENERGY) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen));
+    if (n < 1 || nunits < 1 || unit_stride < n || unit_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
+    const int Lmax = wl_maxtransformlevels(n);
+    const int64_t nt = ((int64_t)1 << Lmax) - 1;
+    if (tree_stride < nt || tree_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
+    if (node_entropy && Lmax > 0 && (entropy_stride < nt + ((int64_t)1 << (Lmax - 1)) || entropy_stride >= ((int64_t)1 << 58) / nunits))
+        return WL_EDIMS;
+    if (Lmax == 0) return WL_EINVAL_SIZE;                                // the reference fails on 2^(Lmax - 1) (entropy.jl:85)
+    int64_t last_set = -1;
+    WL_TRY(check_tree_or_depth(n, tree, ntree, L, &last_set));
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return bestbasis_batch_impl<T>(ctx, st, (const T *)x, n, nunits, unit_stride, taps_of<T>(qmf, flen), tree, L, et, trees_out, tree_stride,
+                                       node_entropy, entropy_stride);
+    });
+}
+
+int wl_wpt_filter_batch_trees(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int64_t nunits, int64_t unit_stride, const double *qmf,
+                              int flen, const uint8_t *trees, int64_t tree_stride, int L, int fw, void *stream)
+{
+    if (!ctx || !y || !x || !qmf || !trees) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen));
+    if (n < 1 || nunits < 1 || unit_stride < n || unit_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
+    const int Lmax = wl_maxtransformlevels(n);
+    if (tree_stride < ((int64_t)1 << Lmax) - 1 || tree_stride >= ((int64_t)1 << 61) / nunits) return WL_EDIMS;
+    if (y == x) return WL_EALIAS;
+    if (L < 0 || L > Lmax) return WL_EINVAL_L;
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        const Taps<T> taps = taps_of<T>(qmf, flen);
+        WptCall<T> c;
+        c.n = n; c.taps = &taps; c.fw = fw;
+        c.nunits = nunits; c.ustride = unit_stride;
+        c.utrees = trees; c.utstride = tree_stride; c.utL = L;
+        // the closed trees of a group (G (2^L - 1) bytes) ride on top of its work buffer
+        return wpt_batch_impl<T>(ctx, st, (T *)y, (const T *)x, c, ((size_t)1 << L) - 1);
+    });
+}
+
+// ---- complex-valued transforms ---------------------------------------------------------------------------------------------------
 int wl_complex_split(wl_ctx *ctx, int dtype, void *planes, int64_t plane_stride, const void *z, int64_t n, int64_t nunits,
                      int64_t unit_stride, void *stream)
 {
     if (!ctx || !planes || !z) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    WL_TRY(check_dtype(dtype));
     if (n < 1 || nunits < 1 || unit_stride < n || plane_stride < n) return WL_EDIMS;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    WL_HIP(ctx, dtype == WL_F32 ? complex_split<float>(st, ctx->cu_count, (float *)planes, plane_stride, (const float *)z, n, nunits, unit_stride)
-                                : complex_split<double>(st, ctx->cu_count, (double *)planes, plane_stride, (const double *)z, n, nunits, unit_stride));
-    return WL_OK;
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) -> int {
+        using T = decltype(t);
+        WL_HIP(ctx, complex_split<T>(st, ctx->cu_count, (T *)planes, plane_stride, (const T *)z, n, nunits, unit_stride));
+        return WL_OK;
+    });
 }
 
 int wl_complex_merge(wl_ctx *ctx, int dtype, void *z, const void *planes, int64_t plane_stride, int64_t n, int64_t nunits,
                      int64_t unit_stride, void *stream)
 {
     if (!ctx || !planes || !z) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    WL_TRY(check_dtype(dtype));
     if (n < 1 || nunits < 1 || unit_stride < n || plane_stride < n) return WL_EDIMS;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    WL_HIP(ctx, dtype == WL_F32 ? complex_merge<float>(st, ctx->cu_count, (float *)z, (const float *)planes, plane_stride, n, nunits, unit_stride)
-                                : complex_merge<double>(st, ctx->cu_count, (double *)z, (const double *)planes, plane_stride, n, nunits, unit_stride));
-    return WL_OK;
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) -> int {
+        using T = decltype(t);
+        WL_HIP(ctx, complex_merge<T>(st, ctx->cu_count, (T *)z, (const T *)planes, plane_stride, n, nunits, unit_stride));
+        return WL_OK;
+    });
 }
 
 int wl_dwt_filter_complex(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, int64_t nunits,
                           int64_t unit_stride, const double *qmf, int flen, int L, int fw, void *stream)
 {
     if (!ctx || !y || !x || !dims || !qmf) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
-    int rc = complex_check(ndims, dims, nunits, unit_stride, L, false);
-    if (rc) return rc;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen));
+    WL_TRY(complex_check(ndims, dims, nunits, unit_stride, L, false));
     if (y == x) return WL_EALIAS;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == WL_F32
-               ? dwt_filter_complex_impl<float>(ctx, st, (float *)y, (const float *)x, ndims, dims, nunits, unit_stride, qmf, flen, L, fw)
-               : dwt_filter_complex_impl<double>(ctx, st, (double *)y, (const double *)x, ndims, dims, nunits, unit_stride, qmf, flen, L, fw);
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return dwt_filter_complex_impl<T>(ctx, st, (T *)y, (const T *)x, ndims, dims, nunits, unit_stride, qmf, flen, L, fw);
+    });
 }
 
 int wl_dwt_lifting_complex(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, int64_t nunits,
                            int64_t unit_stride, int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
                            const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2, int L, int fw, void *stream)
 {
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
     if (!ctx || !y || !x || !dims) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        LiftScheme<float> sc;
-        int rc = make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-        if (rc == WL_OK) rc = complex_check(ndims, dims, nunits, unit_stride, L, true);
-        if (rc) return rc;
-        WL_SCOPE(ctx);
-        return dwt_lifting_complex_impl<float>(ctx, st, (float *)y, (const float *)x, ndims, dims, nunits, unit_stride, sc, L, fw);
-    }
-    LiftScheme<double> sc;
-    int rc = make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-    if (rc == WL_OK) rc = complex_check(ndims, dims, nunits, unit_stride, L, true);
-    if (rc) return rc;
-    WL_SCOPE(ctx);
-    return dwt_lifting_complex_impl<double>(ctx, st, (double *)y, (const double *)x, ndims, dims, nunits, unit_stride, sc, L, fw);
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(s.check());
+    WL_TRY(complex_check(ndims, dims, nunits, unit_stride, L, true));
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        const LiftScheme<T> sc = s.build<T>(fw);
+        return dwt_lifting_complex_impl<T>(ctx, st, (T *)y, (const T *)x, ndims, dims, nunits, unit_stride, sc, L, fw);
+    });
 }
 
 int wl_wpt_filter_complex(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, const double *qmf, int flen, const uint8_t *tree,
                           int64_t ntree, int L, int fw, void *stream)
 {
     if (!ctx || !y || !x || !qmf) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen));
     if (n < 1 || n >= ((int64_t)1 << 61)) return WL_EDIMS;
     if (y == x) return WL_EALIAS;
     int64_t last_set = -1;
-    if (!tree) {
-        if (L < 0 || L > wl_maxtransformlevels(n)) return WL_EINVAL_L;
-    } else if (!isvalidtree(n, tree, ntree, &last_set)) {
-        return WL_EINVAL_TREE;
-    }
-    const int full_depth = tree ? -1 : L;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        Taps<float> t; make_taps<float>(qmf, flen, t);
-        return wpt_complex_impl<float>(ctx, st, (float *)y, (const float *)x, n, &t, nullptr, tree, tree ? ntree : 0, last_set, fw, full_depth);
-    }
-    Taps<double> t; make_taps<double>(qmf, flen, t);
-    return wpt_complex_impl<double>(ctx, st, (double *)y, (const double *)x, n, &t, nullptr, tree, tree ? ntree : 0, last_set, fw, full_depth);
+    WL_TRY(check_tree_or_depth(n, tree, ntree, L, &last_set));
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        const Taps<T> taps = taps_of<T>(qmf, flen);
+        return wpt_complex_impl<T>(ctx, st, (T *)y, (const T *)x, wpt_call<T>(n, &taps, nullptr, tree, ntree, last_set, L, fw));
+    });
 }
 
 int wl_wpt_lifting_complex(wl_ctx *ctx, int dtype, void *y, const void *x, int64_t n, int nsteps, const int32_t *step_is_update,
                            const int32_t *step_ncoef, const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2,
                            const uint8_t *tree, int64_t ntree, int L, int fw, void *stream)
 {
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
     if (!ctx || !y || !x) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    WL_TRY(check_dtype(dtype));
     if (n < 1 || n >= ((int64_t)1 << 61)) return WL_EDIMS;
     int64_t last_set = -1;
-    if (!tree) {
-        if (L < 0 || L > wl_maxtransformlevels(n)) return WL_EINVAL_L;
-    } else if (!isvalidtree(n, tree, ntree, &last_set)) {
-        return WL_EINVAL_TREE;
-    }
-    const int full_depth = tree ? -1 : L;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        LiftScheme<float> sc;
-        int rc = make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-        if (rc) return rc;
-        return wpt_complex_impl<float>(ctx, st, (float *)y, (const float *)x, n, nullptr, &sc, tree, tree ? ntree : 0, last_set, fw, full_depth);
-    }
-    LiftScheme<double> sc;
-    int rc = make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, fw, sc);
-    if (rc) return rc;
-    return wpt_complex_impl<double>(ctx, st, (double *)y, (const double *)x, n, nullptr, &sc, tree, tree ? ntree : 0, last_set, fw, full_depth);
+    WL_TRY(check_tree_or_depth(n, tree, ntree, L, &last_set));
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        WL_TRY(s.check());
+        const LiftScheme<T> sc = s.build<T>(fw);
+        return wpt_complex_impl<T>(ctx, st, (T *)y, (const T *)x, wpt_call<T>(n, nullptr, &sc, tree, ntree, last_set, L, fw));
+    });
 }
 
 }  // extern "C"

@@ -74,12 +74,9 @@ inline int hip_fail(wl_ctx *ctx, hipError_t e)
 // synchronisation (wl_ctx_reserve)
 int wl_ensure_ws(wl_ctx *ctx, size_t bytes, hipStream_t st = nullptr, bool ordered = false);
 
-// lifting transform of a box with a direction-adjusted scheme / makescheme (wl_api.hip; used by wl_ext.hip)
+// lifting transform of a box with a direction-adjusted scheme (wl_api.hip; used by wl_ext.hip)
 template <typename T>
 int wl_lifting_box(wl_ctx *ctx, hipStream_t st, const wl::BoxSpec &b, T *y, const T *x, const wl::LiftScheme<T> &sc, int L, int fw);
 // ... of a batch of cubes of side n, cube i at element offset i * vs of x and of y (the batched 3-D level loop where it is eligible)
 template <typename T>
 int wl_lifting_vols(wl_ctx *ctx, hipStream_t st, int64_t n, int64_t nvol, int64_t vs, T *y, const T *x, const wl::LiftScheme<T> &sc, int L, int fw);
-template <typename T>
-int wl_make_scheme(int nsteps, const int32_t *is_update, const int32_t *ncoef, const int32_t *shift, const double *coefs, double norm1,
-                   double norm2, int fw, wl::LiftScheme<T> &sc);

@@ -6,7 +6,7 @@
 // All of it is HBM-bound element-wise or gather work; the arithmetic follows Julia's promotion rules
 // literally (Float32 data with Float64 taps / threshold: compute in Float64, round on every store) so the
 // results are bit-identical to the reference loops.
-#include "wl_ctx.h"
+#include "wl_entry.h"
 #include "wl_fast.h"
 #include "wl_dev.h"
 
@@ -898,18 +898,11 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
                fwd2d_lds_ok(flen, 1, n0, n1) && (n0 % 4) == 0 && nsp1 <= n1 && nsp0 <= n0 && nsp0 < (1 << 20);
     }
     const size_t zr_elems = virt ? (size_t)N * (size_t)nsp0 : 0;
-    const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
     // (one spin: no shifted copy Z, see below)
     const size_t ncopies = (pns == 1) ? 1 : 2;
     auto need = [&](int64_t B) { return (tw_elems(B) + ncopies * (size_t)N * B + zr_elems + (size_t)n0 + 64) * sizeof(T); };
-    int64_t B = pns;
-    while (B > 1 && need(B) > cap) B = (B + 1) / 2;
-    if (B > 65535) B = 65535;
-    rc = wl_ensure_ws(ctx, need(B), st, true);
-    while (rc == WL_ENOMEM && B > 1) {                      // (another allocator may own most of the HBM: smaller groups of spins)
-        B = (B + 1) / 2;
-        rc = wl_ensure_ws(ctx, need(B), st, true);
-    }
+    int64_t B = 1;
+    rc = group_reserve(ctx, st, pns, 65535, need, B);
     if (rc != WL_OK) return rc;
     T *tw = (T *)ctx->ws;                                   // transform workspace of the batch box (with the generic buffers)
     T *Z = tw + tw_elems(B);
@@ -1057,15 +1050,15 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
 // of shifted CUBES one batched 3-D lifting transform (wl_lifting_vols, as wl_dwt_lifting_batch3; a scheme of no known shape runs
 // cube after cube inside it).
 template <typename T>
-int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, const LiftScheme<T> &scf,
-                            const LiftScheme<T> &sci, int L, int th, double t_unit, const int64_t *nspin, double sigma_host)
+int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, const SchemeArgs &s, int L, int th,
+                            double t_unit, const int64_t *nspin, double sigma_host)
 {
+    const LiftScheme<T> scf = s.build<T>(1), sci = s.build<T>(0);           // the forward and the inverse scheme
     const int64_t n0 = dims[0], n1 = (ndims >= 2) ? dims[1] : 1, n2 = (ndims == 3) ? dims[2] : 1, N = n0 * n1 * n2;
     const int64_t nsp0 = nspin[0], nsp1 = (ndims >= 2) ? nspin[1] : 1, nsp2 = (ndims == 3) ? nspin[2] : 1, pns = nsp0 * nsp1 * nsp2;
     int rc = ensure_aux(ctx);
     if (rc != WL_OK) return rc;
     SelState *sel = (SelState *)ctx->aux;
-    const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
     // transform workspace of the batched box (B lines, or B images: the approximation ping-pong of every image; B cubes: the ping-pong
     // and the two dense inter-pass buffers of the batched 3-D level loop, and no less than one cube's own), then the shifted copies Z
     // and their coefficients XT
@@ -1074,11 +1067,8 @@ int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
         return ws_elems(N * B, 1);
     };
     auto need = [&](int64_t B) { return (tws(B) + (size_t)2 * N * B + (size_t)n0 + 64) * sizeof(T); };
-    int64_t B = pns;
-    while (B > 1 && need(B) > cap) B = (B + 1) / 2;
-    if (B > 65535) B = 65535;
-    rc = wl_ensure_ws(ctx, need(B), st, true);
-    while (rc == WL_ENOMEM && B > 1) { B = (B + 1) / 2; rc = wl_ensure_ws(ctx, need(B), st, true); }
+    int64_t B = 1;
+    rc = group_reserve(ctx, st, pns, 65535, need, B);
     if (rc != WL_OK) return rc;
     T *tw = (T *)ctx->ws;
     T *Z = tw + tws(B);
@@ -1318,22 +1308,6 @@ __global__ void __launch_bounds__(EXT_THREADS) k_threshold_units(T *__restrict__
 }
 
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-// units per group: all of them, halved until the group's buffers fit under the context's cap (as the translation-invariant
-// batch), at most 65535 (a grid row / plane / workgroup per unit in the batched kernels); then the workspace is grown once
-template <typename F>
-int batch_group(wl_ctx *ctx, hipStream_t st, int64_t nunits, F need, int64_t &G)
-{
-    const size_t cap = (size_t)opt("WL_TI_WS_CAP_MB", 8192) << 20;
-    G = nunits;
-    while (G > 1 && need(G) > cap) G = (G + 1) / 2;
-    if (G > 65535) G = 65535;
-    int rc = wl_ensure_ws(ctx, need(G), st, true);
-    while (rc == WL_ENOMEM && G > 1) {                      // (another allocator may own most of the HBM: smaller groups)
-        G = (G + 1) / 2;
-        rc = wl_ensure_ws(ctx, need(G), st, true);
-    }
-    return rc;
-}
 // estimate (or take), publish and apply the sigmas of one group: src = where the level-1 detail range of every unit is read from
 // (nullptr: sigma_in), coef = the coefficients that are thresholded
 template <typename T>
@@ -1366,19 +1340,17 @@ int denoise_batch_filter_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int
     int64_t N = 1;
     for (int d = 0; d < ndims; ++d) N *= dims[d];
     const int64_t vdims[3] = {n0, n0, n0};
-    Taps<T> taps;
-    make_taps<T>(qmf, flen, taps);
+    const Taps<T> taps = taps_of<T>(qmf, flen);
     auto tw_elems = [&](int64_t G) { return ndims == 3 ? ws_vols_elems(N, G) : ws_elems(N * G, ndims); };
     auto need = [&](int64_t G) { return up256(tw_elems(G) * sizeof(T)) + up256((size_t)G * S * sizeof(T)) + up256((size_t)G * sizeof(double)); };
     int64_t G = 1;
-    int rc = batch_group(ctx, st, nunits, need, G);
+    int rc = group_reserve(ctx, st, nunits, 65535, need, G);
     if (rc != WL_OK) return rc;
     char *wsb = (char *)ctx->ws;
     T *Cb = (T *)(wsb + up256(tw_elems(G) * sizeof(T)));
     double *sg = (double *)(wsb + up256(tw_elems(G) * sizeof(T)) + up256((size_t)G * S * sizeof(T)));
     const char *madk = "none", *kn = nullptr;
-    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
-        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
+    WL_TRY(for_groups(nunits, G, [&](int64_t u0, int64_t nb) -> int {
         const T *xg = x + u0 * S;
         T *yg = y + u0 * S;
         BoxSpec bb;                                          // nb lines / images (cubes: a batch of volumes, not a box)
@@ -1410,7 +1382,8 @@ int denoise_batch_filter_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int
             if (rc == WL_RETRY_GEN) rc = WL_EINVAL_ARG;
             if (rc != WL_OK) return rc;
         }
-    }
+        return WL_OK;
+    }));
     WL_HIP(ctx, hipGetLastError());
     ctx->last_kernel = strcmp(madk, "k_mad_units_lds") == 0 ? "denoise_batch+k_mad_units_lds"
                        : (strcmp(madk, "k_mad_units_stream") == 0 ? "denoise_batch+k_mad_units_stream" : "denoise_batch+sigma_in");
@@ -1423,9 +1396,9 @@ int denoise_batch_filter_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int
 // estimate go to a workspace buffer, y is the copy of x.
 template <typename T>
 int denoise_batch_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, int64_t nunits, int64_t S,
-                               const LiftScheme<T> &scf, const LiftScheme<T> &sci, int L, int th, double t_unit, const double *sigma_in,
-                               double *sigma_out)
+                               const SchemeArgs &s, int L, int th, double t_unit, const double *sigma_in, double *sigma_out)
 {
+    const LiftScheme<T> scf = s.build<T>(1), sci = s.build<T>(0);           // the forward and the inverse scheme
     const int64_t n0 = dims[0];
     int64_t N = 1;
     for (int d = 0; d < ndims; ++d) N *= dims[d];
@@ -1438,14 +1411,13 @@ int denoise_batch_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, in
         return up256(tw_elems(G) * sizeof(T)) + up256(est0 ? (size_t)G * S * sizeof(T) : 0) + up256((size_t)G * sizeof(double));
     };
     int64_t G = 1;
-    int rc = batch_group(ctx, st, nunits, need, G);
+    int rc = group_reserve(ctx, st, nunits, 65535, need, G);
     if (rc != WL_OK) return rc;
     char *wsb = (char *)ctx->ws;
     T *Cb = (T *)(wsb + up256(tw_elems(G) * sizeof(T)));
     double *sg = (double *)(wsb + up256(tw_elems(G) * sizeof(T)) + up256(est0 ? (size_t)G * S * sizeof(T) : 0));
     const char *madk = "none";
-    for (int64_t u0 = 0; u0 < nunits; u0 += G) {
-        const int64_t nb = (nunits - u0 < G) ? (nunits - u0) : G;
+    WL_TRY(for_groups(nunits, G, [&](int64_t u0, int64_t nb) -> int {
         const T *xg = x + u0 * S;
         T *yg = y + u0 * S;
         auto transform = [&](T *dst, const T *src, const LiftScheme<T> &sc, int lev, int fw) -> int {
@@ -1469,7 +1441,8 @@ int denoise_batch_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, in
             rc = transform(yg, yg, sci, L, 0);
             if (rc != WL_OK) return rc;
         }
-    }
+        return WL_OK;
+    }));
     WL_HIP(ctx, hipGetLastError());
     ctx->last_kernel = strcmp(madk, "k_mad_units_lds") == 0 ? "denoise_batch+k_mad_units_lds"
                        : (strcmp(madk, "k_mad_units_stream") == 0 ? "denoise_batch+k_mad_units_stream" : "denoise_batch+sigma_in");
@@ -1498,8 +1471,7 @@ int denoise_batch_check(int ndims, const int64_t *dims, int64_t nunits, int64_t 
 inline int ext_enter(wl_ctx *ctx, int dtype)
 {
     if (!ctx) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    return WL_OK;
+    return check_dtype(dtype);
 }
 
 }  // namespace
@@ -1516,37 +1488,38 @@ int wl_maxmodwttransformlevels(int64_t n)
 int wl_modwt(wl_ctx *ctx, int dtype, void *out, int64_t ldo, const void *x, int64_t n, const double *qmf, int flen, int L,
              void *stream)
 {
-    int rc = ext_enter(ctx, dtype);
-    if (rc != WL_OK) return rc;
+    WL_TRY(ext_enter(ctx, dtype));
     WL_SCOPE(ctx);
     if (!out || !x || !qmf) return WL_EINVAL_ARG;
-    if (flen < 1 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
+    WL_TRY(check_flen(flen, 1));
     if (n < 1 || ldo < n) return WL_EDIMS;
     if (L > wl_maxmodwttransformlevels(n)) return WL_EINVAL_SIZE;      // "Too many transform levels (length(x) < 2^L)"
     if (L < 1) return WL_EINVAL_L;                                       // "L must be >= 1"
     hipStream_t st = (hipStream_t)stream;
-    return dtype == WL_F32 ? modwt_impl<float>(ctx, st, (float *)out, ldo, (const float *)x, n, qmf, flen, L)
-                           : modwt_impl<double>(ctx, st, (double *)out, ldo, (const double *)x, n, qmf, flen, L);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return modwt_impl<T>(ctx, st, (T *)out, ldo, (const T *)x, n, qmf, flen, L);
+    });
 }
 
 int wl_imodwt(wl_ctx *ctx, int dtype, void *x, const void *xw, int64_t ldw, int64_t n, int ncols, const double *qmf, int flen,
               void *stream)
 {
-    int rc = ext_enter(ctx, dtype);
-    if (rc != WL_OK) return rc;
+    WL_TRY(ext_enter(ctx, dtype));
     WL_SCOPE(ctx);
     if (!x || !xw || !qmf) return WL_EINVAL_ARG;
-    if (flen < 1 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
+    WL_TRY(check_flen(flen, 1));
     if (n < 1 || ncols < 1 || ldw < n) return WL_EDIMS;
     hipStream_t st = (hipStream_t)stream;
-    return dtype == WL_F32 ? imodwt_impl<float>(ctx, st, (float *)x, (const float *)xw, ldw, n, ncols, qmf, flen)
-                           : imodwt_impl<double>(ctx, st, (double *)x, (const double *)xw, ldw, n, ncols, qmf, flen);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return imodwt_impl<T>(ctx, st, (T *)x, (const T *)xw, ldw, n, ncols, qmf, flen);
+    });
 }
 
 int wl_threshold(wl_ctx *ctx, int dtype, void *x, int64_t n, int th, double t, int t_is_f64, void *stream)
 {
-    int rc = ext_enter(ctx, dtype);
-    if (rc != WL_OK) return rc;
+    WL_TRY(ext_enter(ctx, dtype));
     WL_SCOPE(ctx);
     if (!x && n > 0) return WL_EINVAL_ARG;
     if (th < WL_TH_HARD || th > WL_TH_NEG) return WL_EINVAL_ARG;
@@ -1554,9 +1527,12 @@ int wl_threshold(wl_ctx *ctx, int dtype, void *x, int64_t n, int th, double t, i
     if (n <= 0) return WL_OK;
     hipStream_t st = (hipStream_t)stream;
     const unsigned nb = ext_blocks(n, 4, ctx->cu_count);
-    if (dtype == WL_F64) hipLaunchKernelGGL((k_threshold<double, double>), dim3(nb), dim3(EXT_THREADS), 0, st, (double *)x, n, th, t, vec_ok16(x));
-    else if (t_is_f64) hipLaunchKernelGGL((k_threshold<float, double>), dim3(nb), dim3(EXT_THREADS), 0, st, (float *)x, n, th, t, vec_ok16(x));
-    else hipLaunchKernelGGL((k_threshold<float, float>), dim3(nb), dim3(EXT_THREADS), 0, st, (float *)x, n, th, (float)t, vec_ok16(x));
+    // the threshold is a Float64 for Float64 data; for Float32 data it is what the caller holds (t_is_f64)
+    by_dtype(dtype, [&](auto e) {
+        using T = decltype(e);
+        if (sizeof(T) == 8 || t_is_f64) hipLaunchKernelGGL((k_threshold<T, double>), dim3(nb), dim3(EXT_THREADS), 0, st, (T *)x, n, th, t, vec_ok16(x));
+        else hipLaunchKernelGGL((k_threshold<T, T>), dim3(nb), dim3(EXT_THREADS), 0, st, (T *)x, n, th, (T)t, vec_ok16(x));
+    });
     WL_HIP(ctx, hipGetLastError());
     ctx->last_kernel = "k_threshold";
     return WL_OK;
@@ -1564,65 +1540,53 @@ int wl_threshold(wl_ctx *ctx, int dtype, void *x, int64_t n, int th, double t, i
 
 int wl_threshold_biggest(wl_ctx *ctx, int dtype, void *x, int64_t n, int64_t m, void *stream)
 {
-    int rc = ext_enter(ctx, dtype);
-    if (rc != WL_OK) return rc;
+    WL_TRY(ext_enter(ctx, dtype));
     WL_SCOPE(ctx);
     if ((!x && n > 0) || m < 0) return WL_EINVAL_ARG;
     if (n <= 0) return WL_OK;
     hipStream_t st = (hipStream_t)stream;
-    return dtype == WL_F32 ? biggest_impl<float>(ctx, st, (float *)x, n, m) : biggest_impl<double>(ctx, st, (double *)x, n, m);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return biggest_impl<T>(ctx, st, (T *)x, n, m);
+    });
 }
 
 int wl_median(wl_ctx *ctx, int dtype, const void *v, int64_t n, double *result, void *stream)
 {
-    int rc = ext_enter(ctx, dtype);
-    if (rc != WL_OK) return rc;
+    WL_TRY(ext_enter(ctx, dtype));
     WL_SCOPE(ctx);
     if (!v || !result) return WL_EINVAL_ARG;
     if (n < 1) return WL_EDIMS;
     hipStream_t st = (hipStream_t)stream;
-    if (n <= (dtype == WL_F32 ? mad_lds_max<float>() : mad_lds_max<double>()))        // (the kernel does not write v when do_mad == 0)
-        return dtype == WL_F32 ? mad_small<float>(ctx, st, (float *)const_cast<void *>(v), n, 0, result)
-                               : mad_small<double>(ctx, st, (double *)const_cast<void *>(v), n, 0, result);
-    return dtype == WL_F32 ? median_impl<float>(ctx, st, (const float *)v, n, result, (float *)nullptr)
-                           : median_impl<double>(ctx, st, (const double *)v, n, result, (double *)nullptr);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (n <= mad_lds_max<T>()) return mad_small<T>(ctx, st, (T *)const_cast<void *>(v), n, 0, result);    // (does not write v when do_mad == 0)
+        return median_impl<T>(ctx, st, (const T *)v, n, result, (T *)nullptr);
+    });
 }
 
 int wl_mad(wl_ctx *ctx, int dtype, void *y, int64_t n, double *result, void *stream)
 {
-    int rc = ext_enter(ctx, dtype);
-    if (rc != WL_OK) return rc;
+    WL_TRY(ext_enter(ctx, dtype));
     WL_SCOPE(ctx);
     if (!y || !result) return WL_EINVAL_ARG;
     if (n < 1) return WL_EDIMS;
-    rc = ensure_aux(ctx);
-    if (rc != WL_OK) return rc;
+    WL_TRY(ensure_aux(ctx));
     hipStream_t st = (hipStream_t)stream;
-    if (n <= (dtype == WL_F32 ? mad_lds_max<float>() : mad_lds_max<double>()))
-        return dtype == WL_F32 ? mad_small<float>(ctx, st, (float *)y, n, 1, result) : mad_small<double>(ctx, st, (double *)y, n, 1, result);
-    void *mdev = (char *)ctx->aux + 4096;          // the first median, in the element type
-    const unsigned nb = ext_blocks(n, 4, ctx->cu_count);
-    if (dtype == WL_F32) {
-        rc = median_impl<float>(ctx, st, (const float *)y, n, nullptr, (float *)mdev);
-        if (rc != WL_OK) return rc;
-        hipLaunchKernelGGL((k_absdev<float>), dim3(nb), dim3(EXT_THREADS), 0, st, (float *)y, n, (const float *)mdev, vec_ok16(y));
-        return median_impl<float>(ctx, st, (const float *)y, n, result, (float *)nullptr);
-    }
-    rc = median_impl<double>(ctx, st, (const double *)y, n, nullptr, (double *)mdev);
-    if (rc != WL_OK) return rc;
-    hipLaunchKernelGGL((k_absdev<double>), dim3(nb), dim3(EXT_THREADS), 0, st, (double *)y, n, (const double *)mdev, vec_ok16(y));
-    return median_impl<double>(ctx, st, (const double *)y, n, result, (double *)nullptr);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (n <= mad_lds_max<T>()) return mad_small<T>(ctx, st, (T *)y, n, 1, result);
+        T *mdev = (T *)((char *)ctx->aux + 4096);          // the first median, in the element type
+        WL_TRY(median_impl<T>(ctx, st, (const T *)y, n, nullptr, mdev));
+        hipLaunchKernelGGL((k_absdev<T>), dim3(ext_blocks(n, 4, ctx->cu_count)), dim3(EXT_THREADS), 0, st, (T *)y, n, (const T *)mdev, vec_ok16(y));
+        return median_impl<T>(ctx, st, (const T *)y, n, result, (T *)nullptr);
+    });
 }
 
-int wl_denoise_ti_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, const double *qmf, int flen,
-                         int L, int th, double t_unit, const int64_t *nspin, double sigma_host, void *stream)
+// the rules wl_denoise_ti_* share behind their pointer / ndims (/ filter length) rules, in their order
+static int denoise_ti_check(const void *y, const void *x, int ndims, const int64_t *dims, int L, int th, double t_unit, const int64_t *nspin,
+                            double sigma_host)
 {
-    int rc = ext_enter(ctx, dtype);
-    if (rc != WL_OK) return rc;
-    WL_SCOPE(ctx);
-    if (!y || !x || !dims || !qmf || !nspin) return WL_EINVAL_ARG;
-    if (ndims < 1 || ndims > 3) return WL_EDIMS;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
     // threshold!(xt, dnt.th, sigma*t) (denoising.jl:58) has methods for Hard / Soft / Semisoft / Stein only (threshold_main.jl:21-80)
     if (th < WL_TH_HARD || th > WL_TH_STEIN) return WL_EINVAL_ARG;
     // a custom estimator's value: NaN trips the reference's `@assert t >= 0` (threshold_main.jl:24) and so does Inf * 0; +Inf
@@ -1638,10 +1602,24 @@ int wl_denoise_ti_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndi
     for (int d = 0; d < ndims; ++d)
         if (L >= 62 || (dims[d] % ((int64_t)1 << L)) != 0) return WL_EINVAL_SIZE;
     if (y == x) return WL_EALIAS;
-    if (th <= WL_TH_STEIN && !(t_unit >= 0)) return WL_EINVAL_ARG;
+    if (!(t_unit >= 0)) return WL_EINVAL_ARG;
+    return WL_OK;
+}
+
+int wl_denoise_ti_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, const double *qmf, int flen,
+                         int L, int th, double t_unit, const int64_t *nspin, double sigma_host, void *stream)
+{
+    WL_TRY(ext_enter(ctx, dtype));
+    WL_SCOPE(ctx);
+    if (!y || !x || !dims || !qmf || !nspin) return WL_EINVAL_ARG;
+    if (ndims < 1 || ndims > 3) return WL_EDIMS;
+    WL_TRY(check_flen(flen));
+    WL_TRY(denoise_ti_check(y, x, ndims, dims, L, th, t_unit, nspin, sigma_host));
     hipStream_t st = (hipStream_t)stream;
-    rc = dtype == WL_F32 ? denoise_ti_impl<float>(ctx, st, (float *)y, (const float *)x, ndims, dims, qmf, flen, L, th, t_unit, nspin, sigma_host)
-                         : denoise_ti_impl<double>(ctx, st, (double *)y, (const double *)x, ndims, dims, qmf, flen, L, th, t_unit, nspin, sigma_host);
+    const int rc = by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return denoise_ti_impl<T>(ctx, st, (T *)y, (const T *)x, ndims, dims, qmf, flen, L, th, t_unit, nspin, sigma_host);
+    });
     int64_t pns = 1;
     for (int d = 0; d < ndims; ++d) pns *= nspin[d];
     if (rc == WL_OK && pns > 1) ctx->last_kernel = "denoise_ti_batch";       // (one spin: "denoise_one_spin", set by the branch that ran)
@@ -1653,50 +1631,32 @@ int wl_denoise_ti_lifting(wl_ctx *ctx, int dtype, void *y, const void *x, int nd
                           const double *coefs_flat, double norm1, double norm2,
                           int L, int th, double t_unit, const int64_t *nspin, double sigma_host, void *stream)
 {
-    int rc = ext_enter(ctx, dtype);
-    if (rc != WL_OK) return rc;
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
+    WL_TRY(ext_enter(ctx, dtype));
     WL_SCOPE(ctx);
     if (!y || !x || !dims || !nspin) return WL_EINVAL_ARG;
     if (ndims < 1 || ndims > 3) return WL_EDIMS;
-    if (th < WL_TH_HARD || th > WL_TH_STEIN) return WL_EINVAL_ARG;
-    if (sigma_host != sigma_host || (sigma_host >= 0 && !(sigma_host * t_unit >= 0))) return WL_EINVAL_ARG;
-    for (int d = 0; d < ndims; ++d)
-        if (dims[d] < 1 || nspin[d] < 1) return WL_EDIMS;
-    if (ndims >= 2 && dims[0] != dims[1]) return WL_EINVAL_CUBE;
-    if (ndims == 3 && dims[0] != dims[2]) return WL_EINVAL_CUBE;
-    if (ndims == 3 && dims[0] >= ((int64_t)1 << 20)) return WL_EINVAL_SIZE; // (32-bit extents and column counts in the shift kernels)
-    if (ndims == 2 && dims[1] > 65535) return WL_EINVAL_SIZE;
-    if (L < 0) return WL_EINVAL_L;
-    for (int d = 0; d < ndims; ++d)
-        if (L >= 62 || (dims[d] % ((int64_t)1 << L)) != 0) return WL_EINVAL_SIZE;
-    if (y == x) return WL_EALIAS;
-    if (!(t_unit >= 0)) return WL_EINVAL_ARG;
+    WL_TRY(denoise_ti_check(y, x, ndims, dims, L, th, t_unit, nspin, sigma_host));
+    WL_TRY(s.check());
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        LiftScheme<float> f, i;
-        rc = wl_make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, 1, f);
-        if (rc == WL_OK) rc = wl_make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, 0, i);
-        if (rc == WL_OK) rc = denoise_ti_lifting_impl<float>(ctx, st, (float *)y, (const float *)x, ndims, dims, f, i, L, th, t_unit, nspin, sigma_host);
-    } else {
-        LiftScheme<double> f, i;
-        rc = wl_make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, 1, f);
-        if (rc == WL_OK) rc = wl_make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, 0, i);
-        if (rc == WL_OK) rc = denoise_ti_lifting_impl<double>(ctx, st, (double *)y, (const double *)x, ndims, dims, f, i, L, th, t_unit, nspin, sigma_host);
-    }
-    if (rc == WL_OK) ctx->last_kernel = "denoise_ti_lifting";
-    return rc;
+    WL_TRY(by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return denoise_ti_lifting_impl<T>(ctx, st, (T *)y, (const T *)x, ndims, dims, s, L, th, t_unit, nspin, sigma_host);
+    }));
+    ctx->last_kernel = "denoise_ti_lifting";
+    return WL_OK;
 }
 
 int wl_mad_batch(wl_ctx *ctx, int dtype, void *y, int64_t n, int64_t nunits, int64_t stride, double *result, void *stream)
 {
     if (!ctx || !y || !result) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
+    WL_TRY(check_dtype(dtype));
     if (n < 1 || nunits < 1 || stride < n) return WL_EDIMS;
     if (n >= ((int64_t)1 << 31)) return WL_EINVAL_SIZE;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == WL_F32 ? mad_units<float>(ctx, st, (float *)y, n, nunits, stride, 1, result, &ctx->last_kernel)
-                           : mad_units<double>(ctx, st, (double *)y, n, nunits, stride, 1, result, &ctx->last_kernel);
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return mad_units<T>(ctx, st, (T *)y, n, nunits, stride, 1, result, &ctx->last_kernel);
+    });
 }
 
 int wl_denoise_batch_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, int64_t nunits,
@@ -1706,17 +1666,15 @@ int wl_denoise_batch_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int 
     if (!ctx || !y || !x || !dims || !qmf) return WL_EINVAL_ARG;
     // threshold!(c, dnt.th, sigma * t) (denoising.jl:74) has methods for Hard / Soft / Semisoft / Stein only; @assert t >= 0
     if (th < WL_TH_HARD || th > WL_TH_STEIN || !(t_unit >= 0)) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    if (flen < 2 || flen > WL_MAX_FLEN) return WL_EINVAL_FILTER;
-    int rc = denoise_batch_check(ndims, dims, nunits, unit_stride, L, sigma_in == nullptr);
-    if (rc != WL_OK) return rc;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen));
+    WL_TRY(denoise_batch_check(ndims, dims, nunits, unit_stride, L, sigma_in == nullptr));
     if (y == x) return WL_EALIAS;
-    WL_SCOPE(ctx);
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == WL_F32 ? denoise_batch_filter_impl<float>(ctx, st, (float *)y, (const float *)x, ndims, dims, nunits, unit_stride, qmf, flen, L,
-                                                              th, t_unit, sigma_in, sigma_out)
-                           : denoise_batch_filter_impl<double>(ctx, st, (double *)y, (const double *)x, ndims, dims, nunits, unit_stride, qmf, flen,
-                                                               L, th, t_unit, sigma_in, sigma_out);
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return denoise_batch_filter_impl<T>(ctx, st, (T *)y, (const T *)x, ndims, dims, nunits, unit_stride, qmf, flen, L, th, t_unit, sigma_in,
+                                            sigma_out);
+    });
 }
 
 int wl_denoise_batch_lifting(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, int64_t nunits,
@@ -1724,34 +1682,21 @@ int wl_denoise_batch_lifting(wl_ctx *ctx, int dtype, void *y, const void *x, int
                              const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2, int L, int th, double t_unit,
                              const double *sigma_in, double *sigma_out, void *stream)
 {
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
     if (!ctx || !y || !x || !dims) return WL_EINVAL_ARG;
     if (th < WL_TH_HARD || th > WL_TH_STEIN || !(t_unit >= 0)) return WL_EINVAL_ARG;
-    if (dtype != WL_F32 && dtype != WL_F64) return WL_EINVAL_DTYPE;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == WL_F32) {
-        LiftScheme<float> f, i;
-        int rc = wl_make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, 1, f);
-        if (rc == WL_OK) rc = wl_make_scheme<float>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, 0, i);
-        if (rc == WL_OK) rc = denoise_batch_check(ndims, dims, nunits, unit_stride, L, sigma_in == nullptr);
-        if (rc != WL_OK) return rc;
-        WL_SCOPE(ctx);
-        return denoise_batch_lifting_impl<float>(ctx, st, (float *)y, (const float *)x, ndims, dims, nunits, unit_stride, f, i, L, th, t_unit,
-                                                 sigma_in, sigma_out);
-    }
-    LiftScheme<double> f, i;
-    int rc = wl_make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, 1, f);
-    if (rc == WL_OK) rc = wl_make_scheme<double>(nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2, 0, i);
-    if (rc == WL_OK) rc = denoise_batch_check(ndims, dims, nunits, unit_stride, L, sigma_in == nullptr);
-    if (rc != WL_OK) return rc;
-    WL_SCOPE(ctx);
-    return denoise_batch_lifting_impl<double>(ctx, st, (double *)y, (const double *)x, ndims, dims, nunits, unit_stride, f, i, L, th, t_unit,
-                                              sigma_in, sigma_out);
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(s.check());
+    WL_TRY(denoise_batch_check(ndims, dims, nunits, unit_stride, L, sigma_in == nullptr));
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return denoise_batch_lifting_impl<T>(ctx, st, (T *)y, (const T *)x, ndims, dims, nunits, unit_stride, s, L, th, t_unit, sigma_in, sigma_out);
+    });
 }
 
 int wl_circshift(wl_ctx *ctx, int dtype, void *b, const void *a, int ndims, const int64_t *dims, const int64_t *shift, void *stream)
 {
-    int rc = ext_enter(ctx, dtype);
-    if (rc != WL_OK) return rc;
+    WL_TRY(ext_enter(ctx, dtype));
     WL_SCOPE(ctx);
     if (!b || !a || !dims || !shift) return WL_EINVAL_ARG;
     if (ndims < 1 || ndims > 3) return WL_EDIMS;
@@ -1766,38 +1711,42 @@ int wl_circshift(wl_ctx *ctx, int dtype, void *b, const void *a, int ndims, cons
     }
     hipStream_t st = (hipStream_t)stream;
     const unsigned nb = ext_blocks(n, 4, ctx->cu_count);
-    if (dtype == WL_F32) hipLaunchKernelGGL((k_circshift<float>), dim3(nb), dim3(EXT_THREADS), 0, st, (float *)b, (const float *)a, n, p);
-    else hipLaunchKernelGGL((k_circshift<double>), dim3(nb), dim3(EXT_THREADS), 0, st, (double *)b, (const double *)a, n, p);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_circshift<T>), dim3(nb), dim3(EXT_THREADS), 0, st, (T *)b, (const T *)a, n, p);
+    });
     WL_HIP(ctx, hipGetLastError());
     return WL_OK;
 }
 
 int wl_arrayadd(wl_ctx *ctx, int dtype, void *y, const void *z, int64_t n, void *stream)
 {
-    int rc = ext_enter(ctx, dtype);
-    if (rc != WL_OK) return rc;
+    WL_TRY(ext_enter(ctx, dtype));
     WL_SCOPE(ctx);
     if ((!y || !z) && n > 0) return WL_EINVAL_ARG;
     if (n <= 0) return WL_OK;
     hipStream_t st = (hipStream_t)stream;
     const unsigned nb = ext_blocks(n, 4, ctx->cu_count);
-    if (dtype == WL_F32) hipLaunchKernelGGL((k_arrayadd<float>), dim3(nb), dim3(EXT_THREADS), 0, st, (float *)y, (const float *)z, n, vec_ok16(y) & vec_ok16(z));
-    else hipLaunchKernelGGL((k_arrayadd<double>), dim3(nb), dim3(EXT_THREADS), 0, st, (double *)y, (const double *)z, n, vec_ok16(y) & vec_ok16(z));
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_arrayadd<T>), dim3(nb), dim3(EXT_THREADS), 0, st, (T *)y, (const T *)z, n, vec_ok16(y) & vec_ok16(z));
+    });
     WL_HIP(ctx, hipGetLastError());
     return WL_OK;
 }
 
 int wl_rmul(wl_ctx *ctx, int dtype, void *y, int64_t n, double s, void *stream)
 {
-    int rc = ext_enter(ctx, dtype);
-    if (rc != WL_OK) return rc;
+    WL_TRY(ext_enter(ctx, dtype));
     WL_SCOPE(ctx);
     if (!y && n > 0) return WL_EINVAL_ARG;
     if (n <= 0) return WL_OK;
     hipStream_t st = (hipStream_t)stream;
     const unsigned nb = ext_blocks(n, 4, ctx->cu_count);
-    if (dtype == WL_F32) hipLaunchKernelGGL((k_rmul<float>), dim3(nb), dim3(EXT_THREADS), 0, st, (float *)y, n, s, vec_ok16(y));
-    else hipLaunchKernelGGL((k_rmul<double>), dim3(nb), dim3(EXT_THREADS), 0, st, (double *)y, n, s, vec_ok16(y));
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_rmul<T>), dim3(nb), dim3(EXT_THREADS), 0, st, (T *)y, n, s, vec_ok16(y));
+    });
     WL_HIP(ctx, hipGetLastError());
     return WL_OK;
 }
