@@ -1,7 +1,7 @@
 """Case table of user-defined lifting schemes (GLS built from the user's own steps, as W.GLS((steps, norm1, norm2, name)) takes
 them) and the kernel tier each one must reach.
 
-The shape-specialised lifting kernels are picked by match_shape (wl_lift.hip) from the step types, coefficient counts and
+The shape-specialised lifting kernels are picked by match_shape (wl_lift_shapes.h) from the step types, coefficient counts and
 shifts of the direction-adjusted scheme; the coefficients and norms stay run-time data.  SHAPES restates the Shape<ID>
 specialisations of wl_lift_shapes.h (test_lifting_schemes.py parses the header and fails when the two drift apart), so that a
 test can state which tier a scheme must take:
@@ -9,6 +9,9 @@ test can state which tier a scheme must take:
 - TWINS have the step sequence of cdf9/7, db2 and haar/db1 but other coefficients (c1 != +-c2 in every 2-coefficient step,
   none equal to a table coefficient) and other norms: they run on the shape-specialised kernels, where a swapped operand order
   or a wrong coefficient index would show (every cdf9/7 step has two equal coefficients).
+- REVERSED_TWINS are the twins with their step lists read backwards: their FORWARD step sequence has an inverse shape (IDs 1 / 3 / 5)
+  and their inverse a forward one.  Only the kernel families instantiated for every shape in both directions (k_lift1d_stream,
+  k_lift_axis_stream, k_lift_short_lines) may take them; every direction-bound family must leave them to the generic kernels.
 - CUSTOM schemes match no known shape: 3-coefficient steps, shifts beyond +-1 (operand indices that wrap more than once),
   0, 1, 5 and 16 steps.  They run on the LDS tails and the generic kernels.
 - NEAR_MISSES are the table schemes with exactly one field changed; match_shape must not accept them.
@@ -49,6 +52,9 @@ TWINS = {
 
 # the table scheme each twin copies the shape of
 TWIN_OF = {"twin_cdf97": "cdf97", "twin_db2": "db2", "twin_haar": "haar"}
+
+# the twins read backwards (same coefficients and norms): a user's scheme whose forward pass has the shape of an inverse pass
+REVERSED_TWINS = {"rev_" + name: (steps[::-1], n1, n2) for name, (steps, n1, n2) in TWINS.items()}
 
 _SIXTEEN = tuple((("P", "U")[i % 2], ((0.11, -0.07, 0.05)[: 1 + i % 3] if i % 4 < 2 else (-0.09, 0.06, 0.13)[: 1 + i % 3]),
                   (-2, -1, 0, 1, 2, 3)[i % 6]) for i in range(16))
@@ -125,6 +131,8 @@ ALL = {**TWINS, **CUSTOM, **NEAR_MISSES, **LARGE_SHIFTS}
 def spec(name):
     if name in ALL:
         return ALL[name]
+    if name in REVERSED_TWINS:
+        return REVERSED_TWINS[name]
     return _tbl("haar" if name == "db1" else name)
 
 
@@ -132,7 +140,7 @@ def scheme(W, name):
     """the GLS of a table entry (or of a reference scheme by its WT name), built the way a user builds one"""
     if name in REFERENCE:
         return W.wavelet(getattr(W.WT, name), W.WT.Lifting)
-    steps, n1, n2 = ALL[name]
+    steps, n1, n2 = spec(name)
     WT = W.WT
     st = [WT.make_lsstep(WT.Predict if t == "P" else WT.Update, list(c), s) for t, c, s in steps]
     return W.GLS((st, n1, n2, name))
@@ -144,7 +152,7 @@ def steps_of(sch):
 
 
 def shape_id(sch, fw=True):
-    """match_shape (wl_lift.hip) restated: the ID of the known shape the direction-adjusted scheme has, or -1"""
+    """match_shape (wl_lift_shapes.h) restated: the ID of the known shape the direction-adjusted scheme has, or -1"""
     seq = steps_of(sch)
     if not fw:
         seq = seq[::-1]

@@ -106,6 +106,57 @@ def test_twins_on_every_specialised_family(gpu, W, oracle, name):
     print(name, sorted(seen))
 
 
+# ---- reversed twins: a forward pass with an inverse shape (and the other way round) -----------------------------------------
+# (shape, dtype, L, options, entry point, prefix W.last_kernel() must have, substring it must not have)
+REVERSED_TIERS = [
+    # one level, not streamable (2100 % 8 != 0), above the 2048-sample tail: k_lift1d_gtile exists for its own direction only
+    ((2100,), np.float32, 1, {}, "dwt", "k_generic_lift", "k_lift1d_gtile"),
+    ((2100, 3), np.float32, 1, {}, "dwtc", "k_generic_lift", "k_lift1d_gtile"),
+    # the all-shapes families keep them
+    ((1 << 16,), np.float64, 2, {}, "dwt", "k_lift1d_stream", None),
+    ((512, 512), np.float64, 1, {"WL_LIFT_TILE": 0, "WL_NO_LIFT2D_FUSED": 1}, "dwt", "k_lift_axis_stream", None),
+    # direction-bound and guarded: the 2-D any-size tile, the any-axis pass
+    ((250, 250), np.float32, 1, {}, "dwt", "k_generic_lift", "k_lift2d_gtile"),
+    ((10, 10, 10), np.float64, 1, {}, "dwt", "", "k_lift_any"),
+]
+
+
+@pytest.mark.parametrize("tier", REVERSED_TIERS, ids=lambda t: "%s-%s-%s" % ("x".join(map(str, t[0])), np.dtype(t[1]).name, t[4]))
+@pytest.mark.parametrize("name", sorted(LS.REVERSED_TWINS))
+def test_reversed_twins_stay_off_the_direction_bound_kernels(gpu, W, oracle, name, tier):
+    """forward and inverse, out of place and in place, the oracle's bits; a kernel family instantiated for the shapes of its own
+    direction only must not take a scheme whose steps have the other direction's shape (it would run another shape's steps)"""
+    shape, dtype, L, opts, entry, prefix, banned = tier
+    sch = LS.scheme(W, name)
+    assert LS.shape_id(sch) in (1, 3, 5) and LS.shape_id(sch, fw=False) == LS.shape_id(sch) - 1
+    x = rng_array(shape, dtype, sum(shape) + len(name))
+    cols = entry == "dwtc"
+    ye = oracle.dwtc_lifting(x, sch, L) if cols else oracle.dwt_lifting(x, sch, L)
+    xe = oracle.dwtc_lifting(ye, sch, L, fw=False) if cols else oracle.dwt_lifting(ye, sch, L, fw=False)
+    fwd, inv = (W.dwtc, W.idwtc) if cols else (W.dwt, W.idwt)
+    with W.options(**opts):
+        y = host(W, fwd(dev(W, x), sch, L))
+        k1 = W.last_kernel()
+        xr = host(W, inv(dev(W, ye), sch, L))
+        k2 = W.last_kernel()
+        if cols:
+            yi, xi = dev(W, np.zeros_like(x)), dev(W, np.zeros_like(x))
+            W.dwtc_(yi, dev(W, x), sch, L)
+            W.idwtc_(xi, dev(W, ye), sch, L)
+        else:
+            yi, xi = dev(W, x), dev(W, ye)
+            W.dwt_(yi, sch, L)
+            W.idwt_(xi, sch, L)
+        yi, xi = host(W, yi), host(W, xi)
+    print(name, shape, np.dtype(dtype).name, k1, k2, int((y != ye).sum()), int((xr != xe).sum()))
+    for k in (k1, k2):
+        assert k.startswith(prefix) and (banned is None or banned not in k), (name, shape, k1, k2)
+    assert same_bits(y, ye), (name, shape, "fwd", k1, int((y != ye).sum()))
+    assert same_bits(xr, xe), (name, shape, "inv", k2, int((xr != xe).sum()))
+    assert same_bits(yi, ye), (name, shape, "fwd in place")
+    assert same_bits(xi, xe), (name, shape, "inv in place")
+
+
 # ---- 1-D lines: the LDS tail (<= 2048 samples) and the generic kernels ------------------------------------------------------
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("name", CUSTOM)

@@ -48,13 +48,19 @@ def test_parser_sees_an_added_shape():
 
 
 def test_shape_restatement_matches_the_header():
-    """shape_id restates match_shape: the same shapes, in the order match_shape tries them"""
+    """shape_id restates match_shape: the same shapes, in the order match_shape tries them (ids 0 .. 5 in turn, each through
+    by_shape, whose cases are the ids the header has a Shape<ID> for)"""
     assert header_shapes() == LS.SHAPES
-    with open(os.path.join(CSRC, "wl_lift.hip")) as f:
+    with open(os.path.join(CSRC, "wl_lift_shapes.h")) as f:
         src = f.read()
-    body = re.search(r"static int match_shape\(const LiftScheme<T> &sc\)\s*\{(.*?)\n\}", src, re.S).group(1)
-    tried = [int(v) for v in re.findall(r"shape_matches<(\d+)>", body)]
-    assert tried == sorted(LS.SHAPES), tried
+    body = re.search(r"inline int match_shape\(const LiftScheme<T> &sc\)\s*\{(.*?)\n\}", src, re.S).group(1)
+    lo, hi = re.search(r"for \(int id = (\d+); id <= (\d+); \+\+id\)", body).groups()
+    assert "by_shape(id, false," in body and "return id;" in body
+    dispatch = re.search(r"inline R by_shape\(int id, R none, F f\)\s*\{(.*?)\n\}", src, re.S).group(1)
+    cases = re.findall(r"case (\d+): return f\(ShapeId<(\d+)>\(\)\);", dispatch)
+    assert all(a == b for a, b in cases) and dispatch.count("case ") == len(cases)
+    tried = [int(a) for a, _ in cases if int(lo) <= int(a) <= int(hi)]
+    assert tried == sorted(LS.SHAPES) == list(range(int(lo), int(hi) + 1)), tried
 
 
 def test_every_shape_has_a_twin(W):
@@ -67,6 +73,16 @@ def test_every_shape_has_a_twin(W):
         reached[fw] = reached[inv] = name
     assert sorted(reached) == sorted(header_shapes()), "shapes without a twin in tests/lifting_schemes.py: %s" % (
         sorted(set(header_shapes()) - set(reached)))
+
+
+def test_reversed_twins_have_the_shape_of_the_other_direction(W):
+    """a reversed twin's forward steps have an inverse shape (odd ID), its inverse the forward shape before it"""
+    assert sorted(LS.REVERSED_TWINS) == sorted("rev_" + n for n in LS.TWINS)
+    for name in LS.REVERSED_TWINS:
+        sch, tw = LS.scheme(W, name), LS.scheme(W, name[4:])
+        assert LS.steps_of(sch) == LS.steps_of(tw)[::-1] and (sch.norm1, sch.norm2) == (tw.norm1, tw.norm2), name
+        assert LS.shape_id(sch) in (1, 3, 5) and LS.shape_id(sch, fw=False) == LS.shape_id(sch) - 1, name
+        assert LS.shape_id(sch) == LS.shape_id(tw, fw=False), name
 
 
 def _ref_coefs(W):

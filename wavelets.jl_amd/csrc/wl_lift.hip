@@ -1,4 +1,5 @@
-// wl_lift.hip -- lifting DWT/IDWT fast paths for lines (1-D vectors, batched columns).
+// wl_lift.hip -- lifting DWT/IDWT fast paths: lines (1-D vectors, batched columns), images, cubes, batches of them, and the
+// any-axis pass of the rank-generic driver.  (The cache-resident 2-D levels are in wl_lift_tile.hip.)
 //
 //   k_lift1d_stream  one lifting level of a line, forward or inverse, ALL steps + split/merge +
 //                    normalisation fused (the reference makes >= 6 passes over the level:
@@ -12,6 +13,13 @@
 //                    workgroup with the line in LDS (any scheme, true periodic indexing).
 //   k_lift_axis_stream   one lifting level along a strided axis (dim 2 / dim 3 of square and cubic arrays) as a
 //                    register cascade; k_lift_short_lines: the dim-1 pass for lines of 2..512 samples.
+//   k_lift2d_fwd / k_lift2d_inv   both passes of a 2-D level in one pass over HBM; k_tail_lift2d*, k_tail_lift3d: every
+//                    remaining level of a small block / cube in one workgroup; k_lift1d_gtile, k_lift2d_gtile, k_lift_any:
+//                    lines, blocks and boxes of any even size.
+//
+// A kernel template is chosen from the run-time shape id through by_shape / by_shape_dir (wl_lift_shapes.h).  k_lift1d_stream,
+// k_lift_axis_stream and k_lift_short_lines exist for all six shapes in both directions; every other family only for the
+// shapes of its own direction, and its callers leave a scheme of the other direction's shape to the generic kernels.
 //
 // Rounding follows the reference exactly: an element whose operands do not wrap is updated as
 // x += (c1*a + c2*b [+ c3*c]) (lift_inbounds!, transforms_lifting.jl:455-483), a wrapped one as
@@ -22,15 +30,6 @@
 
 
 namespace wl {
-
-template <int ID>
-static bool shape_matches(int nsteps, const int *upd, const int *nc, const int *sh)
-{
-    if (nsteps != Shape<ID>::NS) return false;
-    for (int i = 0; i < nsteps; ++i)
-        if (upd[i] != Shape<ID>::S[i].upd || nc[i] != Shape<ID>::S[i].nc || sh[i] != Shape<ID>::S[i].sh) return false;
-    return true;
-}
 
 __device__ __forceinline__ int l_dpp_next(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xf, 0xf, false); }
 __device__ __forceinline__ int l_dpp_prev(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, false); }
@@ -52,8 +51,7 @@ struct Lift1DArgs {
     T *o1; int64_t o1_ls;           // fw: ddst           inv: unused
     int64_t n;                      // line length (multiple of 8, >= 512)
     int64_t ntiles;
-    T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
-    T norm1, norm2;
+    LiftCoefs<T> cf;
 };
 
 template <typename T>
@@ -141,7 +139,7 @@ __global__ void __launch_bounds__(256) k_lift1d_stream(Lift1DArgs<T> a)
                 for (int i = 0; i < C; ++i) { sv[c * C + i] = t0[i]; dv[c * C + i] = t1[i]; }
             }
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { s[j] = a.norm1 * sv[j]; d[j] = a.norm2 * dv[j]; }   // normalize! (inverse first)
+            for (int j = 0; j < 4; ++j) { s[j] = a.cf.norm1 * sv[j]; d[j] = a.cf.norm2 * dv[j]; }   // normalize! (inverse first)
         }
 #pragma unroll
         for (int st = 0; st < SH::NS; ++st) {
@@ -185,13 +183,13 @@ __global__ void __launch_bounds__(256) k_lift1d_stream(Lift1DArgs<T> a)
                 const int64_t jg = kw + jj - sh;
                 const bool inb = (jg >= 0) && (jg + nc - 1 <= half - 1);
                 const T x = tgt[jj];
-                T acc = a.c[st][0] * o[0];
-                if (nc > 1) acc = acc + a.c[st][1] * o[1];
-                if (nc > 2) acc = acc + a.c[st][2] * o[2];
+                T acc = a.cf.c[st][0] * o[0];
+                if (nc > 1) acc = acc + a.cf.c[st][1] * o[1];
+                if (nc > 2) acc = acc + a.cf.c[st][2] * o[2];
                 const T xin = x + acc;
-                T xb = x + a.c[st][0] * o[0];
-                if (nc > 1) xb = xb + a.c[st][1] * o[1];
-                if (nc > 2) xb = xb + a.c[st][2] * o[2];
+                T xb = x + a.cf.c[st][0] * o[0];
+                if (nc > 1) xb = xb + a.cf.c[st][1] * o[1];
+                if (nc > 2) xb = xb + a.cf.c[st][2] * o[2];
                 res[jj] = inb ? xin : xb;
             }
 #pragma unroll
@@ -201,7 +199,7 @@ __global__ void __launch_bounds__(256) k_lift1d_stream(Lift1DArgs<T> a)
         if (FW) {
             T so[4], dO[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { so[j] = s[j] * a.norm1; dO[j] = d[j] * a.norm2; }     // normalize!
+            for (int j = 0; j < 4; ++j) { so[j] = s[j] * a.cf.norm1; dO[j] = d[j] * a.cf.norm2; }     // normalize!
             if (valid) {
                 stN<T, 4>(a.o0 + line * a.o0_ls + k0, so);
                 stN<T, 4>(a.o1 + line * a.o1_ls + k0, dO);
@@ -287,8 +285,7 @@ struct Lift3Args {
     T *sdst; int64_t s_ls;          // approximation after three levels
     int64_t n;
     int64_t ntiles;
-    T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
-    T norm1, norm2;
+    LiftCoefs<T> cf;
 };
 
 // (LVL1 only gives the launch that consumes the full-size input its own symbol: rocprofv3 --stats then reports it separately)
@@ -311,26 +308,26 @@ __global__ void __launch_bounds__(256) k_lift1d_fwd3(Lift3Args<T> a)
         T s1[4], d1[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) { s1[j] = v[2 * j]; d1[j] = v[2 * j + 1]; }
-        lift_steps_lane<T, ID, 4>(s1, d1, a.c, kw, half);
+        lift_steps_lane<T, ID, 4>(s1, d1, a.cf.c, kw, half);
         T s2[2], d2[2], dO1[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) dO1[j] = d1[j] * a.norm2;
+        for (int j = 0; j < 4; ++j) dO1[j] = d1[j] * a.cf.norm2;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) { s2[j] = s1[2 * j] * a.norm1; d2[j] = s1[2 * j + 1] * a.norm1; }
-        lift_steps_lane<T, ID, 2>(s2, d2, a.c, kw >> 1, half >> 1);
+        for (int j = 0; j < 2; ++j) { s2[j] = s1[2 * j] * a.cf.norm1; d2[j] = s1[2 * j + 1] * a.cf.norm1; }
+        lift_steps_lane<T, ID, 2>(s2, d2, a.cf.c, kw >> 1, half >> 1);
         T s3[1], d3[1], dO2[2];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) dO2[j] = d2[j] * a.norm2;
-        s3[0] = s2[0] * a.norm1;
-        d3[0] = s2[1] * a.norm1;
-        lift_steps_lane<T, ID, 1>(s3, d3, a.c, kw >> 2, half >> 2);
+        for (int j = 0; j < 2; ++j) dO2[j] = d2[j] * a.cf.norm2;
+        s3[0] = s2[0] * a.cf.norm1;
+        d3[0] = s2[1] * a.cf.norm1;
+        lift_steps_lane<T, ID, 1>(s3, d3, a.cf.c, kw >> 2, half >> 2);
         if (lane >= ML && lane < 64 - ML && k0 < half) {
             stg_pol<WL_P_LIFT3_ST != 0, T, 4>(a.d1 + line * a.d1_ls + k0, dO1);
             typedef T V2 __attribute__((ext_vector_type(2)));
             V2 t2; t2[0] = dO2[0]; t2[1] = dO2[1];
             *reinterpret_cast<V2 *>(a.y + line * a.y_ls + (n >> 2) + (k0 >> 1)) = t2;
-            a.y[line * a.y_ls + (n >> 3) + (k0 >> 2)] = d3[0] * a.norm2;
-            a.sdst[line * a.s_ls + (k0 >> 2)] = s3[0] * a.norm1;
+            a.y[line * a.y_ls + (n >> 3) + (k0 >> 2)] = d3[0] * a.cf.norm2;
+            a.sdst[line * a.s_ls + (k0 >> 2)] = s3[0] * a.cf.norm1;
         }
     }
 }
@@ -346,8 +343,7 @@ struct LiftInv3Args {
     T *dst; int64_t o_ls;           // output lines (n samples)
     int64_t n;                      // OUTPUT line length
     int64_t ntiles;
-    T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
-    T norm1, norm2;                 // already inverted by make_scheme
+    LiftCoefs<T> cf;                // (norms already inverted by make_scheme)
 };
 
 template <typename T, int ID>
@@ -366,22 +362,22 @@ __global__ void __launch_bounds__(256) k_lift1d_inv3(LiftInv3Args<T> a)
         if (kw < 0) kw += h3;
         if (kw >= h3) kw -= h3;
         T s3[1], d3[1], d2[2], d1[4];
-        s3[0] = a.norm1 * a.s3[line * a.s3_ls + kw];
-        d3[0] = a.norm2 * x[h3 + kw];
+        s3[0] = a.cf.norm1 * a.s3[line * a.s3_ls + kw];
+        d3[0] = a.cf.norm2 * x[h3 + kw];
         ldg_pol<WL_P_LIFTI3_LD != 0, T, 2>(x + 2 * h3 + 2 * kw, d2);
         ldg_pol<WL_P_LIFTI3_LD != 0, T, 4>(x + 4 * h3 + 4 * kw, d1);
-        lift_steps_lane<T, ID, 1>(s3, d3, a.c, kw, h3);
+        lift_steps_lane<T, ID, 1>(s3, d3, a.cf.c, kw, h3);
         T s2[2], d2n[2];
-        s2[0] = a.norm1 * s3[0]; s2[1] = a.norm1 * d3[0];                 // merge!, then normalize! of the next level
+        s2[0] = a.cf.norm1 * s3[0]; s2[1] = a.cf.norm1 * d3[0];                 // merge!, then normalize! of the next level
 #pragma unroll
-        for (int j = 0; j < 2; ++j) d2n[j] = a.norm2 * d2[j];
-        lift_steps_lane<T, ID, 2>(s2, d2n, a.c, 2 * kw, 2 * h3);
+        for (int j = 0; j < 2; ++j) d2n[j] = a.cf.norm2 * d2[j];
+        lift_steps_lane<T, ID, 2>(s2, d2n, a.cf.c, 2 * kw, 2 * h3);
         T s1[4], d1n[4];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) { s1[2 * j] = a.norm1 * s2[j]; s1[2 * j + 1] = a.norm1 * d2n[j]; }
+        for (int j = 0; j < 2; ++j) { s1[2 * j] = a.cf.norm1 * s2[j]; s1[2 * j + 1] = a.cf.norm1 * d2n[j]; }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) d1n[j] = a.norm2 * d1[j];
-        lift_steps_lane<T, ID, 4>(s1, d1n, a.c, 4 * kw, 4 * h3);
+        for (int j = 0; j < 4; ++j) d1n[j] = a.cf.norm2 * d1[j];
+        lift_steps_lane<T, ID, 4>(s1, d1n, a.cf.c, 4 * kw, 4 * h3);
         T out[8];
 #pragma unroll
         for (int j = 0; j < 4; ++j) { out[2 * j] = s1[j]; out[2 * j + 1] = d1n[j]; }
@@ -601,8 +597,7 @@ struct LiftRegArgs {
     const T *src; int64_t src_item;
     T *y; int64_t y_item;
     int n0, nlev;
-    T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
-    T norm1, norm2;
+    LiftCoefs<T> cf;
 };
 
 // one sample per lane: levels of <= 32 pairs
@@ -626,18 +621,18 @@ __device__ __forceinline__ void lift_reg_small(T v, int m, int nlev, const LiftR
             const int jg = lane - sh;
             const bool inb = (jg >= 0) && (jg + nc - 1 <= half - 1);
             const T x = upd ? d : s;
-            T acc = a.c[st][0] * o[0];
-            if (nc > 1) acc = acc + a.c[st][1] * o[1];
-            if (nc > 2) acc = acc + a.c[st][2] * o[2];
+            T acc = a.cf.c[st][0] * o[0];
+            if (nc > 1) acc = acc + a.cf.c[st][1] * o[1];
+            if (nc > 2) acc = acc + a.cf.c[st][2] * o[2];
             const T xin = x + acc;
-            T xb = x + a.c[st][0] * o[0];
-            if (nc > 1) xb = xb + a.c[st][1] * o[1];
-            if (nc > 2) xb = xb + a.c[st][2] * o[2];
+            T xb = x + a.cf.c[st][0] * o[0];
+            if (nc > 1) xb = xb + a.cf.c[st][1] * o[1];
+            if (nc > 2) xb = xb + a.cf.c[st][2] * o[2];
             const T r = inb ? xin : xb;
             if (upd) d = r; else s = r;
         }
-        if (lane < half) y[half + lane] = d * a.norm2;
-        v = s * a.norm1;
+        if (lane < half) y[half + lane] = d * a.cf.norm2;
+        v = s * a.cf.norm1;
         if (lev == nlev - 1) { if (lane < half) y[lane] = v; }
         m = half;
     }
@@ -646,11 +641,11 @@ __device__ __forceinline__ void lift_reg_small(T v, int m, int nlev, const LiftR
 template <typename T, int ID, int PPL>
 __device__ __forceinline__ void lift_reg_levels(T (&s)[PPL], T (&d)[PPL], int nlev, const LiftRegArgs<T> &a, T *y, int lane)
 {
-    lift_steps_wave<T, ID, PPL>(s, d, a.c, lane);
+    lift_steps_wave<T, ID, PPL>(s, d, a.cf.c, lane);
     constexpr int half = 64 * PPL;
     T dO[PPL], sO[PPL];
 #pragma unroll
-    for (int j = 0; j < PPL; ++j) { dO[j] = d[j] * a.norm2; sO[j] = s[j] * a.norm1; }
+    for (int j = 0; j < PPL; ++j) { dO[j] = d[j] * a.cf.norm2; sO[j] = s[j] * a.cf.norm1; }
     stv_l<T, PPL>(y + half + PPL * lane, dO);
     if (nlev == 1) { stv_l<T, PPL>(y + PPL * lane, sO); return; }
     if constexpr (PPL > 1) {
@@ -713,8 +708,8 @@ __device__ __forceinline__ void lift_reg_up(T (&s)[PPL], const LiftRegArgs<T> &a
     T d[PPL];
     ldv_l<T, PPL>(src + half + PPL * lane, d);
 #pragma unroll
-    for (int j = 0; j < PPL; ++j) { s[j] = a.norm1 * s[j]; d[j] = a.norm2 * d[j]; }
-    lift_steps_wave<T, ID, PPL>(s, d, a.c, lane);
+    for (int j = 0; j < PPL; ++j) { s[j] = a.cf.norm1 * s[j]; d[j] = a.cf.norm2 * d[j]; }
+    lift_steps_wave<T, ID, PPL>(s, d, a.cf.c, lane);
     T x[2 * PPL];
 #pragma unroll
     for (int j = 0; j < PPL; ++j) { x[2 * j] = s[j]; x[2 * j + 1] = d[j]; }
@@ -734,8 +729,8 @@ __global__ void __launch_bounds__(64) k_tail_lift_reg_inv(LiftRegArgs<T> a)
     const int msmall = n < 64 ? n : 64;
     for (int m = 2 * mstart; m <= msmall; m <<= 1) {
         const int half = m >> 1;
-        T sv = a.norm1 * v;
-        T dv = a.norm2 * ((lane < half) ? src[half + lane] : (T)0);
+        T sv = a.cf.norm1 * v;
+        T dv = a.cf.norm2 * ((lane < half) ? src[half + lane] : (T)0);
 #pragma unroll
         for (int st = 0; st < SH::NS; ++st) {
             const int upd = SH::S[st].upd, nc = SH::S[st].nc, sh = SH::S[st].sh;
@@ -749,13 +744,13 @@ __global__ void __launch_bounds__(64) k_tail_lift_reg_inv(LiftRegArgs<T> a)
             const int jg = lane - sh;
             const bool inb = (jg >= 0) && (jg + nc - 1 <= half - 1);
             const T x = upd ? dv : sv;
-            T acc = a.c[st][0] * o[0];
-            if (nc > 1) acc = acc + a.c[st][1] * o[1];
-            if (nc > 2) acc = acc + a.c[st][2] * o[2];
+            T acc = a.cf.c[st][0] * o[0];
+            if (nc > 1) acc = acc + a.cf.c[st][1] * o[1];
+            if (nc > 2) acc = acc + a.cf.c[st][2] * o[2];
             const T xin = x + acc;
-            T xb = x + a.c[st][0] * o[0];
-            if (nc > 1) xb = xb + a.c[st][1] * o[1];
-            if (nc > 2) xb = xb + a.c[st][2] * o[2];
+            T xb = x + a.cf.c[st][0] * o[0];
+            if (nc > 1) xb = xb + a.cf.c[st][1] * o[1];
+            if (nc > 2) xb = xb + a.cf.c[st][2] * o[2];
             const T r = inb ? xin : xb;
             if (upd) dv = r; else sv = r;
         }
@@ -773,7 +768,7 @@ __global__ void __launch_bounds__(64) k_tail_lift_reg_inv(LiftRegArgs<T> a)
 template <typename T>
 static bool lift_reg_inv_ok(int id, int64_t n0, int nlev, const T *src, int64_t src_item, const T *out, int64_t out_item)
 {
-    if (id != 1 && id != 3 && id != 5) return false;                       // inverse shapes
+    if (!shape_in_dir(id, 0)) return false;                                // inverse shapes
     if (n0 < 2 || (n0 & (n0 - 1)) != 0 || n0 > (sizeof(T) == 4 ? 4096 : 2048)) return false;
     if (nlev < 1 || ((int64_t)1 << nlev) > n0 || (n0 >> nlev) > 64) return false;
     constexpr int VEC = 16 / sizeof(T);
@@ -784,7 +779,7 @@ static bool lift_reg_inv_ok(int id, int64_t n0, int nlev, const T *src, int64_t 
 template <typename T>
 static bool lift_reg_ok(int id, int64_t n, int nlev, const T *src, int64_t src_item, const T *y, int64_t y_item)
 {
-    if (id != 0 && id != 2 && id != 4) return false;                       // forward shapes
+    if (!shape_in_dir(id, 1)) return false;                                // forward shapes
     if (n < 2 || (n & (n - 1)) != 0 || n > (sizeof(T) == 4 ? 4096 : 2048)) return false;
     if (nlev < 1 || ((int64_t)1 << nlev) > n) return false;
     constexpr int VEC = 16 / sizeof(T);
@@ -982,8 +977,7 @@ struct LiftTailRegArgs {
     T *y; int64_t ldy;
     int m0, nlev;
     int64_t bs_src, bs_y;           // batch of independent images (one workgroup each, blockIdx.x): image strides of src and y
-    T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
-    T norm1, norm2;
+    LiftCoefs<T> cf;
 };
 
 template <typename T, int ID, int H>
@@ -1027,18 +1021,18 @@ __device__ __forceinline__ void reg_tail_fwd_level(T *P, const LiftTailRegArgs<T
         T s[H], d[H];
 #pragma unroll
         for (int k = 0; k < H; ++k) { s[k] = P[lane + (2 * k) * ld]; d[k] = P[lane + (2 * k + 1) * ld]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
-        for (int k = 0; k < H; ++k) { P[lane + k * ld] = s[k] * a.norm1; P[lane + (H + k) * ld] = d[k] * a.norm2; }
+        for (int k = 0; k < H; ++k) { P[lane + k * ld] = s[k] * a.cf.norm1; P[lane + (H + k) * ld] = d[k] * a.cf.norm2; }
     }
     reg_tail_sync();
     if (lane < M) {
         T s[H], d[H];
 #pragma unroll
         for (int k = 0; k < H; ++k) { s[k] = P[2 * k + lane * ld]; d[k] = P[2 * k + 1 + lane * ld]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
-        for (int k = 0; k < H; ++k) { P[k + lane * ld] = s[k] * a.norm1; P[H + k + lane * ld] = d[k] * a.norm2; }
+        for (int k = 0; k < H; ++k) { P[k + lane * ld] = s[k] * a.cf.norm1; P[H + k + lane * ld] = d[k] * a.cf.norm2; }
     }
     reg_tail_sync();
 #pragma unroll
@@ -1067,8 +1061,8 @@ __device__ __forceinline__ void reg_tail_inv_level(T *P, const LiftTailRegArgs<T
     if (lane < M) {
         T s[H], d[H];
 #pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = a.norm1 * P[k + lane * ld]; d[k] = a.norm2 * P[H + k + lane * ld]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        for (int k = 0; k < H; ++k) { s[k] = a.cf.norm1 * P[k + lane * ld]; d[k] = a.cf.norm2 * P[H + k + lane * ld]; }
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
         for (int k = 0; k < H; ++k) { P[2 * k + lane * ld] = s[k]; P[2 * k + 1 + lane * ld] = d[k]; }
     }
@@ -1076,8 +1070,8 @@ __device__ __forceinline__ void reg_tail_inv_level(T *P, const LiftTailRegArgs<T
     if (lane < M) {
         T s[H], d[H];
 #pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = a.norm1 * P[lane + k * ld]; d[k] = a.norm2 * P[lane + (H + k) * ld]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        for (int k = 0; k < H; ++k) { s[k] = a.cf.norm1 * P[lane + k * ld]; d[k] = a.cf.norm2 * P[lane + (H + k) * ld]; }
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
         for (int k = 0; k < H; ++k) { P[lane + (2 * k) * ld] = s[k]; P[lane + (2 * k + 1) * ld] = d[k]; }
     }
@@ -1119,24 +1113,16 @@ __global__ void __launch_bounds__(64) k_tail_lift2d_reg(LiftTailRegArgs<T> a)
 template <typename T>
 static bool tail_lift2d_reg_ok(int id, int n0) { return id >= 0 && id <= 5 && n0 >= 2 && n0 <= 64 && (n0 & (n0 - 1)) == 0; }
 template <typename T, int FW>
-static hipError_t launch_tail_lift2d_reg(int id, hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t lds, T *y, int64_t ldy,
+static hipError_t launch_tail_lift2d_reg(int id, hipStream_t st, const LiftCoefs<T> &cf, const T *src, int64_t lds, T *y, int64_t ldy,
                                          int n0, int nlev, int64_t nimg = 1, int64_t bs_src = 0, int64_t bs_y = 0)
 {
     LiftTailRegArgs<T> a;
     a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.m0 = n0; a.nlev = nlev; a.bs_src = bs_src; a.bs_y = bs_y;
-    for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-        for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
-    a.norm1 = sc.norm1; a.norm2 = sc.norm2;
-    if (FW) {
-        if (id == 0) hipLaunchKernelGGL((k_tail_lift2d_reg<T, 0, 1>), dim3((unsigned)nimg), dim3(64), 0, st, a);
-        else if (id == 2) hipLaunchKernelGGL((k_tail_lift2d_reg<T, 2, 1>), dim3((unsigned)nimg), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((k_tail_lift2d_reg<T, 4, 1>), dim3((unsigned)nimg), dim3(64), 0, st, a);
-    } else {
-        if (id == 1) hipLaunchKernelGGL((k_tail_lift2d_reg<T, 1, 0>), dim3((unsigned)nimg), dim3(64), 0, st, a);
-        else if (id == 3) hipLaunchKernelGGL((k_tail_lift2d_reg<T, 3, 0>), dim3((unsigned)nimg), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((k_tail_lift2d_reg<T, 5, 0>), dim3((unsigned)nimg), dim3(64), 0, st, a);
-    }
-    return hipGetLastError();
+    a.cf = cf;
+    return by_shape_dir<FW>(id, hipErrorInvalidValue, [&](auto sid) {
+        hipLaunchKernelGGL((k_tail_lift2d_reg<T, decltype(sid)::value, FW>), dim3((unsigned)nimg), dim3(64), 0, st, a);
+        return hipGetLastError();
+    });
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -1155,9 +1141,9 @@ __device__ __forceinline__ void tail2l_fwd_level(T *P, const LiftTailRegArgs<T> 
         T *q = P + tid;
 #pragma unroll
         for (int k = 0; k < H; ++k) { s[k] = q[(2 * k) * LD]; d[k] = q[(2 * k + 1) * LD]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
-        for (int k = 0; k < H; ++k) { q[k * LD] = s[k] * a.norm1; q[(H + k) * LD] = d[k] * a.norm2; }
+        for (int k = 0; k < H; ++k) { q[k * LD] = s[k] * a.cf.norm1; q[(H + k) * LD] = d[k] * a.cf.norm2; }
     }
     tail2l_barrier();
     if (tid < M) {                                   // columns (dim 1)
@@ -1165,9 +1151,9 @@ __device__ __forceinline__ void tail2l_fwd_level(T *P, const LiftTailRegArgs<T> 
         T *q = P + tid * LD;
 #pragma unroll
         for (int k = 0; k < H; ++k) { s[k] = q[2 * k]; d[k] = q[2 * k + 1]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
-        for (int k = 0; k < H; ++k) { q[k] = s[k] * a.norm1; q[H + k] = d[k] * a.norm2; }
+        for (int k = 0; k < H; ++k) { q[k] = s[k] * a.cf.norm1; q[H + k] = d[k] * a.cf.norm2; }
     }
     tail2l_barrier();
     for (int idx = tid; idx < M * M; idx += nthr) {
@@ -1195,8 +1181,8 @@ __device__ __forceinline__ void tail2l_inv_level(T *P, const LiftTailRegArgs<T> 
         T s[H], d[H];
         T *q = P + tid * LD;
 #pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = a.norm1 * q[k]; d[k] = a.norm2 * q[H + k]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        for (int k = 0; k < H; ++k) { s[k] = a.cf.norm1 * q[k]; d[k] = a.cf.norm2 * q[H + k]; }
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
         for (int k = 0; k < H; ++k) { q[2 * k] = s[k]; q[2 * k + 1] = d[k]; }
     }
@@ -1205,8 +1191,8 @@ __device__ __forceinline__ void tail2l_inv_level(T *P, const LiftTailRegArgs<T> 
         T s[H], d[H];
         T *q = P + tid;
 #pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = a.norm1 * q[k * LD]; d[k] = a.norm2 * q[(H + k) * LD]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        for (int k = 0; k < H; ++k) { s[k] = a.cf.norm1 * q[k * LD]; d[k] = a.cf.norm2 * q[(H + k) * LD]; }
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
         for (int k = 0; k < H; ++k) { q[(2 * k) * LD] = s[k]; q[(2 * k + 1) * LD] = d[k]; }
     }
@@ -1251,36 +1237,21 @@ static hipError_t launch_tail_lift2d_lds_id(hipStream_t st, const LiftTailRegArg
 {
     constexpr int MM = tail2l_max<T>();
     const size_t shmem = (size_t)(MM + 1) * MM * sizeof(T);
-    static thread_local int attr_dev[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    bool done = false;
-    for (int i = 0; i < 8; ++i) done = done || attr_dev[i] == dev;
-    if (!done && shmem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tail_lift2d_lds<T, ID, FW, MM>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (shmem > 48 * 1024) {
+        hipError_t e = lift_max_lds_once<&k_tail_lift2d_lds<T, ID, FW, MM>>();
         if (e != hipSuccess) return e;
-        for (int i = 0; i < 8; ++i) if (attr_dev[i] < 0) { attr_dev[i] = dev; break; }
     }
     hipLaunchKernelGGL((k_tail_lift2d_lds<T, ID, FW, MM>), dim3((unsigned)nimg), dim3(256), shmem, st, a);
     return hipGetLastError();
 }
 template <typename T, int FW>
-static hipError_t launch_tail_lift2d_lds(int id, hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t lds, T *y, int64_t ldy,
+static hipError_t launch_tail_lift2d_lds(int id, hipStream_t st, const LiftCoefs<T> &cf, const T *src, int64_t lds, T *y, int64_t ldy,
                                          int n0, int nlev, int64_t nimg = 1, int64_t bs_src = 0, int64_t bs_y = 0)
 {
     LiftTailRegArgs<T> a;
     a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.m0 = n0; a.nlev = nlev; a.bs_src = bs_src; a.bs_y = bs_y;
-    for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-        for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
-    a.norm1 = sc.norm1; a.norm2 = sc.norm2;
-    if (FW) {
-        if (id == 0) return launch_tail_lift2d_lds_id<T, 0, 1>(st, a, nimg);
-        if (id == 2) return launch_tail_lift2d_lds_id<T, 2, 1>(st, a, nimg);
-        return launch_tail_lift2d_lds_id<T, 4, 1>(st, a, nimg);
-    }
-    if (id == 1) return launch_tail_lift2d_lds_id<T, 1, 0>(st, a, nimg);
-    if (id == 3) return launch_tail_lift2d_lds_id<T, 3, 0>(st, a, nimg);
-    return launch_tail_lift2d_lds_id<T, 5, 0>(st, a, nimg);
+    a.cf = cf;
+    return by_shape_dir<FW>(id, hipErrorInvalidValue, [&](auto sid) { return launch_tail_lift2d_lds_id<T, decltype(sid)::value, FW>(st, a, nimg); });
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -1299,8 +1270,7 @@ struct LiftTail3Args {
     T *y; int64_t y1, y2;           // fw: the coefficient array;   inv: the m0^3 result
     int64_t sv, yv;                 // a batch of cubes: workgroup blockIdx.x owns cube blockIdx.x, at src + blockIdx.x * sv and y + blockIdx.x * yv
     int m0, nlev;
-    T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
-    T norm1, norm2;
+    LiftCoefs<T> cf;
 };
 
 template <typename T, int ID, int M, int MM>
@@ -1315,9 +1285,9 @@ __device__ __forceinline__ void tail3_fwd_level(T *P, const LiftTail3Args<T> &a,
         T *q = P + u + v * L1;
 #pragma unroll
         for (int k = 0; k < H; ++k) { s[k] = q[(2 * k) * L2]; d[k] = q[(2 * k + 1) * L2]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
-        for (int k = 0; k < H; ++k) { q[k * L2] = s[k] * a.norm1; q[(H + k) * L2] = d[k] * a.norm2; }
+        for (int k = 0; k < H; ++k) { q[k * L2] = s[k] * a.cf.norm1; q[(H + k) * L2] = d[k] * a.cf.norm2; }
     }
     tail3_barrier();
     // ---- rows: lines along dim 2 at (i, k) = (u, v) ----
@@ -1326,9 +1296,9 @@ __device__ __forceinline__ void tail3_fwd_level(T *P, const LiftTail3Args<T> &a,
         T *q = P + u + v * L2;
 #pragma unroll
         for (int k = 0; k < H; ++k) { s[k] = q[(2 * k) * L1]; d[k] = q[(2 * k + 1) * L1]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
-        for (int k = 0; k < H; ++k) { q[k * L1] = s[k] * a.norm1; q[(H + k) * L1] = d[k] * a.norm2; }
+        for (int k = 0; k < H; ++k) { q[k * L1] = s[k] * a.cf.norm1; q[(H + k) * L1] = d[k] * a.cf.norm2; }
     }
     tail3_barrier();
     // ---- columns: lines along dim 1 at (j, k) = (u, v) ----
@@ -1337,9 +1307,9 @@ __device__ __forceinline__ void tail3_fwd_level(T *P, const LiftTail3Args<T> &a,
         T *q = P + u * L1 + v * L2;
 #pragma unroll
         for (int k = 0; k < H; ++k) { s[k] = q[2 * k]; d[k] = q[2 * k + 1]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
-        for (int k = 0; k < H; ++k) { q[k] = s[k] * a.norm1; q[H + k] = d[k] * a.norm2; }
+        for (int k = 0; k < H; ++k) { q[k] = s[k] * a.cf.norm1; q[H + k] = d[k] * a.cf.norm2; }
     }
     tail3_barrier();
     // the seven detail octants are final (the approximation octant too after the last level): lanes along dim 1
@@ -1371,8 +1341,8 @@ __device__ __forceinline__ void tail3_inv_level(T *P, const LiftTail3Args<T> &a,
         T s[H], d[H];
         T *q = P + u * L1 + v * L2;
 #pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = a.norm1 * q[k]; d[k] = a.norm2 * q[H + k]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        for (int k = 0; k < H; ++k) { s[k] = a.cf.norm1 * q[k]; d[k] = a.cf.norm2 * q[H + k]; }
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
         for (int k = 0; k < H; ++k) { q[2 * k] = s[k]; q[2 * k + 1] = d[k]; }
     }
@@ -1381,8 +1351,8 @@ __device__ __forceinline__ void tail3_inv_level(T *P, const LiftTail3Args<T> &a,
         T s[H], d[H];
         T *q = P + u + v * L2;
 #pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = a.norm1 * q[k * L1]; d[k] = a.norm2 * q[(H + k) * L1]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        for (int k = 0; k < H; ++k) { s[k] = a.cf.norm1 * q[k * L1]; d[k] = a.cf.norm2 * q[(H + k) * L1]; }
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
         for (int k = 0; k < H; ++k) { q[(2 * k) * L1] = s[k]; q[(2 * k + 1) * L1] = d[k]; }
     }
@@ -1391,8 +1361,8 @@ __device__ __forceinline__ void tail3_inv_level(T *P, const LiftTail3Args<T> &a,
         T s[H], d[H];
         T *q = P + u + v * L1;
 #pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = a.norm1 * q[k * L2]; d[k] = a.norm2 * q[(H + k) * L2]; }
-        reg_line_steps<T, ID, H>(s, d, a.c);
+        for (int k = 0; k < H; ++k) { s[k] = a.cf.norm1 * q[k * L2]; d[k] = a.cf.norm2 * q[(H + k) * L2]; }
+        reg_line_steps<T, ID, H>(s, d, a.cf.c);
 #pragma unroll
         for (int k = 0; k < H; ++k) { q[(2 * k) * L2] = s[k]; q[(2 * k + 1) * L2] = d[k]; }
     }
@@ -1439,15 +1409,9 @@ static hipError_t launch_tail_lift3d_id(hipStream_t st, const LiftTail3Args<T> &
 {
     constexpr int MM = tail3_max<T>();
     const size_t shmem = (size_t)(MM + 1) * MM * MM * sizeof(T);
-    static thread_local int attr_dev[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    bool done = false;
-    for (int i = 0; i < 8; ++i) done = done || attr_dev[i] == dev;
-    if (!done && shmem > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tail_lift3d<T, ID, FW, MM>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (shmem > 48 * 1024) {
+        hipError_t e = lift_max_lds_once<&k_tail_lift3d<T, ID, FW, MM>>();
         if (e != hipSuccess) return e;
-        for (int i = 0; i < 8; ++i) if (attr_dev[i] < 0) { attr_dev[i] = dev; break; }
     }
     const int lines = a.m0 * a.m0;
     const int threads = lines >= 1024 ? 1024 : (lines >= 256 ? 256 : 64);
@@ -1455,22 +1419,13 @@ static hipError_t launch_tail_lift3d_id(hipStream_t st, const LiftTail3Args<T> &
     return hipGetLastError();
 }
 template <typename T, int FW>
-static hipError_t launch_tail_lift3d(int id, hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t s1, int64_t s2, T *y, int64_t y1,
+static hipError_t launch_tail_lift3d(int id, hipStream_t st, const LiftCoefs<T> &cf, const T *src, int64_t s1, int64_t s2, T *y, int64_t y1,
                                      int64_t y2, int m0, int nlev, int64_t nvol = 1, int64_t sv = 0, int64_t yv = 0)
 {
     LiftTail3Args<T> a;
     a.src = src; a.s1 = s1; a.s2 = s2; a.y = y; a.y1 = y1; a.y2 = y2; a.m0 = m0; a.nlev = nlev; a.sv = sv; a.yv = yv;
-    for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-        for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
-    a.norm1 = sc.norm1; a.norm2 = sc.norm2;
-    if (FW) {
-        if (id == 0) return launch_tail_lift3d_id<T, 0, 1>(st, a, nvol);
-        if (id == 2) return launch_tail_lift3d_id<T, 2, 1>(st, a, nvol);
-        return launch_tail_lift3d_id<T, 4, 1>(st, a, nvol);
-    }
-    if (id == 1) return launch_tail_lift3d_id<T, 1, 0>(st, a, nvol);
-    if (id == 3) return launch_tail_lift3d_id<T, 3, 0>(st, a, nvol);
-    return launch_tail_lift3d_id<T, 5, 0>(st, a, nvol);
+    a.cf = cf;
+    return by_shape_dir<FW>(id, hipErrorInvalidValue, [&](auto sid) { return launch_tail_lift3d_id<T, decltype(sid)::value, FW>(st, a, nvol); });
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -1488,8 +1443,7 @@ struct LiftGTileArgs {
     T *ll; int64_t ldl;             // fw: approximation destination or nullptr (-> y);  inv: approximation source or nullptr (-> src)
     int n;                          // block size (even)
     int64_t bs_src, bs_y, bs_ll;    // batch of independent images (blockIdx.z): image strides of src, y and ll
-    T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
-    T norm1, norm2;
+    LiftCoefs<T> cf;
 };
 
 // all steps on an open line of 32 pairs whose first pair has the global (periodic) index kg0 of a line with `half` pairs
@@ -1556,18 +1510,18 @@ __global__ void __launch_bounds__(64) k_lift2d_gtile(LiftGTileArgs<T> a)
             T s[32], d[32];
 #pragma unroll
             for (int k = 0; k < 32; ++k) { s[k] = P[lane + (2 * k) * ld]; d[k] = P[lane + (2 * k + 1) * ld]; }
-            tile_line_steps<T, ID>(s, d, a.c, pc0, h);
+            tile_line_steps<T, ID>(s, d, a.cf.c, pc0, h);
 #pragma unroll
-            for (int k = 0; k < 32; ++k) { P[lane + k * ld] = s[k] * a.norm1; P[lane + (32 + k) * ld] = d[k] * a.norm2; }
+            for (int k = 0; k < 32; ++k) { P[lane + k * ld] = s[k] * a.cf.norm1; P[lane + (32 + k) * ld] = d[k] * a.cf.norm2; }
         }
         reg_tail_sync();
         {   // dim 1: lane = tile column (32 s-columns, 32 d-columns), line along the rows
             T s[32], d[32];
 #pragma unroll
             for (int k = 0; k < 32; ++k) { s[k] = P[2 * k + lane * ld]; d[k] = P[2 * k + 1 + lane * ld]; }
-            tile_line_steps<T, ID>(s, d, a.c, pr0, h);
+            tile_line_steps<T, ID>(s, d, a.cf.c, pr0, h);
 #pragma unroll
-            for (int k = 0; k < 32; ++k) { P[k + lane * ld] = s[k] * a.norm1; P[32 + k + lane * ld] = d[k] * a.norm2; }
+            for (int k = 0; k < 32; ++k) { P[k + lane * ld] = s[k] * a.cf.norm1; P[32 + k + lane * ld] = d[k] * a.cf.norm2; }
         }
         reg_tail_sync();
         // store the owned pairs: lanes along the rows (s rows then d rows), one tile column per iteration
@@ -1603,8 +1557,8 @@ __global__ void __launch_bounds__(64) k_lift2d_gtile(LiftGTileArgs<T> a)
         {   // dim 1 first: lane = tile column, line along the rows: normalize -> steps -> merge
             T s[32], d[32];
 #pragma unroll
-            for (int k = 0; k < 32; ++k) { s[k] = a.norm1 * P[k + lane * ld]; d[k] = a.norm2 * P[32 + k + lane * ld]; }
-            tile_line_steps<T, ID>(s, d, a.c, pr0, h);
+            for (int k = 0; k < 32; ++k) { s[k] = a.cf.norm1 * P[k + lane * ld]; d[k] = a.cf.norm2 * P[32 + k + lane * ld]; }
+            tile_line_steps<T, ID>(s, d, a.cf.c, pr0, h);
 #pragma unroll
             for (int k = 0; k < 32; ++k) { P[2 * k + lane * ld] = s[k]; P[2 * k + 1 + lane * ld] = d[k]; }
         }
@@ -1612,8 +1566,8 @@ __global__ void __launch_bounds__(64) k_lift2d_gtile(LiftGTileArgs<T> a)
         {   // dim 2: lane = tile row, line along the columns
             T s[32], d[32];
 #pragma unroll
-            for (int k = 0; k < 32; ++k) { s[k] = a.norm1 * P[lane + k * ld]; d[k] = a.norm2 * P[lane + (32 + k) * ld]; }
-            tile_line_steps<T, ID>(s, d, a.c, pc0, h);
+            for (int k = 0; k < 32; ++k) { s[k] = a.cf.norm1 * P[lane + k * ld]; d[k] = a.cf.norm2 * P[lane + (32 + k) * ld]; }
+            tile_line_steps<T, ID>(s, d, a.cf.c, pc0, h);
 #pragma unroll
             for (int k = 0; k < 32; ++k) { P[lane + (2 * k) * ld] = s[k]; P[lane + (2 * k + 1) * ld] = d[k]; }
         }
@@ -1633,30 +1587,21 @@ __global__ void __launch_bounds__(64) k_lift2d_gtile(LiftGTileArgs<T> a)
 template <typename T>
 static bool lift2d_gtile_ok(int id, int64_t n) { return id >= 0 && id <= 5 && n >= 2 && (n % 2) == 0 && n < ((int64_t)1 << 30); }
 template <typename T, int FW>
-static hipError_t launch_lift2d_gtile(int id, hipStream_t st, const LiftScheme<T> &sc, const T *src, int64_t lds, T *y, int64_t ldy, T *ll,
+static hipError_t launch_lift2d_gtile(int id, hipStream_t st, const LiftCoefs<T> &cf, const T *src, int64_t lds, T *y, int64_t ldy, T *ll,
                                       int64_t ldl, int64_t n, int64_t nimg = 1, int64_t bs_src = 0, int64_t bs_y = 0, int64_t bs_ll = 0)
 {
     LiftGTileArgs<T> a;
     a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.ll = ll; a.ldl = ldl; a.n = (int)n;
     a.bs_src = bs_src; a.bs_y = bs_y; a.bs_ll = bs_ll;
-    for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-        for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
-    a.norm1 = sc.norm1; a.norm2 = sc.norm2;
+    a.cf = cf;
     const int64_t h = n >> 1;
-#define WL_LGT(ID_)                                                                                             \
-    {                                                                                                           \
-        constexpr int OWN = 32 - 2 * LiftReach<ID_>::HP;                                                        \
-        const unsigned g = (unsigned)((h + OWN - 1) / OWN);                                                     \
-        if (g > 65535) return hipErrorInvalidValue;                                                             \
-        hipLaunchKernelGGL((k_lift2d_gtile<T, ID_, FW>), dim3(g, g, (unsigned)nimg), dim3(64), 0, st, a);       \
-    }
-    if (FW) {
-        if (id == 0) WL_LGT(0) else if (id == 2) WL_LGT(2) else WL_LGT(4)
-    } else {
-        if (id == 1) WL_LGT(1) else if (id == 3) WL_LGT(3) else WL_LGT(5)
-    }
-#undef WL_LGT
-    return hipGetLastError();
+    return by_shape_dir<FW>(id, hipErrorInvalidValue, [&](auto sid) {
+        constexpr int ID = decltype(sid)::value, OWN = 32 - 2 * LiftReach<ID>::HP;
+        const unsigned g = (unsigned)((h + OWN - 1) / OWN);
+        if (g > 65535) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((k_lift2d_gtile<T, ID, FW>), dim3(g, g, (unsigned)nimg), dim3(64), 0, st, a);
+        return hipGetLastError();
+    });
 }
 
 template <typename T, int FW>
@@ -1668,16 +1613,8 @@ static hipError_t launch_tail_lift2d(hipStream_t st, const LiftScheme<T> &sc, co
     a.ld = n0 | 1;
     a.cap = (a.ld * n0 + 15) & ~15;
     const size_t shmem = (size_t)(FW ? 2 : 3) * a.cap * sizeof(T);
-    static unsigned char attr_set[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev &= 63;
-    if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tail_lift2d<T, FW>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = 1;
-    }
+    hipError_t e = lift_max_lds_once<&k_tail_lift2d<T, FW>>();
+    if (e != hipSuccess) return e;
     const int work = n0 * n0;
     int threads = work >= 2048 ? 1024 : (work >= 512 ? 256 : 64);
     if (opt("WL_LIFT_TAIL_THREADS", 0) >= 64) threads = (int)opt("WL_LIFT_TAIL_THREADS", 0);
@@ -1686,92 +1623,73 @@ static hipError_t launch_tail_lift2d(hipStream_t st, const LiftScheme<T> &sc, co
 }
 
 // --------------------------------------------------------------------------------------------------
-static inline int l_env(const char *name, int dflt) { return (int)opt(name, dflt); }   // per-context options
-
 template <typename T>
 constexpr int lift_tail_cap() { return sizeof(T) == 4 ? 16384 : 8192; }
 
-template <typename T, int ID, int FW>
-static void launch_stream_id(hipStream_t st, const Lift1DArgs<T> &a, int64_t nlines, int cu_count)
+// the x grid of the line kernels: four waves per block, a wave per tile, at most eight blocks per CU (the waves stride over the tiles)
+static inline unsigned lines_grid_x(int64_t ntiles, int cu_count)
 {
-    int64_t gx = (a.ntiles + 3) / 4;
-    const int64_t cap = (int64_t)cu_count * 8;
-    if (gx > cap) gx = cap;
-    const int64_t slab = (l_env("WL_SLAB_LINES", 32768) > 0) ? l_env("WL_SLAB_LINES", 32768) : 32768;
-    for (int64_t l0 = 0; l0 < nlines; l0 += slab) {      // gridDim.y <= 65535
-        const int64_t nl = (nlines - l0 < slab) ? (nlines - l0) : slab;
-        Lift1DArgs<T> b = a;
-        b.a = a.a + l0 * a.a_ls; b.b = a.b ? a.b + l0 * a.b_ls : nullptr;
-        b.o0 = a.o0 + l0 * a.o0_ls; b.o1 = a.o1 ? a.o1 + l0 * a.o1_ls : nullptr;
-        hipLaunchKernelGGL((k_lift1d_stream<T, ID, FW>), dim3((unsigned)gx, (unsigned)nl), dim3(256), 0, st, b);
-    }
+    const int64_t gx = (ntiles + 3) / 4, cap = (int64_t)cu_count * 8;
+    return (unsigned)(gx > cap ? cap : gx);
 }
-
-template <typename T, int ID>
-static void launch_fwd3_id(hipStream_t st, const Lift3Args<T> &a, int64_t nlines, int cu_count, bool lvl1 = false)
-{
-    int64_t gx = (a.ntiles + 3) / 4;
-    const int64_t cap = (int64_t)cu_count * 8;
-    if (gx > cap) gx = cap;
-    const int64_t slab = (l_env("WL_SLAB_LINES", 32768) > 0) ? l_env("WL_SLAB_LINES", 32768) : 32768;
-    for (int64_t l0 = 0; l0 < nlines; l0 += slab) {
-        const int64_t nl = (nlines - l0 < slab) ? (nlines - l0) : slab;
-        Lift3Args<T> b = a;
-        b.src = a.src + l0 * a.src_ls; b.y = a.y + l0 * a.y_ls; b.d1 = a.d1 + l0 * a.d1_ls; b.sdst = a.sdst + l0 * a.s_ls;
-        if (lvl1) hipLaunchKernelGGL((k_lift1d_fwd3<T, ID, 1>), dim3((unsigned)gx, (unsigned)nl), dim3(256), 0, st, b);
-        else hipLaunchKernelGGL((k_lift1d_fwd3<T, ID, 0>), dim3((unsigned)gx, (unsigned)nl), dim3(256), 0, st, b);
-    }
-}
-
+// the arguments of the slab of lines that starts at line l0
 template <typename T>
-static int match_shape(const LiftScheme<T> &sc)
+static Lift1DArgs<T> lines_from(const Lift1DArgs<T> &a, int64_t l0)
 {
-    int upd[WL_MAX_STEPS], nc[WL_MAX_STEPS], sh[WL_MAX_STEPS];
-    for (int i = 0; i < sc.nsteps; ++i) { upd[i] = sc.step[i].is_update; nc[i] = sc.step[i].nc; sh[i] = sc.step[i].shift; }
-    if (shape_matches<0>(sc.nsteps, upd, nc, sh)) return 0;
-    if (shape_matches<1>(sc.nsteps, upd, nc, sh)) return 1;
-    if (shape_matches<2>(sc.nsteps, upd, nc, sh)) return 2;
-    if (shape_matches<3>(sc.nsteps, upd, nc, sh)) return 3;
-    if (shape_matches<4>(sc.nsteps, upd, nc, sh)) return 4;
-    if (shape_matches<5>(sc.nsteps, upd, nc, sh)) return 5;
-    return -1;
+    Lift1DArgs<T> b = a;
+    b.a = a.a + l0 * a.a_ls; b.b = a.b ? a.b + l0 * a.b_ls : nullptr;
+    b.o0 = a.o0 + l0 * a.o0_ls; b.o1 = a.o1 ? a.o1 + l0 * a.o1_ls : nullptr;
+    return b;
 }
 
-static inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// Forward or inverse lifting transform of `nlines` lines (1-D vector: nlines = 1; batched columns).
-// Returns 1 in *handled when the whole transform was enqueued by the fast kernels.
-// inverse shapes only (IDs 1, 3, 5); false = not an inverse shape
+// k_lift1d_stream takes the shapes of either direction in either direction (twelve instances per element type): a scheme whose
+// forward steps have the shape of another scheme's inverse runs here as well
 template <typename T>
-static bool launch_inv3_id(int id, hipStream_t st, const LiftInv3Args<T> &a, int64_t nlines, int cu_count)
+static hipError_t lift_lines_stream(int id, int fw, hipStream_t st, const Lift1DArgs<T> &a, int64_t nlines, int cu_count)
 {
-    if (id != 1 && id != 3 && id != 5) return false;
-    int64_t gx = (a.ntiles + 3) / 4;
-    const int64_t cap = (int64_t)cu_count * 8;
-    if (gx > cap) gx = cap;
-    for (int64_t l0 = 0; l0 < nlines; l0 += 32768) {
-        const int64_t nl = (nlines - l0 < 32768) ? (nlines - l0) : 32768;
-        LiftInv3Args<T> b = a;
-        b.s3 = a.s3 + l0 * a.s3_ls; b.x = a.x + l0 * a.x_ls; b.dst = a.dst + l0 * a.o_ls;
-        const dim3 grid((unsigned)gx, (unsigned)nl), block(256);
-        if (id == 1) hipLaunchKernelGGL((k_lift1d_inv3<T, 1>), grid, block, 0, st, b);
-        else if (id == 3) hipLaunchKernelGGL((k_lift1d_inv3<T, 3>), grid, block, 0, st, b);
-        else hipLaunchKernelGGL((k_lift1d_inv3<T, 5>), grid, block, 0, st, b);
-    }
-    return true;
+    return by_shape(id, hipErrorInvalidValue, [&](auto sid) {
+        constexpr int ID = decltype(sid)::value;
+        const unsigned gx = lines_grid_x(a.ntiles, cu_count);
+        for_line_slabs(nlines, slab_lines_opt(), [&](int64_t l0, int64_t nl) {
+            const dim3 grid(gx, (unsigned)nl), block(256);
+            if (fw) hipLaunchKernelGGL((k_lift1d_stream<T, ID, 1>), grid, block, 0, st, lines_from(a, l0));
+            else hipLaunchKernelGGL((k_lift1d_stream<T, ID, 0>), grid, block, 0, st, lines_from(a, l0));
+        });
+        return hipGetLastError();
+    });
 }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is sticky per (function, device) and costs tens of microseconds:
-// raise the limit to the LDS size once per device instead of on every call
-static hipError_t lift_max_lds_once(const void *fn, unsigned char (&done)[64])
+// forward shapes only; hipErrorInvalidValue = not one
+template <typename T>
+static hipError_t launch_fwd3(int id, hipStream_t st, const Lift3Args<T> &a, int64_t nlines, int cu_count, bool lvl1)
 {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    dev &= 63;
-    if (done[dev]) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e == hipSuccess) done[dev] = 1;
-    return e;
+    return by_shape_dir<1>(id, hipErrorInvalidValue, [&](auto sid) {
+        constexpr int ID = decltype(sid)::value;
+        const unsigned gx = lines_grid_x(a.ntiles, cu_count);
+        for_line_slabs(nlines, slab_lines_opt(), [&](int64_t l0, int64_t nl) {
+            Lift3Args<T> b = a;
+            b.src = a.src + l0 * a.src_ls; b.y = a.y + l0 * a.y_ls; b.d1 = a.d1 + l0 * a.d1_ls; b.sdst = a.sdst + l0 * a.s_ls;
+            const dim3 grid(gx, (unsigned)nl), block(256);
+            if (lvl1) hipLaunchKernelGGL((k_lift1d_fwd3<T, ID, 1>), grid, block, 0, st, b);
+            else hipLaunchKernelGGL((k_lift1d_fwd3<T, ID, 0>), grid, block, 0, st, b);
+        });
+        return hipGetLastError();
+    });
+}
+
+// inverse shapes only; hipErrorInvalidValue = not one
+template <typename T>
+static hipError_t launch_inv3(int id, hipStream_t st, const LiftInv3Args<T> &a, int64_t nlines, int cu_count)
+{
+    return by_shape_dir<0>(id, hipErrorInvalidValue, [&](auto sid) {
+        const unsigned gx = lines_grid_x(a.ntiles, cu_count);
+        for_line_slabs(nlines, 32768, [&](int64_t l0, int64_t nl) {
+            LiftInv3Args<T> b = a;
+            b.s3 = a.s3 + l0 * a.s3_ls; b.x = a.x + l0 * a.x_ls; b.dst = a.dst + l0 * a.o_ls;
+            hipLaunchKernelGGL((k_lift1d_inv3<T, decltype(sid)::value>), dim3(gx, (unsigned)nl), dim3(256), 0, st, b);
+        });
+        return hipGetLastError();
+    });
 }
 
 // One 1-D lifting level of lines of ANY even length (known shapes): a lane owns OWN = 32 - 2 HP consecutive pairs, loads the
@@ -1809,8 +1727,8 @@ __global__ void __launch_bounds__(256) k_lift1d_gtile(Lift1DArgs<T> a)
         while (g >= h) g -= h;
 #pragma unroll
         for (int k = 0; k < 32; ++k) {
-            s[k] = a.norm1 * ss[g];
-            d[k] = a.norm2 * ds[g];
+            s[k] = a.cf.norm1 * ss[g];
+            d[k] = a.cf.norm2 * ds[g];
             if (++g >= h) g -= h;
         }
     }
@@ -1821,13 +1739,13 @@ __global__ void __launch_bounds__(256) k_lift1d_gtile(Lift1DArgs<T> a)
         while (p >= h) p -= h;
         kg0 = (int)p;
     }
-    tile_line_steps<T, ID>(s, d, a.c, kg0, (int)h);
+    tile_line_steps<T, ID>(s, d, a.cf.c, kg0, (int)h);
     if (FW) {
         T *so = a.o0 + line * a.o0_ls, *dO = a.o1 + line * a.o1_ls;
 #pragma unroll
         for (int k = HP; k < 32 - HP; ++k) {
             const int64_t gk = own0 + (k - HP);
-            if (gk < h) { so[gk] = s[k] * a.norm1; dO[gk] = d[k] * a.norm2; }
+            if (gk < h) { so[gk] = s[k] * a.cf.norm1; dO[gk] = d[k] * a.cf.norm2; }
         }
     } else {
         T *out = a.o0 + line * a.o0_ls;
@@ -1843,25 +1761,14 @@ static hipError_t launch_lift1d_gtile(int id, hipStream_t st, const Lift1DArgs<T
 {
     const int64_t h = a.n >> 1;
     if (h >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
-#define WL_L1G(ID_)                                                                                              \
-    {                                                                                                            \
-        constexpr int OWN = 32 - 2 * LiftReach<ID_>::HP;                                                         \
-        const int64_t nthreads = (h + OWN - 1) / OWN;                                                            \
-        for (int64_t l0 = 0; l0 < nlines; l0 += 32768) {                                                         \
-            const int64_t nb = (nlines - l0 < 32768) ? (nlines - l0) : 32768;                                    \
-            Lift1DArgs<T> b = a;                                                                                 \
-            b.a = a.a + l0 * a.a_ls; b.b = a.b ? a.b + l0 * a.b_ls : nullptr;                                    \
-            b.o0 = a.o0 + l0 * a.o0_ls; b.o1 = a.o1 ? a.o1 + l0 * a.o1_ls : nullptr;                             \
-            hipLaunchKernelGGL((k_lift1d_gtile<T, ID_, FW>), dim3((unsigned)((nthreads + 255) / 256), (unsigned)nb), dim3(256), 0, st, b); \
-        }                                                                                                        \
-    }
-    if (FW) {
-        if (id == 0) WL_L1G(0) else if (id == 2) WL_L1G(2) else WL_L1G(4)
-    } else {
-        if (id == 1) WL_L1G(1) else if (id == 3) WL_L1G(3) else WL_L1G(5)
-    }
-#undef WL_L1G
-    return hipGetLastError();
+    return by_shape_dir<FW>(id, hipErrorInvalidValue, [&](auto sid) {
+        constexpr int ID = decltype(sid)::value, OWN = 32 - 2 * LiftReach<ID>::HP;
+        const int64_t nthreads = (h + OWN - 1) / OWN;
+        for_line_slabs(nlines, 32768, [&](int64_t l0, int64_t nl) {
+            hipLaunchKernelGGL((k_lift1d_gtile<T, ID, FW>), dim3((unsigned)((nthreads + 255) / 256), (unsigned)nl), dim3(256), 0, st, lines_from(a, l0));
+        });
+        return hipGetLastError();
+    });
 }
 
 // One lifting pass (split -> steps -> normalize, or normalize -> steps -> merge) along ANY axis of a box of any even extent,
@@ -1875,8 +1782,7 @@ struct LiftAnyArgs {
     T *ll; Strides3 ll_st;          // fw: destination of the low corner's s half (or nullptr); inv: its source (or nullptr)
     int n[3], lo[3];
     int axis;
-    T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
-    T norm1, norm2;
+    LiftCoefs<T> cf;
 };
 
 template <typename T, int ID, int FW>
@@ -1924,18 +1830,18 @@ __global__ void __launch_bounds__(256) k_lift_any(LiftAnyArgs<T> a)
                     int g = pr0;
 #pragma unroll
                     for (int k = 0; k < 32; ++k) {
-                        s[k] = a.norm1 * ps[(int64_t)g * ss];
-                        d[k] = a.norm2 * pd[(int64_t)g * sa];
+                        s[k] = a.cf.norm1 * ps[(int64_t)g * ss];
+                        d[k] = a.cf.norm2 * pd[(int64_t)g * sa];
                         if (++g >= h) g -= h;
                     }
                 }
-                tile_line_steps<T, ID>(s, d, a.c, pr0, h);
+                tile_line_steps<T, ID>(s, d, a.cf.c, pr0, h);
 #pragma unroll
                 for (int k = HP; k < 32 - HP; ++k) {
                     const int gk = own0 + (k - HP);
                     if (gk < h) {
                         if (FW) {
-                            const T sv = s[k] * a.norm1, dv = d[k] * a.norm2;
+                            const T sv = s[k] * a.cf.norm1, dv = d[k] * a.cf.norm2;
                             if (low) a.ll[lbase + (int64_t)gk * a.ll_st.s[axis]] = sv;
                             else a.dst[dbase + (int64_t)gk * da] = sv;
                             a.dst[dbase + (int64_t)(h + gk) * da] = dv;
@@ -1955,45 +1861,32 @@ bool lift_any_pass(hipStream_t st, const LiftScheme<T> &sc, int fw, const T *src
 {
     *err = hipSuccess;
     const int id = match_shape<T>(sc);
-    if (id < 0 || (fw ? (id & 1) : !(id & 1))) return false;
+    if (!shape_in_dir(id, fw)) return false;                  // (the kernel is instantiated for the shapes of its own direction)
     for (int d = 0; d < 3; ++d)
         if (n.n[d] < 1 || n.n[d] >= ((int64_t)1 << 30)) return false;
     if (n.n[axis] < 2 || (n.n[axis] % 2) != 0 || opt("WL_LIFT_ANY", 1) == 0) return false;
     LiftAnyArgs<T> a;
     a.src = src; a.sst = sst; a.dst = dst; a.dst_st = dst_st; a.ll = ll; a.ll_st = ll_st; a.axis = axis;
     for (int d = 0; d < 3; ++d) { a.n[d] = (int)n.n[d]; a.lo[d] = (int)lo.n[d]; }
-    for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-        for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
-    a.norm1 = sc.norm1; a.norm2 = sc.norm2;
-#define WL_LANY(ID_, FW_)                                                                                          \
-    {                                                                                                              \
-        constexpr int OWN = 32 - 2 * LiftReach<ID_>::HP;                                                           \
-        int64_t e[3] = {n.n[0], n.n[1], n.n[2]};                                                                   \
-        e[axis] = ((n.n[axis] >> 1) + OWN - 1) / OWN;                                                              \
-        int bx = 256;                                                                                              \
-        while (bx > 1 && (bx >> 1) >= e[0]) bx >>= 1;                                                              \
-        const int by = 256 / bx;                                                                                   \
-        int64_t gx = (e[0] + bx - 1) / bx, gy = (e[1] + by - 1) / by, gz = e[2];                                   \
-        if (gy > 65535) gy = 65535;                                                                                \
-        if (gz > 65535) gz = 65535;                                                                                \
-        while (gx * gy * gz > 8192) {                                                                              \
-            if (gz > 1 && gz >= gy && gz >= gx) gz = (gz + 1) / 2;                                                 \
-            else if (gy > 1 && gy >= gx) gy = (gy + 1) / 2;                                                        \
-            else gx = (gx + 1) / 2;                                                                                \
-        }                                                                                                          \
-        hipLaunchKernelGGL((k_lift_any<T, ID_, FW_>), dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3((unsigned)bx, (unsigned)by, 1), 0, \
-                           st, a);                                                                                 \
-    }
-    switch (id) {
-    case 0: WL_LANY(0, 1) break;
-    case 2: WL_LANY(2, 1) break;
-    case 4: WL_LANY(4, 1) break;
-    case 1: WL_LANY(1, 0) break;
-    case 3: WL_LANY(3, 0) break;
-    default: WL_LANY(5, 0) break;
-    }
-#undef WL_LANY
-    *err = hipGetLastError();
+    a.cf = lift_coefs<T>(sc);
+    *err = by_shape_dir(fw, id, hipErrorInvalidValue, [&](auto sid) {
+        constexpr int ID = decltype(sid)::value, OWN = 32 - 2 * LiftReach<ID>::HP;
+        int64_t e[3] = {n.n[0], n.n[1], n.n[2]};
+        e[axis] = ((n.n[axis] >> 1) + OWN - 1) / OWN;
+        int bx = 256;
+        while (bx > 1 && (bx >> 1) >= e[0]) bx >>= 1;
+        const int by = 256 / bx;
+        int64_t gx = (e[0] + bx - 1) / bx, gy = (e[1] + by - 1) / by, gz = e[2];
+        if (gy > 65535) gy = 65535;
+        if (gz > 65535) gz = 65535;
+        while (gx * gy * gz > 8192) {
+            if (gz > 1 && gz >= gy && gz >= gx) gz = (gz + 1) / 2;
+            else if (gy > 1 && gy >= gx) gy = (gy + 1) / 2;
+            else gx = (gx + 1) / 2;
+        }
+        hipLaunchKernelGGL((k_lift_any<T, ID, shape_fw(ID)>), dim3((unsigned)gx, (unsigned)gy, (unsigned)gz), dim3((unsigned)bx, (unsigned)by, 1), 0, st, a);
+        return hipGetLastError();
+    });
     return true;
 }
 template bool lift_any_pass<float>(hipStream_t, const LiftScheme<float> &, int, const float *, Strides3, float *, Strides3, float *, Strides3,
@@ -2001,6 +1894,8 @@ template bool lift_any_pass<float>(hipStream_t, const LiftScheme<float> &, int, 
 template bool lift_any_pass<double>(hipStream_t, const LiftScheme<double> &, int, const double *, Strides3, double *, Strides3, double *, Strides3,
                                     Extent3, int, Extent3, hipError_t *);
 
+// Forward or inverse lifting transform of `nlines` lines (1-D vector: nlines = 1; batched columns).
+// Returns 1 in *handled when the whole transform was enqueued by the fast kernels; enqueues nothing otherwise.
 template <typename T>
 int lifting_lines_fast(void *ws, int cu_count, hipStream_t st, int64_t n, int64_t nlines, int64_t ld,
                        T *y, const T *x, const LiftScheme<T> &sc, int L, int fw,
@@ -2015,36 +1910,26 @@ int lifting_lines_fast(void *ws, int cu_count, hipStream_t st, int64_t n, int64_
     // samples, because one workgroup is slow on a long line while the streaming kernels use the whole chip
     int cap = (nlines >= 32) ? lift_tail_cap<T>() : 2048;
     // known forward shapes on power-of-two lines: the single-wave register tail takes over at 4096 / 2048 samples
-    const bool reg_tail = fw && l_env("WL_LIFT_REGTAIL", 1) && (id == 0 || id == 2 || id == 4) && (n & (n - 1)) == 0;
-    const bool reg_tail_inv = !fw && l_env("WL_LIFT_REGTAIL", 1) && (id == 1 || id == 3 || id == 5) && (n & (n - 1)) == 0 &&
-                              (n >> L) <= 64;
+    // own_dir: a forward shape run forward or an inverse shape run backward.  Only k_lift1d_stream also takes the others (a user
+    // scheme whose forward steps read like another scheme's inverse); every other kernel here is instantiated for its own direction.
+    const bool own_dir = shape_in_dir(id, fw);
+    const bool reg_tail = fw && l_env("WL_LIFT_REGTAIL", 1) && own_dir && (n & (n - 1)) == 0;
+    const bool reg_tail_inv = !fw && l_env("WL_LIFT_REGTAIL", 1) && own_dir && (n & (n - 1)) == 0 && (n >> L) <= 64;
     if (reg_tail || reg_tail_inv) cap = (sizeof(T) == 4) ? 4096 : 2048;
-    // every level must be either stream-able (known shape, n_l >= 512, n_l % 8 == 0) or inside the tail
+    // every level must be inside the tail, stream-able (known shape, n_l >= 512, n_l % 8 == 0) or, a shape of this direction, on
+    // k_lift1d_gtile (any even length)
+    auto streamable = [](int64_t nl) { return nl >= 512 && (nl % 8) == 0; };
     int l_tail = L + 1;                       // first level (1-based) handled by the tail (fw) ...
     for (int l = 1; l <= L; ++l) {
         const int64_t nl = n >> (l - 1);
         if (nl <= cap) { l_tail = l; break; }
-        if (id < 0) return WL_OK;                 // (known shapes: lines that cannot stream -- nl < 512 or nl % 8 != 0 -- take k_lift1d_gtile)
+        if (id < 0 || (!own_dir && !streamable(nl))) return WL_OK;
     }
     const int64_t N = n * nlines;
     Work<T> w = carve<T>(ws, N);
     const char *dom = nullptr;
-#define WL_LAUNCH_ID(FWV)                                                                    \
-    switch (id) {                                                                            \
-    case 0: launch_stream_id<T, 0, FWV>(st, a, nlines, cu_count); break;                     \
-    case 1: launch_stream_id<T, 1, FWV>(st, a, nlines, cu_count); break;                     \
-    case 2: launch_stream_id<T, 2, FWV>(st, a, nlines, cu_count); break;                     \
-    case 3: launch_stream_id<T, 3, FWV>(st, a, nlines, cu_count); break;                     \
-    case 4: launch_stream_id<T, 4, FWV>(st, a, nlines, cu_count); break;                     \
-    default: launch_stream_id<T, 5, FWV>(st, a, nlines, cu_count); break;                    \
-    }
-#define WL_CHECK_LAUNCH()                                                                    \
-    do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) { if (hip_err) *hip_err = (int)e__; return WL_EHIP; } } while (0)
-
     Lift1DArgs<T> a;
-    for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-        for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
-    a.norm1 = sc.norm1; a.norm2 = sc.norm2;
+    a.cf = lift_coefs<T>(sc);
 
     if (fw) {
         const bool inplace = (y == x);
@@ -2056,21 +1941,16 @@ int lifting_lines_fast(void *ws, int cu_count, hipStream_t st, int64_t n, int64_
             const bool last = (l == L);
             // three levels per launch while the line is long (forward shapes 0/2/4), not for the in-place
             // first level (its outputs would land in regions other waves still read)
-            if ((id == 0 || id == 2 || id == 4) && l_env("WL_LIFT3", 1) && (L - l + 1) >= 3 && (l + 2 < l_tail) &&
+            if (own_dir && l_env("WL_LIFT3", 1) && (L - l + 1) >= 3 && (l + 2 < l_tail) &&
                 nl >= 4096 && (nl % 32) == 0 && !(inplace && l == 1)) {
                 const bool last3 = (l + 2 == L);
                 T *llbuf3 = pp ? w.B : w.A;
                 Lift3Args<T> a3;
-                for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-                    for (int k = 0; k < WL_MAX_NCOEF; ++k) a3.c[i][k] = a.c[i][k];
-                a3.norm1 = a.norm1; a3.norm2 = a.norm2;
+                a3.cf = a.cf;
                 a3.src = cur; a3.src_ls = cur_ls; a3.y = y; a3.y_ls = ld; a3.d1 = y + hl; a3.d1_ls = ld;
                 a3.sdst = last3 ? y : llbuf3; a3.s_ls = last3 ? ld : (nl >> 3);
                 a3.n = nl; a3.ntiles = (hl + 223) / 224;
-                if (id == 0) launch_fwd3_id<T, 0>(st, a3, nlines, cu_count, l == 1);
-                else if (id == 2) launch_fwd3_id<T, 2>(st, a3, nlines, cu_count, l == 1);
-                else launch_fwd3_id<T, 4>(st, a3, nlines, cu_count, l == 1);
-                WL_CHECK_LAUNCH();
+                WL_E((launch_fwd3<T>(id, st, a3, nlines, cu_count, l == 1)));
                 if (!dom) dom = "k_lift1d_fwd3";
                 cur = llbuf3; cur_ls = nl >> 3; pp ^= 1;
                 l += 2;
@@ -2084,17 +1964,14 @@ int lifting_lines_fast(void *ws, int cu_count, hipStream_t st, int64_t n, int64_
             a.o0 = (last && !stage) ? y : llbuf; a.o0_ls = (last && !stage) ? ld : hl;
             a.o1 = stage ? w.W : (y + hl); a.o1_ls = stage ? hl : ld;
             a.n = nl; a.ntiles = (hl + 247) / 248;
-            const bool streamable = nl >= 512 && (nl % 8) == 0;
-            if (streamable) { WL_LAUNCH_ID(1); }
-            else { hipError_t eg = launch_lift1d_gtile<T, 1>(id, st, a, nlines); if (eg != hipSuccess) { if (hip_err) *hip_err = (int)eg; return WL_EHIP; } }
-            WL_CHECK_LAUNCH();
-            if (!streamable && !dom) dom = "k_lift1d_gtile";
+            if (streamable(nl)) WL_E((lift_lines_stream<T>(id, 1, st, a, nlines, cu_count)));
+            else WL_E((launch_lift1d_gtile<T, 1>(id, st, a, nlines)));
+            if (!streamable(nl) && !dom) dom = "k_lift1d_gtile";
             if (stage) {
                 Extent3 e = {{hl, nlines, 1}};
                 Strides3 s0 = {{1, hl, hl * nlines}}, s1 = {{1, ld, ld * nlines}};
-                hipError_t e2 = generic_copy_box<T>(st, w.W, s0, y + hl, s1, e);
-                if (e2 == hipSuccess && last) e2 = generic_copy_box<T>(st, llbuf, s0, y, s1, e);
-                if (e2 != hipSuccess) { if (hip_err) *hip_err = (int)e2; return WL_EHIP; }
+                WL_E(generic_copy_box<T>(st, w.W, s0, y + hl, s1, e));
+                if (last) WL_E(generic_copy_box<T>(st, llbuf, s0, y, s1, e));
             }
             if (!dom) dom = "k_lift1d_stream";
             cur = llbuf; cur_ls = hl; pp ^= 1;
@@ -2103,13 +1980,11 @@ int lifting_lines_fast(void *ws, int cu_count, hipStream_t st, int64_t n, int64_
             lift_reg_ok<T>(id, n >> (l_tail - 1), L - l_tail + 1, cur, cur_ls, y, ld)) {
             LiftRegArgs<T> r;
             r.src = cur; r.src_item = cur_ls; r.y = y; r.y_item = ld; r.n0 = (int)(n >> (l_tail - 1)); r.nlev = L - l_tail + 1;
-            for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-                for (int k = 0; k < WL_MAX_NCOEF; ++k) r.c[i][k] = a.c[i][k];
-            r.norm1 = a.norm1; r.norm2 = a.norm2;
-            if (id == 0) hipLaunchKernelGGL((k_tail_lift_reg<T, 0>), dim3((unsigned)nlines), dim3(64), 0, st, r);
-            else if (id == 2) hipLaunchKernelGGL((k_tail_lift_reg<T, 2>), dim3((unsigned)nlines), dim3(64), 0, st, r);
-            else hipLaunchKernelGGL((k_tail_lift_reg<T, 4>), dim3((unsigned)nlines), dim3(64), 0, st, r);
-            WL_CHECK_LAUNCH();
+            r.cf = a.cf;
+            WL_E(by_shape_dir<1>(id, hipErrorInvalidValue, [&](auto sid) {
+                hipLaunchKernelGGL((k_tail_lift_reg<T, decltype(sid)::value>), dim3((unsigned)nlines), dim3(64), 0, st, r);
+                return hipGetLastError();
+            }));
             if (!dom) dom = "k_tail_lift_reg";
         } else if (l_tail <= L) {
             LiftTailArgs<T> t;
@@ -2117,12 +1992,10 @@ int lifting_lines_fast(void *ws, int cu_count, hipStream_t st, int64_t n, int64_
             t.src = cur; t.src_item = cur_ls; t.y = y; t.y_item = ld; t.ll = nullptr; t.ll_item = 0;
             t.n0 = (int)nl; t.nlev = L - l_tail + 1; t.cap = (int)((nl + 15) & ~15);
             const size_t shmem = 2 * (size_t)t.cap * sizeof(T);
-            static unsigned char attr_fw[64] = {0};
-            hipError_t e = lift_max_lds_once(reinterpret_cast<const void *>(&k_tail_lift<T, 1>), attr_fw);
-            if (e != hipSuccess) { if (hip_err) *hip_err = (int)e; return WL_EHIP; }
+            WL_E((lift_max_lds_once<&k_tail_lift<T, 1>>()));
             int threads = nl >= 4096 ? 1024 : (nl >= 512 ? 256 : 64);
             hipLaunchKernelGGL((k_tail_lift<T, 1>), dim3((unsigned)nlines), dim3(threads), shmem, st, t, sc);
-            WL_CHECK_LAUNCH();
+            WL_EL();
             if (!dom) dom = "k_tail_lift";
         }
     } else {
@@ -2143,13 +2016,11 @@ int lifting_lines_fast(void *ws, int cu_count, hipStream_t st, int64_t n, int64_
             T *out = to_y ? y : (pp ? w.B : w.A);
             LiftRegArgs<T> r;
             r.src = x; r.src_item = ld; r.y = out; r.y_item = to_y ? ld : nout; r.n0 = (int)nout; r.nlev = L - l_lo + 1;
-            for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-                for (int k = 0; k < WL_MAX_NCOEF; ++k) r.c[i][k] = a.c[i][k];
-            r.norm1 = a.norm1; r.norm2 = a.norm2;
-            if (id == 1) hipLaunchKernelGGL((k_tail_lift_reg_inv<T, 1>), dim3((unsigned)nlines), dim3(64), 0, st, r);
-            else if (id == 3) hipLaunchKernelGGL((k_tail_lift_reg_inv<T, 3>), dim3((unsigned)nlines), dim3(64), 0, st, r);
-            else hipLaunchKernelGGL((k_tail_lift_reg_inv<T, 5>), dim3((unsigned)nlines), dim3(64), 0, st, r);
-            WL_CHECK_LAUNCH();
+            r.cf = a.cf;
+            WL_E(by_shape_dir<0>(id, hipErrorInvalidValue, [&](auto sid) {
+                hipLaunchKernelGGL((k_tail_lift_reg_inv<T, decltype(sid)::value>), dim3((unsigned)nlines), dim3(64), 0, st, r);
+                return hipGetLastError();
+            }));
             if (!dom) dom = "k_tail_lift_reg_inv";
             llsrc = out; ll_ls = r.y_item; pp ^= 1;
             l = l_lo - 1;
@@ -2162,44 +2033,37 @@ int lifting_lines_fast(void *ws, int cu_count, hipStream_t st, int64_t n, int64_
             t.y = out; t.y_item = to_y ? ld : nout;
             t.n0 = (int)nout; t.nlev = l_hi - l_lo + 1; t.cap = (int)((nout + 15) & ~15);
             const size_t shmem = 2 * (size_t)t.cap * sizeof(T);
-            static unsigned char attr_inv[64] = {0};
-            hipError_t e = lift_max_lds_once(reinterpret_cast<const void *>(&k_tail_lift<T, 0>), attr_inv);
-            if (e != hipSuccess) { if (hip_err) *hip_err = (int)e; return WL_EHIP; }
+            WL_E((lift_max_lds_once<&k_tail_lift<T, 0>>()));
             int threads = nout >= 4096 ? 1024 : (nout >= 512 ? 256 : 64);
             hipLaunchKernelGGL((k_tail_lift<T, 0>), dim3((unsigned)nlines), dim3(threads), shmem, st, t, sc);
-            WL_CHECK_LAUNCH();
+            WL_EL();
             if (!dom) dom = "k_tail_lift";
             llsrc = out; ll_ls = t.y_item; pp ^= 1;
             l = l_lo - 1;
         }
         for (; l >= 1; --l) {
             // three levels (l, l-1, l-2) per launch while the output of level l-2 is a long line
-            if (l >= 3 && l_env("WL_NO_LIFT_INV3", 0) == 0) {
+            if (own_dir && l >= 3 && l_env("WL_NO_LIFT_INV3", 0) == 0) {
                 const int64_t n3 = n >> (l - 3);                 // output length of level l-2
                 if (n3 >= 4096 && (n3 % 64) == 0 && (nlines == 1 || ((ld % VEC) == 0 && (ll_ls % VEC) == 0))) {
                     const bool to_y3 = (l - 2 == 1);
                     T *out3 = to_y3 ? y : (pp ? w.B : w.A);
                     const bool stage3 = to_y3 && (y == x);       // in place: the details of y are still being read
                     LiftInv3Args<T> q;
-                    for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-                        for (int k = 0; k < WL_MAX_NCOEF; ++k) q.c[i][k] = a.c[i][k];
-                    q.norm1 = a.norm1; q.norm2 = a.norm2;
+                    q.cf = a.cf;
                     q.s3 = llsrc; q.s3_ls = ll_ls; q.x = x; q.x_ls = ld;
                     q.dst = stage3 ? w.W : out3; q.o_ls = stage3 ? n3 : (to_y3 ? ld : n3);
                     q.n = n3; q.ntiles = ((n3 >> 3) + 55) / 56;
-                    if (launch_inv3_id<T>(id, st, q, nlines, cu_count)) {
-                        WL_CHECK_LAUNCH();
-                        if (stage3) {
-                            Extent3 e = {{n3, nlines, 1}};
-                            Strides3 s0 = {{1, n3, n3 * nlines}}, s1 = {{1, ld, ld * nlines}};
-                            hipError_t e2 = generic_copy_box<T>(st, w.W, s0, y, s1, e);
-                            if (e2 != hipSuccess) { if (hip_err) *hip_err = (int)e2; return WL_EHIP; }
-                        }
-                        dom = "k_lift1d_inv3";
-                        llsrc = out3; ll_ls = n3; pp ^= 1;
-                        l -= 2;
-                        continue;
+                    WL_E((launch_inv3<T>(id, st, q, nlines, cu_count)));
+                    if (stage3) {
+                        Extent3 e = {{n3, nlines, 1}};
+                        Strides3 s0 = {{1, n3, n3 * nlines}}, s1 = {{1, ld, ld * nlines}};
+                        WL_E(generic_copy_box<T>(st, w.W, s0, y, s1, e));
                     }
+                    dom = "k_lift1d_inv3";
+                    llsrc = out3; ll_ls = n3; pp ^= 1;
+                    l -= 2;
+                    continue;
                 }
             }
             const int64_t nl = n >> (l - 1), hl = nl >> 1;
@@ -2212,22 +2076,17 @@ int lifting_lines_fast(void *ws, int cu_count, hipStream_t st, int64_t n, int64_
             a.o0 = stage ? w.W : out; a.o0_ls = stage ? nl : (to_y ? ld : nl);
             a.o1 = nullptr; a.o1_ls = 0;
             a.n = nl; a.ntiles = (hl + 247) / 248;
-            const bool streamable = nl >= 512 && (nl % 8) == 0;
-            if (streamable) { WL_LAUNCH_ID(0); }
-            else { hipError_t eg = launch_lift1d_gtile<T, 0>(id, st, a, nlines); if (eg != hipSuccess) { if (hip_err) *hip_err = (int)eg; return WL_EHIP; } }
-            WL_CHECK_LAUNCH();
+            if (streamable(nl)) WL_E((lift_lines_stream<T>(id, 0, st, a, nlines, cu_count)));
+            else WL_E((launch_lift1d_gtile<T, 0>(id, st, a, nlines)));
             if (stage) {
                 Extent3 e = {{nl, nlines, 1}};
                 Strides3 s0 = {{1, nl, nl * nlines}}, s1 = {{1, ld, ld * nlines}};
-                hipError_t e2 = generic_copy_box<T>(st, w.W, s0, y, s1, e);
-                if (e2 != hipSuccess) { if (hip_err) *hip_err = (int)e2; return WL_EHIP; }
+                WL_E(generic_copy_box<T>(st, w.W, s0, y, s1, e));
             }
-            dom = streamable ? "k_lift1d_stream" : "k_lift1d_gtile";
+            dom = streamable(nl) ? "k_lift1d_stream" : "k_lift1d_gtile";
             llsrc = out; ll_ls = nl; pp ^= 1;
         }
     }
-#undef WL_LAUNCH_ID
-#undef WL_CHECK_LAUNCH
     *handled = 1;
     if (kernel_name) *kernel_name = dom ? dom : "none";
     return WL_OK;
@@ -2294,8 +2153,7 @@ struct LiftAxisArgs {
     int64_t R, C;                                  // rows (contiguous), axis length
     int TP;                                        // output pairs per chunk (multiple of 8)
     int nstrips, nchunks;
-    T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
-    T norm1, norm2;
+    LiftCoefs<T> cf;
 };
 
 template <typename T, int ID, int FW, int RPL>
@@ -2342,7 +2200,7 @@ __global__ void __launch_bounds__(64) k_lift_axis_stream(LiftAxisArgs<T> a)
             ldv_l<T, RPL>(base + iw * a.lds, sv);
             ldv_l<T, RPL>(base + (half + iw) * a.lds, dv);
 #pragma unroll
-            for (int q = 0; q < RPL; ++q) { rs[slot][q] = a.norm1 * sv[q]; rd[slot][q] = a.norm2 * dv[q]; }
+            for (int q = 0; q < RPL; ++q) { rs[slot][q] = a.cf.norm1 * sv[q]; rd[slot][q] = a.cf.norm2 * dv[q]; }
         }
     };
 #pragma unroll
@@ -2363,13 +2221,13 @@ __global__ void __launch_bounds__(64) k_lift_axis_stream(LiftAxisArgs<T> a)
                 for (int kk = 0; kk < 3; ++kk)
                     if (kk < nc) o[kk] = upd ? rs[((u - Dk + ak + kk) % R + R) % R][q] : rd[((u - Dk + ak + kk) % R + R) % R][q];
                 const T x = upd ? rd[slot][q] : rs[slot][q];
-                T acc = a.c[k][0] * o[0];
-                if (nc > 1) acc = acc + a.c[k][1] * o[1];
-                if (nc > 2) acc = acc + a.c[k][2] * o[2];
+                T acc = a.cf.c[k][0] * o[0];
+                if (nc > 1) acc = acc + a.cf.c[k][1] * o[1];
+                if (nc > 2) acc = acc + a.cf.c[k][2] * o[2];
                 const T xin = x + acc;
-                T xb = x + a.c[k][0] * o[0];
-                if (nc > 1) xb = xb + a.c[k][1] * o[1];
-                if (nc > 2) xb = xb + a.c[k][2] * o[2];
+                T xb = x + a.cf.c[k][0] * o[0];
+                if (nc > 1) xb = xb + a.cf.c[k][1] * o[1];
+                if (nc > 2) xb = xb + a.cf.c[k][2] * o[2];
                 const T res = inb ? xin : xb;
                 if (upd) rd[slot][q] = res; else rs[slot][q] = res;
             }
@@ -2380,7 +2238,7 @@ __global__ void __launch_bounds__(64) k_lift_axis_stream(LiftAxisArgs<T> a)
             if (FW) {
                 T so[RPL], dO[RPL];
 #pragma unroll
-                for (int q = 0; q < RPL; ++q) { so[q] = rs[slot][q] * a.norm1; dO[q] = rd[slot][q] * a.norm2; }
+                for (int q = 0; q < RPL; ++q) { so[q] = rs[slot][q] * a.cf.norm1; dO[q] = rd[slot][q] * a.cf.norm2; }
                 stv_l<T, RPL>(out + io * a.ldd, so);
                 stv_l<T, RPL>(out + (half + io) * a.ldd, dO);
             } else {
@@ -2414,8 +2272,7 @@ struct Lift2DArgs {
     int TP, nstrips, nchunks;
     // batch of independent blocks (blockIdx.y: the planes of a 3-D level); only the first nll blocks use ll
     int64_t bs_src, bs_y, bs_ll; int nll;
-    T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
-    T norm1, norm2;
+    LiftCoefs<T> cf;
     // a batch of cubes of 2^vsh planes: block blockIdx.y is plane blockIdx.y mod 2^vsh of cube blockIdx.y >> vsh.  The cubes lie vs
     // elements (below 2^31) apart in the coefficient array (fw: y, inv: src); the block to transform / the result block is dense over
     // all planes of the batch (bs_src / bs_y apart), ll holds the nll planes of every cube back to back.  The defaults leave one run of
@@ -2484,15 +2341,15 @@ __device__ __forceinline__ void lift2d_fwd_body(const Lift2DArgs<T> &a, T *const
                 for (int kk = 0; kk < 3; ++kk)
                     if (kk < nc) o[kk] = upd ? rs[((u - Dk + ak + kk) % R + R) % R][q] : rd[((u - Dk + ak + kk) % R + R) % R][q];
                 const T x = upd ? rd[slot][q] : rs[slot][q];
-                T acc = a.c[k][0] * o[0];
-                if (nc > 1) acc = acc + a.c[k][1] * o[1];
-                if (nc > 2) acc = acc + a.c[k][2] * o[2];
+                T acc = a.cf.c[k][0] * o[0];
+                if (nc > 1) acc = acc + a.cf.c[k][1] * o[1];
+                if (nc > 2) acc = acc + a.cf.c[k][2] * o[2];
                 const T xin = x + acc;
                 T res = xin;
                 if constexpr (!FAST) {
-                    T xb = x + a.c[k][0] * o[0];
-                    if (nc > 1) xb = xb + a.c[k][1] * o[1];
-                    if (nc > 2) xb = xb + a.c[k][2] * o[2];
+                    T xb = x + a.cf.c[k][0] * o[0];
+                    if (nc > 1) xb = xb + a.cf.c[k][1] * o[1];
+                    if (nc > 2) xb = xb + a.cf.c[k][2] * o[2];
                     res = inb ? xin : xb;
                 }
                 if (upd) rd[slot][q] = res; else rs[slot][q] = res;
@@ -2505,19 +2362,19 @@ __device__ __forceinline__ void lift2d_fwd_body(const Lift2DArgs<T> &a, T *const
             T s1[2], d1[2], s2[2], d2[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                s1[j] = rs[slot][2 * j] * a.norm1; d1[j] = rs[slot][2 * j + 1] * a.norm1;
-                s2[j] = rd[slot][2 * j] * a.norm2; d2[j] = rd[slot][2 * j + 1] * a.norm2;
+                s1[j] = rs[slot][2 * j] * a.cf.norm1; d1[j] = rs[slot][2 * j + 1] * a.cf.norm1;
+                s2[j] = rd[slot][2 * j] * a.cf.norm2; d2[j] = rd[slot][2 * j + 1] * a.cf.norm2;
             }
-            lift_steps_lane<T, ID, 2, FAST>(s1, d1, a.c, kfirst, h0);
-            lift_steps_lane<T, ID, 2, FAST>(s2, d2, a.c, kfirst, h0);
+            lift_steps_lane<T, ID, 2, FAST>(s1, d1, a.cf.c, kfirst, h0);
+            lift_steps_lane<T, ID, 2, FAST>(s2, d2, a.cf.c, kfirst, h0);
             // lane pairs (2i, 2i+1) own rows k0..k0+1 and k0+2..k0+3 of the same four sub-band columns: they swap
             // halves so that the even lane stores 4 rows of LL and HL (left column), the odd lane 4 rows of LH and HH
             const bool odd = (lane & 1) != 0;
             T ll_[2], hl_[2], lh_[2], hh_[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                ll_[j] = s1[j] * a.norm1; hl_[j] = d1[j] * a.norm2;
-                lh_[j] = s2[j] * a.norm1; hh_[j] = d2[j] * a.norm2;
+                ll_[j] = s1[j] * a.cf.norm1; hl_[j] = d1[j] * a.cf.norm2;
+                lh_[j] = s2[j] * a.cf.norm1; hh_[j] = d2[j] * a.cf.norm2;
             }
             T o0[4], o1[4];
 #pragma unroll
@@ -2634,15 +2491,15 @@ __device__ __forceinline__ void lift2d_inv_body(const Lift2DArgs<T> &a)
             T s1[2], d1[2], s2[2], d2[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                s1[j] = a.norm1 * qLs[u][j]; d1[j] = a.norm2 * qLd[u][j];
-                s2[j] = a.norm1 * qRs[u][j]; d2[j] = a.norm2 * qRd[u][j];
+                s1[j] = a.cf.norm1 * qLs[u][j]; d1[j] = a.cf.norm2 * qLd[u][j];
+                s2[j] = a.cf.norm1 * qRs[u][j]; d2[j] = a.cf.norm2 * qRd[u][j];
             }
-            lift_steps_lane<T, ID, 2, FAST>(s1, d1, a.c, kw, h0);
-            lift_steps_lane<T, ID, 2, FAST>(s2, d2, a.c, kw, h0);
+            lift_steps_lane<T, ID, 2, FAST>(s1, d1, a.cf.c, kw, h0);
+            lift_steps_lane<T, ID, 2, FAST>(s2, d2, a.cf.c, kw, h0);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                rs[u][2 * j] = a.norm1 * s1[j]; rs[u][2 * j + 1] = a.norm1 * d1[j];          // merge!, then normalize! of dim 2
-                rd[u][2 * j] = a.norm2 * s2[j]; rd[u][2 * j + 1] = a.norm2 * d2[j];
+                rs[u][2 * j] = a.cf.norm1 * s1[j]; rs[u][2 * j + 1] = a.cf.norm1 * d1[j];          // merge!, then normalize! of dim 2
+                rd[u][2 * j] = a.cf.norm2 * s2[j]; rd[u][2 * j + 1] = a.cf.norm2 * d2[j];
             }
         }
         load_raw(tau + PF, (u + PF) % R);
@@ -2659,15 +2516,15 @@ __device__ __forceinline__ void lift2d_inv_body(const Lift2DArgs<T> &a)
                 for (int kk = 0; kk < 3; ++kk)
                     if (kk < nc) o[kk] = upd ? rs[((u - Dk + ak + kk) % R + R) % R][q] : rd[((u - Dk + ak + kk) % R + R) % R][q];
                 const T x = upd ? rd[slot][q] : rs[slot][q];
-                T acc = a.c[k][0] * o[0];
-                if (nc > 1) acc = acc + a.c[k][1] * o[1];
-                if (nc > 2) acc = acc + a.c[k][2] * o[2];
+                T acc = a.cf.c[k][0] * o[0];
+                if (nc > 1) acc = acc + a.cf.c[k][1] * o[1];
+                if (nc > 2) acc = acc + a.cf.c[k][2] * o[2];
                 const T xin = x + acc;
                 T res = xin;
                 if constexpr (!FAST) {
-                    T xb = x + a.c[k][0] * o[0];
-                    if (nc > 1) xb = xb + a.c[k][1] * o[1];
-                    if (nc > 2) xb = xb + a.c[k][2] * o[2];
+                    T xb = x + a.cf.c[k][0] * o[0];
+                    if (nc > 1) xb = xb + a.cf.c[k][1] * o[1];
+                    if (nc > 2) xb = xb + a.cf.c[k][2] * o[2];
                     res = inb ? xin : xb;
                 }
                 if (upd) rd[slot][q] = res; else rs[slot][q] = res;
@@ -2725,7 +2582,7 @@ static hipError_t lift2d_launch_split(const Lift2DArgs<T> &a, int64_t nbatch, bo
 }
 
 template <typename T, int ID>
-static hipError_t launch_lift2d_inv(hipStream_t st, Lift2DArgs<T> a, int cu_count, int64_t nbatch = 1)
+static hipError_t launch_lift2d_inv_id(hipStream_t st, Lift2DArgs<T> a, int cu_count, int64_t nbatch)
 {
     constexpr int VR = (64 - 2 * kLift2dML) * 4;
     a.nstrips = (int)((a.n0 + VR - 1) / VR);
@@ -2749,7 +2606,7 @@ static hipError_t launch_lift2d_inv(hipStream_t st, Lift2DArgs<T> a, int cu_coun
 }
 
 template <typename T, int ID>
-static hipError_t launch_lift2d_fwd(hipStream_t st, Lift2DArgs<T> a, int cu_count, int64_t nbatch = 1)
+static hipError_t launch_lift2d_fwd_id(hipStream_t st, Lift2DArgs<T> a, int cu_count, int64_t nbatch)
 {
     constexpr int VR = (64 - 2 * kLift2dML) * 4;
     a.nstrips = (int)((a.n0 + VR - 1) / VR);
@@ -2771,6 +2628,18 @@ static hipError_t launch_lift2d_fwd(hipStream_t st, Lift2DArgs<T> a, int cu_coun
     });
 }
 
+// the fused level kernels take the shapes of their own direction; hipErrorInvalidValue = not one
+template <typename T>
+static hipError_t launch_lift2d_fwd(int id, hipStream_t st, const Lift2DArgs<T> &a, int cu_count, int64_t nbatch)
+{
+    return by_shape_dir<1>(id, hipErrorInvalidValue, [&](auto sid) { return launch_lift2d_fwd_id<T, decltype(sid)::value>(st, a, cu_count, nbatch); });
+}
+template <typename T>
+static hipError_t launch_lift2d_inv(int id, hipStream_t st, const Lift2DArgs<T> &a, int cu_count, int64_t nbatch)
+{
+    return by_shape_dir<0>(id, hipErrorInvalidValue, [&](auto sid) { return launch_lift2d_inv_id<T, decltype(sid)::value>(st, a, cu_count, nbatch); });
+}
+
 template <typename T, int ID, int FW, int RPL>
 static hipError_t launch_lift_axis_r(hipStream_t st, LiftAxisArgs<T> a, int64_t batch, int cu_count)
 {
@@ -2782,12 +2651,11 @@ static hipError_t launch_lift_axis_r(hipStream_t st, LiftAxisArgs<T> a, int64_t 
     if (tpo >= 8 && (tpo % 8) == 0) TP = tpo;
     a.TP = TP;
     a.nchunks = (int)((half + TP - 1) / TP);
-    for (int64_t b0 = 0; b0 < batch; b0 += 32768) {
-        const int64_t nb = (batch - b0 < 32768) ? (batch - b0) : 32768;
+    for_line_slabs(batch, 32768, [&](int64_t b0, int64_t nb) {
         LiftAxisArgs<T> b = a;
         b.src = a.src + b0 * a.bs_src; b.dst = a.dst + b0 * a.bs_dst;
         hipLaunchKernelGGL((k_lift_axis_stream<T, ID, FW, RPL>), dim3((unsigned)(a.nstrips * a.nchunks), (unsigned)nb), dim3(64), 0, st, b);
-    }
+    });
     return hipGetLastError();
 }
 // 16 bytes of rows per lane when the geometry allows it, single rows otherwise (tiny blocks)
@@ -2803,14 +2671,7 @@ static hipError_t launch_lift_axis(hipStream_t st, const LiftAxisArgs<T> &a, int
 template <typename T, int FWV>
 static hipError_t launch_lift_axis_id(int id, hipStream_t st, const LiftAxisArgs<T> &a, int64_t batch, int cu_count)
 {
-    switch (id) {
-    case 0: return launch_lift_axis<T, 0, FWV>(st, a, batch, cu_count);
-    case 1: return launch_lift_axis<T, 1, FWV>(st, a, batch, cu_count);
-    case 2: return launch_lift_axis<T, 2, FWV>(st, a, batch, cu_count);
-    case 3: return launch_lift_axis<T, 3, FWV>(st, a, batch, cu_count);
-    case 4: return launch_lift_axis<T, 4, FWV>(st, a, batch, cu_count);
-    default: return launch_lift_axis<T, 5, FWV>(st, a, batch, cu_count);
-    }
+    return by_shape(id, hipErrorInvalidValue, [&](auto sid) { return launch_lift_axis<T, decltype(sid)::value, FWV>(st, a, batch, cu_count); });
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -2833,8 +2694,7 @@ struct LiftShortArgs {
     int av = 0, bv = 0, o0v = 0, o1v = 0, llv = 0;
     int n, G, c2;
     int64_t nlines;
-    T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
-    T norm1, norm2;
+    LiftCoefs<T> cf;
 };
 
 template <typename T, int ID, int FW, int PPL>
@@ -2864,7 +2724,7 @@ __global__ void __launch_bounds__(256) k_lift_short_lines(LiftShortArgs<T> a)
         ldv_l<T, PPL>((corner ? a.ll + i2 * a.ll2 + i3 * a.ll3 + (int64_t)iv * a.llv : a.a + i2 * a.a2 + i3 * a.a3 + (int64_t)iv * a.av) + PPL * r, sv);
         ldv_l<T, PPL>(a.b + i2 * a.b2 + i3 * a.b3 + (int64_t)iv * a.bv + PPL * r, dv);
 #pragma unroll
-        for (int j = 0; j < PPL; ++j) { s[j] = a.norm1 * sv[j]; d[j] = a.norm2 * dv[j]; }       // normalize! (inverse first)
+        for (int j = 0; j < PPL; ++j) { s[j] = a.cf.norm1 * sv[j]; d[j] = a.cf.norm2 * dv[j]; }       // normalize! (inverse first)
     }
 #pragma unroll
     for (int st = 0; st < SH::NS; ++st) {
@@ -2891,13 +2751,13 @@ __global__ void __launch_bounds__(256) k_lift_short_lines(LiftShortArgs<T> a)
             const int64_t jg = (int64_t)PPL * r + jj - sh;
             const bool inb = (jg >= 0) && (jg + nc - 1 <= half - 1);
             const T x = upd ? d[jj] : s[jj];
-            T acc = a.c[st][0] * o[0];
-            if (nc > 1) acc = acc + a.c[st][1] * o[1];
-            if (nc > 2) acc = acc + a.c[st][2] * o[2];
+            T acc = a.cf.c[st][0] * o[0];
+            if (nc > 1) acc = acc + a.cf.c[st][1] * o[1];
+            if (nc > 2) acc = acc + a.cf.c[st][2] * o[2];
             const T xin = x + acc;
-            T xb = x + a.c[st][0] * o[0];
-            if (nc > 1) xb = xb + a.c[st][1] * o[1];
-            if (nc > 2) xb = xb + a.c[st][2] * o[2];
+            T xb = x + a.cf.c[st][0] * o[0];
+            if (nc > 1) xb = xb + a.cf.c[st][1] * o[1];
+            if (nc > 2) xb = xb + a.cf.c[st][2] * o[2];
             res[jj] = inb ? xin : xb;
         }
 #pragma unroll
@@ -2906,7 +2766,7 @@ __global__ void __launch_bounds__(256) k_lift_short_lines(LiftShortArgs<T> a)
     if (FW) {
         T so[PPL], dO[PPL];
 #pragma unroll
-        for (int j = 0; j < PPL; ++j) { so[j] = s[j] * a.norm1; dO[j] = d[j] * a.norm2; }        // normalize!
+        for (int j = 0; j < PPL; ++j) { so[j] = s[j] * a.cf.norm1; dO[j] = d[j] * a.cf.norm2; }        // normalize!
         if (valid) {
             stv_l<T, PPL>((corner ? a.ll + i2 * a.ll2 + i3 * a.ll3 + (int64_t)iv * a.llv : a.o0 + i2 * a.o02 + i3 * a.o03 + (int64_t)iv * a.o0v) + PPL * r, so);
             stv_l<T, PPL>(a.o1 + i2 * a.o12 + i3 * a.o13 + (int64_t)iv * a.o1v + PPL * r, dO);
@@ -2940,27 +2800,7 @@ static hipError_t launch_lift_short(hipStream_t st, LiftShortArgs<T> a, int n, i
 template <typename T, int FWV>
 static hipError_t launch_lift_short_id(int id, hipStream_t st, const LiftShortArgs<T> &a, int n, int c2, int64_t c3)
 {
-    switch (id) {
-    case 0: return launch_lift_short<T, 0, FWV>(st, a, n, c2, c3);
-    case 1: return launch_lift_short<T, 1, FWV>(st, a, n, c2, c3);
-    case 2: return launch_lift_short<T, 2, FWV>(st, a, n, c2, c3);
-    case 3: return launch_lift_short<T, 3, FWV>(st, a, n, c2, c3);
-    case 4: return launch_lift_short<T, 4, FWV>(st, a, n, c2, c3);
-    default: return launch_lift_short<T, 5, FWV>(st, a, n, c2, c3);
-    }
-}
-
-template <typename T, int FWV>
-static void launch_lines_id(int id, hipStream_t st, const Lift1DArgs<T> &a, int64_t nlines, int cu_count)
-{
-    switch (id) {
-    case 0: launch_stream_id<T, 0, FWV>(st, a, nlines, cu_count); break;
-    case 1: launch_stream_id<T, 1, FWV>(st, a, nlines, cu_count); break;
-    case 2: launch_stream_id<T, 2, FWV>(st, a, nlines, cu_count); break;
-    case 3: launch_stream_id<T, 3, FWV>(st, a, nlines, cu_count); break;
-    case 4: launch_stream_id<T, 4, FWV>(st, a, nlines, cu_count); break;
-    default: launch_stream_id<T, 5, FWV>(st, a, nlines, cu_count); break;
-    }
+    return by_shape(id, hipErrorInvalidValue, [&](auto sid) { return launch_lift_short<T, decltype(sid)::value, FWV>(st, a, n, c2, c3); });
 }
 
 // 2-D (square) lifting transform: per level the dim-2 pass streams along the strided axis (k_lift_axis_stream) and
@@ -2974,9 +2814,10 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
     constexpr int VEC = 16 / sizeof(T);
     const int id = match_shape<T>(sc);
     if (id < 0 || L < 1 || n0 < 2 || nimg < 1 || nimg > 65535) return WL_OK;
+    // a forward shape run forward or an inverse shape run backward: all but the stream, axis and short-line kernels are instantiated
+    // for the shapes of their own direction only
+    const bool own_dir = shape_in_dir(id, fw);
     if (nimg == 1) xs = 0;
-#define WL_E(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { if (hip_err) *hip_err = (int)e__; return WL_EHIP; } } while (0)
-#define WL_EL() WL_E(hipGetLastError())
     const int64_t N = n0 * n0 * nimg;
     Work<T> w = carve<T>(ws, N);
     // A batch is transformed level by level over all its images: image i of the source at xsrc + i * xbs, of the level-l approximation
@@ -2998,14 +2839,8 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
     Lift1DArgs<T> a;
     LiftAxisArgs<T> ax;
     LiftShortArgs<T> sa;
-    for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-        for (int k = 0; k < WL_MAX_NCOEF; ++k) {
-            a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
-            ax.c[i][k] = a.c[i][k];
-            sa.c[i][k] = a.c[i][k];
-        }
-    a.norm1 = ax.norm1 = sa.norm1 = sc.norm1;
-    a.norm2 = ax.norm2 = sa.norm2 = sc.norm2;
+    const LiftCoefs<T> cf = lift_coefs<T>(sc);
+    a.cf = ax.cf = sa.cf = cf;
     Strides3 full = {{1, ldy, nimg > 1 ? xs : ldy * n0}}, xfull = {{1, ldx, nimg > 1 ? xbs : ldx * n0}};
     auto lines_ok = [](int64_t n) { return n >= 512 && (n % 64) == 0; };
     auto fused_ok = [](int64_t n) { return n >= 128 && (n % 8) == 0; };     // k_lift2d_*: a lane's 4 rows wrap at most once
@@ -3024,15 +2859,15 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
             // every remaining level of a block <= 128 x 128 (Float32) in one workgroup's LDS, a thread per line (k_tail_lift2d_lds)
             // (measured r04, cdf9/7 forward: 64^2 all levels 11.2 us against 13.5 in the one-wave register tail; 128^2 24.4 against
             //  23.3 for a tile launch + the register tail -- a 128-sample line per thread keeps two waves busy, the tile kernel 16)
-            if ((id == 0 || id == 2 || id == 4) && tail_lift2d_lds_ok<T>(id, n) && n >= l_env("WL_LIFT_LDSTAIL2D_FMIN", 64) &&
+            if (own_dir && tail_lift2d_lds_ok<T>(id, n) && n >= l_env("WL_LIFT_LDSTAIL2D_FMIN", 64) &&
                 n <= l_env("WL_LIFT_LDSTAIL2D_FMAX", 64) && l_env("WL_NO_LIFT_TAIL2D", 0) == 0 && l_env("WL_LIFT_LDSTAIL2D", 1) != 0) {
-                WL_E((launch_tail_lift2d_lds<T, 1>(id, st, sc, cur, cur_ls, y, ldy, (int)n, L - l + 1, nimg, cur_bs, xs)));
+                WL_E((launch_tail_lift2d_lds<T, 1>(id, st, cf, cur, cur_ls, y, ldy, (int)n, L - l + 1, nimg, cur_bs, xs)));
                 any_fast = true; ldstail = (l == 1);          // (names the call only when the tail is the whole transform)
                 break;
             }
             if (n <= 64 && l_env("WL_NO_LIFT_TAIL2D", 0) == 0) {        // every remaining level inside one workgroup / one wave
-                if ((id == 0 || id == 2 || id == 4) && tail_lift2d_reg_ok<T>(id, (int)n) && l_env("WL_LIFT_REGTAIL2D", 1) != 0)
-                    WL_E((launch_tail_lift2d_reg<T, 1>(id, st, sc, cur, cur_ls, y, ldy, (int)n, L - l + 1, nimg, cur_bs, xs)));
+                if (own_dir && tail_lift2d_reg_ok<T>(id, (int)n) && l_env("WL_LIFT_REGTAIL2D", 1) != 0)
+                    WL_E((launch_tail_lift2d_reg<T, 1>(id, st, cf, cur, cur_ls, y, ldy, (int)n, L - l + 1, nimg, cur_bs, xs)));
                 else
                     WL_E((launch_tail_lift2d<T, 1>(st, sc, cur, cur_ls, y, ldy, (int)n, L - l + 1, nimg, cur_bs, xs)));
                 any_fast = true;
@@ -3051,25 +2886,21 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
                 continue;
             }
             // cache-resident levels: 64 x 64 tiles, one launch per level without the marching kernels' latency chain
-            if (aligned && l_env("WL_LIFT_TILE", 1) != 0 && n <= l_env("WL_LIFT_TILE_MAX", 2048) && lift2d_tile_ok(id, n) && (id == 0 || id == 2 || id == 4) &&
+            if (aligned && l_env("WL_LIFT_TILE", 1) != 0 && n <= l_env("WL_LIFT_TILE_MAX", 2048) && lift2d_tile_ok(id, n) && own_dir &&
                 (cur_ls % VEC) == 0 && al16(cur) && al16(llbuf) && cur != y) {
                 WL_E((lift2d_tile_launch<T>(id, 1, st, sc, cur, cur_ls, y, ldy, last ? (T *)nullptr : llbuf, h, n, nimg, cur_bs, xs, h * h)));
                 any_fast = true; tiled = true;
                 cur = llbuf; cur_ls = h; cur_bs = h * h; pp ^= 1;
                 continue;
             }
-            if (aligned && fused_ok(n) && n > l_env("WL_LIFT_GTILE_MAX", 0) && (id == 0 || id == 2 || id == 4) && l_env("WL_NO_LIFT2D_FUSED", 0) == 0 && (cur_ls % VEC) == 0 &&
+            if (aligned && fused_ok(n) && n > l_env("WL_LIFT_GTILE_MAX", 0) && own_dir && l_env("WL_NO_LIFT2D_FUSED", 0) == 0 && (cur_ls % VEC) == 0 &&
                 al16(cur) && al16(llbuf) && cur != y) {      // (in place, level 1 reads y while writing it: two passes via T0)
                 // both passes of the level in one kernel: read the block once, write the four quadrants once
                 Lift2DArgs<T> q2;
-                for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-                    for (int k = 0; k < WL_MAX_NCOEF; ++k) q2.c[i][k] = a.c[i][k];
-                q2.norm1 = a.norm1; q2.norm2 = a.norm2;
+                q2.cf = cf;
                 q2.src = cur; q2.lds = cur_ls; q2.y = y; q2.ldy = ldy; q2.ll = last ? (T *)nullptr : llbuf; q2.ldl = h; q2.n0 = n; q2.n1 = n;
                 q2.bs_src = cur_bs; q2.bs_y = xs; q2.bs_ll = h * h; q2.nll = (int)nimg;
-                if (id == 0) WL_E((launch_lift2d_fwd<T, 0>(st, q2, cu_count, nimg)));
-                else if (id == 2) WL_E((launch_lift2d_fwd<T, 2>(st, q2, cu_count, nimg)));
-                else WL_E((launch_lift2d_fwd<T, 4>(st, q2, cu_count, nimg)));
+                WL_E((launch_lift2d_fwd<T>(id, st, q2, cu_count, nimg)));
                 any_fast = true; fused = true;
                 cur = llbuf; cur_ls = h; cur_bs = h * h; pp ^= 1;
                 continue;
@@ -3084,10 +2915,10 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
                     a.b = nullptr; a.b_ls = 0; a.n = n; a.ntiles = (h + 247) / 248;
                     // columns [0, h): s -> LL, d -> y[h.., j]
                     a.a = w.T0; a.a_ls = n; a.o0 = lld; a.o0_ls = ldd; a.o1 = y + h; a.o1_ls = ldy;
-                    launch_lines_id<T, 1>(id, st, a, h, cu_count); WL_EL();
+                    WL_E((lift_lines_stream<T>(id, 1, st, a, h, cu_count)));
                     // columns [h, n): s -> y[0..h, j], d -> y[h.., j]
                     a.a = w.T0 + h * n; a.o0 = y + h * ldy; a.o0_ls = ldy; a.o1 = y + h * ldy + h; a.o1_ls = ldy;
-                    launch_lines_id<T, 1>(id, st, a, h, cu_count); WL_EL();
+                    WL_E((lift_lines_stream<T>(id, 1, st, a, h, cu_count)));
                 } else {
                     // every column of T0 in one launch; columns [0, h) send their approximation to the next level's buffer
                     sa.b = nullptr; sa.b2 = sa.b3 = 0; sa.a3 = n * n; sa.o03 = sa.o13 = xs; sa.ll3 = h * h;
@@ -3095,9 +2926,9 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
                     sa.ll = last ? (T *)nullptr : llbuf; sa.ll2 = h; sa.l2 = (int)h; sa.l3 = nimg;
                     WL_E((launch_lift_short_id<T, 1>(id, st, sa, (int)n, (int)n, nimg)));
                 }
-            } else if ((id == 0 || id == 2 || id == 4) && lift2d_gtile_ok<T>(id, n) && cur != y && l_env("WL_LIFT_GTILE", 1) != 0) {
+            } else if (own_dir && lift2d_gtile_ok<T>(id, n) && cur != y && l_env("WL_LIFT_GTILE", 1) != 0) {
                 // any even size: one tile launch instead of twelve one-thread-per-element launches
-                WL_E((launch_lift2d_gtile<T, 1>(id, st, sc, cur, cur_ls, y, ldy, last ? (T *)nullptr : llbuf, h, n, nimg, cur_bs, xs, h * h)));
+                WL_E((launch_lift2d_gtile<T, 1>(id, st, cf, cur, cur_ls, y, ldy, last ? (T *)nullptr : llbuf, h, n, nimg, cur_bs, xs, h * h)));
                 any_fast = true; gtile = true;
             } else {
                 Extent3 ext = {{n, n, nimg}}, lo = {{h, h, nimg}};                      // (the generic kernels leave the third extent alone)
@@ -3122,7 +2953,7 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
             while (l_lo > 1 && (n0 >> (l_lo - 2)) <= 64) --l_lo;
             // ... or, a thread per line in several waves, 128 x 128 (Float32): k_tail_lift2d_lds (inverse 128^2 all levels: 19.1 us
             //     against 20.9 for the register tail + a tile launch)
-            const bool lds128 = (id == 1 || id == 3 || id == 5) && l_env("WL_LIFT_LDSTAIL2D", 1) != 0 && l_lo >= 2 && l_lo <= L + 1 &&
+            const bool lds128 = own_dir && l_env("WL_LIFT_LDSTAIL2D", 1) != 0 && l_lo >= 2 && l_lo <= L + 1 &&
                                 tail_lift2d_lds_ok<T>(id, n0 >> (l_lo - 2)) && (n0 >> (l_lo - 2)) >= l_env("WL_LIFT_LDSTAIL2D_MIN", 128);
             if (lds128) --l_lo;
             if (l_lo <= L) {
@@ -3130,10 +2961,10 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
                 T *out = (l_lo == 1) ? y : (pp ? w.B : w.A);
                 const int64_t ldo = (l_lo == 1) ? ldy : n, out_bs = (l_lo == 1) ? xs : n * n;
                 if (lds128) {
-                    WL_E((launch_tail_lift2d_lds<T, 0>(id, st, sc, xsrc, ldx, out, ldo, (int)n, L - l_lo + 1, nimg, xbs, out_bs)));
+                    WL_E((launch_tail_lift2d_lds<T, 0>(id, st, cf, xsrc, ldx, out, ldo, (int)n, L - l_lo + 1, nimg, xbs, out_bs)));
                     ldstail = (l_lo == 1);
-                } else if ((id == 1 || id == 3 || id == 5) && tail_lift2d_reg_ok<T>(id, (int)n) && l_env("WL_LIFT_REGTAIL2D", 1) != 0)
-                    WL_E((launch_tail_lift2d_reg<T, 0>(id, st, sc, xsrc, ldx, out, ldo, (int)n, L - l_lo + 1, nimg, xbs, out_bs)));
+                } else if (own_dir && tail_lift2d_reg_ok<T>(id, (int)n) && l_env("WL_LIFT_REGTAIL2D", 1) != 0)
+                    WL_E((launch_tail_lift2d_reg<T, 0>(id, st, cf, xsrc, ldx, out, ldo, (int)n, L - l_lo + 1, nimg, xbs, out_bs)));
                 else
                     WL_E((launch_tail_lift2d<T, 0>(st, sc, xsrc, ldx, out, ldo, (int)n, L - l_lo + 1, nimg, xbs, out_bs)));
                 any_fast = true;
@@ -3160,24 +2991,20 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
                     continue;
                 }
             }
-            if (aligned && l_env("WL_LIFT_TILE", 1) != 0 && n <= l_env("WL_LIFT_TILE_MAX", 2048) && lift2d_tile_ok(id, n) && (id == 1 || id == 3 || id == 5) &&
+            if (aligned && l_env("WL_LIFT_TILE", 1) != 0 && n <= l_env("WL_LIFT_TILE_MAX", 2048) && lift2d_tile_ok(id, n) && own_dir &&
                 (!llsrc || (al16(llsrc) && (ll_ls % 2) == 0)) && out != xsrc) {
                 WL_E((lift2d_tile_launch<T>(id, 0, st, sc, xsrc, ldx, out, ldo, const_cast<T *>(llsrc), ll_ls, n, nimg, xbs, out_bs, ll_bs)));
                 any_fast = true; tiled = true;
                 llsrc = out; ll_ls = ldo; ll_bs = out_bs; pp ^= 1;
                 continue;
             }
-            if (aligned && fused_ok(n) && n > l_env("WL_LIFT_GTILE_MAX", 0) && (id == 1 || id == 3 || id == 5) && l_env("WL_NO_LIFT2D_FUSED", 0) == 0 && (ldo % VEC) == 0 && al16(out) &&
+            if (aligned && fused_ok(n) && n > l_env("WL_LIFT_GTILE_MAX", 0) && own_dir && l_env("WL_NO_LIFT2D_FUSED", 0) == 0 && (ldo % VEC) == 0 && al16(out) &&
                 (!llsrc || (al16(llsrc) && (ll_ls % 2) == 0)) && out != xsrc) {   // (in place, level 1 writes y while reading it)
                 Lift2DArgs<T> q2;
-                for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-                    for (int k = 0; k < WL_MAX_NCOEF; ++k) q2.c[i][k] = a.c[i][k];
-                q2.norm1 = a.norm1; q2.norm2 = a.norm2;
+                q2.cf = cf;
                 q2.src = xsrc; q2.lds = ldx; q2.y = out; q2.ldy = ldo; q2.ll = const_cast<T *>(llsrc); q2.ldl = ll_ls; q2.n0 = n; q2.n1 = n;
                 q2.bs_src = xbs; q2.bs_y = out_bs; q2.bs_ll = ll_bs; q2.nll = (int)nimg;
-                if (id == 1) WL_E((launch_lift2d_inv<T, 1>(st, q2, cu_count, nimg)));
-                else if (id == 3) WL_E((launch_lift2d_inv<T, 3>(st, q2, cu_count, nimg)));
-                else WL_E((launch_lift2d_inv<T, 5>(st, q2, cu_count, nimg)));
+                WL_E((launch_lift2d_inv<T>(id, st, q2, cu_count, nimg)));
                 any_fast = true; fused = true;
                 llsrc = out; ll_ls = ldo; ll_bs = out_bs; pp ^= 1;
                 continue;
@@ -3189,9 +3016,9 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
                     a.o0 = w.T0; a.o0_ls = n; a.o1 = nullptr; a.o1_ls = 0; a.n = n; a.ntiles = (h + 247) / 248;
                     if (llsrc) { a.a = llsrc; a.a_ls = ll_ls; } else { a.a = x; a.a_ls = ldy; }
                     a.b = x + h; a.b_ls = ldy;
-                    launch_lines_id<T, 0>(id, st, a, h, cu_count); WL_EL();
+                    WL_E((lift_lines_stream<T>(id, 0, st, a, h, cu_count)));
                     a.a = x + h * ldy; a.a_ls = ldy; a.b = x + h * ldy + h; a.b_ls = ldy; a.o0 = w.T0 + h * n;
-                    launch_lines_id<T, 0>(id, st, a, h, cu_count); WL_EL();
+                    WL_E((lift_lines_stream<T>(id, 0, st, a, h, cu_count)));
                 } else {
                     sa.o1 = nullptr; sa.o12 = sa.o13 = 0; sa.a3 = sa.b3 = xbs; sa.o03 = n * n; sa.ll3 = ll_bs;
                     sa.o0 = w.T0; sa.o02 = n; sa.a = xsrc; sa.a2 = ldx; sa.b = xsrc + h; sa.b2 = ldx;
@@ -3201,8 +3028,8 @@ int lifting_2d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, int64_t 
                 // rows (dim 2): streaming pass along the strided axis straight into the result
                 ax.src = w.T0; ax.lds = n; ax.bs_src = nimg > 1 ? n * n : 0; ax.dst = out; ax.ldd = ldo; ax.bs_dst = nimg > 1 ? out_bs : 0; ax.R = n; ax.C = n;
                 WL_E((launch_lift_axis_id<T, 0>(id, st, ax, nimg, cu_count)));
-            } else if ((id == 1 || id == 3 || id == 5) && lift2d_gtile_ok<T>(id, n) && out != xsrc && l_env("WL_LIFT_GTILE", 1) != 0) {
-                WL_E((launch_lift2d_gtile<T, 0>(id, st, sc, xsrc, ldx, out, ldo, const_cast<T *>(llsrc), ll_ls, n, nimg, xbs, out_bs, ll_bs)));
+            } else if (own_dir && lift2d_gtile_ok<T>(id, n) && out != xsrc && l_env("WL_LIFT_GTILE", 1) != 0) {
+                WL_E((launch_lift2d_gtile<T, 0>(id, st, cf, xsrc, ldx, out, ldo, const_cast<T *>(llsrc), ll_ls, n, nimg, xbs, out_bs, ll_bs)));
                 any_fast = true; gtile = true;
             } else {
                 Extent3 ext = {{n, n, nimg}}, lo = {{h, h, nimg}};
@@ -3246,7 +3073,7 @@ int64_t lifting_3d_fast_ws(const LiftScheme<T> &sc, int64_t n0, int L, int fw, c
     const int id = lift3d_shape<T>(sc, n0, L, x, y, nvol, xs, ys);
     if (id < 0) return -1;
     // the whole transform inside k_tail_lift3d (the tail takes the shapes of its own direction: 0 / 2 / 4 forward, 1 / 3 / 5 inverse)
-    if ((id & 1) == (fw ? 0 : 1) && tail_lift3d_ok<T>(id, n0) && l_env("WL_LIFT_TAIL3D", 1) != 0) return 0;
+    if (shape_in_dir(id, fw) && tail_lift3d_ok<T>(id, n0) && l_env("WL_LIFT_TAIL3D", 1) != 0) return 0;
     const int64_t N = n0 * n0 * n0;
     return (int64_t)(nvol > 1 ? ws_lift_vols_elems(N, nvol) : ws_elems(N));
 }
@@ -3257,6 +3084,7 @@ int lifting_3d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, T *y, co
     *handled = 0;
     const int id = lift3d_shape<T>(sc, n0, L, x, y, nvol, xs, ys);
     if (id < 0) return WL_OK;
+    const bool own_dir = shape_in_dir(id, fw);              // (as in lifting_2d_fast)
     if (nvol == 1) xs = ys = 0;
     const int64_t N = n0 * n0 * n0;
     Work<T> w = carve<T>(ws, N);
@@ -3265,13 +3093,8 @@ int lifting_3d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, T *y, co
     }
     LiftAxisArgs<T> ax;
     LiftShortArgs<T> sa;
-    for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-        for (int k = 0; k < WL_MAX_NCOEF; ++k) {
-            ax.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
-            sa.c[i][k] = ax.c[i][k];
-        }
-    ax.norm1 = sa.norm1 = sc.norm1;
-    ax.norm2 = sa.norm2 = sc.norm2;
+    const LiftCoefs<T> cf = lift_coefs<T>(sc);
+    ax.cf = sa.cf = cf;
     const int64_t y1 = n0, y2 = n0 * n0;
     auto lg2 = [](int64_t n) { int k = 0; while (((int64_t)1 << k) < n) ++k; return k; };
     if (fw) {
@@ -3283,8 +3106,8 @@ int lifting_3d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, T *y, co
             const bool last = (l == L);
             T *llbuf = pp ? w.B : w.A;
             // every remaining level inside one workgroup's LDS (k_tail_lift3d), a workgroup per cube
-            if ((id == 0 || id == 2 || id == 4) && tail_lift3d_ok<T>(id, n) && l_env("WL_LIFT_TAIL3D", 1) != 0) {
-                WL_E((launch_tail_lift3d<T, 1>(id, st, sc, cur, c1, c2, y, y1, y2, (int)n, L - l + 1, nvol, cv, ys)));
+            if (own_dir && tail_lift3d_ok<T>(id, n) && l_env("WL_LIFT_TAIL3D", 1) != 0) {
+                WL_E((launch_tail_lift3d<T, 1>(id, st, cf, cur, c1, c2, y, y1, y2, (int)n, L - l + 1, nvol, cv, ys)));
                 break;
             }
             // planes (dim 3): the cube is an (n*n) x n matrix when its first two dims are dense
@@ -3294,18 +3117,14 @@ int lifting_3d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, T *y, co
             } else {       // (not reached: level 1 reads the dense cube, deeper levels the dense approximation buffer)
                 return WL_OK;
             }
-            if (n >= 128 && (id == 0 || id == 2 || id == 4) && l_env("WL_NO_LIFT2D_FUSED", 0) == 0) {
+            if (n >= 128 && own_dir && l_env("WL_NO_LIFT2D_FUSED", 0) == 0) {
                 // rows + columns of every plane in one launch (fused 2-D level kernel batched over the planes)
                 Lift2DArgs<T> q2;
-                for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-                    for (int k = 0; k < WL_MAX_NCOEF; ++k) q2.c[i][k] = ax.c[i][k];
-                q2.norm1 = ax.norm1; q2.norm2 = ax.norm2;
+                q2.cf = cf;
                 q2.src = w.T0; q2.lds = n; q2.y = y; q2.ldy = y1; q2.ll = last ? (T *)nullptr : llbuf; q2.ldl = h; q2.n0 = n; q2.n1 = n;
                 q2.bs_src = n * n; q2.bs_y = y2; q2.bs_ll = h * h; q2.nll = (int)h;
                 q2.vsh = lg2(n); q2.vs = (int)ys;
-                if (id == 0) WL_E((launch_lift2d_fwd<T, 0>(st, q2, cu_count, n * nvol)));
-                else if (id == 2) WL_E((launch_lift2d_fwd<T, 2>(st, q2, cu_count, n * nvol)));
-                else WL_E((launch_lift2d_fwd<T, 4>(st, q2, cu_count, n * nvol)));
+                WL_E((launch_lift2d_fwd<T>(id, st, q2, cu_count, n * nvol)));
                 cur = llbuf; c1 = h; c2 = h * h; cv = nvol > 1 ? h * h * h : 0; pp ^= 1;
                 continue;
             }
@@ -3327,12 +3146,12 @@ int lifting_3d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, T *y, co
         int l_top = L;
         // the deepest levels (outputs of <= 32^3 Float32 / 16^3 Float64) inside one workgroup's LDS (k_tail_lift3d), a workgroup per cube:
         // each writes its cube's slot of the ping-pong buffer (or its cube of y)
-        if ((id == 1 || id == 3 || id == 5) && l_env("WL_LIFT_TAIL3D", 1) != 0 && tail_lift3d_ok<T>(id, n0 >> (L - 1))) {
+        if (own_dir && l_env("WL_LIFT_TAIL3D", 1) != 0 && tail_lift3d_ok<T>(id, n0 >> (L - 1))) {
             int lt = L;
             while (lt > 1 && tail_lift3d_ok<T>(id, n0 >> (lt - 2))) --lt;
             const int64_t m0 = n0 >> (lt - 1);
             T *out = (lt == 1) ? y : (pp ? w.B : w.A);
-            WL_E((launch_tail_lift3d<T, 0>(id, st, sc, x, y1, y2, out, (lt == 1) ? y1 : m0, (lt == 1) ? y2 : m0 * m0, (int)m0, L - lt + 1, nvol, xs,
+            WL_E((launch_tail_lift3d<T, 0>(id, st, cf, x, y1, y2, out, (lt == 1) ? y1 : m0, (lt == 1) ? y2 : m0 * m0, (int)m0, L - lt + 1, nvol, xs,
                                            (lt == 1) ? ys : m0 * m0 * m0)));
             llsrc = out; pp ^= 1;
             l_top = lt - 1;
@@ -3341,18 +3160,14 @@ int lifting_3d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, T *y, co
             const int64_t n = n0 >> (l - 1), h = n >> 1;
             T *out = (l == 1) ? y : (pp ? w.B : w.A);
             bool planes = false;
-            if (n >= 128 && (id == 1 || id == 3 || id == 5) && l_env("WL_NO_LIFT2D_FUSED", 0) == 0) {
+            if (n >= 128 && own_dir && l_env("WL_NO_LIFT2D_FUSED", 0) == 0) {
                 // columns + rows of every plane in one launch
                 Lift2DArgs<T> q2;
-                for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-                    for (int k = 0; k < WL_MAX_NCOEF; ++k) q2.c[i][k] = ax.c[i][k];
-                q2.norm1 = ax.norm1; q2.norm2 = ax.norm2;
+                q2.cf = cf;
                 q2.src = x; q2.lds = y1; q2.y = w.T1; q2.ldy = n; q2.ll = const_cast<T *>(llsrc); q2.ldl = h; q2.n0 = n; q2.n1 = n;
                 q2.bs_src = y2; q2.bs_y = n * n; q2.bs_ll = h * h; q2.nll = (int)h;
                 q2.vsh = lg2(n); q2.vs = (int)xs;
-                if (id == 1) WL_E((launch_lift2d_inv<T, 1>(st, q2, cu_count, n * nvol)));
-                else if (id == 3) WL_E((launch_lift2d_inv<T, 3>(st, q2, cu_count, n * nvol)));
-                else WL_E((launch_lift2d_inv<T, 5>(st, q2, cu_count, n * nvol)));
+                WL_E((launch_lift2d_inv<T>(id, st, q2, cu_count, n * nvol)));
                 planes = true;
             }
             if (!planes) {
@@ -3374,8 +3189,6 @@ int lifting_3d_fast(void *ws, int cu_count, hipStream_t st, int64_t n0, T *y, co
             llsrc = out; pp ^= 1;
         }
     }
-#undef WL_E
-#undef WL_EL
     *handled = 1;
     if (kernel_name) *kernel_name = nvol > 1 ? "k_lift_axis_stream+k_lift_short_lines_batch" : "k_lift_axis_stream+k_lift_short_lines";
     return WL_OK;

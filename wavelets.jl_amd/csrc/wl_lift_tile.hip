@@ -25,8 +25,7 @@ struct LiftTileArgs {
     T *ll; int64_t ldl;             // fw: approximation destination or nullptr (-> y);  inv: approximation source or nullptr (-> src)
     int n;
     int64_t bs_src, bs_y, bs_ll;    // batch of independent images (blockIdx.z): image strides of src, y and ll
-    T c[LIFT_FAST_STEPS][WL_MAX_NCOEF];
-    T norm1, norm2;
+    LiftCoefs<T> cf;
 };
 
 // the image of this workgroup (blockIdx.z) of a batch
@@ -147,14 +146,14 @@ __global__ void __launch_bounds__(256) k_lift2d_tile_fwd(LiftTileArgs<T> a)
                 s[q] = P[r + (2 * (SEG * seg + q)) * LD];
                 d[q] = P[r + (2 * (SEG * seg + q) + 1) * LD];
             }
-            seg_line_steps<T, ID, NP>(s, d, a.c, wrap_into(32 * by - HPE + SEG * seg, h), h);
+            seg_line_steps<T, ID, NP>(s, d, a.cf.c, wrap_into(32 * by - HPE + SEG * seg, h), h);
         }
         lds_barrier();                                  // every segment has read its cone before anybody overwrites it
         if (active) {
 #pragma unroll
             for (int q = HPE; q < HPE + SEG; ++q) {
-                P[r + (2 * (SEG * seg + q)) * LD] = s[q] * a.norm1;
-                P[r + (2 * (SEG * seg + q) + 1) * LD] = d[q] * a.norm2;
+                P[r + (2 * (SEG * seg + q)) * LD] = s[q] * a.cf.norm1;
+                P[r + (2 * (SEG * seg + q) + 1) * LD] = d[q] * a.cf.norm2;
             }
         }
         lds_barrier();
@@ -174,10 +173,10 @@ __global__ void __launch_bounds__(256) k_lift2d_tile_fwd(LiftTileArgs<T> a)
         T s[NP], d[NP];
 #pragma unroll
         for (int q = 0; q < NP; ++q) { s[q] = v[2 * q]; d[q] = v[2 * q + 1]; }
-        seg_line_steps<T, ID, NP>(s, d, a.c, wrap_into(32 * bx - HPE + SEG * seg, h), h);
+        seg_line_steps<T, ID, NP>(s, d, a.cf.c, wrap_into(32 * bx - HPE + SEG * seg, h), h);
         T so[SEG], dO[SEG];
 #pragma unroll
-        for (int q = 0; q < SEG; ++q) { so[q] = s[HPE + q] * a.norm1; dO[q] = d[HPE + q] * a.norm2; }
+        for (int q = 0; q < SEG; ++q) { so[q] = s[HPE + q] * a.cf.norm1; dO[q] = d[HPE + q] * a.cf.norm2; }
         const int gk = 32 * bx + SEG * seg;             // first owned row pair of this task
         const int gkc = 32 * by + (jc >> 1);            // column pair
         const bool dcol = (jc & 1) != 0;
@@ -261,14 +260,14 @@ __global__ void __launch_bounds__(512) k_lift2d_tile2_fwd(LiftTileArgs<T> a)
                 s[q] = P[r + (2 * (SEG * seg + q)) * LD1];
                 d[q] = P[r + (2 * (SEG * seg + q) + 1) * LD1];
             }
-            seg_line_steps<T, ID, NP>(s, d, a.c, wrap_into(32 * by - HS - HPE + SEG * seg, h), h);
+            seg_line_steps<T, ID, NP>(s, d, a.cf.c, wrap_into(32 * by - HS - HPE + SEG * seg, h), h);
         }
         lds_barrier();
         if (active) {
 #pragma unroll
             for (int q = HPE; q < HPE + SEG; ++q) {
-                P[r + (2 * (SEG * seg + q)) * LD1] = s[q] * a.norm1;
-                P[r + (2 * (SEG * seg + q) + 1) * LD1] = d[q] * a.norm2;
+                P[r + (2 * (SEG * seg + q)) * LD1] = s[q] * a.cf.norm1;
+                P[r + (2 * (SEG * seg + q) + 1) * LD1] = d[q] * a.cf.norm2;
             }
         }
         lds_barrier();
@@ -290,14 +289,14 @@ __global__ void __launch_bounds__(512) k_lift2d_tile2_fwd(LiftTileArgs<T> a)
             T s[NP], d[NP];
 #pragma unroll
             for (int q = 0; q < NP; ++q) { s[q] = v[2 * q]; d[q] = v[2 * q + 1]; }
-            seg_line_steps<T, ID, NP>(s, d, a.c, wrap_into(32 * bx - HS - HPE + SEG * seg, h), h);
+            seg_line_steps<T, ID, NP>(s, d, a.cf.c, wrap_into(32 * bx - HS - HPE + SEG * seg, h), h);
             const bool dcol = (jc & 1) != 0;
             const int pc = (jc >> 1) - HS;              // column pair relative to the tile's owned pairs (owned: 0 .. 31)
             const bool cown = pc >= 0 && pc < 32;
             const int gkc = 32 * by + pc;               // global column pair (valid where cown)
 #pragma unroll
             for (int q = 0; q < SEG; ++q) {
-                const T so = s[HPE + q] * a.norm1, dO = d[HPE + q] * a.norm2;
+                const T so = s[HPE + q] * a.cf.norm1, dO = d[HPE + q] * a.cf.norm2;
                 const int pr = SEG * seg + q - HS;      // row pair relative to the owned ones
                 if (!dcol) Q[(SEG * seg + q) + (jc >> 1) * LD2] = so;                // approximation: level 2's input (all P1 x P1)
                 if (cown && pr >= 0 && pr < 32) {
@@ -323,14 +322,14 @@ __global__ void __launch_bounds__(512) k_lift2d_tile2_fwd(LiftTileArgs<T> a)
                 s[q] = Q[r + (2 * (SEG * seg + q)) * LD2];
                 d[q] = Q[r + (2 * (SEG * seg + q) + 1) * LD2];
             }
-            seg_line_steps<T, ID, NP>(s, d, a.c, wrap_into(16 * by - HPE + SEG * seg, h2), h2);
+            seg_line_steps<T, ID, NP>(s, d, a.cf.c, wrap_into(16 * by - HPE + SEG * seg, h2), h2);
         }
         lds_barrier();
         if (active) {
 #pragma unroll
             for (int q = HPE; q < HPE + SEG; ++q) {
-                Q[r + (2 * (SEG * seg + q)) * LD2] = s[q] * a.norm1;
-                Q[r + (2 * (SEG * seg + q) + 1) * LD2] = d[q] * a.norm2;
+                Q[r + (2 * (SEG * seg + q)) * LD2] = s[q] * a.cf.norm1;
+                Q[r + (2 * (SEG * seg + q) + 1) * LD2] = d[q] * a.cf.norm2;
             }
         }
         lds_barrier();
@@ -344,7 +343,7 @@ __global__ void __launch_bounds__(512) k_lift2d_tile2_fwd(LiftTileArgs<T> a)
             T s[NP], d[NP];
 #pragma unroll
             for (int q = 0; q < NP; ++q) { s[q] = Q[2 * (SEG * seg + q) + c * LD2]; d[q] = Q[2 * (SEG * seg + q) + 1 + c * LD2]; }
-            seg_line_steps<T, ID, NP>(s, d, a.c, wrap_into(16 * bx - HPE + SEG * seg, h2), h2);
+            seg_line_steps<T, ID, NP>(s, d, a.cf.c, wrap_into(16 * bx - HPE + SEG * seg, h2), h2);
             const int gk = 16 * bx + SEG * seg;          // first owned level-2 row pair of this task
             const int gkc = 16 * by + (jc >> 1);
             const bool dcol = (jc & 1) != 0;
@@ -352,8 +351,8 @@ __global__ void __launch_bounds__(512) k_lift2d_tile2_fwd(LiftTileArgs<T> a)
             T *const hi = a.y + h2 + gk + (int64_t)((dcol ? h2 : 0) + gkc) * a.ldy;
 #pragma unroll
             for (int q = 0; q < SEG; ++q) {
-                lo[q] = s[HPE + q] * a.norm1;
-                hi[q] = d[HPE + q] * a.norm2;
+                lo[q] = s[HPE + q] * a.cf.norm1;
+                hi[q] = d[HPE + q] * a.cf.norm2;
             }
         }
     }
@@ -416,9 +415,9 @@ __global__ void __launch_bounds__(256) k_lift2d_tile_inv(LiftTileArgs<T> a)
                 const V t = *reinterpret_cast<const V *>(P + SEG * seg + VEC * e + cs * LD);
                 const V u = *reinterpret_cast<const V *>(P + REGP + SEG * seg + VEC * e + cs * LD);
 #pragma unroll
-                for (int i = 0; i < VEC; ++i) { s[VEC * e + i] = a.norm1 * t[i]; d[VEC * e + i] = a.norm2 * u[i]; }
+                for (int i = 0; i < VEC; ++i) { s[VEC * e + i] = a.cf.norm1 * t[i]; d[VEC * e + i] = a.cf.norm2 * u[i]; }
             }
-            seg_line_steps<T, ID, NP>(s, d, a.c, wrap_into(32 * bx - HPE + SEG * seg, h), h);
+            seg_line_steps<T, ID, NP>(s, d, a.cf.c, wrap_into(32 * bx - HPE + SEG * seg, h), h);
         }
         lds_barrier();
         if (active) {
@@ -441,10 +440,10 @@ __global__ void __launch_bounds__(256) k_lift2d_tile_inv(LiftTileArgs<T> a)
         T s[NP], d[NP];
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
-            s[q] = a.norm1 * P[r + (SEG * seg + q) * LD];
-            d[q] = a.norm2 * P[r + (REGP + SEG * seg + q) * LD];
+            s[q] = a.cf.norm1 * P[r + (SEG * seg + q) * LD];
+            d[q] = a.cf.norm2 * P[r + (REGP + SEG * seg + q) * LD];
         }
-        seg_line_steps<T, ID, NP>(s, d, a.c, wrap_into(32 * by - HPE + SEG * seg, h), h);
+        seg_line_steps<T, ID, NP>(s, d, a.cf.c, wrap_into(32 * by - HPE + SEG * seg, h), h);
         T *const o = a.y + 64 * bx + ir + (int64_t)(2 * (32 * by + SEG * seg)) * a.ldy;
 #pragma unroll
         for (int q = 0; q < SEG; ++q) {
@@ -538,10 +537,10 @@ __global__ void __launch_bounds__(256) k_lift2d_tile2_inv(LiftTileArgs<T> a)
         if (active) {
 #pragma unroll
             for (int q = 0; q < NP; ++q) {
-                s[q] = a.norm1 * C[SEG * seg + q + cs * LDC];
-                d[q] = a.norm2 * C[REGPC + SEG * seg + q + cs * LDC];
+                s[q] = a.cf.norm1 * C[SEG * seg + q + cs * LDC];
+                d[q] = a.cf.norm2 * C[REGPC + SEG * seg + q + cs * LDC];
             }
-            seg_line_steps<T, ID, NP>(s, d, a.c, wrap_into(c0x + SEG * seg, hc), hc);
+            seg_line_steps<T, ID, NP>(s, d, a.cf.c, wrap_into(c0x + SEG * seg, hc), hc);
         }
         lds_barrier();
         if (active) {
@@ -562,10 +561,10 @@ __global__ void __launch_bounds__(256) k_lift2d_tile2_inv(LiftTileArgs<T> a)
             T s[NP], d[NP];
 #pragma unroll
             for (int q = 0; q < NP; ++q) {
-                s[q] = a.norm1 * C[r + (SEG * seg + q) * LDC];
-                d[q] = a.norm2 * C[r + (REGPC + SEG * seg + q) * LDC];
+                s[q] = a.cf.norm1 * C[r + (SEG * seg + q) * LDC];
+                d[q] = a.cf.norm2 * C[r + (REGPC + SEG * seg + q) * LDC];
             }
-            seg_line_steps<T, ID, NP>(s, d, a.c, wrap_into(c0y + SEG * seg, hc), hc);
+            seg_line_steps<T, ID, NP>(s, d, a.cf.c, wrap_into(c0y + SEG * seg, hc), hc);
             // coarse output (row r, columns 2 (SEG seg + q - HPE), + 1) = the fine level's scaling x scaling block
 #pragma unroll
             for (int q = HPE; q < HPE + SEG; ++q) {
@@ -587,9 +586,9 @@ __global__ void __launch_bounds__(256) k_lift2d_tile2_inv(LiftTileArgs<T> a)
                 const V t = *reinterpret_cast<const V *>(P + SEG * seg + VEC * e + cs * LD);
                 const V u = *reinterpret_cast<const V *>(P + REGP + SEG * seg + VEC * e + cs * LD);
 #pragma unroll
-                for (int i = 0; i < VEC; ++i) { s[VEC * e + i] = a.norm1 * t[i]; d[VEC * e + i] = a.norm2 * u[i]; }
+                for (int i = 0; i < VEC; ++i) { s[VEC * e + i] = a.cf.norm1 * t[i]; d[VEC * e + i] = a.cf.norm2 * u[i]; }
             }
-            seg_line_steps<T, ID, NP>(s, d, a.c, wrap_into(32 * bx - HPE + SEG * seg, h), h);
+            seg_line_steps<T, ID, NP>(s, d, a.cf.c, wrap_into(32 * bx - HPE + SEG * seg, h), h);
         }
         lds_barrier();
         if (active) {
@@ -610,10 +609,10 @@ __global__ void __launch_bounds__(256) k_lift2d_tile2_inv(LiftTileArgs<T> a)
         T s[NP], d[NP];
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
-            s[q] = a.norm1 * P[r + (SEG * seg + q) * LD];
-            d[q] = a.norm2 * P[r + (REGP + SEG * seg + q) * LD];
+            s[q] = a.cf.norm1 * P[r + (SEG * seg + q) * LD];
+            d[q] = a.cf.norm2 * P[r + (REGP + SEG * seg + q) * LD];
         }
-        seg_line_steps<T, ID, NP>(s, d, a.c, wrap_into(32 * by - HPE + SEG * seg, h), h);
+        seg_line_steps<T, ID, NP>(s, d, a.cf.c, wrap_into(32 * by - HPE + SEG * seg, h), h);
         T *const o = a.y + 64 * bx + ir + (int64_t)(2 * (32 * by + SEG * seg)) * a.ldy;
 #pragma unroll
         for (int q = 0; q < SEG; ++q) {
@@ -636,39 +635,27 @@ hipError_t launch_tile_id(hipStream_t st, const LiftTileArgs<T> &a, unsigned nim
 
 bool lift2d_tile_ok(int id, int64_t n) { return id >= 0 && id <= 5 && n >= 128 && n <= 16384 && (n % 64) == 0; }
 // two forward levels per launch: the tile grid is that of the first level; the second level (n / 2) must still be a multiple of 32
-bool lift2d_tile2_ok(int id, int64_t n) { return (id == 0 || id == 2 || id == 4) && n >= 128 && n <= 16384 && (n % 64) == 0; }
+bool lift2d_tile2_ok(int id, int64_t n) { return shape_in_dir(id, 1) && n >= 128 && n <= 16384 && (n % 64) == 0; }
 
 template <typename T, int ID>
 static hipError_t launch_tile2_fwd_id(hipStream_t st, const LiftTileArgs<T> &a, unsigned nimg)
 {
     constexpr size_t shmem = (size_t)TileGeom2<ID>::ELEMS * sizeof(T);
-    static thread_local int done_dev = -1;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (done_dev != dev) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lift2d_tile2_fwd<T, ID>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        done_dev = dev;
-    }
+    hipError_t e = lift_max_lds_once<&k_lift2d_tile2_fwd<T, ID>>();
+    if (e != hipSuccess) return e;
     const unsigned g = (unsigned)(a.n / 64);
     hipLaunchKernelGGL((k_lift2d_tile2_fwd<T, ID>), dim3(g, g, nimg), dim3(512), shmem, st, a);
     return hipGetLastError();
 }
 
-bool lift2d_tile2_inv_ok(int id, int64_t n) { return (id == 1 || id == 3 || id == 5) && n >= 256 && n <= 16384 && (n % 64) == 0; }
+bool lift2d_tile2_inv_ok(int id, int64_t n) { return shape_in_dir(id, 0) && n >= 256 && n <= 16384 && (n % 64) == 0; }
 
 template <typename T, int ID>
 static hipError_t launch_tile2_inv_id(hipStream_t st, const LiftTileArgs<T> &a, unsigned nimg)
 {
     constexpr size_t shmem = (size_t)TileGeomInv2<ID>::ELEMS * sizeof(T);
-    static thread_local int done_dev = -1;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (done_dev != dev) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_lift2d_tile2_inv<T, ID>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        done_dev = dev;
-    }
+    hipError_t e = lift_max_lds_once<&k_lift2d_tile2_inv<T, ID>>();
+    if (e != hipSuccess) return e;
     const unsigned g = (unsigned)(a.n / 64);
     hipLaunchKernelGGL((k_lift2d_tile2_inv<T, ID>), dim3(g, g, nimg), dim3(256), shmem, st, a);
     return hipGetLastError();
@@ -684,15 +671,8 @@ hipError_t lift2d_tile2_inv_launch(int id, hipStream_t st, const LiftScheme<T> &
     LiftTileArgs<T> a;
     a.src = x; a.lds = ldx; a.y = out; a.ldy = ldo; a.ll = const_cast<T *>(ll); a.ldl = ldl; a.n = (int)n;
     a.bs_src = bs_x; a.bs_y = bs_out; a.bs_ll = bs_ll;
-    for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-        for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
-    a.norm1 = sc.norm1; a.norm2 = sc.norm2;
-    switch (id) {
-    case 1: return launch_tile2_inv_id<T, 1>(st, a, (unsigned)nimg);
-    case 3: return launch_tile2_inv_id<T, 3>(st, a, (unsigned)nimg);
-    case 5: return launch_tile2_inv_id<T, 5>(st, a, (unsigned)nimg);
-    default: return hipErrorInvalidValue;
-    }
+    a.cf = lift_coefs<T>(sc);
+    return by_shape_dir<0>(id, hipErrorInvalidValue, [&](auto sid) { return launch_tile2_inv_id<T, decltype(sid)::value>(st, a, (unsigned)nimg); });
 }
 template hipError_t lift2d_tile2_inv_launch<float>(int, hipStream_t, const LiftScheme<float> &, const float *, int64_t, float *, int64_t, const float *, int64_t,
                                                    int64_t, int64_t, int64_t, int64_t, int64_t);
@@ -708,15 +688,8 @@ hipError_t lift2d_tile2_fwd_launch(int id, hipStream_t st, const LiftScheme<T> &
     LiftTileArgs<T> a;
     a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.ll = ll; a.ldl = ldl; a.n = (int)n;
     a.bs_src = bs_src; a.bs_y = bs_y; a.bs_ll = bs_ll;
-    for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-        for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
-    a.norm1 = sc.norm1; a.norm2 = sc.norm2;
-    switch (id) {
-    case 0: return launch_tile2_fwd_id<T, 0>(st, a, (unsigned)nimg);
-    case 2: return launch_tile2_fwd_id<T, 2>(st, a, (unsigned)nimg);
-    case 4: return launch_tile2_fwd_id<T, 4>(st, a, (unsigned)nimg);
-    default: return hipErrorInvalidValue;
-    }
+    a.cf = lift_coefs<T>(sc);
+    return by_shape_dir<1>(id, hipErrorInvalidValue, [&](auto sid) { return launch_tile2_fwd_id<T, decltype(sid)::value>(st, a, (unsigned)nimg); });
 }
 template hipError_t lift2d_tile2_fwd_launch<float>(int, hipStream_t, const LiftScheme<float> &, const float *, int64_t, float *, int64_t, float *, int64_t, int64_t, int64_t, int64_t,
                                                    int64_t, int64_t);
@@ -731,18 +704,11 @@ hipError_t lift2d_tile_launch(int id, int fw, hipStream_t st, const LiftScheme<T
     LiftTileArgs<T> a;
     a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.ll = ll; a.ldl = ldl; a.n = (int)n;
     a.bs_src = bs_src; a.bs_y = bs_y; a.bs_ll = bs_ll;
-    for (int i = 0; i < LIFT_FAST_STEPS; ++i)
-        for (int k = 0; k < WL_MAX_NCOEF; ++k) a.c[i][k] = (i < sc.nsteps) ? sc.step[i].c[k] : (T)0;
-    a.norm1 = sc.norm1; a.norm2 = sc.norm2;
-    switch (id) {
-    case 0: return fw ? launch_tile_id<T, 0, 1>(st, a, (unsigned)nimg) : hipErrorInvalidValue;
-    case 2: return fw ? launch_tile_id<T, 2, 1>(st, a, (unsigned)nimg) : hipErrorInvalidValue;
-    case 4: return fw ? launch_tile_id<T, 4, 1>(st, a, (unsigned)nimg) : hipErrorInvalidValue;
-    case 1: return fw ? hipErrorInvalidValue : launch_tile_id<T, 1, 0>(st, a, (unsigned)nimg);
-    case 3: return fw ? hipErrorInvalidValue : launch_tile_id<T, 3, 0>(st, a, (unsigned)nimg);
-    case 5: return fw ? hipErrorInvalidValue : launch_tile_id<T, 5, 0>(st, a, (unsigned)nimg);
-    default: return hipErrorInvalidValue;
-    }
+    a.cf = lift_coefs<T>(sc);
+    return by_shape_dir(fw, id, hipErrorInvalidValue, [&](auto sid) {
+        constexpr int ID = decltype(sid)::value;
+        return launch_tile_id<T, ID, shape_fw(ID)>(st, a, (unsigned)nimg);
+    });
 }
 
 template hipError_t lift2d_tile_launch<float>(int, int, hipStream_t, const LiftScheme<float> &, const float *, int64_t, float *, int64_t, float *,
