@@ -296,6 +296,37 @@ WL_API int wl_modwt(wl_ctx *ctx, int dtype, void *out, int64_t ldo, const void *
  * replaces imodwt + imodwt_step, transforms_maximal_overlap.jl:72-107.                     */
 WL_API int wl_imodwt(wl_ctx *ctx, int dtype, void *x, const void *xw, int64_t ldw, int64_t n, int ncols,
               const double *qmf, int flen, void *stream);
+/* ---- maximal-overlap DWT of a batch ------------------------------------------------------------------- */
+/* out_u = modwt(x_u, filter, L) of nunits independent vectors: unit u of x is the n elements at element offset u * unit_stride
+ * (>= n); unit u of out is the column-major n x (L+1) matrix at u * out_unit_stride, leading dimension ldo >= n,
+ * out_unit_stride >= ldo * (L+1); columns as wl_modwt lays them out (column j-1 = level-j details, column L = level-L scaling
+ * coefficients).  The reference has no batched form; the result is BIT FOR BIT what nunits calls of wl_modwt give (the arithmetic
+ * is the one of wl_modwt on every path: Float64 taps / sqrt 2, tap order, every partial sum rounded to the element type).  In the
+ * fused library the batch meets the tolerance contract of wl_modwt there; bit equality between the tiers is not claimed in it.
+ * Nothing outside [0, n) of any column of any unit is written: not the rows n .. ldo-1, not the columns behind L, not the padding
+ * between units.  The call only enqueues on `stream`, never synchronises, and is capturable in a hipGraph once the workspace is
+ * held.  Two tiers, named by wl_last_kernel:
+ *  - "k_modwt_lds": units with 2 * n * sizeof(T) <= 64 KB (n <= 8192 Float32, n <= 4096 Float64): ONE launch runs all L levels,
+ *    the scaling coefficients ping-ponged in LDS; each unit is read once and each output column written once.  No limit on nunits.
+ *  - "k_modwt_step_b": longer units, or every batch after wl_ctx_set_option(ctx, "WL_MODWT_FUSED", 0): one launch per level over
+ *    all units of a group (the kernels of wl_modwt with the unit in the grid's y).  16-byte accesses need every unit base on a
+ *    16-byte boundary (n, ldo and, for nunits > 1, the two unit strides multiples of 16 bytes, x and out aligned); any other
+ *    batch takes the element-wise kernel, as wl_modwt does.
+ * Status codes in this order: WL_EINVAL_ARG (NULL ctx / out / x / qmf), WL_EINVAL_DTYPE, WL_EINVAL_FILTER, WL_EDIMS (n < 1,
+ * nunits < 1, unit_stride < n, ldo < n, out_unit_stride < ldo * (L+1), a product that no int64 holds or nunits * stride >= 2^60),
+ * WL_EALIAS (the units of out and of x overlap), WL_EINVAL_SIZE (L > floor(log2 n)), WL_EINVAL_L (L < 1).
+ * Workspace: the LDS tier holds nothing.  The per-level tier takes the units in groups of G -- all of them, at most 65535 (context
+ * option WL_MODWT_BATCH_GROUP lowers it), halved until the group's two scaling buffers, 2 * G * n elements, are below the
+ * context's cap (option WL_TI_WS_CAP_MB, default 8192) -- and holds those 2 * G * n elements; groups change no bit.              */
+WL_API int wl_modwt_batch(wl_ctx *ctx, int dtype, void *out, int64_t ldo, int64_t out_unit_stride, const void *x, int64_t n,
+                          int64_t nunits, int64_t unit_stride, const double *qmf, int flen, int L, void *stream);
+/* x_u = imodwt(xw_u, filter) of nunits coefficient matrices laid out as wl_modwt_batch writes them (n x ncols, leading dimension
+ * ldw >= n, unit u at u * xw_unit_stride >= ldw * ncols); x_u is the n elements at u * unit_stride (>= n).  BIT FOR BIT nunits calls
+ * of wl_imodwt; ncols == 1 copies the column, as wl_imodwt does ("copy").  Tiers "k_imodwt_lds" / "k_imodwt_step_b", padding,
+ * stream and workspace rules as above.  Status codes in this order: WL_EINVAL_ARG (NULL ctx / x / xw / qmf), WL_EINVAL_DTYPE,
+ * WL_EINVAL_FILTER, WL_EDIMS (as above, with ldw, xw_unit_stride and ncols), WL_EALIAS, WL_EINVAL_L (ncols < 1, ncols - 1 > 62).  */
+WL_API int wl_imodwt_batch(wl_ctx *ctx, int dtype, void *x, int64_t unit_stride, const void *xw, int64_t ldw, int64_t xw_unit_stride,
+                           int64_t n, int ncols, int64_t nunits, const double *qmf, int flen, void *stream);
 
 /* ---- thresholding and noise estimate -------------------- */
 /* THType of src/Threshold/threshold_main.jl:8-15 (BiggestTH has its own entry point).      */

@@ -82,6 +82,8 @@ SIGNATURES = {
     "wl_maxmodwttransformlevels": (C.c_int, [C.c_int64]),
     "wl_modwt": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _f64p, C.c_int, C.c_int, _vp]),
     "wl_imodwt": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, C.c_int64, C.c_int, _f64p, C.c_int, _vp]),
+    "wl_modwt_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int64, _f64p, C.c_int, C.c_int, _vp]),
+    "wl_imodwt_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, _f64p, C.c_int, _vp]),
     "wl_threshold": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int, C.c_double, C.c_int, _vp]),
     "wl_threshold_biggest": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int64, _vp]),
     "wl_median": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _f64p, _vp]),

@@ -446,5 +446,6 @@ include("WaveletsMI355X_denoise_batch.jl")
 include("WaveletsMI355X_wpt_batch.jl")
 include("WaveletsMI355X_complex.jl")
 include("WaveletsMI355X_bestbasis_batch.jl")
+include("WaveletsMI355X_modwt_batch.jl")
 
 end # module
