@@ -441,6 +441,47 @@ WL_API int wl_denoise_batch_lifting(wl_ctx *ctx, int dtype, void *y, const void 
                                     double norm1, double norm2, int L, int th, double t_unit,
                                     const double *sigma_in, double *sigma_out, void *stream);
 
+/* y[.., i] = denoise(x[.., i], OrthoFilter(qmf); L, dnt = (th, t_unit), TI = true, nspin) for nunits independent units, bit for
+ * bit: units, layout and unit_stride as wl_denoise_batch_filter, nspin (ndims entries) and the shift of a spin as
+ * wl_denoise_ti_filter -- spin s (0-based) shifts dimension d by nspin2circ with the first dimension fastest, vectors by s mod n.
+ * Every unit gets its own sigma_i = noisest(x_i, wt), estimated from the unshifted unit and consumed on the device; sigma_in /
+ * sigma_out as wl_denoise_batch_filter.  A plane is one shifted copy of one unit: plane p = u * prod(nspin) + s, unit-major.
+ * Sequence: (1) unless sigma_in, a level-1 forward batch of the unshifted units into workspace, in groups of units, the per-unit MAD
+ * of rows [n0/2, n0) of the first column (the kernels of wl_mad_batch) and sigma = mad / 0.6745, for all units first; (2) the planes
+ * G at a time -- a group may begin and end inside a unit --: shift (k_ti_shift_units), forward batch (the level loops
+ * wl_denoise_ti_filter runs for its spins; L = 0 thresholds the shifted copy), one threshold launch with
+ * t = sigma[p / prod(nspin)] * t_unit in Float64 (k_threshold_planes), inverse batch, one un-shift / accumulate launch
+ * (k_ti_accumulate_units) that adds a unit's planes in ascending spin order -- from (T)0 when the group holds the unit's spin 0,
+ * from the stored y_u otherwise: the reference's arrayadd! order -- and scales the rounded sum by 1 / prod(nspin) when the group
+ * holds the unit's last spin (rmul!).  prod(nspin) == 1 takes the same path: (0 + z) * 1, a -0.0 comes back +0.0, as in the
+ * reference's TI branch.  x is not modified, the padding between units of y is never written.  Enqueues only: no synchronisation,
+ * capturable in a hipGraph once the workspace is held.  wl_last_kernel: "denoise_ti_units+k_mad_units_lds", "...+k_mad_units_stream"
+ * or "...+sigma_in".
+ * Status codes in this order: WL_EINVAL_ARG (NULL ctx / y / x / dims / qmf / nspin, th outside 0..3, t_unit negative or NaN),
+ * WL_EINVAL_DTYPE, WL_EINVAL_FILTER, WL_EINVAL_CUBE, WL_EDIMS (the rules of wl_denoise_batch_filter; an nspin[d] < 1; a product
+ * nunits * prod(nspin) that no int64 holds), WL_EINVAL_L, WL_EINVAL_SIZE (the rules of wl_denoise_batch_filter; images of more than
+ * 65535 columns, cubes from 2^20 per side), WL_EALIAS (y == x).
+ * Workspace (wl_workspace_bytes_full does not cover it), with N = prod(dims), S = unit_stride and G planes per group -- all
+ * nunits * prod(nspin), halved until the sum is below the context's cap (option WL_TI_WS_CAP_MB) and at most 65535; context option
+ * WL_TI_BATCH_GROUP (0 = automatic) lowers G after the workspace is sized; groups change no bit --, each part rounded up to 256 bytes:
+ *   the transform workspace of G planes   as wl_denoise_batch_filter's for G units
+ * + the planes Z and their coefficients   max(2 G N, min(G, nunits) * S without sigma_in) elements (the level-1 coefficients of
+ *                                         the estimate, at the caller's stride, live here before the first group)
+ * + the sigmas                            nunits doubles, for the whole call.                                                      */
+WL_API int wl_denoise_ti_batch_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims,
+                                      int64_t nunits, int64_t unit_stride, const double *qmf, int flen, int L, int th,
+                                      double t_unit, const int64_t *nspin, const double *sigma_in, double *sigma_out, void *stream);
+/* The same for a GLS (scheme arguments as wl_dwt_lifting): the transforms are those wl_denoise_ti_lifting runs for its spins (a
+ * batched-lines call, one batched 2-D or one batched 3-D lifting transform per group, with their fallbacks; L = 0 copies).  Status
+ * codes in the order above with WL_EINVAL_SCHEME in the place of WL_EINVAL_FILTER; y == x is WL_EALIAS here as well, because x is
+ * re-read for every group of spins.  Workspace: as above with the lifting transform workspace of wl_denoise_batch_lifting for G
+ * units in the first part.                                                                                                     */
+WL_API int wl_denoise_ti_batch_lifting(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims,
+                                       int64_t nunits, int64_t unit_stride, int nsteps, const int32_t *step_is_update,
+                                       const int32_t *step_ncoef, const int32_t *step_shift, const double *coefs_flat,
+                                       double norm1, double norm2, int L, int th, double t_unit, const int64_t *nspin,
+                                       const double *sigma_in, double *sigma_out, void *stream);
+
 /* ---- best-basis search of packet trees (src/Threshold/entropy.jl) ----------------------- */
 /* Entropy measures: ShannonEntropy (-s log s) and LogEnergyEntropy (-log s) of s = (x / nrm)^2; s == 0 contributes -0.0.    */
 enum wl_entropy { WL_ENTROPY_SHANNON = 0, WL_ENTROPY_LOGENERGY = 1 };

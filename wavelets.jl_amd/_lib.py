@@ -97,6 +97,10 @@ SIGNATURES = {
                                           C.c_double, _f64p, _f64p, _vp]),
     "wl_denoise_batch_lifting": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i64p, C.c_int64, C.c_int64, C.c_int, _i32p, _i32p, _i32p, _f64p,
                                            C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, _f64p, _f64p, _vp]),
+    "wl_denoise_ti_batch_filter": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i64p, C.c_int64, C.c_int64, _f64p, C.c_int, C.c_int, C.c_int,
+                                             C.c_double, _i64p, _f64p, _f64p, _vp]),
+    "wl_denoise_ti_batch_lifting": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i64p, C.c_int64, C.c_int64, C.c_int, _i32p, _i32p, _i32p, _f64p,
+                                              C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, _i64p, _f64p, _f64p, _vp]),
     "wl_complex_split": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int64, _vp]),
     "wl_complex_merge": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp]),
     "wl_dwt_filter_complex": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i64p, C.c_int64, C.c_int64, _f64p, C.c_int, C.c_int, C.c_int, _vp]),

@@ -1704,11 +1704,11 @@ __global__ void __launch_bounds__(EXT_THREADS) k_threshold_units(T *__restrict__
 }
 
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-// estimate (or take), publish and apply the sigmas of one group: src = where the level-1 detail range of every unit is read from
-// (nullptr: sigma_in), coef = the coefficients that are thresholded
+// estimate (or take) and publish the sigmas of one group of at most 65535 * 256 units: src = where the level-1 detail range of every
+// unit is read from (not read with sigma_in)
 template <typename T>
-int batch_sigma_threshold(wl_ctx *ctx, hipStream_t st, const T *src, T *coef, int64_t n0, int64_t N, int64_t nb, int64_t S, double *sg,
-                          const double *sigma_in, double *sigma_out, int th, double t_unit, const char **madk)
+int batch_sigma(wl_ctx *ctx, hipStream_t st, const T *src, int64_t n0, int64_t nb, int64_t S, double *sg, const double *sigma_in,
+                double *sigma_out, const char **madk)
 {
     if (!sigma_in) {
         const int64_t lo = (int64_t)llround((double)n0 / 2 + 1) - 1, nd = n0 - lo;        // detailrange(n0, 1), 0-based half open
@@ -1718,6 +1718,14 @@ int batch_sigma_threshold(wl_ctx *ctx, hipStream_t st, const T *src, T *coef, in
         *madk = "sigma_in";
     }
     hipLaunchKernelGGL(k_sigma_units, dim3((unsigned)((nb + EXT_THREADS - 1) / EXT_THREADS)), dim3(EXT_THREADS), 0, st, sg, nb, sigma_in, sigma_out);
+    return WL_OK;
+}
+// ... and apply them: coef = the coefficients that are thresholded
+template <typename T>
+int batch_sigma_threshold(wl_ctx *ctx, hipStream_t st, const T *src, T *coef, int64_t n0, int64_t N, int64_t nb, int64_t S, double *sg,
+                          const double *sigma_in, double *sigma_out, int th, double t_unit, const char **madk)
+{
+    WL_TRY(batch_sigma<T>(ctx, st, src, n0, nb, S, sg, sigma_in, sigma_out, madk));
     hipLaunchKernelGGL((k_threshold_units<T>), dim3(ext_blocks(N, 4, ctx->cu_count), (unsigned)nb), dim3(EXT_THREADS), 0, st, coef, N, S, th, sg, t_unit);
     WL_HIP(ctx, hipGetLastError());
     return WL_OK;
@@ -1861,6 +1869,311 @@ int denoise_batch_check(int ndims, const int64_t *dims, int64_t nunits, int64_t 
     if (L >= 62 || (dims[0] % ((int64_t)1 << L)) != 0) return WL_EINVAL_SIZE;
     if (estimate && (dims[0] % 2) != 0) return WL_EINVAL_SIZE;                 // noisest needs level 1
     if (estimate && dims[0] >= ((int64_t)1 << 32)) return WL_EINVAL_SIZE;      // (32-bit counters of the per-unit selection)
+    return WL_OK;
+}
+
+// ---- translation-invariant denoise of a batch of units (wl_denoise_ti_batch_filter / _lifting) ------------
+// A plane is one shifted copy of one unit: plane p = u * pns + s is spin s of unit u (unit-major).  A group is the nb planes
+// p0 .. p0 + nb - 1, dense in Z (plane stride N); it may begin and end in the middle of a unit.  Unit u sits at x + u * S.
+struct TibGeom { int64_t n0, n1, n2, N; int64_t nsp0, nsp1, nsp2, pns; int64_t S, p0, nb; };
+// a / b for a >= 0, b > 0: one 32-bit division where both fit (every shape these kernels exist for)
+__device__ __forceinline__ int64_t tib_div(int64_t a, int64_t b)
+{
+    return (((uint64_t)a | (uint64_t)b) >> 32) == 0 ? (int64_t)((uint32_t)a / (uint32_t)b) : a / b;
+}
+// ti_shift_of for spin s < pns
+__device__ __forceinline__ void tib_shift_of(const TibGeom &g, int64_t s, int64_t &s0, int64_t &s1, int64_t &s2)
+{
+    const int64_t q0 = tib_div(s, g.nsp0), r0 = s - q0 * g.nsp0;
+    const int64_t q1 = tib_div(q0, g.nsp1), r1 = q0 - q1 * g.nsp1;
+    s0 = r0 - tib_div(r0, g.n0) * g.n0;
+    s1 = r1 - tib_div(r1, g.n1) * g.n1;
+    s2 = q1 - tib_div(q1, g.n2) * g.n2;
+}
+// Z[z] = circshift(x_u, +shift(s)) for the planes z < nb of a group, p0 + z = u * pns + s.  The work of the whole group is indexed
+// flat -- item = four consecutive rows of one column of one plane, consecutive lanes take consecutive items across columns and
+// planes -- so a 64-sample plane costs 16 lanes, not a workgroup.  16-byte stores where n0 % 4 == 0 and Z's base allows them, the
+// shifted reads are four scalar loads from a contiguous run (k_ti_shift).
+template <typename T>
+__global__ void __launch_bounds__(256) k_ti_shift_units(T *__restrict__ Z, const T *__restrict__ x, TibGeom g)
+{
+    typedef T V4 __attribute__((ext_vector_type(4)));
+    const int64_t ipc = (g.n0 + 3) >> 2, ncol = g.n1 * g.n2, ipp = ipc * ncol, total = ipp * g.nb;
+    const bool vec = (g.n0 & 3) == 0 && (reinterpret_cast<uintptr_t>(Z) % (4 * sizeof(T))) == 0;
+    const int64_t nthr = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += nthr) {
+        const int64_t z = tib_div(it, ipp), r = it - z * ipp;
+        const int64_t c = (ncol == 1) ? 0 : tib_div(r, ipc), i0 = 4 * (r - c * ipc);
+        const int64_t p = g.p0 + z, u = tib_div(p, g.pns);
+        int64_t s0, s1, s2;
+        tib_shift_of(g, p - u * g.pns, s0, s1, s2);
+        const int64_t i2 = (ncol == 1) ? 0 : tib_div(c, g.n1), i1 = c - i2 * g.n1;
+        int64_t j1 = i1 - s1, j2 = i2 - s2;
+        if (j1 < 0) j1 += g.n1;
+        if (j2 < 0) j2 += g.n2;
+        const T *src = x + u * g.S + g.n0 * (j1 + g.n1 * j2);
+        T *dst = Z + z * g.N + g.n0 * c + i0;
+        T v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            int64_t j0 = i0 + e - s0;
+            if (j0 < 0) j0 += g.n0;
+            v[e] = (i0 + e < g.n0) ? src[j0] : (T)0;
+        }
+        if (vec) {
+            *reinterpret_cast<V4 *>(dst) = V4{v[0], v[1], v[2], v[3]};
+        } else {
+            for (int e = 0; e < 4 && i0 + e < g.n0; ++e) dst[e] = v[e];
+        }
+    }
+}
+// threshold!(c_z, th, sigma[(p0 + z) / pns] * t_unit) on the nb dense planes of a group: the product in Float64 as k_threshold_units
+// forms it, the group indexed flat.  vec_ok: N is a multiple of the 16-byte vector and c is aligned, so no vector straddles two planes.
+template <typename T>
+__global__ void __launch_bounds__(EXT_THREADS) k_threshold_planes(T *__restrict__ c, int64_t N, int64_t nb, int64_t p0, int64_t pns, int th,
+                                                                  const double *__restrict__ sigma, double t_unit, int vec_ok)
+{
+    constexpr int V = 16 / sizeof(T);
+    typedef T VT __attribute__((ext_vector_type(V)));
+    const int64_t nthr = (int64_t)gridDim.x * blockDim.x, gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (vec_ok) {
+        VT *cv = reinterpret_cast<VT *>(c);
+        const int64_t vpp = N / V, nv = vpp * nb;
+        for (int64_t i = gid; i < nv; i += nthr) {
+            const double t = sigma[tib_div(p0 + tib_div(i, vpp), pns)] * t_unit;
+            VT v = cv[i];
+#pragma unroll
+            for (int e = 0; e < V; ++e) v[e] = threshold_one<T, double>(v[e], th, t);
+            cv[i] = v;
+        }
+    } else {
+        const int64_t n = N * nb;
+        for (int64_t i = gid; i < n; i += nthr) {
+            const double t = sigma[tib_div(p0 + tib_div(i, N), pns)] * t_unit;
+            c[i] = threshold_one<T, double>(c[i], th, t);
+        }
+    }
+}
+// For every unit u the group touches: y_u (+)= circshift(Z[z], -shift(s)) over the unit's planes of the group IN ASCENDING SPIN ORDER
+// (arrayadd! once per spin, the reference's summation order), starting from (T)0 when the group holds the unit's spin 0 and from the
+// stored y_u otherwise (k_ti_accumulate's rule); when the group holds the unit's last spin the rounded sum is scaled by inv = 1 / pns
+// (k_rmul's expression on the value k_rmul would read).  Flat over the elements of the touched units: consecutive lanes own
+// consecutive elements, so every shifted plane is read along contiguous runs and a 64-sample unit costs one wave.  The shifts depend
+// on the spin alone: they sit in LDS, 256 spins at a time (a unit may have more), the planes are read eight at a time, loads before
+// the adds.  Every loop with a barrier has a trip count that is uniform in the workgroup.
+template <typename T>
+__global__ void __launch_bounds__(256) k_ti_accumulate_units(T *__restrict__ y, const T *__restrict__ Z, TibGeom g, double inv)
+{
+    __shared__ int sh0[256], sh1[256], sh2[256];
+    const int64_t u_lo = g.p0 / g.pns, u_hi = (g.p0 + g.nb - 1) / g.pns, pend = g.p0 + g.nb;
+    const int64_t total = (u_hi - u_lo + 1) * g.N, ncol = g.n1 * g.n2;
+    const bool one_table = g.pns <= 256;
+    auto fill = [&](int64_t sb) {
+        const int64_t s = sb + threadIdx.x;
+        if (s < g.pns) {
+            int64_t s0, s1, s2;
+            tib_shift_of(g, s, s0, s1, s2);
+            sh0[threadIdx.x] = (int)s0;
+            sh1[threadIdx.x] = (int)s1;
+            sh2[threadIdx.x] = (int)s2;
+        }
+    };
+    if (one_table) {
+        fill(0);
+        __syncthreads();
+    }
+    for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < total; base += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t e = base + threadIdx.x;
+        const bool live = e < total;
+        int64_t i0 = 0, i1 = 0, i2 = 0, pu = 0, slo = 0, shi = 0;
+        T *yp = y;
+        T acc = (T)0;
+        if (live) {
+            const int64_t ul = tib_div(e, g.N), r = e - ul * g.N, u = u_lo + ul;
+            const int64_t c = (ncol == 1) ? 0 : tib_div(r, g.n0);
+            i0 = r - c * g.n0;
+            i2 = (ncol == 1) ? 0 : tib_div(c, g.n1);
+            i1 = c - i2 * g.n1;
+            pu = u * g.pns;
+            slo = (g.p0 > pu ? g.p0 : pu) - pu;
+            shi = (pend < pu + g.pns ? pend : pu + g.pns) - pu;
+            yp = y + u * g.S + r;
+            if (slo != 0) acc = *yp;
+        }
+        for (int64_t sb = 0; sb < g.pns; sb += 256) {
+            if (!one_table) {
+                __syncthreads();
+                fill(sb);
+                __syncthreads();
+            }
+            if (!live) continue;
+            const int64_t a = slo > sb ? slo : sb, b = shi < sb + 256 ? shi : sb + 256;
+            for (int64_t s8 = a; s8 < b; s8 += 8) {
+                T v[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    if (s8 + k < b) {
+                        const int t = (int)(s8 + k - sb);
+                        int64_t j0 = i0 + sh0[t], j1 = i1 + sh1[t], j2 = i2 + sh2[t];
+                        if (j0 >= g.n0) j0 -= g.n0;
+                        if (j1 >= g.n1) j1 -= g.n1;
+                        if (j2 >= g.n2) j2 -= g.n2;
+                        v[k] = Z[(pu + s8 + k - g.p0) * g.N + g.n0 * (j1 + g.n1 * j2) + j0];
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    if (s8 + k < b) acc = acc + v[k];
+            }
+        }
+        if (live) {
+            if (shi == g.pns) acc = (T)((double)acc * inv);
+            *yp = acc;
+        }
+    }
+}
+
+// The sequence the two entry points share.  tw_elems(G): the transform workspace of G planes (and of up to G unshifted units of the
+// estimate); est(C, xg, nu): level-1 forward of nu units at stride S, xg -> C; fwd / inv(dst, src, nb): all L levels of nb dense planes.
+// l0_copies: the transforms are called at L = 0 too (the lifting transforms copy then, as the single call's do); otherwise L = 0
+// thresholds the shifted copy itself (denoise_ti_impl).
+template <typename T, typename TW, typename Est, typename Fwd, typename Inv>
+int denoise_ti_batch_run(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, int64_t nunits, int64_t S, int L, int th,
+                         double t_unit, const int64_t *nspin, const double *sigma_in, double *sigma_out, bool l0_copies, TW tw_elems, Est est,
+                         Fwd fwd, Inv inv)
+{
+    TibGeom g;
+    g.n0 = dims[0]; g.n1 = (ndims >= 2) ? dims[1] : 1; g.n2 = (ndims == 3) ? dims[2] : 1; g.N = g.n0 * g.n1 * g.n2;
+    g.nsp0 = nspin[0]; g.nsp1 = (ndims >= 2) ? nspin[1] : 1; g.nsp2 = (ndims == 3) ? nspin[2] : 1; g.pns = g.nsp0 * g.nsp1 * g.nsp2;
+    g.S = S;
+    const int64_t N = g.N, pns = g.pns, nplanes = nunits * pns;
+    // units per group of the estimate: as many as a group has planes; their level-1 coefficients (stride S) share the planes' buffers
+    auto est_units = [&](int64_t G) { return G < nunits ? G : nunits; };
+    auto zx_elems = [&](int64_t G) {
+        const size_t a = (size_t)2 * N * G, b = sigma_in ? 0 : (size_t)est_units(G) * S;
+        return a > b ? a : b;
+    };
+    auto need = [&](int64_t G) { return up256(tw_elems(G) * sizeof(T)) + up256(zx_elems(G) * sizeof(T)) + up256((size_t)nunits * sizeof(double)); };
+    int64_t G = 1;
+    int rc = group_reserve(ctx, st, nplanes, 65535, need, G);
+    if (rc != WL_OK) return rc;
+    double *sg = (double *)((char *)ctx->ws + up256(tw_elems(G) * sizeof(T)) + up256(zx_elems(G) * sizeof(T)));     // (where the held G puts it)
+    T *Z = (T *)((char *)ctx->ws + up256(tw_elems(G) * sizeof(T)));
+    const long long lower = opt("WL_TI_BATCH_GROUP", 0);
+    if (lower >= 1 && lower < G) G = lower;                  // (the buffers stay carved for the G that was reserved)
+    else G = (nplanes + (nplanes + G - 1) / G - 1) / ((nplanes + G - 1) / G);     // the same number of groups, of even size
+    T *XT = Z + N * G;
+    // ---- the sigmas of all units ----
+    const char *madk = "none";
+    if (sigma_in) {
+        const int64_t chunk = (int64_t)65535 * EXT_THREADS;
+        for (int64_t u0 = 0; u0 < nunits; u0 += chunk)
+            WL_TRY(batch_sigma<T>(ctx, st, nullptr, g.n0, (nunits - u0 < chunk) ? (nunits - u0) : chunk, S, sg + u0, sigma_in + u0,
+                                  sigma_out ? sigma_out + u0 : nullptr, &madk));
+    } else {
+        WL_TRY(for_groups(nunits, est_units(G), [&](int64_t u0, int64_t nu) -> int {
+            WL_TRY(est(Z, x + u0 * S, nu));
+            return batch_sigma<T>(ctx, st, Z, g.n0, nu, S, sg + u0, nullptr, sigma_out ? sigma_out + u0 : nullptr, &madk);
+        }));
+    }
+    // ---- the planes, G at a time ----
+    const bool transforms = L > 0 || l0_copies;
+    const int vec_th = ((N * sizeof(T)) % 16) == 0 ? 1 : 0;
+    WL_TRY(for_groups(nplanes, G, [&](int64_t p0, int64_t nb) -> int {
+        g.p0 = p0; g.nb = nb;
+        const int64_t items = ((g.n0 + 3) >> 2) * g.n1 * g.n2 * nb;
+        hipLaunchKernelGGL((k_ti_shift_units<T>), dim3(ext_blocks(items, 1, ctx->cu_count)), dim3(256), 0, st, Z, x, g);
+        if (transforms) WL_TRY(fwd(XT, Z, nb));
+        T *const coef = transforms ? XT : Z;
+        hipLaunchKernelGGL((k_threshold_planes<T>), dim3(ext_blocks(N * nb, 16 / sizeof(T), ctx->cu_count)), dim3(EXT_THREADS), 0, st, coef, N, nb, p0,
+                           pns, th, sg, t_unit, vec_th & vec_ok16(coef));
+        if (transforms) WL_TRY(inv(Z, XT, nb));
+        const int64_t touched = ((p0 + nb - 1) / pns - p0 / pns + 1) * N;
+        hipLaunchKernelGGL((k_ti_accumulate_units<T>), dim3(ext_blocks(touched, 1, ctx->cu_count)), dim3(256), 0, st, y, Z, g, 1.0 / (double)pns);
+        return WL_OK;
+    }));
+    WL_HIP(ctx, hipGetLastError());
+    ctx->last_kernel = strcmp(madk, "k_mad_units_lds") == 0 ? "denoise_ti_units+k_mad_units_lds"
+                       : (strcmp(madk, "k_mad_units_stream") == 0 ? "denoise_ti_units+k_mad_units_stream" : "denoise_ti_units+sigma_in");
+    return WL_OK;
+}
+
+template <typename T>
+int denoise_ti_batch_filter_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, int64_t nunits, int64_t S,
+                                 const double *qmf, int flen, int L, int th, double t_unit, const int64_t *nspin, const double *sigma_in,
+                                 double *sigma_out)
+{
+    const int64_t n0 = dims[0];
+    int64_t N = 1;
+    for (int d = 0; d < ndims; ++d) N *= dims[d];
+    const int64_t vdims[3] = {n0, n0, n0};
+    const Taps<T> taps = taps_of<T>(qmf, flen);
+    const char *kn = nullptr;
+    auto no_retry = [](int rc) { return rc == WL_RETRY_GEN ? WL_EINVAL_ARG : rc; };     // (the full workspace is held: no level can ask for more)
+    auto tw_elems = [&](int64_t G) { return ndims == 3 ? ws_vols_elems(N, G) : ws_elems(N * G, ndims); };
+    // nb lines / images with plane stride ps (cubes: a batch of volumes, not a box)
+    auto box = [&](int64_t nb, int64_t ps) {
+        BoxSpec bb;
+        bb.nd = ndims + 1; bb.nt = ndims;
+        bb.dims[0] = n0; bb.dims[1] = (ndims == 2) ? n0 : nb; bb.dims[2] = (ndims == 2) ? nb : 1;
+        bb.full.s[0] = 1; bb.full.s[1] = (ndims == 2) ? n0 : ps; bb.full.s[2] = (ndims == 2) ? ps : ps * nb;
+        return bb;
+    };
+    auto levels = [&](bool fw, T *dst, const T *src, int64_t nb, int64_t ps, int lev) -> int {
+        void *ws = ctx->ws;
+        if (ndims == 3)
+            return no_retry(fw ? filter_fwd_levels_vols<T>(ws, true, ctx->cu_count, ctx->path, st, vdims, nb, ps, ps, dst, src, taps, lev, &kn, &ctx->last_hip)
+                               : filter_inv_levels_vols<T>(ws, true, ctx->cu_count, ctx->path, st, vdims, nb, ps, ps, dst, src, taps, lev, &kn, &ctx->last_hip));
+        const BoxSpec bb = box(nb, ps);
+        return no_retry(fw ? filter_fwd_levels<T>(ws, true, ctx->cu_count, ctx->path, st, bb, dst, src, taps, lev, &kn, &ctx->last_hip)
+                           : filter_inv_levels<T>(ws, true, ctx->cu_count, ctx->path, st, bb, dst, src, taps, lev, &kn, &ctx->last_hip));
+    };
+    return denoise_ti_batch_run<T>(ctx, st, y, x, ndims, dims, nunits, S, L, th, t_unit, nspin, sigma_in, sigma_out, false, tw_elems,
+                                   [&](T *C, const T *xg, int64_t nu) { return levels(true, C, xg, nu, S, 1); },
+                                   [&](T *dst, const T *src, int64_t nb) { return levels(true, dst, src, nb, N, L); },
+                                   [&](T *dst, const T *src, int64_t nb) { return levels(false, dst, src, nb, N, L); });
+}
+
+template <typename T>
+int denoise_ti_batch_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, int64_t nunits, int64_t S,
+                                  const SchemeArgs &s, int L, int th, double t_unit, const int64_t *nspin, const double *sigma_in,
+                                  double *sigma_out)
+{
+    const LiftScheme<T> scf = s.build<T>(1), sci = s.build<T>(0);           // the forward and the inverse scheme
+    const int64_t n0 = dims[0];
+    int64_t N = 1;
+    for (int d = 0; d < ndims; ++d) N *= dims[d];
+    auto tw_elems = [&](int64_t G) -> size_t {
+        if (ndims == 3) { const size_t a = ws_lift_vols_elems(N, G), b = ws_elems(N, 1); return a > b ? a : b; }
+        return ws_elems(N * G, 1);
+    };
+    // nb lines of one batched call / nb images as the third extent / nb cubes as one batch of volumes, plane stride ps
+    auto transform = [&](T *dst, const T *src, int64_t nb, int64_t ps, const LiftScheme<T> &sc, int lev, int fw) -> int {
+        if (ndims == 3) return wl_lifting_vols<T>(ctx, st, n0, nb, ps, dst, src, sc, lev, fw);
+        BoxSpec bb;
+        bb.nd = ndims + 1; bb.nt = ndims;
+        bb.dims[0] = n0; bb.dims[1] = (ndims == 2) ? n0 : nb; bb.dims[2] = (ndims == 2) ? nb : 1;
+        bb.full.s[0] = 1; bb.full.s[1] = (ndims == 2) ? n0 : ps; bb.full.s[2] = (ndims == 2) ? ps : ps * nb;
+        return wl_lifting_box<T>(ctx, st, bb, dst, src, sc, lev, fw);
+    };
+    return denoise_ti_batch_run<T>(ctx, st, y, x, ndims, dims, nunits, S, L, th, t_unit, nspin, sigma_in, sigma_out, true, tw_elems,
+                                   [&](T *C, const T *xg, int64_t nu) { return transform(C, xg, nu, S, scf, 1, 1); },
+                                   [&](T *dst, const T *src, int64_t nb) { return transform(dst, src, nb, N, scf, L, 1); },
+                                   [&](T *dst, const T *src, int64_t nb) { return transform(dst, src, nb, N, sci, L, 0); });
+}
+
+// the rules the two denoise_ti_batch entry points share after their pointer / th / t_unit / dtype / wavelet rules: those of
+// denoise_batch_check with nspin in the WL_EDIMS group and the extent limits of denoise_ti_check in the WL_EINVAL_SIZE group
+int denoise_ti_batch_check(int ndims, const int64_t *dims, int64_t nunits, int64_t unit_stride, int L, bool estimate, const int64_t *nspin)
+{
+    const int rc = denoise_batch_check(ndims, dims, nunits, unit_stride, L, estimate);
+    if (rc == WL_EINVAL_CUBE || rc == WL_EDIMS) return rc;
+    int64_t planes = nunits;
+    for (int d = 0; d < ndims; ++d)
+        if (nspin[d] < 1 || __builtin_mul_overflow(planes, nspin[d], &planes)) return WL_EDIMS;
+    if (rc != WL_OK) return rc;
+    if (ndims == 3 && dims[0] >= ((int64_t)1 << 20)) return WL_EINVAL_SIZE;
+    if (ndims == 2 && dims[1] > 65535) return WL_EINVAL_SIZE;
     return WL_OK;
 }
 
@@ -2118,6 +2431,42 @@ int wl_denoise_batch_lifting(wl_ctx *ctx, int dtype, void *y, const void *x, int
     return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
         using T = decltype(t);
         return denoise_batch_lifting_impl<T>(ctx, st, (T *)y, (const T *)x, ndims, dims, nunits, unit_stride, s, L, th, t_unit, sigma_in, sigma_out);
+    });
+}
+
+int wl_denoise_ti_batch_filter(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, int64_t nunits,
+                               int64_t unit_stride, const double *qmf, int flen, int L, int th, double t_unit, const int64_t *nspin,
+                               const double *sigma_in, double *sigma_out, void *stream)
+{
+    if (!ctx || !y || !x || !dims || !qmf || !nspin) return WL_EINVAL_ARG;
+    if (th < WL_TH_HARD || th > WL_TH_STEIN || !(t_unit >= 0)) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen));
+    WL_TRY(denoise_ti_batch_check(ndims, dims, nunits, unit_stride, L, sigma_in == nullptr, nspin));
+    if (y == x) return WL_EALIAS;
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return denoise_ti_batch_filter_impl<T>(ctx, st, (T *)y, (const T *)x, ndims, dims, nunits, unit_stride, qmf, flen, L, th, t_unit, nspin,
+                                               sigma_in, sigma_out);
+    });
+}
+
+int wl_denoise_ti_batch_lifting(wl_ctx *ctx, int dtype, void *y, const void *x, int ndims, const int64_t *dims, int64_t nunits,
+                                int64_t unit_stride, int nsteps, const int32_t *step_is_update, const int32_t *step_ncoef,
+                                const int32_t *step_shift, const double *coefs_flat, double norm1, double norm2, int L, int th, double t_unit,
+                                const int64_t *nspin, const double *sigma_in, double *sigma_out, void *stream)
+{
+    const SchemeArgs s = {nsteps, step_is_update, step_ncoef, step_shift, coefs_flat, norm1, norm2};
+    if (!ctx || !y || !x || !dims || !nspin) return WL_EINVAL_ARG;
+    if (th < WL_TH_HARD || th > WL_TH_STEIN || !(t_unit >= 0)) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(s.check());
+    WL_TRY(denoise_ti_batch_check(ndims, dims, nunits, unit_stride, L, sigma_in == nullptr, nspin));
+    if (y == x) return WL_EALIAS;                            // (x is re-read for every group of spins)
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return denoise_ti_batch_lifting_impl<T>(ctx, st, (T *)y, (const T *)x, ndims, dims, nunits, unit_stride, s, L, th, t_unit, nspin, sigma_in,
+                                                sigma_out);
     });
 }
 

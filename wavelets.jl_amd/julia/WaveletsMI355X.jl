@@ -443,6 +443,7 @@ end
 
 include("WaveletsMI355X_bestbasis.jl")
 include("WaveletsMI355X_denoise_batch.jl")
+include("WaveletsMI355X_denoise_ti_batch.jl")
 include("WaveletsMI355X_wpt_batch.jl")
 include("WaveletsMI355X_complex.jl")
 include("WaveletsMI355X_bestbasis_batch.jl")

@@ -5,7 +5,8 @@
 # The reference has no batched form: denoise_batch(x, wt) equals the loop of `denoise(x[.., i], wt)` over the units, bit for bit,
 # but every unit's sigma = noisest(x_i, wt) is estimated and applied on the device (wl_denoise_batch_filter /
 # wl_denoise_batch_lifting: one forward transform, one MAD launch, one threshold launch and one inverse per group of units, no host
-# round trip).  Not part of these calls: wt = nothing, BiggestTH / PosTH / NegTH and TI = true (use the loop of denoise).
+# round trip).  Not part of these calls: wt = nothing, BiggestTH / PosTH / NegTH and TI = true (denoise_ti_batch,
+# WaveletsMI355X_denoise_ti_batch.jl).
 # tests/test_julia_glue_denoise_batch.py lints every ccall of this file against the ABI.
 using Wavelets.Threshold: DNFT, VisuShrink, HardTH, SoftTH, SemiSoftTH, SteinTH
 

@@ -363,19 +363,49 @@ def denoise_batch(x, wt=_DEFAULT, L: Optional[int] = None, dnt: Optional[DNFT] =
     sigma: per-unit noise levels instead of the estimate -- a host sequence / array (validated: every entry >= 0, else
     AssertionError; uploaded) or a Float64 device tensor of B values (not validated).  y: the output (lifting schemes: may be x).
     return_sigma: also return the Float64 device tensor of the B sigmas used.
-    Not part of this call (TypeError): wt=None, BiggestTH / PosTH / NegTH, translation-invariant denoising."""
-    _reject_complex(x, "denoise_batch")
+    Not part of this call (TypeError): wt=None, BiggestTH / PosTH / NegTH, and the TI keyword: translation-invariant denoising of a
+    batch is denoise_ti_batch."""
+    return _denoise_units("denoise_batch", x, wt, L, dnt, sigma, y, return_sigma)
+
+
+def denoise_ti_batch(x, wt=_DEFAULT, L: Optional[int] = None, dnt: Optional[DNFT] = None, nspin: Union[int, Sequence[int], None] = None,
+                     sigma=None, y=None, return_sigma: bool = False):
+    """denoise(x[.., i], wt; L, dnt, TI=true, nspin) of every unit of a batch in one call (wl_denoise_ti_batch_filter /
+    wl_denoise_ti_batch_lifting): x, L, dnt, sigma, y and return_sigma as denoise_batch, except that y must not be x.  Every unit gets
+    its OWN sigma = noisest(unit, wt), estimated from the unshifted unit on the device; the shifted copies of all units are transformed,
+    thresholded and inverted as batches, un-shifted and summed in spin order: the same bits as the loop of denoise(unit, wt, TI=True)
+    over the units, without its per-unit launches.
+    nspin: 8 per unit dimension by default; for signals an int or any tuple, whose product is the number of spins (shifts 0 .. prod - 1);
+    for images and cubes one entry per unit dimension (ArgumentError otherwise).
+    Not part of this call (TypeError): wt=None, BiggestTH / PosTH / NegTH."""
+    return _denoise_units("denoise_ti_batch", x, wt, L, dnt, sigma, y, return_sigma, ti=True, nspin=nspin)
+
+
+def _denoise_units(what, x, wt, L, dnt, sigma, y, return_sigma, ti=False, nspin=None):
+    """the body denoise_batch and denoise_ti_batch (ti: with nspin) share: validation before any device call, then one ABI call"""
+    _reject_complex(x, what)
     wt = DEFAULT_WAVELET if wt is _DEFAULT else wt
     if not isinstance(wt, (OrthoFilter, GLS)):
-        raise TypeError("denoise_batch is defined for orthogonal filters and lifting schemes (wt=None is not part of it)")
-    unit, nb = _batch_unit_shape(x, "denoise_batch")
+        raise TypeError(what + " is defined for orthogonal filters and lifting schemes (wt=None is not part of it)")
+    unit, nb = _batch_unit_shape(x, what)
     L = min(Util.maxtransformlevels(unit[0]), 6) if L is None else int(L)
     dnt = VisuShrink(int(x.shape[0])) if dnt is None else dnt
     if not isinstance(dnt, DNFT) or not isinstance(dnt.th, THType) or dnt.th.code is None or not 0 <= dnt.th.code <= 3:
-        raise TypeError("denoise_batch thresholds with HardTH, SoftTH, SemiSoftTH or SteinTH (threshold!(x, TH, t)); "
+        raise TypeError(what + " thresholds with HardTH, SoftTH, SemiSoftTH or SteinTH (threshold!(x, TH, t)); "
                         "BiggestTH / PosTH / NegTH are not part of it")
     if not float(dnt.t) >= 0:
         raise AssertionError("t >= 0")
+    spins = []
+    if ti:
+        nspin = tuple(8 for _ in unit) if nspin is None else nspin
+        nsp = (int(nspin),) if not hasattr(nspin, "__len__") else tuple(int(s) for s in nspin)
+        if len(unit) == 1:
+            nsp = (int(np.prod(nsp)),)                       # vectors: prod(nspin) spins shifted by 0 .. pns-1 (denoising.jl:38-42)
+        if len(nsp) != len(unit):
+            raise ArgumentError("nspin must have one entry per unit dimension")
+        if any(s < 1 for s in nsp):
+            raise ArgumentError("nspin must be positive")
+        spins = [(C.c_int64 * 3)(*(list(nsp) + [1] * (3 - len(nsp))))]
     sig_host = None
     if sigma is not None and not isinstance(sigma, torch.Tensor):
         sig_host = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(-1))
@@ -398,14 +428,16 @@ def denoise_batch(x, wt=_DEFAULT, L: Optional[int] = None, dnt: Optional[DNFT] =
     h, st = _context(x.device)
     dims = (C.c_int64 * 3)(*(list(unit) + [1] * (3 - len(unit))))
     nunit = int(np.prod(unit))
+    tail = spins + [f64(sig_dev), f64(sig_out), st]          # (the translation-invariant entry points take nspin in front of the sigmas)
     if isinstance(wt, GLS):
         iu, nc, sh, cf = wt.flatten()
-        rc = lib.wl_denoise_batch_lifting(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), len(unit), dims, nb, nunit,
-                                          len(iu), _i32p(iu), _i32p(nc), _i32p(sh), _f64p(cf), wt.norm1, wt.norm2, L, dnt.th.code,
-                                          float(dnt.t), f64(sig_dev), f64(sig_out), st)
+        fn = lib.wl_denoise_ti_batch_lifting if ti else lib.wl_denoise_batch_lifting
+        rc = fn(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), len(unit), dims, nb, nunit,
+                len(iu), _i32p(iu), _i32p(nc), _i32p(sh), _f64p(cf), wt.norm1, wt.norm2, L, dnt.th.code, float(dnt.t), *tail)
     else:
         q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
-        rc = lib.wl_denoise_batch_filter(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), len(unit), dims, nb, nunit,
-                                         _f64p(q), len(q), L, dnt.th.code, float(dnt.t), f64(sig_dev), f64(sig_out), st)
+        fn = lib.wl_denoise_ti_batch_filter if ti else lib.wl_denoise_batch_filter
+        rc = fn(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), len(unit), dims, nb, nunit,
+                _f64p(q), len(q), L, dnt.th.code, float(dnt.t), *tail)
     _check(rc, h)
     return (y, sig_out) if return_sigma else y
