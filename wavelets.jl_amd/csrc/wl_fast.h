@@ -98,9 +98,10 @@ template <typename T>
 hipError_t fwd2d_tile_launch(hipStream_t st, const Taps<T> &taps, int NL, const T *src, int64_t lds, T *y, int64_t ldy, T *ll,
                              int64_t ldll, int M, int N);
 
-// ... and its variant without the staging buffer (two levels, Float32): four workgroups per CU for blocks of 2048 rows
+// ... and its variant without the staging buffer (two levels, Float32): four workgroups per CU for blocks of 2048 rows; tall != 0: tiles
+// of 256 x 64 where the rows are a multiple of 256
 hipError_t fwd2d_tileB_launch(hipStream_t st, const Taps<float> &taps, const float *src, int64_t lds, float *y, int64_t ldy, float *ll,
-                              int64_t ldll, int M, int N);
+                              int64_t ldll, int M, int N, int tall);
 
 // Deep tail of a forward transform (wl_tail.hip): every remaining level of a small power-of-two block / line in one launch.
 // one 2-D lifting level of a square block of 128 ... 2048 rows (a multiple of 64) in one launch of 64 x 64 tiles (wl_lift_tile.hip);

@@ -193,26 +193,164 @@ __global__ void __launch_bounds__(256, 4) k_fwd2d_tileB(TileArgs<float, F> a)
     if (tid == 0) WL_STAMP_AT(tileB, wgid, 4);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// k_fwd2d_tileB_tall<F, TR>: the kernel above on tiles of TR x 64 (TR rows per 64 columns), 4 TR threads.  The row halo of 24
+// samples is paid once per TR rows: the tile with halo is (TR + 24)(64 + 18) samples -- 1.40x the payload at TR = 256 against
+// 1.76x -- and the dim-2 and dim-1 passes of the first level shrink by the same row factor.  Same one-sided windows, same
+// detail-row shift, same arithmetic and store policies; the waves per CU stay what they were (one workgroup of 16 waves instead of
+// four of 4).  TR = 256 is the instance that ships: 2048^2 two levels 12.2 -> 10.2 us, TR = 128 (two workgroups per CU) 11.0;
+// window loads of half the column groups held in flight under the dim-1 pass of the other half: +-0.1 us, not kept
+// (profiles/tileb_tall.md).
+template <int F, int TR>
+__global__ void __launch_bounds__(4 * TR, 1) k_fwd2d_tileB_tall(TileArgs<float, F> a)
+{
+    typedef float T;
+    typedef TileLds<F, 2, 64, TR> L;
+    typedef T F4t __attribute__((ext_vector_type(4)));
+    constexpr int NT = 4 * TR;
+    constexpr int ldT = L::ldx(L::R0), ld1 = L::ldx(L::R1);
+    constexpr int R0 = L::R0, R1 = L::R1, C1 = L::C1;
+    static_assert(R0 == TR + 24 && R1 == TR / 2 + 8 && L::R2 == TR / 4 && C1 == 32 + F - 2 && L::C2 == 16, "tall tile: TR rows x 64 columns");
+    constexpr int RQ = R0 / 4, QG = R1 / 4, OWNR = TR / 2, OWN = 32;
+    constexpr int KG = 4, NG = (C1 + KG - 1) / KG, NC = F + 2 * (KG - 1);
+    static_assert(NT <= 1024 && RQ * NG <= NT, "the dim-2 pass is one round of the workgroup");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    T *Ts = reinterpret_cast<T *>(smem_raw);                     // [ldT x (C1 + 32)]: dim-2 results, then the second level's
+    T *X1s = Ts + ldT * (C1 + OWN);                              // [ld1 x C1] (+ 16): the first approximation
+    const int tid = threadIdx.x;
+    const int wgid = (int)(blockIdx.x + gridDim.x * blockIdx.y);
+    // XCD-aware tile map as above: gx / 2 x gy / 4 tiles (TR x 64 each) per XCD
+    int tbx = (int)blockIdx.x, tby = (int)blockIdx.y;
+#if WL_TILEB_REMAP
+    if ((gridDim.x & 1) == 0 && (gridDim.y & 3) == 0) {
+        const int xcd = wgid & 7, i = wgid >> 3, rx = (int)gridDim.x >> 1;
+        tbx = (xcd & 1) * rx + i % rx;
+        tby = (xcd >> 1) * ((int)gridDim.y >> 2) + i / rx;
+    }
+#endif
+    const int r0 = tbx * TR, c0 = tby * 64;
+    const int hm = a.M >> 1, hn = a.N >> 1;
+    // ---- level 1, dim-2 pass from global: a thread owns four rows and KG output columns (work item it = row quad + RQ * group) ----
+    auto win_load = [&](const int it, F4t (&xw)[NC]) __attribute__((always_inline)) {
+        int gr = r0 + 4 * (it % RQ);
+        if (gr >= a.M) gr -= a.M;
+        int gc = c0 + 2 * KG * (it / RQ);
+        if (gc >= a.N) gc -= a.N;
+#pragma unroll
+        for (int m = 0; m < NC; ++m) {
+            int c = gc + m;
+            if (c >= a.N) c -= a.N;
+            xw[m] = load_pol<WL_P_TILE_LD != 0>(reinterpret_cast<const F4t *>(a.src + gr + (int64_t)c * a.lds));
+        }
+        __builtin_amdgcn_sched_barrier(0);                       // all NC loads issued before the first of them is consumed
+    };
+    auto win_pass = [&](const int it, const F4t (&xw)[NC]) __attribute__((always_inline)) {
+        const int iq = it % RQ, k0 = (it / RQ) * KG;
+#pragma unroll
+        for (int kk = 0; kk < KG; ++kk) {
+            const int k = k0 + kk;
+            F4t sv = a.tp.h[0] * xw[2 * kk], dv = a.tp.g[F - 1] * xw[2 * kk];
+#pragma unroll
+            for (int m = 1; m < F; ++m) {
+                sv = sv + a.tp.h[m] * xw[2 * kk + m];
+                dv = dv + a.tp.g[F - 1 - m] * xw[2 * kk + m];
+            }
+            if (k < C1) *reinterpret_cast<F4t *>(Ts + 4 * iq + k * ldT) = sv;
+            if (k < OWN) *reinterpret_cast<F4t *>(Ts + 4 * iq + (C1 + k) * ldT) = dv;
+        }
+    };
+    if (tid < RQ * NG) {
+        F4t xw[NC];
+        win_load(tid, xw);
+        win_pass(tid, xw);
+    }
+    lds_barrier();
+    // ---- level 1, dim-1 pass (the second half of tile_level) ----
+    {
+        constexpr int SH = (F - 2) / 2;
+        const int r0h = r0 >> 1, c0h = c0 >> 1;
+        for (int it = tid; it < QG * (C1 + OWN); it += NT) {
+            const int q = it % QG, c = it / QG;
+            const bool is_s = c < C1;
+            const int cc = is_s ? c : c - C1;
+            const T *p = Ts + 8 * q + c * ldT;
+            T E[16];
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const F4t t = *reinterpret_cast<const F4t *>(p + 4 * v);
+                E[4 * v] = t.x; E[4 * v + 1] = t.y; E[4 * v + 2] = t.z; E[4 * v + 3] = t.w;
+            }
+            F4t so, dO;
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) {
+                T sv = a.tp.h[0] * E[2 * jj];
+#pragma unroll
+                for (int m = 1; m < F; ++m) sv = sv + a.tp.h[m] * E[2 * jj + m];
+                T dv = a.tp.g[F - 1] * E[2 * jj + 10 - F];
+#pragma unroll
+                for (int m = F - 2; m >= 0; --m) dv = dv + a.tp.g[m] * E[2 * jj + 9 - m];
+                so[jj] = sv; dO[jj] = dv;
+            }
+            if (is_s) *reinterpret_cast<F4t *>(X1s + 4 * q + cc * ld1) = so;
+            if (cc < OWN && 4 * q < OWNR) {
+                int64_t col;
+                if (is_s) col = c0h + cc;
+                else { int kd = c0h + cc + SH; if (kd >= hn) kd -= hn; col = hn + kd; }
+                int rd = r0h + 4 * q + 4;
+                if (rd >= hm) rd -= hm;
+                T *yc = a.y + col * a.ldy;
+                store_pol<WL_P_TILE_ST>(reinterpret_cast<F4t *>(yc + hm + rd), dO);                  // ds or dd
+                if (!is_s) store_pol<WL_P_TILE_ST>(reinterpret_cast<F4t *>(yc + (r0h + 4 * q)), so);  // sd
+            }
+        }
+    }
+    lds_barrier();
+    // ---- level 2: LDS -> LDS as in the staging kernel ----
+    tile_level<T, F, R1, C1, TR / 4, 16, 16, true, TR / 4>(X1s, ld1, Ts, ld1, nullptr, 0, a.tp, a.y, a.ldy, a.ll, a.ldll, r0 >> 2, c0 >> 2, hm >> 1,
+                                                          hn >> 1, tid, NT);
+}
+
+template <int F, int TR>
+static hipError_t launch_tileB_tall_f(hipStream_t st, const TileArgs<float, F> &a)
+{
+    typedef TileLds<F, 2, 64, TR> L;
+    constexpr size_t shmem = (size_t)(L::ldx(L::R0) * (L::C1 + 32) + L::ldx(L::R1) * L::C1 + 16) * sizeof(float);
+    static_assert(shmem <= 160 * 1024, "one workgroup per CU");
+    static thread_local int done_dev = -1;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (done_dev != dev) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fwd2d_tileB_tall<F, TR>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           160 * 1024);
+        if (e != hipSuccess) return e;
+        done_dev = dev;
+    }
+    hipLaunchKernelGGL((k_fwd2d_tileB_tall<F, TR>), dim3((unsigned)(a.M / TR), (unsigned)(a.N / 64)), dim3(4 * TR), shmem, st, a);
+    return hipGetLastError();
+}
+
+// tall (decided in wl_fwd.hip: WL_TILEB_TALL and the CU count): tiles of 256 x 64, rows a multiple of 256; 0: the 64 x 64 tiles
 template <int F>
 static hipError_t launch_tileB_f(hipStream_t st, const Taps<float> &taps, const float *src, int64_t lds, float *y, int64_t ldy, float *ll,
-                                 int64_t ldll, int M, int N)
+                                 int64_t ldll, int M, int N, int tall)
 {
     TileArgs<float, F> a;
     a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.ll = ll; a.ldll = ldll; a.M = M; a.N = N;
     a.tp = shrink<float, F>(taps);
+    if (tall != 0 && M % 256 == 0) return launch_tileB_tall_f<F, 256>(st, a);
     hipLaunchKernelGGL((k_fwd2d_tileB<F>), dim3((unsigned)(M / 64), (unsigned)(N / 64)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
 hipError_t fwd2d_tileB_launch(hipStream_t st, const Taps<float> &taps, const float *src, int64_t lds, float *y, int64_t ldy, float *ll,
-                              int64_t ldll, int M, int N)
+                              int64_t ldll, int M, int N, int tall)
 {
     switch (taps.F) {
-    case 2: return launch_tileB_f<2>(st, taps, src, lds, y, ldy, ll, ldll, M, N);
-    case 4: return launch_tileB_f<4>(st, taps, src, lds, y, ldy, ll, ldll, M, N);
-    case 6: return launch_tileB_f<6>(st, taps, src, lds, y, ldy, ll, ldll, M, N);
-    case 8: return launch_tileB_f<8>(st, taps, src, lds, y, ldy, ll, ldll, M, N);
-    case 10: return launch_tileB_f<10>(st, taps, src, lds, y, ldy, ll, ldll, M, N);
+    case 2: return launch_tileB_f<2>(st, taps, src, lds, y, ldy, ll, ldll, M, N, tall);
+    case 4: return launch_tileB_f<4>(st, taps, src, lds, y, ldy, ll, ldll, M, N, tall);
+    case 6: return launch_tileB_f<6>(st, taps, src, lds, y, ldy, ll, ldll, M, N, tall);
+    case 8: return launch_tileB_f<8>(st, taps, src, lds, y, ldy, ll, ldll, M, N, tall);
+    case 10: return launch_tileB_f<10>(st, taps, src, lds, y, ldy, ll, ldll, M, N, tall);
     default: return hipErrorInvalidValue;
     }
 }

@@ -32,25 +32,26 @@ struct TileGeomF {
     static constexpr int HR = WINR - 8;
 };
 // extents of the tile at level l (l = 0: the launch's input), OT owned input samples per side (64; 32 for the three-level tiles of
-// blocks with too few 64-sample tiles to fill the chip, round 6)
-template <int F, int NL, int l, int OT = 64>
+// blocks with too few 64-sample tiles to fill the chip, round 6); OTR = owned rows where the tile is taller than wide (the tall
+// instances of k_fwd2d_tileB: the row halo of 24 samples is paid once per OTR rows)
+template <int F, int NL, int l, int OT = 64, int OTR = OT>
 struct TileDim {
     static constexpr int HR = TileGeomF<F>::HR, HC = F - 2;        // one-sided halos per level: rows (d rows shifted by DS), columns
-    static constexpr int R = 2 * TileDim<F, NL, l + 1, OT>::R + HR;    // rows / columns of this level's input that the tile needs
-    static constexpr int C = 2 * TileDim<F, NL, l + 1, OT>::C + HC;
+    static constexpr int R = 2 * TileDim<F, NL, l + 1, OT, OTR>::R + HR;    // rows / columns of this level's input that the tile needs
+    static constexpr int C = 2 * TileDim<F, NL, l + 1, OT, OTR>::C + HC;
 };
-template <int F, int NL, int OT>
-struct TileDim<F, NL, NL, OT> {
-    static constexpr int R = OT >> NL, C = OT >> NL;
+template <int F, int NL, int OT, int OTR>
+struct TileDim<F, NL, NL, OT, OTR> {
+    static constexpr int R = OTR >> NL, C = OT >> NL;
 };
 
-template <int F, int NL, int OT = 64>
+template <int F, int NL, int OT = 64, int OTR = OT>
 struct TileLds {
     // X0 | T | X1 | X2 (float offsets); leading dimensions padded to a multiple of 4 rows plus 4 (bank spread, 16-byte aligned)
     static constexpr int ldx(int r) { return ((r + 3) & ~3) + 4; }
-    static constexpr int R0 = TileDim<F, NL, 0, OT>::R, C0 = TileDim<F, NL, 0, OT>::C;
-    static constexpr int R1 = TileDim<F, NL, (NL >= 1 ? 1 : 0), OT>::R, C1 = TileDim<F, NL, (NL >= 1 ? 1 : 0), OT>::C;
-    static constexpr int R2 = TileDim<F, NL, (NL >= 2 ? 2 : NL), OT>::R, C2 = TileDim<F, NL, (NL >= 2 ? 2 : NL), OT>::C;
+    static constexpr int R0 = TileDim<F, NL, 0, OT, OTR>::R, C0 = TileDim<F, NL, 0, OT, OTR>::C;
+    static constexpr int R1 = TileDim<F, NL, (NL >= 1 ? 1 : 0), OT, OTR>::R, C1 = TileDim<F, NL, (NL >= 1 ? 1 : 0), OT, OTR>::C;
+    static constexpr int R2 = TileDim<F, NL, (NL >= 2 ? 2 : NL), OT, OTR>::R, C2 = TileDim<F, NL, (NL >= 2 ? 2 : NL), OT, OTR>::C;
     static constexpr int X0 = 0;
     static constexpr int T = X0 + ldx(R0) * C0;
     static constexpr int X1 = T + ldx(R0) * (C1 + OT / 2);         // T: R0 rows x (C1 s-columns + OT / 2 owned d-columns)
@@ -60,7 +61,7 @@ struct TileLds {
 
 
 // One level inside the tile.  X: input R x C (leading dimension ldx), T: scratch, XN: next level's input (RN x CN) in LDS.
-// OWN = owned outputs per side at this level (32, 16, 8); (r0h, c0h) = tile origin in this level's OUTPUT coordinates;
+// OWN = owned outputs per side at this level (32, 16, 8; OWNR rows where the tile is taller than wide); (r0h, c0h) = tile origin in this level's OUTPUT coordinates;
 // hm, hn = half extents of this level's block; LAST: the approximation goes to global memory (ll) instead of XN.
 // The taps travel BY VALUE (round 6).  By reference, hipcc kept the kernel argument's tap array addressable -- the SLP vectoriser loads
 // runs of consecutive taps as vectors -- and parked it in scratch: 28-48 bytes per lane, reloaded before every pass, in every
@@ -70,7 +71,7 @@ struct TileLds {
 #else
 #define WL_TILE_TAPS const TapsF<TT, F>
 #endif
-template <typename TT, int F, int R, int C, int RN, int CN, int OWN, bool LAST>
+template <typename TT, int F, int R, int C, int RN, int CN, int OWN, bool LAST, int OWNR = OWN>
 __device__ __forceinline__ void tile_level(const TT *X, int ldX, TT *T, int ldT, TT *XN, int ldN, WL_TILE_TAPS tp,
                                            TT *y, int64_t ldy, TT *ll, int64_t ldll, int r0h, int c0h, int hm, int hn, int tid,
                                            int nthr)
@@ -123,11 +124,11 @@ __device__ __forceinline__ void tile_level(const TT *X, int ldX, TT *T, int ldT,
         // approximation of an s-column: next level's input (all RN rows), or global when this is the launch's last level
         if (is_s) {
             if (!LAST) *reinterpret_cast<F4t *>(XN + 4 * q + c * ldN) = so;
-            else if (c < OWN && 4 * q < OWN) store_pol<WL_P_TILE_LL>(reinterpret_cast<F4t *>(ll + (r0h + 4 * q) + (int64_t)(c0h + c) * ldll), so);
+            else if (c < OWN && 4 * q < OWNR) store_pol<WL_P_TILE_LL>(reinterpret_cast<F4t *>(ll + (r0h + 4 * q) + (int64_t)(c0h + c) * ldll), so);
         }
         // details: owned rows / columns only
         const int cc = is_s ? c : c - CN;
-        if (cc < OWN && 4 * q < OWN) {
+        if (cc < OWN && 4 * q < OWNR) {
             int64_t col;
             if (is_s) col = c0h + cc;                                   // s along dim 2
             else { int kd = c0h + cc + SH; if (kd >= hn) kd -= hn; col = hn + kd; }
