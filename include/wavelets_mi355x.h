@@ -342,6 +342,34 @@ WL_API int wl_threshold(wl_ctx *ctx, int dtype, void *x, int64_t n, int th, doub
  * the reference's QuickSort leaves that order unspecified).  Synchronises `stream` once.
  * replaces threshold_main.jl:22-34.                                                        */
 WL_API int wl_threshold_biggest(wl_ctx *ctx, int dtype, void *x, int64_t n, int64_t m, void *stream);
+/* threshold!(x_u, TH, t_u) in place on every unit x_u = x[u * unit_stride .. + n), u < nunits, in one launch ("k_threshold_batch",
+ * one launch per 65535 units; "k_threshold_batch_wave", a wave per unit, for units of at most 256 elements): the arithmetic of
+ * wl_threshold on every unit, so each unit has the bits of wl_threshold on that
+ * unit.  th: wl_thtype, all six kinds.  t_dev == NULL: the scalar t serves every unit; otherwise t_dev is a DEVICE array of nunits
+ * doubles, one threshold per unit (t is ignored).  t_is_f64 as in wl_threshold; with 0 every threshold is converted to the element
+ * type before the arithmetic.  A host t < 0 (or NaN) -> WL_EINVAL_ARG for Hard / Soft / Semisoft / Stein; device thresholds are
+ * NOT validated (that would need a synchronisation): a negative or NaN entry yields whatever the reference's arithmetic yields
+ * without its @assert (Hard with t < 0 keeps everything, NaN compares false throughout).  The padding between units is never read
+ * or written.  No workspace.  Enqueues only: no synchronisation, capturable in a hipGraph.  Status codes in this order:
+ * WL_EINVAL_ARG (NULL ctx / x), WL_EINVAL_DTYPE, WL_EDIMS (n < 1, nunits < 1, unit_stride < n, nunits * unit_stride overflows or
+ * reaches 2^60), WL_EINVAL_ARG (th not a wl_thtype; host t < 0).                                                              */
+WL_API int wl_threshold_batch(wl_ctx *ctx, int dtype, void *x, int64_t n, int64_t nunits, int64_t unit_stride, int th, double t,
+                              const double *t_dev, int t_is_f64, void *stream);
+/* threshold!(x_u, BiggestTH(), m_u) in place on every unit: the m_u entries of largest magnitude of unit u keep their bits, the
+ * others become +0; ties at the cut are cleared in index order, lower index first, and NaNs order above every finite magnitude
+ * -- unit for unit the bits of wl_threshold_biggest.  m_dev == NULL: the scalar m serves every unit (m > n is n); otherwise m_dev
+ * is a DEVICE array of nunits int64, each entry clamped on the device to [0, n] (m is ignored).  Only cleared entries are written,
+ * a unit with m_u >= n is not even read; the padding between units is never read or written.  Three tiers, chosen from n and
+ * nunits alone: "k_thbig_lds" (a workgroup per unit, keys in LDS: units of up to 8192 Float32 / 4096 Float64 values; context
+ * option WL_THB_LDS_MAX lowers the limit, 0 = never), "k_thbig_stream" (a workgroup per unit streams it from memory), and
+ * "k_thbig_split" (several workgroups per unit, a fixed number of launches whatever nunits: units of at least WL_THB_SPLIT_N
+ * elements in batches of at most WL_THB_SPLIT_UNITS units, and every unit of 2^31 elements or more; WL_THB_CHUNK = elements per
+ * workgroup).  Only the split tier takes workspace (a state block per unit and a counter per chunk; units in groups under the
+ * context's cap).  Enqueues only: never synchronises, no counter comes back to the host, capturable in a hipGraph once the
+ * workspace is reserved.  Status codes in this order: WL_EINVAL_ARG (NULL ctx / x), WL_EINVAL_DTYPE, WL_EDIMS (as above),
+ * WL_EINVAL_ARG (host m < 0), then WL_ENOMEM / WL_EHIP.                                                                         */
+WL_API int wl_threshold_biggest_batch(wl_ctx *ctx, int dtype, void *x, int64_t n, int64_t nunits, int64_t unit_stride, int64_t m,
+                                      const int64_t *m_dev, void *stream);
 /* *result = median(v) (Statistics.median!: middle order statistic, or a/2 + b/2 of the two
  * middle ones; NaN if any NaN), computed in the element type and widened to double.  `v` is
  * not modified.  Synchronises `stream` (the result is a host scalar, as in the reference).  */

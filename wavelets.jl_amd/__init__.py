@@ -23,7 +23,7 @@ from .transforms import (dwt, idwt, dwt_, idwt_, dwt_oop_, idwt_oop_, dwtc, idwt
 from .modwt import modwt, imodwt, modwt_batch, imodwt_batch, maxmodwttransformlevels
 from .threshold import (THType, HardTH, SoftTH, SemiSoftTH, SteinTH, BiggestTH, PosTH, NegTH, DEFAULT_TH, threshold, threshold_,
                         DNFT, VisuShrink, denoise, noisest, mad_, median, nspin2circ, circshift, DEFAULT_WAVELET,
-                        denoise_batch, noisest_batch, mad_batch_, denoise_ti_batch)
+                        denoise_batch, noisest_batch, mad_batch_, denoise_ti_batch, threshold_batch, threshold_batch_)
 from .entropy import Entropy, ShannonEntropy, LogEnergyEntropy, coefentropy, bestbasistree, bestbasistree_batch
 from . import _lib
 
@@ -40,6 +40,6 @@ __all__ = [
     "modwt", "imodwt", "modwt_batch", "imodwt_batch", "maxmodwttransformlevels",
     "THType", "HardTH", "SoftTH", "SemiSoftTH", "SteinTH", "BiggestTH", "PosTH", "NegTH", "DEFAULT_TH", "threshold", "threshold_",
     "DNFT", "VisuShrink", "denoise", "noisest", "mad_", "median", "nspin2circ", "circshift", "DEFAULT_WAVELET",
-    "denoise_batch", "noisest_batch", "mad_batch_", "denoise_ti_batch",
+    "denoise_batch", "noisest_batch", "mad_batch_", "denoise_ti_batch", "threshold_batch", "threshold_batch_",
     "Entropy", "ShannonEntropy", "LogEnergyEntropy", "coefentropy", "bestbasistree", "bestbasistree_batch",
 ]

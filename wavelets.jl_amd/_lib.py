@@ -86,6 +86,9 @@ SIGNATURES = {
     "wl_imodwt_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, _f64p, C.c_int, _vp]),
     "wl_threshold": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int, C.c_double, C.c_int, _vp]),
     "wl_threshold_biggest": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int64, _vp]),
+    # (t_dev / m_dev are DEVICE pointers: passed as addresses)
+    "wl_threshold_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_double, _vp, C.c_int, _vp]),
+    "wl_threshold_biggest_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp, _vp]),
     "wl_median": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _f64p, _vp]),
     "wl_mad": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _f64p, _vp]),
     "wl_denoise_ti_filter": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int, _i64p, _f64p, C.c_int, C.c_int, C.c_int, C.c_double, _i64p,

@@ -9,6 +9,7 @@
 #include "wl_entry.h"
 #include "wl_fast.h"
 #include "wl_dev.h"
+#include "wl_select.h"
 
 #include <cmath>
 #include <cstring>
@@ -16,51 +17,6 @@
 using namespace wl;
 
 namespace {
-
-constexpr int EXT_THREADS = 256;
-inline unsigned ext_blocks(int64_t n, int per_thread, int cu_count)
-{
-    int64_t b = (n + (int64_t)EXT_THREADS * per_thread - 1) / ((int64_t)EXT_THREADS * per_thread);
-    const int64_t cap = (int64_t)cu_count * 16;
-    if (b > cap) b = cap;
-    if (b < 1) b = 1;
-    return (unsigned)b;
-}
-
-
-// element-wise in-place pass: 16-byte vectors when the pointer is aligned, scalar tail
-template <typename T, typename F>
-__device__ __forceinline__ void ew_inplace(T *__restrict__ x, int64_t n, int vec_ok, F f)
-{
-    constexpr int V = 16 / sizeof(T);
-    typedef T VT __attribute__((ext_vector_type(V)));
-    constexpr int U = 4;                      // independent 16-byte accesses in flight per lane
-    const int64_t nthr = (int64_t)gridDim.x * blockDim.x, gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t nv = vec_ok ? n / V : 0;
-    VT *xv = reinterpret_cast<VT *>(x);
-    const int64_t tile = (int64_t)U * blockDim.x, ntiles = nv / tile;
-    for (int64_t tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
-        const int64_t base = tl * tile + threadIdx.x;
-        VT v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) v[u] = xv[base + (int64_t)u * blockDim.x];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-#pragma unroll
-            for (int e = 0; e < V; ++e) v[u][e] = f(v[u][e], (base + (int64_t)u * blockDim.x) * V + e);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) xv[base + (int64_t)u * blockDim.x] = v[u];
-    }
-    for (int64_t i = ntiles * tile + gid; i < nv; i += nthr) {
-        VT v = xv[i];
-#pragma unroll
-        for (int e = 0; e < V; ++e) v[e] = f(v[e], i * V + e);
-        xv[i] = v;
-    }
-    for (int64_t i = nv * V + gid; i < n; i += nthr) x[i] = f(x[i], i);
-}
-inline int vec_ok16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 ? 1 : 0; }
 
 // ---- MODWT -----------------------------------------------------------------------------------------
 struct ModwtTaps { int F; double h[WL_MAX_FLEN]; double g[WL_MAX_FLEN]; };   // h: detail, g: scaling (both / sqrt 2)
@@ -721,7 +677,7 @@ __global__ void __launch_bounds__(EXT_THREADS) k_threshold(T *__restrict__ x, in
     ew_inplace<T>(x, n, vec_ok, [=](T v, int64_t) { return threshold_one<T, C>(v, th, t); });
 }
 
-// ---- order statistics: MSB-first radix select on monotone integer keys -------------------------------
+// ---- order statistics: MSB-first radix select on monotone integer keys (KeyOf, lds_select, wave_pick_bin: wl_select.h) ------
 // Two ranks are resolved together (the two middle order statistics of an even-length median).
 struct SelState {
     unsigned long long prefix[2];
@@ -732,38 +688,6 @@ struct SelState {
     double result;                      // median / order statistic as Float64
     double value[2];                    // the two selected values
     unsigned long long less, equal;     // counts relative to value[0] (threshold_biggest)
-};
-
-template <typename T> struct KeyOf;
-template <> struct KeyOf<float> {
-    typedef unsigned int U;
-    static constexpr int BYTES = 4;
-    __device__ static U key(float v, int absmode)
-    {
-        U b = __float_as_uint(v);
-        if (absmode) return b & 0x7fffffffu;
-        return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    }
-    __device__ static float val(U k, int absmode)
-    {
-        if (absmode) return __uint_as_float(k);
-        return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-    }
-};
-template <> struct KeyOf<double> {
-    typedef unsigned long long U;
-    static constexpr int BYTES = 8;
-    __device__ static U key(double v, int absmode)
-    {
-        U b = (U)__double_as_longlong(v);
-        if (absmode) return b & 0x7fffffffffffffffull;
-        return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-    }
-    __device__ static double val(U k, int absmode)
-    {
-        if (absmode) return __longlong_as_double((long long)k);
-        return __longlong_as_double((long long)((k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k));
-    }
 };
 
 __global__ void k_sel_init(SelState *s, unsigned long long k0, unsigned long long k1)
@@ -905,59 +829,6 @@ int ensure_aux(wl_ctx *ctx)
 
 // Small arrays (<= 8192 elements, e.g. the noise estimate of a 2-D array: the lower half of one column): the whole
 // median / mad! in ONE workgroup with the keys in LDS -- the multi-launch radix select above is launch-bound there.
-// (INST: a caller that must not share the instantiation of k_mad_lds -- and with it that kernel's inlining and register allocation --
-// asks for its own)
-template <typename T, int INST = 0>
-__device__ typename KeyOf<T>::U lds_select(const typename KeyOf<T>::U *keys, int n, unsigned long long k, unsigned int *hist,
-                                             unsigned long long *sh)
-{
-    typedef typename KeyOf<T>::U U;
-    constexpr int NB = KeyOf<T>::BYTES;
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    if (tid == 0) { sh[0] = 0; sh[1] = k; }
-    for (int pass = 0; pass < NB; ++pass) {
-        const int shift = 8 * (NB - 1 - pass);
-        for (int b = tid; b < 256; b += nthr) hist[b] = 0;
-        __syncthreads();
-        const U prefix = (U)sh[0];
-        for (int i = tid; i < n; i += nthr) {
-            const U key = keys[i];
-            if (pass == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(unsigned)((key >> shift) & 0xff)], 1u);
-        }
-        __syncthreads();
-        // the bin that holds rank kk: first b with kk < hist[0] + ... + hist[b] (255 when none).  One wave scans the 256 bins, four
-        // per lane (thread 0 walking them one dependent LDS read at a time cost ~8 us per pass: 16 passes per mad!)
-        if (tid < 64) {
-            const unsigned int h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-            const unsigned int mine = h0 + h1 + h2 + h3;
-            unsigned int incl = mine;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const unsigned int o = __shfl_up(incl, d, 64);
-                if (tid >= d) incl += o;
-            }
-            const unsigned long long kk = sh[1];
-            const unsigned long long excl = incl - mine;
-            const bool hit = kk < (unsigned long long)incl;
-            const unsigned long long m = __ballot(hit);
-            const int first = m ? (__ffsll((long long)m) - 1) : 64;
-            if (tid == first) {
-                int b = 4 * tid;
-                unsigned long long cum = excl;
-                if (kk >= cum + h0) { cum += h0; ++b; if (kk >= cum + h1) { cum += h1; ++b; if (kk >= cum + h2) { cum += h2; ++b; } } }
-                sh[1] = kk - cum;
-                sh[0] = sh[0] | (((unsigned long long)b) << shift);
-            } else if (first == 64 && tid == 63) {       // (cannot happen for kk < n; mirrors the serial walk: bin 255, all lower bins skipped)
-                sh[1] = kk - (excl + h0 + h1 + h2);
-                sh[0] = sh[0] | (255ull << shift);
-            }
-        }
-        __syncthreads();
-    }
-    const U r = (U)sh[0];
-    __syncthreads();                // the next call re-initialises sh
-    return r;
-}
 template <typename T, int INST = 0>
 __device__ T lds_median(typename KeyOf<T>::U *keys, int n, unsigned int *hist, unsigned long long *sh, unsigned int nan_count)
 {
@@ -1005,11 +876,6 @@ __global__ void __launch_bounds__(1024) k_mad_lds(T *v, int n, int do_mad, SelSt
     }
     if (tid == 0) s->result = (double)m;
 }
-// keys of n elements in dynamic LDS next to ~1 KiB of static LDS: stay under the 64 KiB a kernel gets without
-// hipFuncSetAttribute (Float64 keys are 8 bytes)
-template <typename T>
-constexpr int64_t mad_lds_max() { return sizeof(T) == 4 ? 8192 : 4096; }
-
 template <typename T>
 int mad_small(wl_ctx *ctx, hipStream_t st, T *v, int64_t n, int do_mad, double *result_host)
 {
@@ -1569,33 +1435,6 @@ __global__ void __launch_bounds__(1024) k_mad_units_lds(T *v0, int n, int64_t st
     if (tid == 0) result[blockIdx.x] = (double)m;
 }
 
-// the bin that holds rank kk among the 256 counts h[] -- first b with kk < h[0] + ... + h[b], 255 when none -- and the rank left
-// inside it: one wave, four bins per lane (the scan of lds_select)
-__device__ __forceinline__ void wave_pick_bin(const unsigned int *h, int lane, int shift, unsigned long long *prefix, unsigned long long *rank)
-{
-    const unsigned int h0 = h[4 * lane], h1 = h[4 * lane + 1], h2 = h[4 * lane + 2], h3 = h[4 * lane + 3];
-    const unsigned int mine = h0 + h1 + h2 + h3;
-    unsigned int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
-    const unsigned long long kk = *rank;
-    const unsigned long long excl = incl - mine;
-    const unsigned long long m = __ballot(kk < (unsigned long long)incl);
-    const int first = m ? (__ffsll((long long)m) - 1) : 64;
-    if (lane == first) {
-        int b = 4 * lane;
-        unsigned long long cum = excl;
-        if (kk >= cum + h0) { cum += h0; ++b; if (kk >= cum + h1) { cum += h1; ++b; if (kk >= cum + h2) { cum += h2; ++b; } } }
-        *rank = kk - cum;
-        *prefix = *prefix | (((unsigned long long)b) << shift);
-    } else if (first == 64 && lane == 63) {          // (cannot happen for kk < n; mirrors the serial walk of k_sel_scan)
-        *rank = kk - (excl + h0 + h1 + h2);
-        *prefix = *prefix | (255ull << shift);
-    }
-}
 // Units too long for LDS keys: a workgroup per unit streams its n values from memory once per radix byte (the unit stays in L2 between
 // passes), the two histograms in LDS, both middle ranks resolved per pass (k_sel_hist / k_sel_scan without a selection state in
 // HBM and without global atomics).  The second median runs the same passes on |v - m| computed on the fly; the deviations are

@@ -448,5 +448,6 @@ include("WaveletsMI355X_wpt_batch.jl")
 include("WaveletsMI355X_complex.jl")
 include("WaveletsMI355X_bestbasis_batch.jl")
 include("WaveletsMI355X_modwt_batch.jl")
+include("WaveletsMI355X_threshold_batch.jl")
 
 end # module

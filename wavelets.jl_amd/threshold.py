@@ -3,7 +3,8 @@ singletons) and src/Threshold/denoising.jl (VisuShrink, denoise, noisest, mad!),
 caller of the transform path.  Julia's `f!` is spelled `f_`.
 
 Everything runs on the device through libwavelets_mi355x.so (wl_threshold, wl_threshold_biggest,
-wl_mad, wl_circshift, wl_arrayadd, wl_rmul + the dwt/idwt entry points); the only host scalars are
+wl_threshold_batch, wl_threshold_biggest_batch, wl_mad, wl_circshift, wl_arrayadd, wl_rmul + the
+dwt/idwt entry points); the only host scalars are
 the ones the reference also has on the host (the noise estimate sigma and the threshold t).
 """
 from __future__ import annotations
@@ -117,6 +118,93 @@ def threshold(x, TH: THType, t=None):
     y = similar(x)
     y.copy_(x)
     return threshold_(y, TH, t)
+
+
+# ---- threshold! of a batch: per-unit thresholds and the best m-term approximation on the device ----------
+def _batch_units(x: torch.Tensor):
+    """(n, B, unit_stride) of a tensor whose last dimension is the batch, or None when its layout is not a batch of column-major
+    units a fixed number of elements apart"""
+    nb = int(x.shape[-1])
+    unit = tuple(int(s) for s in x.shape[:-1])
+    n = int(np.prod(unit)) if unit else 1
+    if n > 1 and not is_julia_layout(x[..., 0]):
+        return None
+    us = int(x.stride(-1)) if nb > 1 else n
+    return (n, nb, us) if us >= n else None
+
+
+def threshold_batch_(x, TH: THType, t=None):
+    """threshold!(x[.., u], TH, t_u) for every unit of a batch, in place, in one call (wl_threshold_batch /
+    wl_threshold_biggest_batch): x is column-major with the batch as its last dimension, a unit is everything in front of it (any
+    shape); units may be padded apart (the stride of the last dimension), the padding is never touched.
+    t: a Python number -- one threshold for all units, int versus float choosing the arithmetic type as in threshold_ -- or a 1-D
+    device tensor of B entries, one per unit: Float64 for HardTH / SoftTH / SemiSoftTH / SteinTH (a Float32 tensor with Float32
+    data: the arithmetic stays in Float32), Int64 for BiggestTH (the m of the best m-term approximation; entries are clamped to
+    [0, n] on the device).  Host numbers are validated as threshold_ does; device entries are not (no synchronisation): a negative
+    or NaN threshold yields what the reference's arithmetic yields without its assertion.  Same bits as the loop of threshold_ over
+    the units; nothing synchronises, a captured graph may hold the call."""
+    _reject_complex(x, "threshold_batch_")
+    if not isinstance(TH, THType) or TH.code is None:
+        raise TypeError("unknown threshold type")
+    big = isinstance(TH, BiggestTH)
+    tens = isinstance(t, torch.Tensor)
+    if big:
+        if t is None or (tens and t.dtype != torch.int64) or (not tens and int(t) != t):
+            raise TypeError("threshold!(x, BiggestTH(), m::Int): m is an integer or an Int64 tensor of one m per unit")
+        if not tens and int(t) < 0:
+            raise AssertionError("m >= 0")
+    elif isinstance(TH, (PosTH, NegTH)):
+        if t is not None:
+            raise TypeError("threshold!(x, PosTH()/NegTH()) takes no threshold (MethodError in the reference)")
+    else:
+        if t is None:
+            raise TypeError("threshold!(x, TH, t): t is required (MethodError in the reference)")
+        if tens and t.dtype not in (torch.float64, torch.float32):
+            raise TypeError("per-unit thresholds are a Float64 tensor (Float32 with Float32 data)")
+        if not tens and not float(t) >= 0:
+            raise AssertionError("t >= 0")
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+        raise HIPError("expected a torch tensor resident on an MI355X device (use to_device(array)); there is no CPU path")
+    _dtype_code(x)
+    if x.dim() < 1 or int(x.numel()) == 0:
+        raise DimensionMismatch("threshold_batch_ expects a non-empty array whose last dimension is the batch")
+    lay = _batch_units(x)
+    if lay is None:
+        raise ArgumentError("threshold_batch_ works in place: units must be column-major and a fixed stride >= their length apart")
+    n, nb, us = lay
+    tdev, is64 = None, 1
+    if tens:
+        if t.device != x.device or t.dim() != 1 or int(t.numel()) != nb:
+            raise ArgumentError("the per-unit tensor must be 1-D with B entries on x's device")
+        if t.dtype == torch.float32:
+            if x.dtype != torch.float32:
+                raise TypeError("Float32 thresholds go with Float32 data")
+            tdev, is64 = t.to(torch.float64), 0
+        else:
+            tdev = t.contiguous()
+    lib = _lib.load()
+    h, st = _context(x.device)
+    if big:
+        rc = lib.wl_threshold_biggest_batch(h, _dtype_code(x), C.c_void_p(x.data_ptr()), n, nb, us, 0 if tens else int(t),
+                                            C.c_void_p(tdev.data_ptr()) if tens else None, st)
+    else:
+        tv = 0.0 if (tens or t is None) else float(t)
+        if not tens and t is not None:
+            is64 = _t_is_f64(x, t)
+        rc = lib.wl_threshold_batch(h, _dtype_code(x), C.c_void_p(x.data_ptr()), n, nb, us, TH.code, tv,
+                                    C.c_void_p(tdev.data_ptr()) if tens else None, is64, st)
+    _check(rc, h)
+    return x
+
+
+def threshold_batch(x, TH: THType, t=None):
+    """threshold_batch_ on a dense column-major copy of x"""
+    _reject_complex(x, "threshold_batch")
+    if isinstance(x, torch.Tensor) and x.device.type == "cuda" and x.dim() >= 1:
+        y = similar(x)
+        y.copy_(x)
+        x = y
+    return threshold_batch_(x, TH, t)
 
 
 # ---- denoising (denoising.jl) -------------------------------------------------------------------
