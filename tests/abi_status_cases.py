@@ -111,7 +111,7 @@ ENTRIES = [
      [("ctx", "CTX"), ("dtype", 1), ("z", "B0"), ("planes", "B1"), ("plane_stride", 64), ("n", 64), ("nunits", 2), ("unit_stride", 64),
       ("stream", None)],
      [_nulls("ctx", "z", "planes"), _DT, (EDIMS, [dict(n=0), dict(nunits=0), dict(unit_stride=63), dict(plane_stride=63)]), SCOPE]),
-    # ---- wl_ext.hip: the older entry points enter the scope right behind ctx and dtype ----
+    # ---- wl_modwt.hip, wl_ext.hip: the older entry points enter the scope right behind ctx and dtype (ext_enter, wl_entry.h) ----
     ("wl_modwt",
      [("ctx", "CTX"), ("dtype", 0), ("out", "B0"), ("ldo", 64), ("x", "B1"), ("n", 64), ("qmf", "QMF"), ("flen", 4), ("L", 2), ("stream", None)],
      [_nulls("ctx"), _DT, SCOPE, _nulls("out", "x", "qmf"), _FL1, (EDIMS, [dict(n=0), dict(ldo=63)]), (SIZE, [dict(L=7)]),

@@ -26,9 +26,12 @@ def test_modwt_bitexact(gpu, W, oracle, dtype):
             for L in Ls:
                 we = oracle.modwt(x, wt.qmf, L)
                 wg = W.modwt(W.to_device(x), wt, L)
+                assert W.last_kernel() == "k_modwt_step", (n, fname, L)
                 assert tuple(wg.shape) == we.shape and W.is_julia_layout(wg)
                 assert np.array_equal(host(W, wg), we), (n, fname, L)
-                xr = host(W, W.imodwt(W.to_device(we), wt))
+                xr = W.imodwt(W.to_device(we), wt)
+                assert W.last_kernel() == "k_imodwt_step", (n, fname, L)           # (every `we` here has two columns or more)
+                xr = host(W, xr)
                 assert np.array_equal(xr, oracle.imodwt(we, wt.qmf)), (n, fname, L, "inv")
                 with W.options(WL_MODWT_SMALL=0):        # levels 1-2 on the scalar kernels instead of the small-stride vector kernels
                     assert np.array_equal(host(W, W.modwt(W.to_device(x), wt, L)), we), (n, fname, L, "scalar")
@@ -36,6 +39,12 @@ def test_modwt_bitexact(gpu, W, oracle, dtype):
                 if fname != "batt2":          # the Battle tables are not orthogonal: imodwt is only the adjoint there
                     assert np.abs(xr - x).max() <= (1e-4 if dtype == np.float32 else 1e-10) * max(1.0, np.abs(x).max())
     wt = W.wavelet(W.WT.db4)
+    # a vector that fits the LDS tier of the batch: the single calls share the batch's level launcher and still never take k_modwt_lds
+    xd = W.to_device(rng_array((1000,), dtype, 1))
+    wd = W.modwt(xd, wt, 3)
+    assert W.last_kernel() == "k_modwt_step"
+    W.imodwt(wd, wt)
+    assert W.last_kernel() == "k_imodwt_step"
     xd = W.to_device(rng_array((100,), dtype, 0))
     assert W.maxmodwttransformlevels(xd) == 6
     with pytest.raises(W.ArgumentError, match="Too many transform levels"):

@@ -1107,8 +1107,6 @@ static WptCall<T> wpt_call(int64_t n, const Taps<T> *taps, const LiftScheme<T> *
 // base is 16-byte aligned (what the batched tiers ask for).  Workspace layout (bytes): [the inner level loop's region | P | Q].
 namespace {
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 template <typename T>
 inline int64_t plane_stride_of(int64_t N)
 {
@@ -1116,17 +1114,8 @@ inline int64_t plane_stride_of(int64_t N)
     return (N + E - 1) / E * E;
 }
 
-// (groups: group_reserve with a limit of 32767 units -- 2 G planes, a grid row / plane / workgroup per plane in the batched kernels)
-
-// the box of np real planes of stride ps as the batched real entry points describe it: lines (wl_dwtc_*) or images (wl_dwt_*_batch)
-inline BoxSpec planes_box(int ndims, const int64_t *dims, int64_t np, int64_t ps)
-{
-    BoxSpec b;
-    b.nd = ndims + 1; b.nt = ndims;
-    b.dims[0] = dims[0]; b.dims[1] = (ndims == 2) ? dims[1] : np; b.dims[2] = (ndims == 2) ? np : 1;
-    b.full.s[0] = 1; b.full.s[1] = (ndims == 2) ? dims[0] : ps; b.full.s[2] = (ndims == 2) ? ps : ps * np;
-    return b;
-}
+// (groups: group_reserve with a limit of 32767 units -- 2 G planes, a grid row / plane / workgroup per plane in the batched kernels;
+// the planes of a group are one batch for filter_levels_planes / lifting_levels_planes, wl_entry.h)
 
 template <typename T>
 int dwt_filter_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, int64_t nunits, int64_t S,
@@ -1137,7 +1126,7 @@ int dwt_filter_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
     if (L == 0) return copy_units<T>(ctx, st, y, x, 2 * N, y != x ? nunits : 0, 2 * S);      // (a unit: 2 N reals)
     const int64_t ps = plane_stride_of<T>(N);
     const Taps<T> taps = taps_of<T>(qmf, flen);
-    auto tw_bytes = [&](int64_t G) { return up256((ndims == 3 ? ws_vols_elems(N, 2 * G) : ws_elems(N * 2 * G, ndims)) * sizeof(T)); };
+    auto tw_bytes = [&](int64_t G) { return up256(ws_filter_planes_elems(ndims, N, 2 * G) * sizeof(T)); };
     auto pl_bytes = [&](int64_t G) { return up256((size_t)(2 * G * ps) * sizeof(T)); };
     auto need = [&](int64_t G) { return tw_bytes(G) + 2 * pl_bytes(G); };
     int64_t G = 1;
@@ -1148,14 +1137,7 @@ int dwt_filter_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
     const char *kn = ctx->last_kernel;
     WL_TRY(for_groups(nunits, G, [&](int64_t u0, int64_t nb) -> int {
         WL_HIP(ctx, complex_split<T>(st, ctx->cu_count, P, ps, x + 2 * u0 * S, N, nb, S));
-        if (ndims == 3) {
-            rc = fw ? filter_fwd_levels_vols<T>(wsb, true, ctx->cu_count, ctx->path, st, dims, 2 * nb, ps, ps, Q, P, taps, L, &kn, &ctx->last_hip)
-                    : filter_inv_levels_vols<T>(wsb, true, ctx->cu_count, ctx->path, st, dims, 2 * nb, ps, ps, Q, P, taps, L, &kn, &ctx->last_hip);
-        } else {
-            const BoxSpec b = planes_box(ndims, dims, 2 * nb, ps);
-            rc = fw ? filter_fwd_levels<T>(wsb, true, ctx->cu_count, ctx->path, st, b, Q, P, taps, L, &kn, &ctx->last_hip)
-                    : filter_inv_levels<T>(wsb, true, ctx->cu_count, ctx->path, st, b, Q, P, taps, L, &kn, &ctx->last_hip);
-        }
+        rc = filter_levels_planes<T>(ctx, st, fw, ndims, dims, 2 * nb, ps, Q, P, taps, L, &kn);
         if (rc == WL_RETRY_GEN) rc = WL_EINVAL_ARG;          // (the full workspace is held: no level can ask for more)
         if (rc != WL_OK) return rc;
         WL_HIP(ctx, complex_merge<T>(st, ctx->cu_count, y + 2 * u0 * S, Q, ps, N, nb, S));
@@ -1174,11 +1156,7 @@ int dwt_lifting_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int 
     if (L == 0) return copy_units<T>(ctx, st, y, x, 2 * N, y != x ? nunits : 0, 2 * S);      // (a unit: 2 N reals)
     const int64_t ps = plane_stride_of<T>(N);
     // the lifting workspace of the planes of a group, as wl_denoise_batch_lifting sizes it (the loops below ask for no more)
-    auto tw_bytes = [&](int64_t G) -> size_t {
-        size_t e = ws_elems(N * 2 * G, 1);
-        if (ndims == 3) { const size_t a = ws_lift_vols_elems(N, 2 * G), b = ws_elems(N, 1); e = a > b ? a : b; }
-        return up256(e * sizeof(T));
-    };
+    auto tw_bytes = [&](int64_t G) { return up256(ws_lifting_planes_elems(ndims, N, 2 * G) * sizeof(T)); };
     auto need = [&](int64_t G) { return tw_bytes(G) + up256((size_t)(2 * G * ps) * sizeof(T)); };
     int64_t G = 1;
     int rc = group_reserve(ctx, st, nunits, 32767, need, G);
@@ -1187,8 +1165,7 @@ int dwt_lifting_complex_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int 
     T *P = (T *)((char *)ctx->ws + tw_bytes(G));
     return for_groups(nunits, G, [&](int64_t u0, int64_t nb) -> int {
         WL_HIP(ctx, complex_split<T>(st, ctx->cu_count, P, ps, x + 2 * u0 * S, N, nb, S));
-        rc = ndims == 3 ? wl_lifting_vols<T>(ctx, st, dims[0], 2 * nb, ps, P, P, sc, L, fw)
-                        : wl_lifting_box<T>(ctx, st, planes_box(ndims, dims, 2 * nb, ps), P, P, sc, L, fw);
+        rc = lifting_levels_planes<T>(ctx, st, ndims, dims[0], 2 * nb, ps, P, P, sc, L, fw);
         if (rc != WL_OK) return rc;
         if (ctx->ws != held) return WL_ENOMEM;               // (a loop that outgrew the reservation would have moved P: not reached)
         WL_HIP(ctx, complex_merge<T>(st, ctx->cu_count, y + 2 * u0 * S, P, ps, N, nb, S));

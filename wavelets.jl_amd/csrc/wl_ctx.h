@@ -1,5 +1,5 @@
 // wl_ctx.h -- the context object behind the C ABI (one per device + stream) and the helpers shared by
-// the translation units that implement entry points (wl_api.hip, wl_ext.hip).
+// the translation units that implement entry points (wl_api.hip, wl_ext.hip, wl_modwt.hip, wl_thbatch.hip).
 #pragma once
 #include "wl_internal.h"
 
@@ -74,7 +74,7 @@ inline int hip_fail(wl_ctx *ctx, hipError_t e)
 // synchronisation (wl_ctx_reserve)
 int wl_ensure_ws(wl_ctx *ctx, size_t bytes, hipStream_t st = nullptr, bool ordered = false);
 
-// lifting transform of a box with a direction-adjusted scheme (wl_api.hip; used by wl_ext.hip)
+// lifting transform of a box with a direction-adjusted scheme (wl_api.hip; used by wl_ext.hip and by lifting_levels_planes, wl_entry.h)
 template <typename T>
 int wl_lifting_box(wl_ctx *ctx, hipStream_t st, const wl::BoxSpec &b, T *y, const T *x, const wl::LiftScheme<T> &sc, int L, int fw);
 // ... of a batch of cubes of side n, cube i at element offset i * vs of x and of y (the batched 3-D level loop where it is eligible)

@@ -1,8 +1,10 @@
-// wl_entry.h -- what the extern "C" entry points (wl_api.hip, wl_ext.hip) share: the element-type dispatch, the dtype / filter
-// length rules, the lifting scheme as the ABI passes it, and the grouping of a batch's units.  Every entry point applies its
-// rules in the order the header documents for it, then dispatches once through by_dtype.
+// wl_entry.h -- what the extern "C" entry points (wl_api.hip, wl_ext.hip, wl_modwt.hip, wl_thbatch.hip) share: the element-type
+// dispatch, the dtype / filter length rules, the lifting scheme as the ABI passes it, the grouping of a batch's units and the level
+// loops of a batch of planes.  Every entry point applies its rules in the order the header documents for it, then dispatches once
+// through by_dtype.
 #pragma once
 #include "wl_ctx.h"
+#include "wl_fast.h"
 
 // return a status that is not WL_OK
 #define WL_TRY(expr)                \
@@ -28,6 +30,12 @@ inline int scoped_by_dtype(wl_ctx *ctx, int dtype, void *stream, F f)
 }
 
 inline int check_dtype(int dtype) { return (dtype != WL_F32 && dtype != WL_F64) ? WL_EINVAL_DTYPE : WL_OK; }
+// the first two rules of the older entry points, which enter the scope right behind them
+inline int ext_enter(wl_ctx *ctx, int dtype)
+{
+    if (!ctx) return WL_EINVAL_ARG;
+    return check_dtype(dtype);
+}
 // min: 2 for the transforms, 1 for modwt / imodwt
 inline int check_flen(int flen, int min = 2) { return (flen < min || flen > WL_MAX_FLEN) ? WL_EINVAL_FILTER : WL_OK; }
 
@@ -122,4 +130,29 @@ inline int for_groups(int64_t nunits, int64_t G, F f)
 {
     for (int64_t u0 = 0; u0 < nunits; u0 += G) WL_TRY(f(u0, (nunits - u0 < G) ? (nunits - u0) : G));
     return WL_OK;
+}
+
+inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// ---- all `lev` levels on nb planes of stride ps (planes_box, wl_fast.h; cubes: a batch of volumes) in the context's workspace ---------
+// The status of the level loop comes back untranslated (WL_RETRY_GEN, WL_RETRY_NOVIEW: the caller's business); *kn = the kernel's name.
+template <typename T>
+inline int filter_levels_planes(wl_ctx *ctx, hipStream_t st, int fw, int ndims, const int64_t *dims, int64_t nb, int64_t ps, T *dst, const T *src,
+                                const wl::Taps<T> &taps, int lev, const char **kn)
+{
+    if (ndims == 3)
+        return fw ? wl::filter_fwd_levels_vols<T>(ctx->ws, true, ctx->cu_count, ctx->path, st, dims, nb, ps, ps, dst, src, taps, lev, kn, &ctx->last_hip)
+                  : wl::filter_inv_levels_vols<T>(ctx->ws, true, ctx->cu_count, ctx->path, st, dims, nb, ps, ps, dst, src, taps, lev, kn, &ctx->last_hip);
+    const wl::BoxSpec b = wl::planes_box(ndims, dims, nb, ps);
+    return fw ? wl::filter_fwd_levels<T>(ctx->ws, true, ctx->cu_count, ctx->path, st, b, dst, src, taps, lev, kn, &ctx->last_hip)
+              : wl::filter_inv_levels<T>(ctx->ws, true, ctx->cu_count, ctx->path, st, b, dst, src, taps, lev, kn, &ctx->last_hip);
+}
+// the same with a direction-adjusted lifting scheme on lines / squares / cubes of side n0
+template <typename T>
+inline int lifting_levels_planes(wl_ctx *ctx, hipStream_t st, int ndims, int64_t n0, int64_t nb, int64_t ps, T *dst, const T *src,
+                                 const wl::LiftScheme<T> &sc, int lev, int fw)
+{
+    if (ndims == 3) return wl_lifting_vols<T>(ctx, st, n0, nb, ps, dst, src, sc, lev, fw);
+    const int64_t dims[2] = {n0, n0};
+    return wl_lifting_box<T>(ctx, st, wl::planes_box(ndims, dims, nb, ps), dst, src, sc, lev, fw);
 }

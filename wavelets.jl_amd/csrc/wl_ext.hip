@@ -1,10 +1,9 @@
-// wl_ext.hip -- the callers around the hot path:
-//   modwt / imodwt                       transforms_maximal_overlap.jl:10-107
+// wl_ext.hip -- the callers around the hot path (row 4, modwt / imodwt: wl_modwt.hip):
 //   threshold! (all THTypes)             threshold_main.jl:21-117
 //   median! / mad! (noise estimate)      denoising.jl:92-110 (+ Statistics.median!)
 //   circshift / arrayadd! / rmul!        util_main.jl:105-130, denoising.jl:82-88 (translation-invariant denoising)
 // All of it is HBM-bound element-wise or gather work; the arithmetic follows Julia's promotion rules
-// literally (Float32 data with Float64 taps / threshold: compute in Float64, round on every store) so the
+// literally (Float32 data with a Float64 threshold: compute in Float64, round on every store) so the
 // results are bit-identical to the reference loops.
 #include "wl_entry.h"
 #include "wl_fast.h"
@@ -17,657 +16,6 @@
 using namespace wl;
 
 namespace {
-
-// ---- MODWT -----------------------------------------------------------------------------------------
-struct ModwtTaps { int F; double h[WL_MAX_FLEN]; double g[WL_MAX_FLEN]; };   // h: detail, g: scaling (both / sqrt 2)
-
-// WT.makereverseqmfpair(wt) (fw, Float64: g = reverse(qmf), h = mirror(qmf)) then `/= sqrt(2)`, :50-52
-void make_modwt_taps(const double *qmf, int F, ModwtTaps &t)
-{
-    const double r2 = std::sqrt(2.0);
-    t.F = F;
-    for (int i = 0; i < WL_MAX_FLEN; ++i) { t.h[i] = 0.0; t.g[i] = 0.0; }
-    for (int i = 0; i < F; ++i) {
-        t.g[i] = qmf[F - 1 - i] / r2;
-        t.h[i] = ((i & 1) ? -qmf[i] : qmf[i]) / r2;
-    }
-}
-
-// a 16-byte vector of T
-template <typename T>
-using Vec16 = T __attribute__((ext_vector_type(16 / sizeof(T))));
-
-// modwt_step (:10-31): w1[t] = sum_n h[n] v[t - n*stride], v1[t] = sum_n g[n] v[...], accumulated in tap order,
-// every partial sum rounded to T (Julia: `w1[t] += h[n] * v[k]` with w1::Vector{T}, h::Vector{Float64}).
-// The arithmetic of one output (or of the V outputs of one 16-byte chunk) lives in the device functions below: the single-unit
-// kernels, the batched per-level kernels and the LDS kernels all call them, so every tier rounds alike.  I is the index type:
-// int64_t over global memory, int inside a workgroup's LDS copy of a unit.
-template <typename T, typename I>
-__device__ __forceinline__ void modwt_point(const T *v, I N, I t, I stride, const ModwtTaps &tp, T &w, T &s)
-{
-    I k = t;
-    double x = (double)v[k];
-    w = (T)(tp.h[0] * x);
-    s = (T)(tp.g[0] * x);
-    for (int n = 1; n < tp.F; ++n) {
-        k -= stride;
-        if (k < 0) { k += N; if (k < 0) { k %= N; if (k < 0) k += N; } }   // one add unless the stride exceeds N (tiny signals)
-        x = (double)v[k];
-        w = (T)((double)w + tp.h[n] * x);
-        s = (T)((double)s + tp.g[n] * x);
-    }
-}
-// imodwt_step (:72-93): v0[t] = sum_n (h[n] w[t + n*stride] + g[n] v[t + n*stride])
-template <typename T, typename I>
-__device__ __forceinline__ T imodwt_point(const T *v, const T *w, I N, I t, I stride, const ModwtTaps &tp)
-{
-    I k = t;
-    T acc = (T)(tp.h[0] * (double)w[k] + tp.g[0] * (double)v[k]);
-    for (int n = 1; n < tp.F; ++n) {
-        k += stride;
-        if (k >= N) { k -= N; if (k >= N) k %= N; }
-        acc = (T)((double)acc + (tp.h[n] * (double)w[k] + tp.g[n] * (double)v[k]));
-    }
-    return acc;
-}
-
-// the same for strides that are multiples of the 16-byte vector width (levels >= 3 for Float32, >= 2 for Float64) and N a
-// multiple of it: every tap of V consecutive outputs is one aligned vector load.  t, NV and strideV count vectors.
-template <typename T, typename I>
-__device__ __forceinline__ void modwt_chunk_v(const T *v, I NV, I t, I strideV, const ModwtTaps &tp,
-                                              Vec16<T> &w,
-                                              Vec16<T> &s)
-{
-    constexpr int V = 16 / sizeof(T);
-    typedef T VT __attribute__((ext_vector_type(V)));
-    const VT *vv = reinterpret_cast<const VT *>(v);
-    I k = t;
-    VT x = vv[k];
-#pragma unroll
-    for (int e = 0; e < V; ++e) { const double xd = (double)x[e]; w[e] = (T)(tp.h[0] * xd); s[e] = (T)(tp.g[0] * xd); }
-    for (int n = 1; n < tp.F; ++n) {
-        k -= strideV;
-        if (k < 0) { k += NV; if (k < 0) { k %= NV; if (k < 0) k += NV; } }
-        x = vv[k];
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            const double xd = (double)x[e];
-            w[e] = (T)((double)w[e] + tp.h[n] * xd);
-            s[e] = (T)((double)s[e] + tp.g[n] * xd);
-        }
-    }
-}
-template <typename T, typename I>
-__device__ __forceinline__ Vec16<T> imodwt_chunk_v(const T *v, const T *w, I NV, I t, I strideV, const ModwtTaps &tp)
-{
-    constexpr int V = 16 / sizeof(T);
-    typedef T VT __attribute__((ext_vector_type(V)));
-    const VT *vv = reinterpret_cast<const VT *>(v), *wv = reinterpret_cast<const VT *>(w);
-    I k = t;
-    VT a = vv[k], b = wv[k], acc;
-#pragma unroll
-    for (int e = 0; e < V; ++e) acc[e] = (T)(tp.h[0] * (double)b[e] + tp.g[0] * (double)a[e]);
-    for (int n = 1; n < tp.F; ++n) {
-        k += strideV;
-        if (k >= NV) { k -= NV; if (k >= NV) k %= NV; }
-        a = vv[k];
-        b = wv[k];
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc[e] = (T)((double)acc[e] + (tp.h[n] * (double)b[e] + tp.g[n] * (double)a[e]));
-    }
-    return acc;
-}
-
-// strides below the vector width (levels 1-2 for Float32, level 1 for Float64; S divides V): a thread still produces V
-// consecutive outputs from aligned 16-byte loads -- the V/S taps that fall into one vector step are served from the register
-// pair [previous chunk | current chunk] with compile-time offsets, then the pair slides by one chunk.  Same tap order and
-// per-tap rounding as modwt_point (a scalar kernel issues one 4-byte load per lane and tap: 1.2 TB/s of level traffic).
-// NV >= 2.
-template <typename T, int S, typename I>
-__device__ __forceinline__ void modwt_chunk_s(const T *v, I NV, I t, const ModwtTaps &tp,
-                                              Vec16<T> &w,
-                                              Vec16<T> &s)
-{
-    constexpr int V = 16 / sizeof(T), G = V / S;
-    typedef T VT __attribute__((ext_vector_type(V)));
-    const VT *vv = reinterpret_cast<const VT *>(v);
-    I k = t;
-    VT c = vv[k];
-    I kp = (k == 0) ? NV - 1 : k - 1;
-    VT p = vv[kp];
-    for (int n0 = 0; n0 < tp.F; n0 += G) {
-        T win[2 * V];
-#pragma unroll
-        for (int e = 0; e < V; ++e) { win[e] = p[e]; win[V + e] = c[e]; }
-        c = p;                                         // slide: the next group of taps starts one chunk back
-        kp = (kp == 0) ? NV - 1 : kp - 1;
-        p = vv[kp];
-#pragma unroll
-        for (int r = 0; r < G; ++r) {
-            const int n = n0 + r;
-            if (n < tp.F) {
-#pragma unroll
-                for (int e = 0; e < V; ++e) {
-                    const double xd = (double)win[V + e - r * S];
-                    if (n == 0) { w[e] = (T)(tp.h[0] * xd); s[e] = (T)(tp.g[0] * xd); }
-                    else { w[e] = (T)((double)w[e] + tp.h[n] * xd); s[e] = (T)((double)s[e] + tp.g[n] * xd); }
-                }
-            }
-        }
-    }
-}
-template <typename T, int S, typename I>
-__device__ __forceinline__ Vec16<T> imodwt_chunk_s(const T *v, const T *w, I NV, I t, const ModwtTaps &tp)
-{
-    constexpr int V = 16 / sizeof(T), G = V / S;
-    typedef T VT __attribute__((ext_vector_type(V)));
-    const VT *vv = reinterpret_cast<const VT *>(v), *wv = reinterpret_cast<const VT *>(w);
-    I kn = (t + 1 == NV) ? 0 : t + 1;
-    VT ca = vv[t], cb = wv[t], na = vv[kn], nb = wv[kn], acc;
-    for (int n0 = 0; n0 < tp.F; n0 += G) {
-        T wa[2 * V], wb[2 * V];
-#pragma unroll
-        for (int e = 0; e < V; ++e) { wa[e] = ca[e]; wa[V + e] = na[e]; wb[e] = cb[e]; wb[V + e] = nb[e]; }
-        ca = na; cb = nb;
-        kn = (kn + 1 == NV) ? 0 : kn + 1;
-        na = vv[kn]; nb = wv[kn];
-#pragma unroll
-        for (int r = 0; r < G; ++r) {
-            const int n = n0 + r;
-            if (n < tp.F) {
-#pragma unroll
-                for (int e = 0; e < V; ++e) {
-                    const double term = tp.h[n] * (double)wb[e + r * S] + tp.g[n] * (double)wa[e + r * S];
-                    acc[e] = (n == 0) ? (T)term : (T)((double)acc[e] + term);
-                }
-            }
-        }
-    }
-    return acc;
-}
-
-// the first index and the step of a grid-stride loop in x (taken in the kernel itself, where the block size is known to be uniform)
-#define GRID_X_FIRST ((int64_t)blockIdx.x * blockDim.x + threadIdx.x)
-#define GRID_X_THREADS ((int64_t)gridDim.x * blockDim.x)
-
-// one level of one unit, grid-stride in x from t0 in steps of nthr: the bodies of the single-unit kernels and of their batched twins
-// (k_*_b: the unit is blockIdx.y, the pointers are moved to it, nothing else differs)
-template <typename T>
-__device__ __forceinline__ void modwt_step_body(const T *__restrict__ v, T *__restrict__ v1, T *__restrict__ w1, int64_t N, int64_t stride,
-                                                const ModwtTaps &tp, int64_t t0, int64_t nthr)
-{
-    for (int64_t t = t0; t < N; t += nthr) {
-        T w, s;
-        modwt_point<T, int64_t>(v, N, t, stride, tp, w, s);
-        w1[t] = w;
-        v1[t] = s;
-    }
-}
-template <typename T>
-__device__ __forceinline__ void imodwt_step_body(const T *__restrict__ v, const T *__restrict__ w, T *__restrict__ v0, int64_t N,
-                                                 int64_t stride, const ModwtTaps &tp, int64_t t0, int64_t nthr)
-{
-    for (int64_t t = t0; t < N; t += nthr) v0[t] = imodwt_point<T, int64_t>(v, w, N, t, stride, tp);
-}
-template <typename T>
-__device__ __forceinline__ void modwt_step_v_body(const T *__restrict__ v, T *__restrict__ v1, T *__restrict__ w1, int64_t NV,
-                                                  int64_t strideV, const ModwtTaps &tp, int64_t t0, int64_t nthr)
-{
-    typedef Vec16<T> VT;
-    for (int64_t t = t0; t < NV; t += nthr) {
-        VT w, s;
-        modwt_chunk_v<T, int64_t>(v, NV, t, strideV, tp, w, s);
-        reinterpret_cast<VT *>(w1)[t] = w;
-        reinterpret_cast<VT *>(v1)[t] = s;
-    }
-}
-template <typename T>
-__device__ __forceinline__ void imodwt_step_v_body(const T *__restrict__ v, const T *__restrict__ w, T *__restrict__ v0, int64_t NV,
-                                                   int64_t strideV, const ModwtTaps &tp, int64_t t0, int64_t nthr)
-{
-    typedef Vec16<T> VT;
-    for (int64_t t = t0; t < NV; t += nthr)
-        reinterpret_cast<VT *>(v0)[t] = imodwt_chunk_v<T, int64_t>(v, w, NV, t, strideV, tp);
-}
-template <typename T, int S>
-__device__ __forceinline__ void modwt_step_s_body(const T *__restrict__ v, T *__restrict__ v1, T *__restrict__ w1, int64_t NV,
-                                                  const ModwtTaps &tp, int64_t t0, int64_t nthr)
-{
-    typedef Vec16<T> VT;
-    for (int64_t t = t0; t < NV; t += nthr) {
-        VT w, s;
-        modwt_chunk_s<T, S, int64_t>(v, NV, t, tp, w, s);
-        reinterpret_cast<VT *>(w1)[t] = w;
-        reinterpret_cast<VT *>(v1)[t] = s;
-    }
-}
-template <typename T, int S>
-__device__ __forceinline__ void imodwt_step_s_body(const T *__restrict__ v, const T *__restrict__ w, T *__restrict__ v0, int64_t NV,
-                                                   const ModwtTaps &tp, int64_t t0, int64_t nthr)
-{
-    typedef Vec16<T> VT;
-    for (int64_t t = t0; t < NV; t += nthr)
-        reinterpret_cast<VT *>(v0)[t] = imodwt_chunk_s<T, S, int64_t>(v, w, NV, t, tp);
-}
-
-template <typename T>
-__global__ void __launch_bounds__(EXT_THREADS) k_modwt_step(const T *__restrict__ v, T *__restrict__ v1, T *__restrict__ w1,
-                                                            int64_t N, int64_t stride, ModwtTaps tp)
-{
-    modwt_step_body<T>(v, v1, w1, N, stride, tp, GRID_X_FIRST, GRID_X_THREADS);
-}
-template <typename T>
-__global__ void __launch_bounds__(EXT_THREADS) k_imodwt_step(const T *__restrict__ v, const T *__restrict__ w, T *__restrict__ v0,
-                                                             int64_t N, int64_t stride, ModwtTaps tp)
-{
-    imodwt_step_body<T>(v, w, v0, N, stride, tp, GRID_X_FIRST, GRID_X_THREADS);
-}
-template <typename T>
-__global__ void __launch_bounds__(EXT_THREADS) k_modwt_step_v(const T *__restrict__ v, T *__restrict__ v1, T *__restrict__ w1,
-                                                              int64_t NV, int64_t strideV, ModwtTaps tp)
-{
-    modwt_step_v_body<T>(v, v1, w1, NV, strideV, tp, GRID_X_FIRST, GRID_X_THREADS);
-}
-template <typename T>
-__global__ void __launch_bounds__(EXT_THREADS) k_imodwt_step_v(const T *__restrict__ v, const T *__restrict__ w, T *__restrict__ v0,
-                                                               int64_t NV, int64_t strideV, ModwtTaps tp)
-{
-    imodwt_step_v_body<T>(v, w, v0, NV, strideV, tp, GRID_X_FIRST, GRID_X_THREADS);
-}
-template <typename T, int S>
-__global__ void __launch_bounds__(EXT_THREADS) k_modwt_step_s(const T *__restrict__ v, T *__restrict__ v1, T *__restrict__ w1,
-                                                              int64_t NV, ModwtTaps tp)
-{
-    modwt_step_s_body<T, S>(v, v1, w1, NV, tp, GRID_X_FIRST, GRID_X_THREADS);
-}
-template <typename T, int S>
-__global__ void __launch_bounds__(EXT_THREADS) k_imodwt_step_s(const T *__restrict__ v, const T *__restrict__ w, T *__restrict__ v0,
-                                                               int64_t NV, ModwtTaps tp)
-{
-    imodwt_step_s_body<T, S>(v, w, v0, NV, tp, GRID_X_FIRST, GRID_X_THREADS);
-}
-
-// ---- the batched per-level tier: one launch per level over the units of a group, unit blockIdx.y at v + y * vs (and so on) ------
-template <typename T>
-__global__ void __launch_bounds__(EXT_THREADS) k_modwt_step_b(const T *__restrict__ v, int64_t vs, T *__restrict__ v1, int64_t v1s,
-                                                              T *__restrict__ w1, int64_t w1s, int64_t N, int64_t stride, ModwtTaps tp)
-{
-    const int64_t u = blockIdx.y;
-    modwt_step_body<T>(v + u * vs, v1 + u * v1s, w1 + u * w1s, N, stride, tp, GRID_X_FIRST, GRID_X_THREADS);
-}
-template <typename T>
-__global__ void __launch_bounds__(EXT_THREADS) k_imodwt_step_b(const T *__restrict__ v, int64_t vs, const T *__restrict__ w, int64_t ws,
-                                                               T *__restrict__ v0, int64_t v0s, int64_t N, int64_t stride, ModwtTaps tp)
-{
-    const int64_t u = blockIdx.y;
-    imodwt_step_body<T>(v + u * vs, w + u * ws, v0 + u * v0s, N, stride, tp, GRID_X_FIRST, GRID_X_THREADS);
-}
-template <typename T>
-__global__ void __launch_bounds__(EXT_THREADS) k_modwt_step_v_b(const T *__restrict__ v, int64_t vs, T *__restrict__ v1, int64_t v1s,
-                                                                T *__restrict__ w1, int64_t w1s, int64_t NV, int64_t strideV, ModwtTaps tp)
-{
-    const int64_t u = blockIdx.y;
-    modwt_step_v_body<T>(v + u * vs, v1 + u * v1s, w1 + u * w1s, NV, strideV, tp, GRID_X_FIRST, GRID_X_THREADS);
-}
-template <typename T>
-__global__ void __launch_bounds__(EXT_THREADS) k_imodwt_step_v_b(const T *__restrict__ v, int64_t vs, const T *__restrict__ w, int64_t ws,
-                                                                 T *__restrict__ v0, int64_t v0s, int64_t NV, int64_t strideV, ModwtTaps tp)
-{
-    const int64_t u = blockIdx.y;
-    imodwt_step_v_body<T>(v + u * vs, w + u * ws, v0 + u * v0s, NV, strideV, tp, GRID_X_FIRST, GRID_X_THREADS);
-}
-template <typename T, int S>
-__global__ void __launch_bounds__(EXT_THREADS) k_modwt_step_s_b(const T *__restrict__ v, int64_t vs, T *__restrict__ v1, int64_t v1s,
-                                                                T *__restrict__ w1, int64_t w1s, int64_t NV, ModwtTaps tp)
-{
-    const int64_t u = blockIdx.y;
-    modwt_step_s_body<T, S>(v + u * vs, v1 + u * v1s, w1 + u * w1s, NV, tp, GRID_X_FIRST, GRID_X_THREADS);
-}
-template <typename T, int S>
-__global__ void __launch_bounds__(EXT_THREADS) k_imodwt_step_s_b(const T *__restrict__ v, int64_t vs, const T *__restrict__ w, int64_t ws,
-                                                                 T *__restrict__ v0, int64_t v0s, int64_t NV, ModwtTaps tp)
-{
-    const int64_t u = blockIdx.y;
-    imodwt_step_s_body<T, S>(v + u * vs, w + u * ws, v0 + u * v0s, NV, tp, GRID_X_FIRST, GRID_X_THREADS);
-}
-
-// ---- the LDS tier of the batch: every level of a short unit in one launch ------------------------------------
-// which function a level of the LDS kernels takes, by the rules of the single-unit dispatch: 1 chunk_v, 2 chunk_s<1>, 3 chunk_s<2>
-// (Float32 only), 0 the point function (an unaligned batch, or a unit of one chunk)
-template <typename T>
-__device__ __forceinline__ int modwt_lds_kind(int vec, int64_t stride, int n)
-{
-    constexpr int V = 16 / sizeof(T);
-    if (!vec) return 0;
-    if ((stride % V) == 0) return 1;
-    if (stride == 1 && n >= 2 * V) return 2;
-    return (stride == 2 && V == 4 && n >= 2 * V) ? 3 : 0;
-}
-// A workgroup owns `upw` whole units at a time (more than one when a unit has fewer work items than the workgroup has threads)
-// and walks the batch with a grid-stride loop.  The units are loaded into LDS buffer A; level j reads V from the current buffer
-// with the wrap-around index of modwt_point / modwt_chunk_*, stores W to its global column and V to the other buffer (level L:
-// to column L); one barrier between levels.  vec != 0: n, ldo, the unit strides and the bases are multiples of 16 bytes -- a
-// work item is one 16-byte chunk (aligned 16-byte LDS reads of consecutive lanes, 16-byte global loads and stores) and the level
-// takes the chunk function the single-unit dispatch takes at that stride; otherwise a work item is one element.
-constexpr int MODWT_LDS_BYTES = 65536;         // two buffers of one unit: n <= 8192 (Float32) / 4096 (Float64)
-constexpr int MODWT_LDS_THREADS = 1024;
-
-template <typename T>
-__global__ void __launch_bounds__(MODWT_LDS_THREADS) k_modwt_lds(T *__restrict__ out, int64_t ldo, int64_t ous, const T *__restrict__ x,
-                                                                 int64_t xs, int n, int64_t nunits, int L, int upw, int vec, ModwtTaps tp)
-{
-    constexpr int V = 16 / sizeof(T);
-    typedef T VT __attribute__((ext_vector_type(V)));
-    extern __shared__ __attribute__((aligned(16))) char modwt_lds_mem[];
-    T *bufA = reinterpret_cast<T *>(modwt_lds_mem), *bufB = bufA + (size_t)upw * n;
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    const int ipu = vec ? n / V : n;                   // work items of one unit
-    for (int64_t u0 = (int64_t)blockIdx.x * upw; u0 < nunits; u0 += (int64_t)gridDim.x * upw) {
-        const int nu = (nunits - u0 < upw) ? (int)(nunits - u0) : upw;
-        for (int i = tid; i < nu * ipu; i += nthr) {
-            int slot = 0, c = i;
-            if (upw > 1) { slot = i / ipu; c = i - slot * ipu; }
-            const T *xu = x + (u0 + slot) * xs;
-            if (vec) reinterpret_cast<VT *>(bufA + (size_t)slot * n)[c] = reinterpret_cast<const VT *>(xu)[c];
-            else bufA[(size_t)slot * n + c] = xu[c];
-        }
-        __syncthreads();
-        T *cur = bufA, *nxt = bufB;
-        for (int j = 1; j <= L; ++j) {
-            const int stride = 1 << (j - 1);           // < n: L <= floor(log2 n)
-            const int kind = modwt_lds_kind<T>(vec, stride, n);
-            // (vec with kind 0, n == V: the items of this level are elements)
-            const int ipl = kind ? n / V : n;
-            for (int i = tid; i < nu * ipl; i += nthr) {
-                int slot = 0, c = i;
-                if (upw > 1) { slot = i / ipl; c = i - slot * ipl; }
-                const T *vsrc = cur + (size_t)slot * n;
-                T *ou = out + (u0 + slot) * ous;
-                T *vdst = (j == L) ? ou + (int64_t)L * ldo : nxt + (size_t)slot * n;
-                T *wdst = ou + (int64_t)(j - 1) * ldo;
-                if (kind == 0) {
-                    T w, s;
-                    modwt_point<T, int>(vsrc, n, c, stride, tp, w, s);
-                    wdst[c] = w;
-                    vdst[c] = s;
-                } else {
-                    VT w, s;
-                    if (kind == 1) modwt_chunk_v<T, int>(vsrc, n / V, c, stride / V, tp, w, s);
-                    else if (kind == 2) modwt_chunk_s<T, 1, int>(vsrc, n / V, c, tp, w, s);
-                    else modwt_chunk_s<T, (V == 4 ? 2 : 1), int>(vsrc, n / V, c, tp, w, s);
-                    reinterpret_cast<VT *>(wdst)[c] = w;
-                    reinterpret_cast<VT *>(vdst)[c] = s;
-                }
-            }
-            __syncthreads();
-            T *sw = cur; cur = nxt; nxt = sw;
-        }
-    }
-}
-// the mirror image: column ncols - 1 of every unit into LDS; level j reads W's column from global memory and V from LDS and
-// writes V of level j - 1 to the other buffer -- level 1 writes x.  ncols >= 2.  A stride 2^(j-1) may exceed n many times over
-// (ncols is not bounded by n): it is reduced mod n once, which leaves every index what imodwt_point computes.
-template <typename T>
-__global__ void __launch_bounds__(MODWT_LDS_THREADS) k_imodwt_lds(T *__restrict__ x, int64_t xs, const T *__restrict__ xw, int64_t ldw,
-                                                                  int64_t ws, int n, int64_t nunits, int ncols, int upw, int vec, ModwtTaps tp)
-{
-    constexpr int V = 16 / sizeof(T);
-    typedef T VT __attribute__((ext_vector_type(V)));
-    extern __shared__ __attribute__((aligned(16))) char modwt_lds_mem[];
-    T *bufA = reinterpret_cast<T *>(modwt_lds_mem), *bufB = bufA + (size_t)upw * n;
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    const int ipu = vec ? n / V : n;
-    for (int64_t u0 = (int64_t)blockIdx.x * upw; u0 < nunits; u0 += (int64_t)gridDim.x * upw) {
-        const int nu = (nunits - u0 < upw) ? (int)(nunits - u0) : upw;
-        for (int i = tid; i < nu * ipu; i += nthr) {
-            int slot = 0, c = i;
-            if (upw > 1) { slot = i / ipu; c = i - slot * ipu; }
-            const T *vu = xw + (u0 + slot) * ws + (int64_t)(ncols - 1) * ldw;
-            if (vec) reinterpret_cast<VT *>(bufA + (size_t)slot * n)[c] = reinterpret_cast<const VT *>(vu)[c];
-            else bufA[(size_t)slot * n + c] = vu[c];
-        }
-        __syncthreads();
-        T *cur = bufA, *nxt = bufB;
-        for (int j = ncols - 1; j >= 1; --j) {
-            const int64_t stride = (int64_t)1 << (j - 1);
-            const int kind = modwt_lds_kind<T>(vec, stride, n);
-            const int ipl = kind ? n / V : n;
-            const int sred = (kind == 1) ? (int)((stride / V) % (n / V)) : (int)(stride % n);
-            for (int i = tid; i < nu * ipl; i += nthr) {
-                int slot = 0, c = i;
-                if (upw > 1) { slot = i / ipl; c = i - slot * ipl; }
-                const T *vsrc = cur + (size_t)slot * n;
-                const T *wsrc = xw + (u0 + slot) * ws + (int64_t)(j - 1) * ldw;
-                T *dst = (j == 1) ? x + (u0 + slot) * xs : nxt + (size_t)slot * n;
-                if (kind == 0) dst[c] = imodwt_point<T, int>(vsrc, wsrc, n, c, sred, tp);
-                else if (kind == 1) reinterpret_cast<VT *>(dst)[c] = imodwt_chunk_v<T, int>(vsrc, wsrc, n / V, c, sred, tp);
-                else if (kind == 2) reinterpret_cast<VT *>(dst)[c] = imodwt_chunk_s<T, 1, int>(vsrc, wsrc, n / V, c, tp);
-                else reinterpret_cast<VT *>(dst)[c] = imodwt_chunk_s<T, (V == 4 ? 2 : 1), int>(vsrc, wsrc, n / V, c, tp);
-            }
-            __syncthreads();
-            T *sw = cur; cur = nxt; nxt = sw;
-        }
-    }
-}
-
-template <typename T>
-int modwt_impl(wl_ctx *ctx, hipStream_t st, T *out, int64_t ldo, const T *x, int64_t N, const double *qmf, int flen, int L)
-{
-    constexpr int V = 16 / sizeof(T);
-    int rc = wl_ensure_ws(ctx, (size_t)2 * N * sizeof(T), st, true);
-    if (rc != WL_OK) return rc;
-    ModwtTaps tp;
-    make_modwt_taps(qmf, flen, tp);
-    T *A = (T *)ctx->ws, *B = A + N;
-    const T *cur = x;
-    const bool vec_base = (N % V) == 0 && (ldo % V) == 0 && vec_ok16(x) && vec_ok16(out);
-    for (int j = 1; j <= L; ++j) {
-        T *vdst = (j == L) ? out + (int64_t)L * ldo : ((j & 1) ? A : B);
-        const int64_t stride = (int64_t)1 << (j - 1);
-        if (vec_base && (stride % V) == 0) {
-            hipLaunchKernelGGL((k_modwt_step_v<T>), dim3(ext_blocks(N / V, 1, ctx->cu_count)), dim3(EXT_THREADS), 0, st, cur, vdst,
-                               out + (int64_t)(j - 1) * ldo, N / V, stride / V, tp);
-        } else if (vec_base && stride == 1 && N >= 2 * V && opt("WL_MODWT_SMALL", 1) != 0) {
-            hipLaunchKernelGGL((k_modwt_step_s<T, 1>), dim3(ext_blocks(N / V, 1, ctx->cu_count)), dim3(EXT_THREADS), 0, st, cur, vdst,
-                               out + (int64_t)(j - 1) * ldo, N / V, tp);
-        } else if (vec_base && stride == 2 && V == 4 && N >= 2 * V && opt("WL_MODWT_SMALL", 1) != 0) {
-            hipLaunchKernelGGL((k_modwt_step_s<T, (sizeof(T) == 4 ? 2 : 1)>), dim3(ext_blocks(N / V, 1, ctx->cu_count)), dim3(EXT_THREADS), 0, st,
-                               cur, vdst, out + (int64_t)(j - 1) * ldo, N / V, tp);
-        } else {
-            hipLaunchKernelGGL((k_modwt_step<T>), dim3(ext_blocks(N, 1, ctx->cu_count)), dim3(EXT_THREADS), 0, st, cur, vdst,
-                               out + (int64_t)(j - 1) * ldo, N, stride, tp);
-        }
-        WL_HIP(ctx, hipGetLastError());
-        cur = vdst;
-    }
-    ctx->last_kernel = "k_modwt_step";
-    return WL_OK;
-}
-template <typename T>
-int imodwt_impl(wl_ctx *ctx, hipStream_t st, T *x, const T *xw, int64_t ldw, int64_t N, int ncols, const double *qmf, int flen)
-{
-    constexpr int V = 16 / sizeof(T);
-    int rc = wl_ensure_ws(ctx, (size_t)2 * N * sizeof(T), st, true);
-    if (rc != WL_OK) return rc;
-    ModwtTaps tp;
-    make_modwt_taps(qmf, flen, tp);
-    T *A = (T *)ctx->ws, *B = A + N;
-    const T *cur = xw + (int64_t)(ncols - 1) * ldw;
-    if (ncols == 1) { WL_HIP(ctx, hipMemcpyAsync(x, cur, (size_t)N * sizeof(T), hipMemcpyDeviceToDevice, st)); return WL_OK; }
-    const bool vec_base = (N % V) == 0 && (ldw % V) == 0 && vec_ok16(x) && vec_ok16(xw);
-    for (int j = ncols - 1; j >= 1; --j) {
-        if (j - 1 >= 62) return WL_EINVAL_L;
-        T *dst = (j == 1) ? x : ((j & 1) ? A : B);
-        const int64_t stride = (int64_t)1 << (j - 1);
-        if (vec_base && (stride % V) == 0) {
-            hipLaunchKernelGGL((k_imodwt_step_v<T>), dim3(ext_blocks(N / V, 1, ctx->cu_count)), dim3(EXT_THREADS), 0, st, cur,
-                               xw + (int64_t)(j - 1) * ldw, dst, N / V, stride / V, tp);
-        } else if (vec_base && stride == 1 && N >= 2 * V && opt("WL_MODWT_SMALL", 1) != 0) {
-            hipLaunchKernelGGL((k_imodwt_step_s<T, 1>), dim3(ext_blocks(N / V, 1, ctx->cu_count)), dim3(EXT_THREADS), 0, st, cur,
-                               xw + (int64_t)(j - 1) * ldw, dst, N / V, tp);
-        } else if (vec_base && stride == 2 && V == 4 && N >= 2 * V && opt("WL_MODWT_SMALL", 1) != 0) {
-            hipLaunchKernelGGL((k_imodwt_step_s<T, (sizeof(T) == 4 ? 2 : 1)>), dim3(ext_blocks(N / V, 1, ctx->cu_count)), dim3(EXT_THREADS), 0, st,
-                               cur, xw + (int64_t)(j - 1) * ldw, dst, N / V, tp);
-        } else {
-            hipLaunchKernelGGL((k_imodwt_step<T>), dim3(ext_blocks(N, 1, ctx->cu_count)), dim3(EXT_THREADS), 0, st, cur,
-                               xw + (int64_t)(j - 1) * ldw, dst, N, stride, tp);
-        }
-        WL_HIP(ctx, hipGetLastError());
-        cur = dst;
-    }
-    ctx->last_kernel = "k_imodwt_step";
-    return WL_OK;
-}
-
-// ---- modwt / imodwt of a batch (wl_modwt_batch / wl_imodwt_batch) ------------------------------------------
-// The launch shape of the LDS tier.  A unit has `items` work items per level (16-byte chunks, or elements); the workgroup has that
-// many threads, at least EXT_THREADS and at most MODWT_LDS_THREADS, and takes threads / items whole units when a unit has fewer
-// items than that, so that no lane idles on a panel of tiny units.
-struct ModwtLdsShape { unsigned threads, grid; int upw; size_t lds; };
-template <typename T>
-ModwtLdsShape modwt_lds_shape(int64_t n, int64_t nunits, bool vec, int cu_count)
-{
-    const int64_t items = vec ? n / (int64_t)(16 / sizeof(T)) : n;
-    int64_t threads = (items + 63) / 64 * 64;
-    if (threads < EXT_THREADS) threads = EXT_THREADS;
-    if (threads > MODWT_LDS_THREADS) threads = MODWT_LDS_THREADS;
-    int64_t upw = items < threads ? threads / items : 1;
-    if (upw > nunits) upw = nunits;
-    int64_t grid = (nunits + upw - 1) / upw;
-    if (grid > (int64_t)cu_count * 8) grid = (int64_t)cu_count * 8;        // the rest by the grid-stride loop
-    return {(unsigned)threads, (unsigned)grid, (int)upw, (size_t)2 * upw * n * sizeof(T)};
-}
-// every unit base of a batch on a 16-byte boundary: what the chunk functions need (the single calls' rule, and the unit strides)
-template <typename T>
-bool modwt_batch_vec(const T *x, int64_t xs, const T *m, int64_t ld, int64_t ms, int64_t N, int64_t nunits)
-{
-    constexpr int V = 16 / sizeof(T);
-    return (N % V) == 0 && (ld % V) == 0 && vec_ok16(x) && vec_ok16(m) && (nunits == 1 || ((xs % V) == 0 && (ms % V) == 0));
-}
-
-template <typename T>
-int modwt_batch_impl(wl_ctx *ctx, hipStream_t st, T *out, int64_t ldo, int64_t ous, const T *x, int64_t N, int64_t nunits, int64_t xs,
-                     const double *qmf, int flen, int L)
-{
-    constexpr int V = 16 / sizeof(T);
-    ModwtTaps tp;
-    make_modwt_taps(qmf, flen, tp);
-    const bool vec = modwt_batch_vec<T>(x, xs, out, ldo, ous, N, nunits);
-    if (opt("WL_MODWT_FUSED", 1) != 0 && (size_t)2 * N * sizeof(T) <= (size_t)MODWT_LDS_BYTES) {
-        const ModwtLdsShape sh = modwt_lds_shape<T>(N, nunits, vec, ctx->cu_count);
-        hipLaunchKernelGGL((k_modwt_lds<T>), dim3(sh.grid), dim3(sh.threads), sh.lds, st, out, ldo, ous, x, xs, (int)N, nunits, L, sh.upw,
-                           vec ? 1 : 0, tp);
-        WL_HIP(ctx, hipGetLastError());
-        ctx->last_kernel = "k_modwt_lds";
-        return WL_OK;
-    }
-    auto bytes = [&](int64_t G) { return (size_t)2 * G * N * sizeof(T); };
-    const int64_t G = group_size(nunits, 65535, opt("WL_MODWT_BATCH_GROUP", 0), true, group_cap(), bytes);
-    WL_TRY(wl_ensure_ws(ctx, bytes(G), st, true));
-    T *A = (T *)ctx->ws, *B = A + G * N;
-    const bool small = opt("WL_MODWT_SMALL", 1) != 0;
-    WL_TRY(for_groups(nunits, G, [&](int64_t u0, int64_t nb) -> int {
-        const T *cur = x + u0 * xs;
-        int64_t cs = xs;
-        T *og = out + u0 * ous;
-        for (int j = 1; j <= L; ++j) {
-            T *vdst = (j == L) ? og + (int64_t)L * ldo : ((j & 1) ? A : B);
-            const int64_t vds = (j == L) ? ous : N;
-            T *wdst = og + (int64_t)(j - 1) * ldo;
-            const int64_t stride = (int64_t)1 << (j - 1);
-            const dim3 gv(ext_blocks(N / V, 1, ctx->cu_count), (unsigned)nb), gs(ext_blocks(N, 1, ctx->cu_count), (unsigned)nb);
-            if (vec && (stride % V) == 0)
-                hipLaunchKernelGGL((k_modwt_step_v_b<T>), gv, dim3(EXT_THREADS), 0, st, cur, cs, vdst, vds, wdst, ous, N / V, stride / V, tp);
-            else if (vec && stride == 1 && N >= 2 * V && small)
-                hipLaunchKernelGGL((k_modwt_step_s_b<T, 1>), gv, dim3(EXT_THREADS), 0, st, cur, cs, vdst, vds, wdst, ous, N / V, tp);
-            else if (vec && stride == 2 && V == 4 && N >= 2 * V && small)
-                hipLaunchKernelGGL((k_modwt_step_s_b<T, (sizeof(T) == 4 ? 2 : 1)>), gv, dim3(EXT_THREADS), 0, st, cur, cs, vdst, vds, wdst, ous,
-                                   N / V, tp);
-            else
-                hipLaunchKernelGGL((k_modwt_step_b<T>), gs, dim3(EXT_THREADS), 0, st, cur, cs, vdst, vds, wdst, ous, N, stride, tp);
-            WL_HIP(ctx, hipGetLastError());
-            cur = vdst;
-            cs = vds;
-        }
-        return WL_OK;
-    }));
-    ctx->last_kernel = "k_modwt_step_b";
-    return WL_OK;
-}
-template <typename T>
-int imodwt_batch_impl(wl_ctx *ctx, hipStream_t st, T *x, int64_t xs, const T *xw, int64_t ldw, int64_t ws, int64_t N, int ncols,
-                      int64_t nunits, const double *qmf, int flen)
-{
-    constexpr int V = 16 / sizeof(T);
-    if (ncols == 1) {                                        // no level: the scaling column is the signal
-        WL_HIP(ctx, hipMemcpy2DAsync(x, (size_t)xs * sizeof(T), xw, (size_t)ws * sizeof(T), (size_t)N * sizeof(T), (size_t)nunits,
-                                     hipMemcpyDeviceToDevice, st));
-        ctx->last_kernel = "copy";
-        return WL_OK;
-    }
-    ModwtTaps tp;
-    make_modwt_taps(qmf, flen, tp);
-    const bool vec = modwt_batch_vec<T>(x, xs, xw, ldw, ws, N, nunits);
-    if (opt("WL_MODWT_FUSED", 1) != 0 && (size_t)2 * N * sizeof(T) <= (size_t)MODWT_LDS_BYTES) {
-        const ModwtLdsShape sh = modwt_lds_shape<T>(N, nunits, vec, ctx->cu_count);
-        hipLaunchKernelGGL((k_imodwt_lds<T>), dim3(sh.grid), dim3(sh.threads), sh.lds, st, x, xs, xw, ldw, ws, (int)N, nunits, ncols, sh.upw,
-                           vec ? 1 : 0, tp);
-        WL_HIP(ctx, hipGetLastError());
-        ctx->last_kernel = "k_imodwt_lds";
-        return WL_OK;
-    }
-    auto bytes = [&](int64_t G) { return (size_t)2 * G * N * sizeof(T); };
-    const int64_t G = group_size(nunits, 65535, opt("WL_MODWT_BATCH_GROUP", 0), true, group_cap(), bytes);
-    WL_TRY(wl_ensure_ws(ctx, bytes(G), st, true));
-    T *A = (T *)ctx->ws, *B = A + G * N;
-    const bool small = opt("WL_MODWT_SMALL", 1) != 0;
-    WL_TRY(for_groups(nunits, G, [&](int64_t u0, int64_t nb) -> int {
-        const T *wg = xw + u0 * ws;
-        const T *cur = wg + (int64_t)(ncols - 1) * ldw;
-        int64_t cs = ws;
-        for (int j = ncols - 1; j >= 1; --j) {
-            T *dst = (j == 1) ? x + u0 * xs : ((j & 1) ? A : B);
-            const int64_t ds = (j == 1) ? xs : N;
-            const T *wsrc = wg + (int64_t)(j - 1) * ldw;
-            const int64_t stride = (int64_t)1 << (j - 1);
-            const dim3 gv(ext_blocks(N / V, 1, ctx->cu_count), (unsigned)nb), gs(ext_blocks(N, 1, ctx->cu_count), (unsigned)nb);
-            if (vec && (stride % V) == 0)
-                hipLaunchKernelGGL((k_imodwt_step_v_b<T>), gv, dim3(EXT_THREADS), 0, st, cur, cs, wsrc, ws, dst, ds, N / V, stride / V, tp);
-            else if (vec && stride == 1 && N >= 2 * V && small)
-                hipLaunchKernelGGL((k_imodwt_step_s_b<T, 1>), gv, dim3(EXT_THREADS), 0, st, cur, cs, wsrc, ws, dst, ds, N / V, tp);
-            else if (vec && stride == 2 && V == 4 && N >= 2 * V && small)
-                hipLaunchKernelGGL((k_imodwt_step_s_b<T, (sizeof(T) == 4 ? 2 : 1)>), gv, dim3(EXT_THREADS), 0, st, cur, cs, wsrc, ws, dst, ds,
-                                   N / V, tp);
-            else
-                hipLaunchKernelGGL((k_imodwt_step_b<T>), gs, dim3(EXT_THREADS), 0, st, cur, cs, wsrc, ws, dst, ds, N, stride, tp);
-            WL_HIP(ctx, hipGetLastError());
-            cur = dst;
-            cs = ds;
-        }
-        return WL_OK;
-    }));
-    ctx->last_kernel = "k_imodwt_step_b";
-    return WL_OK;
-}
-
-// the extent rules the two batch entry points share: unit u of the vectors at u * xs (>= n), of the matrices at u * ms, leading
-// dimension ld (>= n), ms >= ld * cols; every product must fit an int64.  cols < 1 breaks a later rule, not this one.
-int modwt_batch_dims(int64_t n, int64_t nunits, int64_t xs, int64_t ld, int64_t ms, int64_t cols)
-{
-    if (n < 1 || nunits < 1 || xs < n || ld < n) return WL_EDIMS;
-    int64_t need = 0, tot = 0;
-    if (cols >= 1 && (__builtin_mul_overflow(ld, cols, &need) || ms < need)) return WL_EDIMS;
-    if (__builtin_mul_overflow(nunits, xs, &tot) || __builtin_mul_overflow(nunits, ms, &tot) || tot >= ((int64_t)1 << 60)) return WL_EDIMS;
-    return WL_OK;
-}
-// the units of the vectors against the units of the matrices, as byte ranges (cols clamped to what the dims rule has seen)
-bool modwt_batch_overlap(const void *x, int64_t xs, const void *m, int64_t ld, int64_t ms, int64_t n, int64_t nunits, int64_t cols, size_t sz)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(x), b0 = reinterpret_cast<uintptr_t>(m);
-    const uintptr_t a1 = a0 + (uintptr_t)((nunits - 1) * xs + n) * sz;
-    const uintptr_t b1 = b0 + (uintptr_t)((nunits - 1) * ms + (cols >= 1 ? cols - 1 : 0) * ld + n) * sz;
-    return a0 < b1 && b0 < a1;
-}
 
 // ---- threshold! ------------------------------------------------------------------------------------
 // (threshold_one: wl_dev.h -- the level-1 kernel of the translation-invariant batch applies it at its stores)
@@ -925,6 +273,19 @@ int median_impl(wl_ctx *ctx, hipStream_t st, const T *v, int64_t n, double *resu
     return WL_OK;
 }
 
+// mad!(v): v[i] = abs(v[i] - median(v)) and the median of that -- in the selection state on the device, and in *result_host when
+// that is not nullptr (the call then waits for it).  One workgroup with the keys in LDS where they fit, else the radix select twice.
+template <typename T>
+int mad_one(wl_ctx *ctx, hipStream_t st, T *v, int64_t n, double *result_host)
+{
+    if (n <= mad_lds_max<T>()) return mad_small<T>(ctx, st, v, n, 1, result_host);
+    WL_TRY(ensure_aux(ctx));
+    T *mdev = (T *)((char *)ctx->aux + 4096);              // the first median, in the element type
+    WL_TRY(median_impl<T>(ctx, st, v, n, nullptr, mdev));
+    hipLaunchKernelGGL((k_absdev<T>), dim3(ext_blocks(n, 4, ctx->cu_count)), dim3(EXT_THREADS), 0, st, v, n, (const T *)mdev, vec_ok16(v));
+    return median_impl<T>(ctx, st, v, n, result_host, (T *)nullptr);
+}
+
 template <typename T>
 int biggest_impl(wl_ctx *ctx, hipStream_t st, T *x, int64_t n, int64_t m)
 {
@@ -1134,13 +495,42 @@ __global__ void __launch_bounds__(EXT_THREADS) k_copy_range(T *__restrict__ dst,
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += nthr) dst[e] = src[e];
 }
 
+// The noise estimate of one array from its level-1 coefficients c1 (noisest, denoising.jl:92-101): mad! of c1[detailrange(c1, 1)]
+// (linear indexing: the upper half of the first column) on a copy dr of those n0 / 2 samples.  Nobody waits: the MAD stays in the
+// selection state, where k_threshold_dev reads it.
+template <typename T>
+int sigma_of_detail(wl_ctx *ctx, hipStream_t st, T *dr, const T *c1, int64_t n0)
+{
+    const int64_t lo = (int64_t)llround((double)n0 / 2 + 1) - 1, nd = n0 - lo;        // detailrange(n0, 1), 0-based half open
+    hipLaunchKernelGGL((k_copy_range<T>), dim3(ext_blocks(nd, 1, ctx->cu_count)), dim3(EXT_THREADS), 0, st, dr, c1 + lo, nd);
+    return mad_one<T>(ctx, st, dr, nd, nullptr);
+}
+// the launches of k_ti_shift / k_ti_accumulate on the nb spins from g.b0: x = groups of 4 rows (at most 64 workgroups), y = the
+// columns (i1, i2), eight per workgroup of the shift, with a grid stride beyond 65535 workgroups
+inline unsigned ti_grid_x(int64_t n0)
+{
+    const int64_t gx = (n0 / 4 + 255) / 256;
+    return (unsigned)(gx > 64 ? 64 : (gx > 0 ? gx : 1));
+}
+template <typename T>
+void ti_shift(hipStream_t st, T *Z, const T *x, const TiGeom &g, int64_t nb)
+{
+    const int64_t gy = (g.n1 * g.n2 + 7) / 8;
+    hipLaunchKernelGGL((k_ti_shift<T>), dim3(ti_grid_x(g.n0), (unsigned)(gy > 65535 ? 65535 : gy), (unsigned)nb), dim3(256), 0, st, Z, x, g);
+}
+template <typename T>
+void ti_accumulate(hipStream_t st, T *y, const T *Z, const TiGeom &g, int64_t nb, int first)
+{
+    const int64_t gy = g.n1 * g.n2;
+    hipLaunchKernelGGL((k_ti_accumulate<T>), dim3(ti_grid_x(g.n0), (unsigned)(gy > 65535 ? 65535 : gy)), dim3(256), 0, st, y, Z, g, nb, first);
+}
+
 template <typename T>
 int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, const int64_t *dims, const double *qmf, int flen, int L,
                     int th, double t_unit, const int64_t *nspin, double sigma_host)
 {
     const int64_t n0 = dims[0], n1 = (ndims >= 2) ? dims[1] : 1, n2 = (ndims == 3) ? dims[2] : 1, N = n0 * n1 * n2;
     const int64_t nsp0 = nspin[0], nsp1 = (ndims >= 2) ? nspin[1] : 1, nsp2 = (ndims == 3) ? nspin[2] : 1, pns = nsp0 * nsp1 * nsp2;
-    const int64_t vdims[3] = {n0, n1, n2};
     Taps<T> taps;
     make_taps<T>(qmf, flen, taps);
     int rc = ensure_aux(ctx);
@@ -1148,7 +538,7 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
     SelState *sel = (SelState *)ctx->aux;
     // cubes: the spins of a group are a batch of volumes (filter_*_levels_vols, wl_batch3d.hip: every level of the one-launch 3-D
     // kernels one launch over all spins); its workspace is the approximation ping-pong per spin + one volume's generic buffers
-    auto tw_elems = [&](int64_t B) { return ndims == 3 ? ws_vols_elems(N, B) : ws_elems(N * B, ndims); };
+    auto tw_elems = [&](int64_t B) { return ws_filter_planes_elems(ndims, N, B); };
     // spins per batch: the whole set unless the buffers (2 N B for the shifted copies and their coefficients, plus the
     // transform workspace of the batch box) would pass the cap
     // Virtual shifts (Float32 square images on the LDS-exchange level kernel): a circular shift along dim 2 is an offset of the
@@ -1173,38 +563,21 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
     T *dr = ZR + zr_elems;                                  // detail range of the noise estimate (n0/2 samples)
     const unsigned nbk = ext_blocks(N * B, 4, ctx->cu_count);
 
+    BoxSpec b1;                                             // the array itself
+    b1.nd = ndims; b1.nt = ndims;
+    b1.dims[0] = n0; b1.dims[1] = n1; b1.dims[2] = n2;
+    b1.full = dense_strides(b1.dims);
     // ---- sigma = noisest(x, wt): level-1 transform, MAD of y1[detailrange(y1, 1)] (linear indexing: first column) ----
     if (!(sigma_host >= 0)) {
-        BoxSpec b1;
-        b1.nd = ndims; b1.nt = ndims;
-        b1.dims[0] = n0; b1.dims[1] = n1; b1.dims[2] = n2;
-        b1.full = dense_strides(b1.dims);
         if (n0 < 2 || (n0 % 2) != 0 || (ndims >= 2 && (n1 % 2) != 0) || (ndims == 3 && (n2 % 2) != 0)) return WL_EINVAL_SIZE;
         rc = filter_fwd_levels<T>(tw, true, ctx->cu_count, ctx->path, st, b1, XT, x, taps, 1, &ctx->last_kernel, &ctx->last_hip);
         if (rc != WL_OK) return rc;
-        const int64_t lo = (int64_t)llround((double)n0 / 2 + 1) - 1, hi = n0;        // detailrange(n0, 1), 0-based half open
-        const int64_t nd = hi - lo;
-        hipLaunchKernelGGL((k_copy_range<T>), dim3(ext_blocks(nd, 1, ctx->cu_count)), dim3(EXT_THREADS), 0, st, dr, XT + lo, nd);
-        if (nd <= mad_lds_max<T>()) {
-            rc = mad_small<T>(ctx, st, dr, nd, 1, nullptr);
-            if (rc != WL_OK) return rc;
-        } else {
-            void *mdev = (char *)ctx->aux + 4096;
-            rc = median_impl<T>(ctx, st, dr, nd, nullptr, (T *)mdev);
-            if (rc != WL_OK) return rc;
-            hipLaunchKernelGGL((k_absdev<T>), dim3(ext_blocks(nd, 4, ctx->cu_count)), dim3(EXT_THREADS), 0, st, dr, nd, (const T *)mdev, vec_ok16(dr));
-            rc = median_impl<T>(ctx, st, dr, nd, nullptr, (T *)nullptr);
-            if (rc != WL_OK) return rc;
-        }
+        WL_TRY(sigma_of_detail<T>(ctx, st, dr, XT, n0));
     }
     // ---- one spin of shift zero (the plain, not translation-invariant denoise routed here so that sigma stays on the device):
     //      y = idwt(threshold!(dwt(x))) with no shifted copy, no accumulation and no scaling -- the reference's own sequence
     //      (denoising.jl:69-80), signed zeros included, and a quarter of the batch path's memory ----
     if (pns == 1) {
-        BoxSpec b1;
-        b1.nd = ndims; b1.nt = ndims;
-        b1.dims[0] = n0; b1.dims[1] = n1; b1.dims[2] = n2;
-        b1.full = dense_strides(b1.dims);
         const T *coef_src = x;
         if (L > 0) {
             rc = filter_fwd_levels<T>(tw, true, ctx->cu_count, ctx->path, st, b1, XT, x, taps, L, &ctx->last_kernel, &ctx->last_hip);
@@ -1228,32 +601,16 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
         return WL_OK;
     }
     // ---- the spins, B at a time ----
-    BoxSpec bb;
-    bb.nd = ndims + 1; bb.nt = ndims;
-    bb.dims[0] = n0; bb.dims[1] = (ndims == 2) ? n1 : 0; bb.dims[2] = 1;
     TiGeom g;
     g.n0 = n0; g.n1 = n1; g.n2 = n2; g.N = N; g.nsp0 = nsp0; g.nsp1 = nsp1; g.nsp2 = nsp2;
-    const unsigned gxs = (unsigned)((n0 / 4 + 255) / 256 > 0 ? ((n0 / 4 + 255) / 256 > 64 ? 64 : (n0 / 4 + 255) / 256) : 1);
-    // columns (i1, i2) of the shift / accumulate kernels: grid-stride beyond 65535 workgroups along y
-    const int64_t ncol = n1 * n2;
-    const unsigned gy_shift = (unsigned)((ncol + 7) / 8 > 65535 ? 65535 : (ncol + 7) / 8), gy_acc = (unsigned)(ncol > 65535 ? 65535 : ncol);
     if (virt) {
         TiGeom gr = g;                                      // spins 0 .. nsp0-1 shift dim 1 only
         gr.nsp1 = 1; gr.b0 = 0;
-        hipLaunchKernelGGL((k_ti_shift<T>), dim3(gxs, gy_shift, (unsigned)nsp0), dim3(256), 0, st, ZR, x, gr);
+        ti_shift<T>(st, ZR, x, gr, nsp0);
     }
     for (int64_t b0 = 0; b0 < pns; b0 += B) {
         const int64_t nb = (pns - b0 < B) ? (pns - b0) : B;
         g.b0 = b0;
-        if (ndims == 2) { bb.dims[2] = nb; }
-        else { bb.dims[1] = nb; bb.dims[2] = 1; }
-        bb.full = dense_strides(bb.dims);                   // (cubes: the batch of volumes below, not a box)
-        auto fwd_group = [&](T *dst, const T *src) -> int {
-            if (ndims == 3)
-                return filter_fwd_levels_vols<T>(tw, true, ctx->cu_count, ctx->path, st, vdims, nb, N, N, dst, src, taps, L, &ctx->last_kernel,
-                                                 &ctx->last_hip);
-            return filter_fwd_levels<T>(tw, true, ctx->cu_count, ctx->path, st, bb, dst, src, taps, L, &ctx->last_kernel, &ctx->last_hip);
-        };
         bool shifted = false, thresholded_l1 = false;
         int64_t th_c0 = n0, th_c1 = n1;                      // what the level kernels left unthresholded: the low corner of every plane
         if (virt) {
@@ -1264,7 +621,8 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
             const bool fuse_th = opt("WL_TI_FUSE_TH", 1) != 0 && th >= WL_TH_HARD && th <= WL_TH_STEIN &&
                                  (th == WL_TH_HARD || opt("WL_TI_FUSE_SOFT", 1) != 0);
             tl_srcview.th = fuse_th ? th : -1; tl_srcview.t_unit = t_unit; tl_srcview.sigma_host = sigma_host; tl_srcview.mad_dev = &sel->result;
-            rc = filter_fwd_levels<T>(tw, true, ctx->cu_count, ctx->path, st, bb, XT, ZR, taps, L, &ctx->last_kernel, &ctx->last_hip);
+            rc = filter_fwd_levels<T>(tw, true, ctx->cu_count, ctx->path, st, planes_box(ndims, dims, nb, N), XT, ZR, taps, L, &ctx->last_kernel,
+                                      &ctx->last_hip);
             shifted = tl_srcview.used != 0;
             th_c0 = tl_srcview.corner0; th_c1 = tl_srcview.corner1;
             tl_srcview.mod = 0; tl_srcview.th = -1;
@@ -1274,11 +632,8 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
             thresholded_l1 = shifted && fuse_th;
         }
         if (!shifted) {                                     // (materialised shifted planes: every other case)
-            hipLaunchKernelGGL((k_ti_shift<T>), dim3(gxs, gy_shift, (unsigned)nb), dim3(256), 0, st, Z, x, g);
-            if (L > 0) {
-                rc = fwd_group(XT, Z);
-                if (rc != WL_OK) return rc;
-            }
+            ti_shift<T>(st, Z, x, g, nb);
+            if (L > 0) WL_TRY(filter_levels_planes<T>(ctx, st, 1, ndims, dims, nb, N, XT, Z, taps, L, &ctx->last_kernel));
         }
         // L == 0: dwt / idwt are copies (transforms_filter.jl:36-38), so the shifted signal itself is thresholded
         T *const coef = (L == 0) ? Z : XT;
@@ -1293,11 +648,9 @@ int denoise_ti_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndims, co
         }
         if (L > 0) {
             const char *kn = nullptr;
-            rc = ndims == 3 ? filter_inv_levels_vols<T>(tw, true, ctx->cu_count, ctx->path, st, vdims, nb, N, N, Z, XT, taps, L, &kn, &ctx->last_hip)
-                            : filter_inv_levels<T>(tw, true, ctx->cu_count, ctx->path, st, bb, Z, XT, taps, L, &kn, &ctx->last_hip);
-            if (rc != WL_OK) return rc;
+            WL_TRY(filter_levels_planes<T>(ctx, st, 0, ndims, dims, nb, N, Z, XT, taps, L, &kn));
         }
-        hipLaunchKernelGGL((k_ti_accumulate<T>), dim3(gxs, gy_acc), dim3(256), 0, st, y, Z, g, nb, b0 == 0 ? 1 : 0);
+        ti_accumulate<T>(st, y, Z, g, nb, b0 == 0 ? 1 : 0);
     }
     hipLaunchKernelGGL((k_rmul<T>), dim3(ext_blocks(N, 4, ctx->cu_count)), dim3(EXT_THREADS), 0, st, y, N, 1.0 / (double)pns, vec_ok16(y));
     WL_HIP(ctx, hipGetLastError());
@@ -1324,10 +677,7 @@ int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
     // transform workspace of the batched box (B lines, or B images: the approximation ping-pong of every image; B cubes: the ping-pong
     // and the two dense inter-pass buffers of the batched 3-D level loop, and no less than one cube's own), then the shifted copies Z
     // and their coefficients XT
-    auto tws = [&](int64_t B) {
-        if (ndims == 3) { const size_t a = ws_lift_vols_elems(N, B), b = ws_elems(N, 1); return a > b ? a : b; }
-        return ws_elems(N * B, 1);
-    };
+    auto tws = [&](int64_t B) { return ws_lifting_planes_elems(ndims, N, B); };
     auto need = [&](int64_t B) { return (tws(B) + (size_t)2 * N * B + (size_t)n0 + 64) * sizeof(T); };
     int64_t B = 1;
     rc = group_reserve(ctx, st, pns, 65535, need, B);
@@ -1343,55 +693,21 @@ int denoise_ti_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int n
     // ---- sigma = noisest(x, wt): level-1 transform, MAD of y1[detailrange(y1, 1)] (linear indexing with size(x, 1)) ----
     if (!(sigma_host >= 0)) {
         if (n0 < 2 || (n0 % 2) != 0 || (ndims >= 2 && (n1 % 2) != 0) || (ndims == 3 && (n2 % 2) != 0)) return WL_EINVAL_SIZE;
-        rc = wl_lifting_box<T>(ctx, st, b1, XT, x, scf, 1, 1);
-        if (rc != WL_OK) return rc;
-        const int64_t lo = (int64_t)llround((double)n0 / 2 + 1) - 1, hi = n0;
-        const int64_t nd = hi - lo;
-        hipLaunchKernelGGL((k_copy_range<T>), dim3(ext_blocks(nd, 1, ctx->cu_count)), dim3(EXT_THREADS), 0, st, dr, XT + lo, nd);
-        if (nd <= mad_lds_max<T>()) {
-            rc = mad_small<T>(ctx, st, dr, nd, 1, nullptr);
-            if (rc != WL_OK) return rc;
-        } else {
-            void *mdev = (char *)ctx->aux + 4096;
-            rc = median_impl<T>(ctx, st, dr, nd, nullptr, (T *)mdev);
-            if (rc != WL_OK) return rc;
-            hipLaunchKernelGGL((k_absdev<T>), dim3(ext_blocks(nd, 4, ctx->cu_count)), dim3(EXT_THREADS), 0, st, dr, nd, (const T *)mdev, vec_ok16(dr));
-            rc = median_impl<T>(ctx, st, dr, nd, nullptr, (T *)nullptr);
-            if (rc != WL_OK) return rc;
-        }
+        WL_TRY(wl_lifting_box<T>(ctx, st, b1, XT, x, scf, 1, 1));
+        WL_TRY(sigma_of_detail<T>(ctx, st, dr, XT, n0));
     }
     TiGeom g;
     g.n0 = n0; g.n1 = n1; g.n2 = n2; g.N = N; g.nsp0 = nsp0; g.nsp1 = nsp1; g.nsp2 = nsp2;
-    const unsigned gxs = (unsigned)((n0 / 4 + 255) / 256 > 0 ? ((n0 / 4 + 255) / 256 > 64 ? 64 : (n0 / 4 + 255) / 256) : 1);
-    // columns (i1, i2) of the shift / accumulate kernels: grid-stride beyond 65535 workgroups along y
-    const int64_t ncol = n1 * n2;
-    const unsigned gy_shift = (unsigned)((ncol + 7) / 8 > 65535 ? 65535 : (ncol + 7) / 8), gy_acc = (unsigned)(ncol > 65535 ? 65535 : ncol);
-    auto transform = [&](T *dst, const T *src, int64_t nb, const LiftScheme<T> &sc, int fw) -> int {
-        if (ndims == 1) {                                    // nb signals = nb lines of one batched call
-            BoxSpec bb;
-            bb.nd = 2; bb.nt = 1;
-            bb.dims[0] = n0; bb.dims[1] = nb; bb.dims[2] = 1;
-            bb.full = dense_strides(bb.dims);
-            return wl_lifting_box<T>(ctx, st, bb, dst, src, sc, L, fw);
-        }
-        if (ndims == 3) return wl_lifting_vols<T>(ctx, st, n0, nb, N, dst, src, sc, L, fw);      // nb cubes = one batch of volumes
-        BoxSpec bb;                                          // nb images = the third extent of one batched call
-        bb.nd = 3; bb.nt = 2;
-        bb.dims[0] = n0; bb.dims[1] = n1; bb.dims[2] = nb;
-        bb.full = dense_strides(bb.dims);
-        return wl_lifting_box<T>(ctx, st, bb, dst, src, sc, L, fw);
-    };
+    // nb shifted signals are the lines of one batched call, nb images the third extent of one, nb cubes one batch of volumes
     for (int64_t b0 = 0; b0 < pns; b0 += B) {
         const int64_t nb = (pns - b0 < B) ? (pns - b0) : B;
         g.b0 = b0;
-        hipLaunchKernelGGL((k_ti_shift<T>), dim3(gxs, gy_shift, (unsigned)nb), dim3(256), 0, st, Z, x, g);
-        rc = transform(XT, Z, nb, scf, 1);                   // (L = 0: a copy, as the reference's dwt is)
-        if (rc != WL_OK) return rc;
+        ti_shift<T>(st, Z, x, g, nb);
+        WL_TRY(lifting_levels_planes<T>(ctx, st, ndims, n0, nb, N, XT, Z, scf, L, 1));       // (L = 0: a copy, as the reference's dwt is)
         hipLaunchKernelGGL((k_threshold_dev<T>), dim3(ext_blocks(N * nb, 4, ctx->cu_count)), dim3(EXT_THREADS), 0, st, XT, N * nb, th, &sel->result,
                            t_unit, sigma_host, vec_ok16(XT));
-        rc = transform(Z, XT, nb, sci, 0);
-        if (rc != WL_OK) return rc;
-        hipLaunchKernelGGL((k_ti_accumulate<T>), dim3(gxs, gy_acc), dim3(256), 0, st, y, Z, g, nb, b0 == 0 ? 1 : 0);
+        WL_TRY(lifting_levels_planes<T>(ctx, st, ndims, n0, nb, N, Z, XT, sci, L, 0));
+        ti_accumulate<T>(st, y, Z, g, nb, b0 == 0 ? 1 : 0);
     }
     hipLaunchKernelGGL((k_rmul<T>), dim3(ext_blocks(N, 4, ctx->cu_count)), dim3(EXT_THREADS), 0, st, y, N, 1.0 / (double)pns, vec_ok16(y));
     WL_HIP(ctx, hipGetLastError());
@@ -1542,7 +858,14 @@ __global__ void __launch_bounds__(EXT_THREADS) k_threshold_units(T *__restrict__
     ew_inplace<T>(xu, N, vec_ok, [=](T v, int64_t) { return threshold_one<T, double>(v, th, t); });
 }
 
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+// last_kernel of the batch denoises: the family and the kernel of the noise estimate that mad_units / batch_sigma named
+const char *denoise_label(bool ti, const char *madk)
+{
+    static const char *const names[2][3] = {
+        {"denoise_batch+k_mad_units_lds", "denoise_batch+k_mad_units_stream", "denoise_batch+sigma_in"},
+        {"denoise_ti_units+k_mad_units_lds", "denoise_ti_units+k_mad_units_stream", "denoise_ti_units+sigma_in"}};
+    return names[ti ? 1 : 0][strcmp(madk, "k_mad_units_lds") == 0 ? 0 : (strcmp(madk, "k_mad_units_stream") == 0 ? 1 : 2)];
+}
 // estimate (or take) and publish the sigmas of one group of at most 65535 * 256 units: src = where the level-1 detail range of every
 // unit is read from (not read with sigma_in)
 template <typename T>
@@ -1582,9 +905,8 @@ int denoise_batch_filter_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int
     const int64_t n0 = dims[0];
     int64_t N = 1;
     for (int d = 0; d < ndims; ++d) N *= dims[d];
-    const int64_t vdims[3] = {n0, n0, n0};
     const Taps<T> taps = taps_of<T>(qmf, flen);
-    auto tw_elems = [&](int64_t G) { return ndims == 3 ? ws_vols_elems(N, G) : ws_elems(N * G, ndims); };
+    auto tw_elems = [&](int64_t G) { return ws_filter_planes_elems(ndims, N, G); };
     auto need = [&](int64_t G) { return up256(tw_elems(G) * sizeof(T)) + up256((size_t)G * S * sizeof(T)) + up256((size_t)G * sizeof(double)); };
     int64_t G = 1;
     int rc = group_reserve(ctx, st, nunits, 65535, need, G);
@@ -1596,16 +918,8 @@ int denoise_batch_filter_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int
     WL_TRY(for_groups(nunits, G, [&](int64_t u0, int64_t nb) -> int {
         const T *xg = x + u0 * S;
         T *yg = y + u0 * S;
-        BoxSpec bb;                                          // nb lines / images (cubes: a batch of volumes, not a box)
-        bb.nd = ndims + 1; bb.nt = ndims;
-        bb.dims[0] = n0; bb.dims[1] = (ndims == 2) ? n0 : nb; bb.dims[2] = (ndims == 2) ? nb : 1;
-        bb.full.s[0] = 1; bb.full.s[1] = (ndims == 2) ? n0 : S; bb.full.s[2] = (ndims == 2) ? S : S * nb;
-        auto fwd = [&](int lev) -> int {
-            return ndims == 3 ? filter_fwd_levels_vols<T>(wsb, true, ctx->cu_count, ctx->path, st, vdims, nb, S, S, Cb, xg, taps, lev, &kn, &ctx->last_hip)
-                              : filter_fwd_levels<T>(wsb, true, ctx->cu_count, ctx->path, st, bb, Cb, xg, taps, lev, &kn, &ctx->last_hip);
-        };
         if (L > 0 || !sigma_in) {
-            rc = fwd(L > 0 ? L : 1);
+            rc = filter_levels_planes<T>(ctx, st, 1, ndims, dims, nb, S, Cb, xg, taps, L > 0 ? L : 1, &kn);
             if (rc == WL_RETRY_GEN) rc = WL_EINVAL_ARG;      // (the full workspace is held: no level can ask for more)
             if (rc != WL_OK) return rc;
         }
@@ -1620,16 +934,14 @@ int denoise_batch_filter_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int
                                       th, t_unit, &madk);
         if (rc != WL_OK) return rc;
         if (L > 0) {
-            rc = ndims == 3 ? filter_inv_levels_vols<T>(wsb, true, ctx->cu_count, ctx->path, st, vdims, nb, S, S, yg, Cb, taps, L, &kn, &ctx->last_hip)
-                            : filter_inv_levels<T>(wsb, true, ctx->cu_count, ctx->path, st, bb, yg, Cb, taps, L, &kn, &ctx->last_hip);
+            rc = filter_levels_planes<T>(ctx, st, 0, ndims, dims, nb, S, yg, Cb, taps, L, &kn);
             if (rc == WL_RETRY_GEN) rc = WL_EINVAL_ARG;
             if (rc != WL_OK) return rc;
         }
         return WL_OK;
     }));
     WL_HIP(ctx, hipGetLastError());
-    ctx->last_kernel = strcmp(madk, "k_mad_units_lds") == 0 ? "denoise_batch+k_mad_units_lds"
-                       : (strcmp(madk, "k_mad_units_stream") == 0 ? "denoise_batch+k_mad_units_stream" : "denoise_batch+sigma_in");
+    ctx->last_kernel = denoise_label(false, madk);
     return WL_OK;
 }
 
@@ -1646,10 +958,7 @@ int denoise_batch_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, in
     int64_t N = 1;
     for (int d = 0; d < ndims; ++d) N *= dims[d];
     const bool est0 = (L == 0 && !sigma_in);
-    auto tw_elems = [&](int64_t G) -> size_t {
-        if (ndims == 3) { const size_t a = ws_lift_vols_elems(N, G), b = ws_elems(N, 1); return a > b ? a : b; }
-        return ws_elems(N * G, 1);
-    };
+    auto tw_elems = [&](int64_t G) { return ws_lifting_planes_elems(ndims, N, G); };
     auto need = [&](int64_t G) {
         return up256(tw_elems(G) * sizeof(T)) + up256(est0 ? (size_t)G * S * sizeof(T) : 0) + up256((size_t)G * sizeof(double));
     };
@@ -1663,13 +972,8 @@ int denoise_batch_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, in
     WL_TRY(for_groups(nunits, G, [&](int64_t u0, int64_t nb) -> int {
         const T *xg = x + u0 * S;
         T *yg = y + u0 * S;
-        auto transform = [&](T *dst, const T *src, const LiftScheme<T> &sc, int lev, int fw) -> int {
-            if (ndims == 3) return wl_lifting_vols<T>(ctx, st, n0, nb, S, dst, src, sc, lev, fw);
-            BoxSpec bb;                                      // nb lines of one batched call / nb images as the third extent
-            bb.nd = ndims + 1; bb.nt = ndims;
-            bb.dims[0] = n0; bb.dims[1] = (ndims == 2) ? n0 : nb; bb.dims[2] = (ndims == 2) ? nb : 1;
-            bb.full.s[0] = 1; bb.full.s[1] = (ndims == 2) ? n0 : S; bb.full.s[2] = (ndims == 2) ? S : S * nb;
-            return wl_lifting_box<T>(ctx, st, bb, dst, src, sc, lev, fw);
+        auto transform = [&](T *dst, const T *src, const LiftScheme<T> &sc, int lev, int fw) {
+            return lifting_levels_planes<T>(ctx, st, ndims, n0, nb, S, dst, src, sc, lev, fw);
         };
         if (est0) {
             rc = transform(Cb, xg, scf, 1, 1);
@@ -1687,8 +991,7 @@ int denoise_batch_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, in
         return WL_OK;
     }));
     WL_HIP(ctx, hipGetLastError());
-    ctx->last_kernel = strcmp(madk, "k_mad_units_lds") == 0 ? "denoise_batch+k_mad_units_lds"
-                       : (strcmp(madk, "k_mad_units_stream") == 0 ? "denoise_batch+k_mad_units_stream" : "denoise_batch+sigma_in");
+    ctx->last_kernel = denoise_label(false, madk);
     return WL_OK;
 }
 
@@ -1932,8 +1235,7 @@ int denoise_ti_batch_run(wl_ctx *ctx, hipStream_t st, T *y, const T *x, int ndim
         return WL_OK;
     }));
     WL_HIP(ctx, hipGetLastError());
-    ctx->last_kernel = strcmp(madk, "k_mad_units_lds") == 0 ? "denoise_ti_units+k_mad_units_lds"
-                       : (strcmp(madk, "k_mad_units_stream") == 0 ? "denoise_ti_units+k_mad_units_stream" : "denoise_ti_units+sigma_in");
+    ctx->last_kernel = denoise_label(true, madk);
     return WL_OK;
 }
 
@@ -1942,30 +1244,15 @@ int denoise_ti_batch_filter_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, 
                                  const double *qmf, int flen, int L, int th, double t_unit, const int64_t *nspin, const double *sigma_in,
                                  double *sigma_out)
 {
-    const int64_t n0 = dims[0];
     int64_t N = 1;
     for (int d = 0; d < ndims; ++d) N *= dims[d];
-    const int64_t vdims[3] = {n0, n0, n0};
     const Taps<T> taps = taps_of<T>(qmf, flen);
     const char *kn = nullptr;
-    auto no_retry = [](int rc) { return rc == WL_RETRY_GEN ? WL_EINVAL_ARG : rc; };     // (the full workspace is held: no level can ask for more)
-    auto tw_elems = [&](int64_t G) { return ndims == 3 ? ws_vols_elems(N, G) : ws_elems(N * G, ndims); };
-    // nb lines / images with plane stride ps (cubes: a batch of volumes, not a box)
-    auto box = [&](int64_t nb, int64_t ps) {
-        BoxSpec bb;
-        bb.nd = ndims + 1; bb.nt = ndims;
-        bb.dims[0] = n0; bb.dims[1] = (ndims == 2) ? n0 : nb; bb.dims[2] = (ndims == 2) ? nb : 1;
-        bb.full.s[0] = 1; bb.full.s[1] = (ndims == 2) ? n0 : ps; bb.full.s[2] = (ndims == 2) ? ps : ps * nb;
-        return bb;
-    };
-    auto levels = [&](bool fw, T *dst, const T *src, int64_t nb, int64_t ps, int lev) -> int {
-        void *ws = ctx->ws;
-        if (ndims == 3)
-            return no_retry(fw ? filter_fwd_levels_vols<T>(ws, true, ctx->cu_count, ctx->path, st, vdims, nb, ps, ps, dst, src, taps, lev, &kn, &ctx->last_hip)
-                               : filter_inv_levels_vols<T>(ws, true, ctx->cu_count, ctx->path, st, vdims, nb, ps, ps, dst, src, taps, lev, &kn, &ctx->last_hip));
-        const BoxSpec bb = box(nb, ps);
-        return no_retry(fw ? filter_fwd_levels<T>(ws, true, ctx->cu_count, ctx->path, st, bb, dst, src, taps, lev, &kn, &ctx->last_hip)
-                           : filter_inv_levels<T>(ws, true, ctx->cu_count, ctx->path, st, bb, dst, src, taps, lev, &kn, &ctx->last_hip));
+    auto tw_elems = [&](int64_t G) { return ws_filter_planes_elems(ndims, N, G); };
+    // all `lev` levels of nb lines / images / cubes with plane stride ps
+    auto levels = [&](bool fw, T *dst, const T *src, int64_t nb, int64_t ps, int lev) {
+        const int rc = filter_levels_planes<T>(ctx, st, fw ? 1 : 0, ndims, dims, nb, ps, dst, src, taps, lev, &kn);
+        return rc == WL_RETRY_GEN ? WL_EINVAL_ARG : rc;      // (the full workspace is held: no level can ask for more)
     };
     return denoise_ti_batch_run<T>(ctx, st, y, x, ndims, dims, nunits, S, L, th, t_unit, nspin, sigma_in, sigma_out, false, tw_elems,
                                    [&](T *C, const T *xg, int64_t nu) { return levels(true, C, xg, nu, S, 1); },
@@ -1982,18 +1269,10 @@ int denoise_ti_batch_lifting_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x,
     const int64_t n0 = dims[0];
     int64_t N = 1;
     for (int d = 0; d < ndims; ++d) N *= dims[d];
-    auto tw_elems = [&](int64_t G) -> size_t {
-        if (ndims == 3) { const size_t a = ws_lift_vols_elems(N, G), b = ws_elems(N, 1); return a > b ? a : b; }
-        return ws_elems(N * G, 1);
-    };
+    auto tw_elems = [&](int64_t G) { return ws_lifting_planes_elems(ndims, N, G); };
     // nb lines of one batched call / nb images as the third extent / nb cubes as one batch of volumes, plane stride ps
-    auto transform = [&](T *dst, const T *src, int64_t nb, int64_t ps, const LiftScheme<T> &sc, int lev, int fw) -> int {
-        if (ndims == 3) return wl_lifting_vols<T>(ctx, st, n0, nb, ps, dst, src, sc, lev, fw);
-        BoxSpec bb;
-        bb.nd = ndims + 1; bb.nt = ndims;
-        bb.dims[0] = n0; bb.dims[1] = (ndims == 2) ? n0 : nb; bb.dims[2] = (ndims == 2) ? nb : 1;
-        bb.full.s[0] = 1; bb.full.s[1] = (ndims == 2) ? n0 : ps; bb.full.s[2] = (ndims == 2) ? ps : ps * nb;
-        return wl_lifting_box<T>(ctx, st, bb, dst, src, sc, lev, fw);
+    auto transform = [&](T *dst, const T *src, int64_t nb, int64_t ps, const LiftScheme<T> &sc, int lev, int fw) {
+        return lifting_levels_planes<T>(ctx, st, ndims, n0, nb, ps, dst, src, sc, lev, fw);
     };
     return denoise_ti_batch_run<T>(ctx, st, y, x, ndims, dims, nunits, S, L, th, t_unit, nspin, sigma_in, sigma_out, true, tw_elems,
                                    [&](T *C, const T *xg, int64_t nu) { return transform(C, xg, nu, S, scf, 1, 1); },
@@ -2016,85 +1295,9 @@ int denoise_ti_batch_check(int ndims, const int64_t *dims, int64_t nunits, int64
     return WL_OK;
 }
 
-inline int ext_enter(wl_ctx *ctx, int dtype)
-{
-    if (!ctx) return WL_EINVAL_ARG;
-    return check_dtype(dtype);
-}
-
 }  // namespace
 
 extern "C" {
-
-int wl_maxmodwttransformlevels(int64_t n)
-{
-    int l = 0;
-    while (n > 1) { n >>= 1; ++l; }
-    return l;
-}
-
-int wl_modwt(wl_ctx *ctx, int dtype, void *out, int64_t ldo, const void *x, int64_t n, const double *qmf, int flen, int L,
-             void *stream)
-{
-    WL_TRY(ext_enter(ctx, dtype));
-    WL_SCOPE(ctx);
-    if (!out || !x || !qmf) return WL_EINVAL_ARG;
-    WL_TRY(check_flen(flen, 1));
-    if (n < 1 || ldo < n) return WL_EDIMS;
-    if (L > wl_maxmodwttransformlevels(n)) return WL_EINVAL_SIZE;      // "Too many transform levels (length(x) < 2^L)"
-    if (L < 1) return WL_EINVAL_L;                                       // "L must be >= 1"
-    hipStream_t st = (hipStream_t)stream;
-    return by_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        return modwt_impl<T>(ctx, st, (T *)out, ldo, (const T *)x, n, qmf, flen, L);
-    });
-}
-
-int wl_imodwt(wl_ctx *ctx, int dtype, void *x, const void *xw, int64_t ldw, int64_t n, int ncols, const double *qmf, int flen,
-              void *stream)
-{
-    WL_TRY(ext_enter(ctx, dtype));
-    WL_SCOPE(ctx);
-    if (!x || !xw || !qmf) return WL_EINVAL_ARG;
-    WL_TRY(check_flen(flen, 1));
-    if (n < 1 || ncols < 1 || ldw < n) return WL_EDIMS;
-    hipStream_t st = (hipStream_t)stream;
-    return by_dtype(dtype, [&](auto t) {
-        using T = decltype(t);
-        return imodwt_impl<T>(ctx, st, (T *)x, (const T *)xw, ldw, n, ncols, qmf, flen);
-    });
-}
-
-int wl_modwt_batch(wl_ctx *ctx, int dtype, void *out, int64_t ldo, int64_t out_unit_stride, const void *x, int64_t n, int64_t nunits,
-                   int64_t unit_stride, const double *qmf, int flen, int L, void *stream)
-{
-    if (!ctx || !out || !x || !qmf) return WL_EINVAL_ARG;
-    WL_TRY(check_dtype(dtype));
-    WL_TRY(check_flen(flen, 1));
-    WL_TRY(modwt_batch_dims(n, nunits, unit_stride, ldo, out_unit_stride, (int64_t)L + 1));
-    if (modwt_batch_overlap(x, unit_stride, out, ldo, out_unit_stride, n, nunits, (int64_t)L + 1, dtype == WL_F32 ? 4 : 8)) return WL_EALIAS;
-    if (L > wl_maxmodwttransformlevels(n)) return WL_EINVAL_SIZE;      // "Too many transform levels (length(x) < 2^L)"
-    if (L < 1) return WL_EINVAL_L;                                       // "L must be >= 1"
-    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
-        using T = decltype(t);
-        return modwt_batch_impl<T>(ctx, st, (T *)out, ldo, out_unit_stride, (const T *)x, n, nunits, unit_stride, qmf, flen, L);
-    });
-}
-
-int wl_imodwt_batch(wl_ctx *ctx, int dtype, void *x, int64_t unit_stride, const void *xw, int64_t ldw, int64_t xw_unit_stride, int64_t n,
-                    int ncols, int64_t nunits, const double *qmf, int flen, void *stream)
-{
-    if (!ctx || !x || !xw || !qmf) return WL_EINVAL_ARG;
-    WL_TRY(check_dtype(dtype));
-    WL_TRY(check_flen(flen, 1));
-    WL_TRY(modwt_batch_dims(n, nunits, unit_stride, ldw, xw_unit_stride, ncols));
-    if (modwt_batch_overlap(x, unit_stride, xw, ldw, xw_unit_stride, n, nunits, ncols, dtype == WL_F32 ? 4 : 8)) return WL_EALIAS;
-    if (ncols < 1 || ncols - 1 > 62) return WL_EINVAL_L;
-    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
-        using T = decltype(t);
-        return imodwt_batch_impl<T>(ctx, st, (T *)x, unit_stride, (const T *)xw, ldw, xw_unit_stride, n, ncols, nunits, qmf, flen);
-    });
-}
 
 int wl_threshold(wl_ctx *ctx, int dtype, void *x, int64_t n, int th, double t, int t_is_f64, void *stream)
 {
@@ -2150,15 +1353,10 @@ int wl_mad(wl_ctx *ctx, int dtype, void *y, int64_t n, double *result, void *str
     WL_SCOPE(ctx);
     if (!y || !result) return WL_EINVAL_ARG;
     if (n < 1) return WL_EDIMS;
-    WL_TRY(ensure_aux(ctx));
     hipStream_t st = (hipStream_t)stream;
     return by_dtype(dtype, [&](auto t) {
         using T = decltype(t);
-        if (n <= mad_lds_max<T>()) return mad_small<T>(ctx, st, (T *)y, n, 1, result);
-        T *mdev = (T *)((char *)ctx->aux + 4096);          // the first median, in the element type
-        WL_TRY(median_impl<T>(ctx, st, (const T *)y, n, nullptr, mdev));
-        hipLaunchKernelGGL((k_absdev<T>), dim3(ext_blocks(n, 4, ctx->cu_count)), dim3(EXT_THREADS), 0, st, (T *)y, n, (const T *)mdev, vec_ok16(y));
-        return median_impl<T>(ctx, st, (const T *)y, n, result, (T *)nullptr);
+        return mad_one<T>(ctx, st, (T *)y, n, result);
     });
 }
 

@@ -286,4 +286,24 @@ template <typename T>
 int filter_inv_levels_vols(void *ws, bool ws_gen, int cu_count, int path, hipStream_t st, const int64_t dims[3], int64_t nvol, int64_t xs,
                            int64_t ys, T *y, const T *x, const Taps<T> &taps, int L, const char **kernel_name, int *hip_err);
 
+// ---- np planes of stride ps: lines / images / cubes of dims[0 .. ndims) as one batch (the batch denoises, the complex transforms) ----
+// the box of np lines or images as the batched entry points describe it (wl_dwtc_*, wl_dwt_*_batch); cubes are a batch of volumes
+inline BoxSpec planes_box(int ndims, const int64_t *dims, int64_t np, int64_t ps)
+{
+    BoxSpec b;
+    b.nd = ndims + 1; b.nt = ndims;
+    b.dims[0] = dims[0]; b.dims[1] = (ndims == 2) ? dims[1] : np; b.dims[2] = (ndims == 2) ? np : 1;
+    b.full.s[0] = 1; b.full.s[1] = (ndims == 2) ? dims[0] : ps; b.full.s[2] = (ndims == 2) ? ps : ps * np;
+    return b;
+}
+// the transform workspace (elements) of np planes of N elements: all levels of a filter bank / of a lifting scheme (cubes: the batched
+// 3-D level loop, and no less than one cube's own)
+inline size_t ws_filter_planes_elems(int ndims, int64_t N, int64_t np) { return ndims == 3 ? ws_vols_elems(N, np) : ws_elems(N * np, ndims); }
+inline size_t ws_lifting_planes_elems(int ndims, int64_t N, int64_t np)
+{
+    if (ndims != 3) return ws_elems(N * np, 1);
+    const size_t a = ws_lift_vols_elems(N, np), b = ws_elems(N, 1);
+    return a > b ? a : b;
+}
+
 }  // namespace wl

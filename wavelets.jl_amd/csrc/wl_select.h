@@ -1,6 +1,7 @@
 // wl_select.h -- the device primitives that the order-statistic kernels of wl_ext.hip (median!, mad!, threshold_biggest and the
 // per-unit noise estimates) and of wl_thbatch.hip (threshold! of a batch) share: the element-wise in-place pass, the monotone
-// integer keys, the radix select over keys in LDS and the one-wave bin pick of a 256-bin histogram.
+// integer keys, the radix select over keys in LDS and the one-wave bin pick of a 256-bin histogram.  wl_modwt.hip takes the launch
+// geometry of the element-wise kernels (EXT_THREADS, ext_blocks, vec_ok16) from here.
 // Everything here has internal linkage: each translation unit instantiates its own copies, and a kernel that must not share an
 // instantiation with another one (its inlining, its register allocation) asks for its own through INST.
 #pragma once

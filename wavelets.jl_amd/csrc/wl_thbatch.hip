@@ -3,7 +3,7 @@
 //                                unit, or a wave per unit of at most 256 elements)
 //   wl_threshold_biggest_batch   threshold!(x_u, BiggestTH(), m_u): the best m-term approximation of every unit
 // Unit u is x[u * unit_stride .. + n); the padding between units is never read or written.  Neither call synchronises or brings a
-// counter back to the host.  The single calls (wl_threshold, wl_threshold_biggest, wl_ext.hip) launch none of these kernels.
+// counter back to the host.  The single calls (wl_threshold, wl_threshold_biggest: wl_ext.hip) launch none of these kernels.
 //
 // BiggestTH of one unit, as wl_threshold_biggest computes it: a = the (n - m)-th smallest |x| (radix select on the abs-mode keys:
 // NaN above every finite magnitude), less / equal = the counts of |x| < a and |x| == a (floating-point compares, so nothing
@@ -224,7 +224,6 @@ struct ThbUnit {
     unsigned long long pad[3];
     unsigned long long hist[256];       // the radix byte in flight, zero between launches
 };
-inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 __global__ void __launch_bounds__(256) k_thb_init(ThbUnit *s, long long n, long long m, const long long *__restrict__ m_dev)
 {
