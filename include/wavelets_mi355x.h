@@ -327,6 +327,34 @@ WL_API int wl_modwt_batch(wl_ctx *ctx, int dtype, void *out, int64_t ldo, int64_
  * WL_EINVAL_FILTER, WL_EDIMS (as above, with ldw, xw_unit_stride and ncols), WL_EALIAS, WL_EINVAL_L (ncols < 1, ncols - 1 > 62).  */
 WL_API int wl_imodwt_batch(wl_ctx *ctx, int dtype, void *x, int64_t unit_stride, const void *xw, int64_t ldw, int64_t xw_unit_stride,
                            int64_t n, int ncols, int64_t nunits, const double *qmf, int flen, void *stream);
+/* ---- MODWT multiresolution analysis of a batch --------------------------------------------------------- */
+/* out_u = mra(xw_u, filter): the details D_1 .. D_L and the smooth S_L of nunits coefficient matrices (L = ncols - 1).  xw and out
+ * are laid out as wl_modwt_batch writes its result: unit u is the column-major n x ncols matrix at u * unit stride, leading
+ * dimension >= n, unit stride >= ld * ncols.  Column c of out_u is imodwt(Z_c, filter), Z_c = xw_u with every column but c set to
+ * +0: columns 0 .. L-1 are D_1 .. D_L, column L is S_L; they are aligned with x and add up to it for an orthogonal filter.  The
+ * reference has no such function; it is defined by that loop of its own imodwt.  The device computes column c without the zero
+ * terms: one one-sided step with h at level c+1 (the smooth: with g at level L), then one-sided steps with g down to level 1, each
+ * with the tap order, the per-tap rounding to the element type and the wrap-around of wl_imodwt.  For finite input the result is
+ * == the loop's, element for element; the sign of a zero is not part of the contract (dropping `h * 0 +` can turn -0 into +0).
+ * For non-finite input the loop turns a column into NaN wherever 0 * Inf reaches it from the zeroed columns; this call propagates
+ * only what is in the column's own cascade.  ncols is not bounded by log2 n (strides are reduced mod n once per level);
+ * ncols == 1 copies the column ("copy").  In the fused library the call meets the tolerance contract of wl_modwt there.
+ * Nothing outside [0, n) of a column of a unit of out is written.  The call only enqueues on `stream`, never synchronises, and is
+ * capturable in a hipGraph once the workspace is held.  There is no in-place form.  Two tiers, named by wl_last_kernel:
+ *  - "k_modwt_mra_lds": units with 2 * n * sizeof(T) <= 64 KB: ONE launch; a workgroup owns whole planes (unit, column), loads the
+ *    column into LDS, runs the plane's cascade there and stores the last step to out: each coefficient column is read once and each
+ *    column of out written once.  No limit on nunits * ncols.
+ *  - "k_modwt_mra_step_b": longer units, or every batch after wl_ctx_set_option(ctx, "WL_MODWT_FUSED", 0): for level s = L .. 1 two
+ *    launches over the planes active at that level (column s-1 takes h from xw; the columns behind it take g from their buffer).
+ *    16-byte accesses under the rule of wl_modwt_batch, applied to both tensors.
+ * Status codes in this order: WL_EINVAL_ARG (NULL ctx / out / xw / qmf), WL_EINVAL_DTYPE, WL_EINVAL_FILTER, WL_EDIMS (n < 1,
+ * nunits < 1, ldo < n, ldw < n, a unit stride below ld * ncols, a product that no int64 holds or nunits * stride >= 2^60),
+ * WL_EALIAS (the byte ranges of out and xw overlap), WL_EINVAL_L (ncols < 1, ncols - 1 > 62).
+ * Workspace: the LDS tier and the copy hold nothing.  The per-level tier takes the units in groups of G -- all of them, at most
+ * 65535 / ncols (option WL_MODWT_BATCH_GROUP lowers it), halved until the group's two plane buffers are below the context's cap
+ * (option WL_TI_WS_CAP_MB) -- and holds 2 * G * ncols * n elements; groups change no bit.                                       */
+WL_API int wl_modwt_mra_batch(wl_ctx *ctx, int dtype, void *out, int64_t ldo, int64_t out_unit_stride, const void *xw, int64_t ldw,
+                              int64_t xw_unit_stride, int64_t n, int ncols, int64_t nunits, const double *qmf, int flen, void *stream);
 
 /* ---- thresholding and noise estimate -------------------- */
 /* THType of src/Threshold/threshold_main.jl:8-15 (BiggestTH has its own entry point).      */

@@ -20,7 +20,7 @@ from .transforms import (dwt, idwt, dwt_, idwt_, dwt_oop_, idwt_oop_, dwtc, idwt
                          to_device, to_host, similar, julia_layout, is_julia_layout, complex_split, complex_merge, set_complex_arrays, get_complex_arrays, complex_arrays,
                          reserve_workspace, workspace_held, set_kernel_path, last_kernel, destroy_contexts, set_option, clear_options, options, set_arithmetic, get_arithmetic, arithmetic,
                          DimensionMismatch, ArgumentError, HIPError)
-from .modwt import modwt, imodwt, modwt_batch, imodwt_batch, maxmodwttransformlevels
+from .modwt import modwt, imodwt, modwt_batch, imodwt_batch, modwt_mra, modwt_mra_batch, maxmodwttransformlevels
 from .threshold import (THType, HardTH, SoftTH, SemiSoftTH, SteinTH, BiggestTH, PosTH, NegTH, DEFAULT_TH, threshold, threshold_,
                         DNFT, VisuShrink, denoise, noisest, mad_, median, nspin2circ, circshift, DEFAULT_WAVELET,
                         denoise_batch, noisest_batch, mad_batch_, denoise_ti_batch, threshold_batch, threshold_batch_)
@@ -37,7 +37,7 @@ __all__ = [
     "to_device", "to_host", "similar", "julia_layout", "is_julia_layout", "complex_split", "complex_merge", "set_complex_arrays", "get_complex_arrays", "complex_arrays",
     "reserve_workspace", "workspace_held", "set_kernel_path", "last_kernel", "destroy_contexts", "set_option", "clear_options", "options", "set_arithmetic", "get_arithmetic", "arithmetic",
     "DimensionMismatch", "ArgumentError", "HIPError",
-    "modwt", "imodwt", "modwt_batch", "imodwt_batch", "maxmodwttransformlevels",
+    "modwt", "imodwt", "modwt_batch", "imodwt_batch", "modwt_mra", "modwt_mra_batch", "maxmodwttransformlevels",
     "THType", "HardTH", "SoftTH", "SemiSoftTH", "SteinTH", "BiggestTH", "PosTH", "NegTH", "DEFAULT_TH", "threshold", "threshold_",
     "DNFT", "VisuShrink", "denoise", "noisest", "mad_", "median", "nspin2circ", "circshift", "DEFAULT_WAVELET",
     "denoise_batch", "noisest_batch", "mad_batch_", "denoise_ti_batch", "threshold_batch", "threshold_batch_",

@@ -84,6 +84,8 @@ SIGNATURES = {
     "wl_imodwt": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, C.c_int64, C.c_int, _f64p, C.c_int, _vp]),
     "wl_modwt_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int64, _f64p, C.c_int, C.c_int, _vp]),
     "wl_imodwt_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, _f64p, C.c_int, _vp]),
+    "wl_modwt_mra_batch": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int64, _f64p, C.c_int,
+                                     _vp]),
     "wl_threshold": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int, C.c_double, C.c_int, _vp]),
     "wl_threshold_biggest": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, C.c_int64, _vp]),
     # (t_dev / m_dev are DEVICE pointers: passed as addresses)

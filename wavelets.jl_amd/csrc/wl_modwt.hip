@@ -1,6 +1,7 @@
 // wl_modwt.hip -- the maximal-overlap transforms:
 //   modwt / imodwt                       transforms_maximal_overlap.jl:10-107
-// and their batched forms (wl_modwt_batch / wl_imodwt_batch).  HBM-bound gather work; the arithmetic follows
+// their batched forms (wl_modwt_batch / wl_imodwt_batch) and the multiresolution analysis built from one-sided
+// inverse steps (wl_modwt_mra_batch).  HBM-bound gather work; the arithmetic follows
 // Julia's promotion rules literally (Float32 data with Float64 taps: compute in Float64, round on every store) so the results are
 // bit-identical to the reference loops.
 #include "wl_entry.h"
@@ -180,6 +181,72 @@ __device__ __forceinline__ Vec16<T> imodwt_chunk_s(const T *v, const T *w, I NV,
     return acc;
 }
 
+// ---- one-sided synthesis steps (the multiresolution analysis) -----------------------------------------------
+// imodwt_step with one of its two inputs all zero: v0[t] = sum_n c[n] s[t + n*stride], c = tp.h (s holds details) or tp.g (s holds
+// scaling coefficients).  Tap order, per-tap rounding and wrap-around of imodwt_point / imodwt_chunk_v / imodwt_chunk_s, restricted
+// to the non-zero side: `c[n] * s + 0` is `c[n] * s` in Float64 up to the sign of a zero.
+template <typename T, typename I>
+__device__ __forceinline__ T imodwt1_point(const T *s, I N, I t, I stride, const double *c, int F)
+{
+    I k = t;
+    T acc = (T)(c[0] * (double)s[k]);
+    for (int n = 1; n < F; ++n) {
+        k += stride;
+        if (k >= N) { k -= N; if (k >= N) k %= N; }
+        acc = (T)((double)acc + c[n] * (double)s[k]);
+    }
+    return acc;
+}
+template <typename T, typename I>
+__device__ __forceinline__ Vec16<T> imodwt1_chunk_v(const T *s, I NV, I t, I strideV, const double *c, int F)
+{
+    constexpr int V = 16 / sizeof(T);
+    typedef T VT __attribute__((ext_vector_type(V)));
+    const VT *sv = reinterpret_cast<const VT *>(s);
+    I k = t;
+    VT a = sv[k], acc;
+#pragma unroll
+    for (int e = 0; e < V; ++e) acc[e] = (T)(c[0] * (double)a[e]);
+    for (int n = 1; n < F; ++n) {
+        k += strideV;
+        if (k >= NV) { k -= NV; if (k >= NV) k %= NV; }
+        a = sv[k];
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc[e] = (T)((double)acc[e] + c[n] * (double)a[e]);
+    }
+    return acc;
+}
+// (S divides V, NV >= 2: the register pair [current chunk | next chunk] slides forward by one chunk per V / S taps)
+template <typename T, int S, typename I>
+__device__ __forceinline__ Vec16<T> imodwt1_chunk_s(const T *s, I NV, I t, const double *c, int F)
+{
+    constexpr int V = 16 / sizeof(T), G = V / S;
+    typedef T VT __attribute__((ext_vector_type(V)));
+    const VT *sv = reinterpret_cast<const VT *>(s);
+    I kn = (t + 1 == NV) ? 0 : t + 1;
+    VT ca = sv[t], na = sv[kn], acc;
+    for (int n0 = 0; n0 < F; n0 += G) {
+        T wa[2 * V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) { wa[e] = ca[e]; wa[V + e] = na[e]; }
+        ca = na;
+        kn = (kn + 1 == NV) ? 0 : kn + 1;
+        na = sv[kn];
+#pragma unroll
+        for (int r = 0; r < G; ++r) {
+            const int n = n0 + r;
+            if (n < F) {
+#pragma unroll
+                for (int e = 0; e < V; ++e) {
+                    const double term = c[n] * (double)wa[e + r * S];
+                    acc[e] = (n == 0) ? (T)term : (T)((double)acc[e] + term);
+                }
+            }
+        }
+    }
+    return acc;
+}
+
 // the first index and the step of a grid-stride loop in x (taken in the kernel itself, where the block size is known to be uniform)
 #define GRID_X_FIRST ((int64_t)blockIdx.x * blockDim.x + threadIdx.x)
 #define GRID_X_THREADS ((int64_t)gridDim.x * blockDim.x)
@@ -325,6 +392,35 @@ __global__ void __launch_bounds__(EXT_THREADS) k_imodwt_step_s_b(const T *__rest
     imodwt_step_s_body<T, S>(v + u * vs, w + u * ws, v0 + u * v0s, NV, tp, GRID_X_FIRST, GRID_X_THREADS);
 }
 
+// ---- the per-level tier of the multiresolution analysis: one one-sided step of the planes (unit, column) of
+// a group.  Plane blockIdx.y is column c0 + y % ncnt of unit y / ncnt; it reads src + unit * sus + column * sld and writes dst
+// likewise.  KIND: the function of modwt_lds_kind's numbering (0 point, 1 chunk_v, 2 chunk_s<1>, 3 chunk_s<2>); N counts elements,
+// stride elements (KIND 0) or 16-byte chunks (KIND 1), already reduced mod the unit.
+template <typename T, int KIND>
+__global__ void __launch_bounds__(EXT_THREADS) k_modwt_mra_step_b(const T *__restrict__ src, int64_t sld, int64_t sus, T *__restrict__ dst,
+                                                                  int64_t dld, int64_t dus, int c0, int ncnt, int64_t N, int64_t stride,
+                                                                  int useh, ModwtTaps tp)
+{
+    constexpr int V = 16 / sizeof(T);
+    typedef Vec16<T> VT;
+    const unsigned y = blockIdx.y;
+    const int64_t u = y / (unsigned)ncnt, c = c0 + (int64_t)(y % (unsigned)ncnt);
+    const T *s = src + u * sus + c * sld;
+    T *d = dst + u * dus + c * dld;
+    const double *taps = useh ? tp.h : tp.g;
+    const int64_t t0 = GRID_X_FIRST, nthr = GRID_X_THREADS;
+    if (KIND == 0) {
+        for (int64_t t = t0; t < N; t += nthr) d[t] = imodwt1_point<T, int64_t>(s, N, t, stride, taps, tp.F);
+    } else {
+        const int64_t NV = N / V;
+        for (int64_t t = t0; t < NV; t += nthr) {
+            if (KIND == 1) reinterpret_cast<VT *>(d)[t] = imodwt1_chunk_v<T, int64_t>(s, NV, t, stride, taps, tp.F);
+            else if (KIND == 2) reinterpret_cast<VT *>(d)[t] = imodwt1_chunk_s<T, 1, int64_t>(s, NV, t, taps, tp.F);
+            else reinterpret_cast<VT *>(d)[t] = imodwt1_chunk_s<T, (V == 4 ? 2 : 1), int64_t>(s, NV, t, taps, tp.F);
+        }
+    }
+}
+
 // ---- the LDS tier of the batch: every level of a short unit in one launch ------------------------------------
 // which function a level of the LDS kernels takes, by the rules of the per-level dispatch (modwt_level): 1 chunk_v, 2 chunk_s<1>, 3 chunk_s<2>
 // (Float32 only), 0 the point function (an unaligned batch, or a unit of one chunk)
@@ -438,6 +534,93 @@ __global__ void __launch_bounds__(MODWT_LDS_THREADS) k_imodwt_lds(T *__restrict_
                 else if (kind == 2) reinterpret_cast<VT *>(dst)[c] = imodwt_chunk_s<T, 1, int>(vsrc, wsrc, n / V, c, tp);
                 else reinterpret_cast<VT *>(dst)[c] = imodwt_chunk_s<T, (V == 4 ? 2 : 1), int>(vsrc, wsrc, n / V, c, tp);
             }
+            __syncthreads();
+            T *sw = cur; cur = nxt; nxt = sw;
+        }
+    }
+}
+
+// ---- the LDS tier of the multiresolution analysis -------------------------------------------------------------
+// A work unit is a plane (unit u, column c): column c of xw, one step with h at level c + 1 (the smooth, c = L: with g at level L),
+// then steps with g down to level 1, which stores column c of out.  Planes are numbered p = q * nunits + u with q the column's rank
+// by depth, column L - q: the smooth and D_L (L steps each) first, D_1 (one step) last.  A workgroup takes `ppw` consecutive planes
+// at a time (modwt_lds_shape) and walks the planes with a grid-stride loop.  It runs levels s = first .. 1 of its pack, `first` the
+// level its first (deepest) slot starts at, one barrier per level; a slot whose column starts below `first` (a pack that straddles a
+// column boundary) is loaded into the buffer that is the source at its own first level and waits.  The slots are sorted by depth, so
+// at level s those on g, those on h and those still waiting are three consecutive ranges with workgroup-uniform bounds: the taps stay
+// a uniform (scalar) operand.  Access widths and chunk functions as in k_imodwt_lds.
+// plane p0 + slot of the pack that starts at rank q0, unit u0 (slot < 1024)
+__device__ __forceinline__ void mra_plane(int q0, int64_t u0, int slot, int64_t nunits, int &q, int64_t &u)
+{
+    q = q0;
+    u = u0 + slot;
+    if (u >= nunits) {
+        u -= nunits;
+        ++q;
+        if (u >= nunits) { const int d = (int)u, nn = (int)nunits; q += d / nn; u = d % nn; }     // (nunits <= u < 1024 here)
+    }
+}
+template <typename T>
+__global__ void __launch_bounds__(MODWT_LDS_THREADS) k_modwt_mra_lds(T *__restrict__ out, int64_t ldo, int64_t ous, const T *__restrict__ xw,
+                                                                     int64_t ldw, int64_t ws, int n, int64_t nunits, int ncols, int ppw, int vec,
+                                                                     ModwtTaps tp)
+{
+    constexpr int V = 16 / sizeof(T);
+    typedef T VT __attribute__((ext_vector_type(V)));
+    extern __shared__ __attribute__((aligned(16))) char modwt_lds_mem[];
+    T *bufA = reinterpret_cast<T *>(modwt_lds_mem), *bufB = bufA + (size_t)ppw * n;
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int L = ncols - 1;                           // >= 1
+    const int64_t nplanes = nunits * ncols;
+    const int ipu = vec ? n / V : n;                   // work items of one plane
+    for (int64_t p0 = (int64_t)blockIdx.x * ppw; p0 < nplanes; p0 += (int64_t)gridDim.x * ppw) {
+        const int np = (nplanes - p0 < ppw) ? (int)(nplanes - p0) : ppw;
+        const int q0 = (int)(p0 / nunits);
+        const int64_t u0 = p0 - (int64_t)q0 * nunits;
+        const int first = (q0 == 0) ? L : L - q0 + 1;
+        for (int i = tid; i < np * ipu; i += nthr) {
+            int slot = 0, e = i;
+            if (ppw > 1) { slot = i / ipu; e = i - slot * ipu; }
+            int q;
+            int64_t u;
+            mra_plane(q0, u0, slot, nunits, q, u);
+            const int start = (q == 0) ? L : L - q + 1;
+            T *b = (((first - start) & 1) ? bufB : bufA) + (size_t)slot * n;
+            const T *src = xw + u * ws + (int64_t)(L - q) * ldw;
+            if (vec) reinterpret_cast<VT *>(b)[e] = reinterpret_cast<const VT *>(src)[e];
+            else b[e] = src[e];
+        }
+        __syncthreads();
+        T *cur = bufA, *nxt = bufB;
+        for (int s = first; s >= 1; --s) {
+            const int64_t stride = (int64_t)1 << (s - 1);
+            const int kind = modwt_lds_kind<T>(vec, stride, n);
+            // (vec with kind 0, n == V: the items of this level are elements)
+            const int ipl = kind ? n / V : n;
+            const int sred = (kind == 1) ? (int)((stride / V) % (n / V)) : (int)(stride % n);
+            // slots [0, a): ranks below L - s + 1, on g; [a, b): rank L - s + 1, the column that enters at this level, on h
+            const int64_t ra = (int64_t)(L - s + 1) * nunits - p0, rb = ra + nunits;
+            const int a = ra < 0 ? 0 : (ra > np ? np : (int)ra), b = rb < 0 ? 0 : (rb > np ? np : (int)rb);
+            auto items = [&](int i0, int i1, const double *taps) {
+                for (int i = i0 + tid; i < i1; i += nthr) {
+                    int slot = 0, e = i;
+                    if (ppw > 1) { slot = i / ipl; e = i - slot * ipl; }
+                    const T *src = cur + (size_t)slot * n;
+                    T *dst = nxt + (size_t)slot * n;
+                    if (s == 1) {
+                        int q;
+                        int64_t u;
+                        mra_plane(q0, u0, slot, nunits, q, u);
+                        dst = out + u * ous + (int64_t)(L - q) * ldo;
+                    }
+                    if (kind == 0) dst[e] = imodwt1_point<T, int>(src, n, e, sred, taps, tp.F);
+                    else if (kind == 1) reinterpret_cast<VT *>(dst)[e] = imodwt1_chunk_v<T, int>(src, n / V, e, sred, taps, tp.F);
+                    else if (kind == 2) reinterpret_cast<VT *>(dst)[e] = imodwt1_chunk_s<T, 1, int>(src, n / V, e, taps, tp.F);
+                    else reinterpret_cast<VT *>(dst)[e] = imodwt1_chunk_s<T, (V == 4 ? 2 : 1), int>(src, n / V, e, taps, tp.F);
+                }
+            };
+            items(0, a * ipl, tp.g);
+            items(a * ipl, b * ipl, tp.h);
             __syncthreads();
             T *sw = cur; cur = nxt; nxt = sw;
         }
@@ -649,6 +832,88 @@ bool modwt_batch_overlap(const void *x, int64_t xs, const void *m, int64_t ld, i
     return a0 < b1 && b0 < a1;
 }
 
+// ---- the multiresolution analysis of a batch (wl_modwt_mra_batch) ------------------------------------------
+// One one-sided step of nb * ncnt planes on the per-level tier: columns c0 .. c0 + ncnt - 1 of nb units, by the rules of imodwt_level.
+template <typename T>
+void modwt_mra_level(hipStream_t st, int cu_count, bool vec, bool small, int64_t nb, const T *src, int64_t sld, int64_t sus, T *dst, int64_t dld,
+                     int64_t dus, int c0, int ncnt, int64_t N, int64_t stride, bool useh, const ModwtTaps &tp)
+{
+    constexpr int V = 16 / sizeof(T);
+    const unsigned ny = (unsigned)(nb * ncnt);
+    const dim3 gv(ext_blocks(N / V, 1, cu_count), ny), gs(ext_blocks(N, 1, cu_count), ny), th(EXT_THREADS);
+    auto launch = [&](auto k, dim3 grid, int64_t sred) {
+        hipLaunchKernelGGL(k, grid, th, 0, st, src, sld, sus, dst, dld, dus, c0, ncnt, N, sred, useh ? 1 : 0, tp);
+    };
+    if (vec && (stride % V) == 0) launch(k_modwt_mra_step_b<T, 1>, gv, (stride / V) % (N / V));
+    else if (vec && stride == 1 && N >= 2 * V && small) launch(k_modwt_mra_step_b<T, 2>, gv, 1);
+    else if (vec && stride == 2 && V == 4 && N >= 2 * V && small) launch(k_modwt_mra_step_b<T, 3>, gv, 2);
+    else launch(k_modwt_mra_step_b<T, 0>, gs, stride % N);
+}
+// Levels L .. 1 of the nb units of a group.  At level s column s - 1 enters with h from xw, and the columns s .. L that are under way
+// (the smooth among them) take g from the buffer level s + 1 wrote -- at level L the smooth alone, from xw.  Level s writes buffer
+// A (s odd) or B, plane (unit, column) at (unit * ncols + column) * N; level 1 writes out.
+template <typename T>
+int modwt_mra_levels(wl_ctx *ctx, hipStream_t st, bool vec, int64_t nb, T *out, int64_t ldo, int64_t ous, const T *xw, int64_t ldw, int64_t ws,
+                     int64_t N, int ncols, T *A, T *B, const ModwtTaps &tp)
+{
+    const bool small = opt("WL_MODWT_SMALL", 1) != 0;
+    const int L = ncols - 1;
+    const int64_t pus = (int64_t)ncols * N;
+    for (int s = L; s >= 1; --s) {
+        const int64_t stride = (int64_t)1 << (s - 1);
+        T *dst = (s == 1) ? out : ((s & 1) ? A : B);
+        const T *prev = (s & 1) ? B : A;
+        const int64_t dld = (s == 1) ? ldo : N, dus = (s == 1) ? ous : pus;
+        modwt_mra_level<T>(st, ctx->cu_count, vec, small, nb, xw, ldw, ws, dst, dld, dus, s - 1, 1, N, stride, true, tp);
+        WL_HIP(ctx, hipGetLastError());
+        if (s == L) modwt_mra_level<T>(st, ctx->cu_count, vec, small, nb, xw, ldw, ws, dst, dld, dus, L, 1, N, stride, false, tp);
+        else modwt_mra_level<T>(st, ctx->cu_count, vec, small, nb, prev, N, pus, dst, dld, dus, s, L - s + 1, N, stride, false, tp);
+        WL_HIP(ctx, hipGetLastError());
+    }
+    return WL_OK;
+}
+template <typename T>
+int modwt_mra_batch_impl(wl_ctx *ctx, hipStream_t st, T *out, int64_t ldo, int64_t ous, const T *xw, int64_t ldw, int64_t ws, int64_t N,
+                         int ncols, int64_t nunits, const double *qmf, int flen)
+{
+    if (ncols == 1) {                                        // no level: the smooth is the scaling column
+        WL_HIP(ctx, hipMemcpy2DAsync(out, (size_t)ous * sizeof(T), xw, (size_t)ws * sizeof(T), (size_t)N * sizeof(T), (size_t)nunits,
+                                     hipMemcpyDeviceToDevice, st));
+        ctx->last_kernel = "copy";
+        return WL_OK;
+    }
+    ModwtTaps tp;
+    make_modwt_taps(qmf, flen, tp);
+    const bool vec = modwt_batch_vec<T>(out, ous, xw, ldw, ws, N, nunits) && (ldo % (int64_t)(16 / sizeof(T))) == 0;
+    if (opt("WL_MODWT_FUSED", 1) != 0 && (size_t)2 * N * sizeof(T) <= (size_t)MODWT_LDS_BYTES) {
+        const ModwtLdsShape sh = modwt_lds_shape<T>(N, nunits * ncols, vec, ctx->cu_count);
+        hipLaunchKernelGGL((k_modwt_mra_lds<T>), dim3(sh.grid), dim3(sh.threads), sh.lds, st, out, ldo, ous, xw, ldw, ws, (int)N, nunits, ncols,
+                           sh.upw, vec ? 1 : 0, tp);
+        WL_HIP(ctx, hipGetLastError());
+        ctx->last_kernel = "k_modwt_mra_lds";
+        return WL_OK;
+    }
+    auto bytes = [&](int64_t G) { return (size_t)2 * G * ncols * N * sizeof(T); };
+    const int64_t G = group_size(nunits, 65535 / ncols, opt("WL_MODWT_BATCH_GROUP", 0), true, group_cap(), bytes);
+    WL_TRY(wl_ensure_ws(ctx, bytes(G), st, true));
+    T *A = (T *)ctx->ws, *B = A + G * ncols * N;
+    WL_TRY(for_groups(nunits, G, [&](int64_t u0, int64_t nb) -> int {
+        return modwt_mra_levels<T>(ctx, st, vec, nb, out + u0 * ous, ldo, ous, xw + u0 * ws, ldw, ws, N, ncols, A, B, tp);
+    }));
+    ctx->last_kernel = "k_modwt_mra_step_b";
+    return WL_OK;
+}
+// the units of two coefficient tensors as byte ranges (cols clamped to what the dims rule has seen)
+bool modwt_mats_overlap(const void *a, int64_t lda, int64_t as, const void *b, int64_t ldb, int64_t bs, int64_t n, int64_t nunits, int64_t cols,
+                        size_t sz)
+{
+    const int64_t lastc = cols >= 1 ? cols - 1 : 0;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    const uintptr_t a1 = a0 + (uintptr_t)((nunits - 1) * as + lastc * lda + n) * sz;
+    const uintptr_t b1 = b0 + (uintptr_t)((nunits - 1) * bs + lastc * ldb + n) * sz;
+    return a0 < b1 && b0 < a1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -720,6 +985,22 @@ int wl_imodwt_batch(wl_ctx *ctx, int dtype, void *x, int64_t unit_stride, const 
     return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
         using T = decltype(t);
         return imodwt_batch_impl<T>(ctx, st, (T *)x, unit_stride, (const T *)xw, ldw, xw_unit_stride, n, ncols, nunits, qmf, flen);
+    });
+}
+
+int wl_modwt_mra_batch(wl_ctx *ctx, int dtype, void *out, int64_t ldo, int64_t out_unit_stride, const void *xw, int64_t ldw,
+                       int64_t xw_unit_stride, int64_t n, int ncols, int64_t nunits, const double *qmf, int flen, void *stream)
+{
+    if (!ctx || !out || !xw || !qmf) return WL_EINVAL_ARG;
+    WL_TRY(check_dtype(dtype));
+    WL_TRY(check_flen(flen, 1));
+    WL_TRY(modwt_batch_dims(n, nunits, n, ldo, out_unit_stride, ncols));
+    WL_TRY(modwt_batch_dims(n, nunits, n, ldw, xw_unit_stride, ncols));
+    if (modwt_mats_overlap(out, ldo, out_unit_stride, xw, ldw, xw_unit_stride, n, nunits, ncols, dtype == WL_F32 ? 4 : 8)) return WL_EALIAS;
+    if (ncols < 1 || ncols - 1 > 62) return WL_EINVAL_L;
+    return scoped_by_dtype(ctx, dtype, stream, [&](auto t, hipStream_t st) {
+        using T = decltype(t);
+        return modwt_mra_batch_impl<T>(ctx, st, (T *)out, ldo, out_unit_stride, (const T *)xw, ldw, xw_unit_stride, n, ncols, nunits, qmf, flen);
     });
 }
 

@@ -3,8 +3,9 @@
 
 `modwt(x, wt, L)` returns the n x (L+1) coefficient matrix as a column-major device tensor (each
 level's coefficients are one contiguous column; the scaling coefficients are the last column),
-`imodwt(xw, wt)` inverts it; `modwt_batch` / `imodwt_batch` do the same for every column of a len x B panel in one call.  The
-compute is libwavelets_mi355x.so (wl_modwt / wl_imodwt / wl_modwt_batch / wl_imodwt_batch); there is
+`imodwt(xw, wt)` inverts it; `modwt_batch` / `imodwt_batch` do the same for every column of a len x B panel in one call;
+`modwt_mra` / `modwt_mra_batch` turn coefficients into the multiresolution analysis (details D_1 .. D_L and smooth S_L).  The
+compute is libwavelets_mi355x.so (wl_modwt / wl_imodwt / wl_modwt_batch / wl_imodwt_batch / wl_modwt_mra_batch); there is
 no CPU path.
 """
 from __future__ import annotations
@@ -171,3 +172,55 @@ def imodwt_batch(xw, wt: OrthoFilter) -> torch.Tensor:
                                      _f64p(q), len(q), st)
     _check(rc, h)
     return x
+
+
+# ---- multiresolution analysis (wl_modwt_mra_batch) --------------------------------------------------------
+def _mra(name, xw, wt, y, dim, what):
+    _reject_complex(xw, name)
+    _reject_complex(y, name)
+    if not isinstance(wt, OrthoFilter):
+        raise TypeError(name + " is defined for OrthoFilter wavelets only (MethodError in the reference)")
+    if isinstance(xw, torch.Tensor):                         # (the shape rules before anything touches the device)
+        if xw.dim() != dim:
+            raise TypeError(f"{name} expects {what}")
+        if min(int(v) for v in xw.shape) < 1:
+            raise DimensionMismatch("empty coefficient array")
+    xw = _batch_in(xw)
+    if dim == 2:                                             # one matrix: a batch of one unit
+        xw = xw.unsqueeze(2)
+    if _coef_strides(xw) is None:
+        xw = julia_layout(xw)
+    ldw, ws = _coef_strides(xw)
+    n, ncols, nb = (int(v) for v in xw.shape)
+    if y is None:
+        y = torch.empty((nb, ncols, n), dtype=xw.dtype, device=xw.device).permute(2, 1, 0)      # column-major n x ncols x B
+    else:
+        y = _batch_in(y)
+        if tuple(y.shape) != (n, ncols, nb):
+            raise DimensionMismatch(f"{name}: y must have the shape of xw, {(n, ncols, nb)}, got {tuple(y.shape)}")
+        if y.dtype != xw.dtype or y.device != xw.device:
+            raise TypeError("xw and y must have the same element type and device")
+        if _coef_strides(y) is None:
+            raise ArgumentError(name + ": y must be column-major (stride 1 along n, columns >= n apart, units >= ld * ncols apart)")
+    ldo, ous = _coef_strides(y)
+    h, st = _context(xw.device)
+    q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
+    rc = _lib.load().wl_modwt_mra_batch(h, _dtype_code(xw), C.c_void_p(y.data_ptr()), ldo, ous, C.c_void_p(xw.data_ptr()), ldw, ws, n, ncols, nb,
+                                        _f64p(q), len(q), st)
+    _check(rc, h)
+    return y[:, :, 0] if dim == 2 else y
+
+
+def modwt_mra_batch(xw, wt: OrthoFilter, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MODWT multiresolution analysis of every n x ncols slice xw[:, :, u] (what modwt_batch returns) in one call: the n x ncols x B
+    tensor whose [:, c, u] is imodwt of xw[:, :, u] with every column but c set to zero -- the details D_1 .. D_L in columns
+    0 .. L-1 and the smooth S_L in column L = ncols - 1, aligned with x and adding up to it.  Equal (==) to that loop for finite
+    input.  A padded column-major xw is taken in place, any other layout is copied once.  y: an n x ncols x B result tensor,
+    dense or padded (stride 1 along the first dimension), not overlapping xw."""
+    return _mra("modwt_mra_batch", xw, wt, y, 3, "an n x ncols x B array (unit i = xw[:, :, i])")
+
+
+def modwt_mra(xw, wt: OrthoFilter) -> torch.Tensor:
+    """MODWT multiresolution analysis of one n x ncols coefficient matrix (what modwt returns): n x ncols, columns D_1 .. D_L, S_L --
+    modwt_mra_batch of a batch of one"""
+    return _mra("modwt_mra", xw, wt, None, 2, "a matrix (MethodError in the reference)")
