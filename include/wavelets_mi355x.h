@@ -705,6 +705,50 @@ WL_API int wl_wpt_filter_batch_trees(wl_ctx *ctx, int dtype, void *y, const void
                                      const double *qmf, int flen, const uint8_t *trees, int64_t tree_stride, int L, int fw,
                                      void *stream);
 
+/* ---- matching pursuit (src/Threshold/basis_functions.jl:8-55) ---------------------------------------------------------------
+ *   r = x; y = 0; it = 0; cap = (nmax == -1 ? N : nmax)
+ *   while nrm(r) > tol && it < cap:  ftr = ft(r); i = findmaxabs(ftr); aphi = f(ftr[i] e_i); r = T(r - aphi); y[i] = T(y[i] + ftr[i]); it += 1
+ * findmaxabs(v) is the FIRST index whose magnitude is strictly greater than every earlier one: v[0] NaN gives 0, a NaN anywhere else
+ * never wins, an all-zero or all-equal vector gives 0, -0.0 and +0.0 tie.  nrm(r) = (double)(T)sqrt(s) with s the Float64 sum of
+ * squares in a fixed order (same input, same bits; about 1 ulp of T from BLAS nrm2): the only place where the loop is not the
+ * reference bit for bit, and it only gates termination.  A NaN norm ends the loop.
+ * Option "WL_MP_MAX_BLOCKS" (wl_ctx_set_option; default 4 workgroups per CU, at most 65536) caps the grid of the two reductions: it
+ * changes the order of the Float64 sum, never an index.
+ *
+ * *idx_dev = findmaxabs(v[0 .. len)), a 0-based index in DEVICE memory.  Enqueues only; capturable in a hipGraph once the workspace
+ * is held (len > 4096 takes a few KiB of it).
+ * Status codes in this order: WL_EINVAL_ARG (NULL ctx / v / idx_dev), WL_EINVAL_DTYPE, WL_EDIMS (len < 1).                        */
+WL_API int wl_findmaxabs(wl_ctx *ctx, int dtype, const void *v, int64_t len, int64_t *idx_dev, void *stream);
+/* The select of one atom, i = *idx_dev (device memory): spat[i % n] = ftr[i]; y[i] = T(y[i] + ftr[i]).  ftr and y hold ncoef
+ * coefficients, spat holds n (a union of ncoef / n bases of n: the atom's position inside its base; a dense dictionary passes
+ * n = ncoef).  An index outside [0, ncoef) selects nothing.  Enqueues only; capturable in a hipGraph.
+ * Status codes in this order: WL_EINVAL_ARG (NULL ctx / spat / y / ftr / idx_dev), WL_EINVAL_DTYPE, WL_EDIMS (n < 1, ncoef < 1,
+ * ncoef % n != 0).                                                                                                                 */
+WL_API int wl_mp_select(wl_ctx *ctx, int dtype, void *spat, int64_t n, void *y, const void *ftr, int64_t ncoef,
+                        const int64_t *idx_dev, void *stream);
+/* r[t] = T(r[t] - aphi[t]) for t < n (one rounding per element), then *nrm = nrm(r).  aphi == NULL: r is left alone and only the
+ * norm is formed.  spat != NULL (then spat_len == n and idx_dev != NULL): spat[*idx_dev % n] = 0, the spike wl_mp_select set.
+ * Synchronises `stream` (the norm is a host scalar, as in the reference).
+ * Status codes in this order: WL_EINVAL_ARG (NULL ctx / r / nrm, spat without idx_dev), WL_EINVAL_DTYPE, WL_EDIMS (n < 1, spat_len
+ * neither 0 nor n, spat with spat_len 0).                                                                                          */
+WL_API int wl_mp_residual(wl_ctx *ctx, int dtype, void *r, const void *aphi, int64_t n, void *spat, int64_t spat_len,
+                          const int64_t *idx_dev, double *nrm, void *stream);
+/* matchingpursuit over a union of `nbases` orthonormal wavelet bases of a vector of n (N = nbases * n coefficients):
+ * ft(r)[k n + p] = dwt(r, filter k, Ls[k])[p], f of a spike in block k = idwt(that block, filter k, Ls[k]); the all-zero blocks are
+ * not transformed, so for finite input the atom is == the literal sum and the sign of a zero is not part of the contract.  Ls[k] = 0
+ * is the identity (the Dirac basis).  qmfs: the host concatenation of the flens[k] taps.  r holds the signal on entry and the
+ * residual on exit (the reference's r = x overwrites x); y receives the N coefficients; *niter (atoms taken) and *nrm (the last
+ * norm) are host outputs.  Per atom: nbases forward transforms, arg-max + select, ONE 24-byte read-back of {index, norm} behind a
+ * stream synchronisation (the host must know which base to invert and whether to stop), one inverse transform, residual + norm.
+ * wl_last_kernel: "matchingpursuit+<forward kernel of base 0>".
+ * Status codes in this order: WL_EINVAL_ARG (NULL ctx / y / r / qmfs / flens / Ls / niter / nrm, nbases < 1, !(tol > 0), nmax < -1),
+ * WL_EINVAL_DTYPE, WL_EINVAL_FILTER (any flens[k]), WL_EDIMS (n < 1, nbases * n beyond 2^60), WL_EALIAS (the byte ranges of y and r
+ * overlap), then base by base what wl_dwt_filter returns for a vector of n with Ls[k] (WL_EINVAL_L, WL_EINVAL_SIZE).
+ * Workspace: one transform's own (2 * (n / 2 + 64) + 3 n + 64 elements) + (nbases + 2) * n elements + a few KiB of partials.        */
+WL_API int wl_matchingpursuit_filter(wl_ctx *ctx, int dtype, void *y, void *r, int64_t n, int nbases, const double *qmfs,
+                                     const int *flens, const int *Ls, double tol, int64_t nmax,
+                                     int64_t *niter, double *nrm, void *stream);
+
 /* ---- introspection (tests / bench) ---------------------------------------------------- */
 /* Select the kernel family: 0 = auto (fast paths where they apply), 1 = generic kernels
  * only.  Both produce bit-identical results; the switch exists so tests can prove it.   */

@@ -25,6 +25,7 @@ from .threshold import (THType, HardTH, SoftTH, SemiSoftTH, SteinTH, BiggestTH, 
                         DNFT, VisuShrink, denoise, noisest, mad_, median, nspin2circ, circshift, DEFAULT_WAVELET,
                         denoise_batch, noisest_batch, mad_batch_, denoise_ti_batch, threshold_batch, threshold_batch_)
 from .entropy import Entropy, ShannonEntropy, LogEnergyEntropy, coefentropy, bestbasistree, bestbasistree_batch
+from .pursuit import matchingpursuit, findmaxabs
 from . import _lib
 
 __all__ = [
@@ -42,4 +43,5 @@ __all__ = [
     "DNFT", "VisuShrink", "denoise", "noisest", "mad_", "median", "nspin2circ", "circshift", "DEFAULT_WAVELET",
     "denoise_batch", "noisest_batch", "mad_batch_", "denoise_ti_batch", "threshold_batch", "threshold_batch_",
     "Entropy", "ShannonEntropy", "LogEnergyEntropy", "coefentropy", "bestbasistree", "bestbasistree_batch",
+    "matchingpursuit", "findmaxabs",
 ]

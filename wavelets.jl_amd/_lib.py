@@ -128,6 +128,12 @@ SIGNATURES = {
                                                 C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "wl_wpt_filter_batch_trees": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, C.c_int64, C.c_int64, _f64p, C.c_int, _vp, C.c_int64, C.c_int,
                                             C.c_int, _vp]),
+    # (idx_dev is a DEVICE pointer: passed as an address)
+    "wl_findmaxabs": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, _vp]),
+    "wl_mp_select": (C.c_int, [_vp, C.c_int, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp]),
+    "wl_mp_residual": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _f64p, _vp]),
+    "wl_matchingpursuit_filter": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int64, C.c_int, _f64p, _i32p, _i32p, C.c_double, C.c_int64,
+                                            _i64p, _f64p, _vp]),
 }
 
 

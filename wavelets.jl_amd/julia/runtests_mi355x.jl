@@ -126,5 +126,20 @@ same(a, b) = Array(b) == a          # bit-for-bit (0.0 == -0.0)
         @test same(w, modwt(ROCArray(x), wt, 4))
         @test same(imodwt(w, wt), imodwt(ROCArray(w), wt))
     end
+    @testset "matching pursuit" begin
+        # an integer dictionary keeps every product and sum exact: the CPU loop is the expected result bit for bit
+        A = Float64.(rand(-2:2, 16, 64)); y0 = zeros(64); y0[[3, 17, 40]] = [2.0, -1.0, 1.0]
+        x = A * y0
+        Ad, Atd = ROCArray(A), ROCArray(collect(A'))
+        yd = matchingpursuit(ROCArray(x), a -> Ad * a, a -> Atd * a, 0.1, 3)
+        @test same(matchingpursuit(copy(x), a -> A * a, a -> A' * a, 0.1, 3), yd)
+        # a union of two wavelet bases against the reference's loop over dwt / idwt (few atoms: the norms are far from tol)
+        n = 256; v = randn(Float32, n); wts = [wavelet(WT.haar), wavelet(WT.db4)]
+        ft(r) = vcat(dwt(r, wts[1]), dwt(r, wts[2]))
+        f(c) = idwt(c[1:n], wts[1]) + idwt(c[n+1:2n], wts[2])
+        @test matchingpursuit(ROCArray(v), wts, 1f-3, 5) |> Array == matchingpursuit(copy(v), f, ft, 1f-3, 5)
+        @test WaveletsMI355X.Threshold.findmaxabs(ROCArray(Float32[1, -3, 3, NaN])) == 2
+        @test_throws AssertionError matchingpursuit(ROCArray(v), wts, 0.0)
+    end
 end
 WaveletsMI355X.destroy_contexts!()
