@@ -281,6 +281,32 @@ WL_API int wl_wpt_lifting_full(wl_ctx *ctx, int dtype, void *y, int64_t n,
                         const int32_t *step_shift, const double *coefs_flat,
                         double norm1, double norm2, int L, int fw, void *stream);
 
+/* ---- wavelet packet transform (2-D) --------------------------------------------------- */
+/* y = wpt2(x, filter, tree) / iwpt2 of a dims[0] x dims[1] column-major image over a quadtree.  The reference has no such
+ * transform (WPTArray = AbstractVector); the definition is DESIGN.md section 22: the node at depth d with block coordinates
+ * (bi, bj) is the sub-block of rows bi dims[0] / 2^d ... and columns bj dims[1] / 2^d ...; splitting it replaces the block by its
+ * one-level 2-D dwt, periodic within the block, whose quadrants [[ss, sd], [ds, dd]] are the children c = ci + 2 cj (ci = 1: the
+ * lower half of dimension 0, cj = 1: the right half of dimension 1).  tree: one byte per node in breadth-first order, node k has
+ * the children 4k + 1 + c, depth d starts at (4^d - 1) / 3 and is ordered by the Morton code of (bi, bj) with bi in the even bits;
+ * ntree = (4^L - 1) / 3 for an L >= 0 with dims[i] % 2^L == 0, and no set node below a clear one -- otherwise WL_EINVAL_TREE.  A
+ * tree whose root is clear (and ntree == 0) is a copy.  iwpt2 (fw == 0) undoes the splits, children before parents.
+ * tree is a HOST pointer; it is copied before the call returns (through a pinned staging buffer of the context) and the stream is
+ * NOT synchronised.  A call with a partially split tree is not capturable in a hipGraph (its staging copy would be replayed with
+ * stale bits).  Out of place only.  Two kernels, named by wl_last_kernel: "k_wpt2_level" (one depth per pass over the image) and
+ * "k_wpt2_tail" (every depth from the first whose nodes hold at most "WL_WPT2_TAIL_MAX" elements, in one launch; the option is
+ * clamped to 1 .. 4096, the default is 256, and 1 means the tail is never used); "copy" when nothing splits.  Workspace: one plane of the
+ * image (when two or more passes run) plus the tree.
+ * Status codes in this order: WL_EINVAL_ARG (NULL ctx / y / x / dims / qmf, NULL tree with ntree > 0), WL_EINVAL_DTYPE,
+ * WL_EINVAL_FILTER, WL_EDIMS (an extent < 1 or >= 2^31), WL_EALIAS (y == x), WL_EINVAL_TREE.                                  */
+WL_API int wl_wpt2_filter(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims,
+                          const double *qmf, int flen, const uint8_t *tree, int64_t ntree, int fw, void *stream);
+/* The FULL quadtree of depth L without a tree vector: never sees a tree, no stream synchronisation, capturable in a hipGraph
+ * once the workspace is held.  Same results as wl_wpt2_filter with the full tree of depth L; L == 0 is a copy.
+ * Status codes in this order: WL_EINVAL_ARG, WL_EINVAL_DTYPE, WL_EINVAL_FILTER, WL_EDIMS, WL_EINVAL_L (L < 0), WL_EINVAL_SIZE
+ * (dims[i] % 2^L != 0), WL_EALIAS (y == x).                                                                                  */
+WL_API int wl_wpt2_filter_full(wl_ctx *ctx, int dtype, void *y, const void *x, const int64_t *dims,
+                               const double *qmf, int flen, int L, int fw, void *stream);
+
 /* ---- maximal-overlap DWT, 1-D -------------------------- */
 /* floor(log2(n)) -- replaces maxmodwttransformlevels, src/Util/non_dyadic.jl:24-25.        */
 WL_API int wl_maxmodwttransformlevels(int64_t n);

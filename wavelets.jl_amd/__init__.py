@@ -13,10 +13,10 @@ from . import wt as WT
 from . import util as Util
 from .wt import wavelet, OrthoFilter, GLS
 from .util import (maxtransformlevels, sufficientpoweroftwo, detailindex, detailrange, detailn,
-                   ndyadicscales, maketree, isvalidtree, iscube, isdyadic,
+                   ndyadicscales, maketree, isvalidtree, maketree2, isvalidtree2, iscube, isdyadic,
                    dyadicdetailindex, dyadicdetailrange, dyadicscalingrange, dyadicdetailn, maxdyadiclevel, tl2dyadiclevel,
                    dyadiclevel2tl, mirror, upsample, downsample, wcount, testfunction)
-from .transforms import (dwt, idwt, dwt_, idwt_, dwt_oop_, idwt_oop_, dwtc, idwtc, dwtc_, idwtc_, wpt, iwpt, wpt_, iwpt_, dwt_batch, idwt_batch, wpt_batch, iwpt_batch,
+from .transforms import (dwt, idwt, dwt_, idwt_, dwt_oop_, idwt_oop_, dwtc, idwtc, dwtc_, idwtc_, wpt, iwpt, wpt_, iwpt_, wpt2, iwpt2, wpt2_, iwpt2_, dwt_batch, idwt_batch, wpt_batch, iwpt_batch,
                          to_device, to_host, similar, julia_layout, is_julia_layout, complex_split, complex_merge, set_complex_arrays, get_complex_arrays, complex_arrays,
                          reserve_workspace, workspace_held, set_kernel_path, last_kernel, destroy_contexts, set_option, clear_options, options, set_arithmetic, get_arithmetic, arithmetic,
                          DimensionMismatch, ArgumentError, HIPError)
@@ -44,4 +44,5 @@ __all__ = [
     "denoise_batch", "noisest_batch", "mad_batch_", "denoise_ti_batch", "threshold_batch", "threshold_batch_",
     "Entropy", "ShannonEntropy", "LogEnergyEntropy", "coefentropy", "bestbasistree", "bestbasistree_batch",
     "matchingpursuit", "findmaxabs",
+    "wpt2", "iwpt2", "wpt2_", "iwpt2_", "maketree2", "isvalidtree2",
 ]

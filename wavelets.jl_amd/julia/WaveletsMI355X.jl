@@ -450,6 +450,7 @@ include("WaveletsMI355X_bestbasis_batch.jl")
 include("WaveletsMI355X_modwt_batch.jl")
 include("WaveletsMI355X_threshold_batch.jl")
 include("WaveletsMI355X_matchingpursuit.jl")
+include("WaveletsMI355X_wpt2.jl")
 include("WaveletsMI355X_modwt_mra.jl")
 
 end # module

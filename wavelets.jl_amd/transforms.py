@@ -760,6 +760,88 @@ def iwpt_(*args) -> torch.Tensor:
     return _xwpt_inplace(args, False)
 
 
+# ---- wavelet packet transforms of images (quadtrees) ------------------------
+def _wpt2_args(fname, x, wt, L_or_tree):
+    """Every argument rule of wpt2 / iwpt2 that needs no device, in the order TypeError, ArgumentError; returns the
+    depth of the full quadtree (an int) or the quadtree (a uint8 array)."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("expected a torch tensor resident on an MI355X device (use to_device(array)); there is no CPU path")
+    if not isinstance(wt, OrthoFilter):
+        raise TypeError(f"{fname} takes an OrthoFilter (lifting schemes are not supported)")
+    if x.dim() != 2:
+        raise TypeError(f"{fname} is defined for matrices only")
+    if x.dtype.is_complex:
+        raise TypeError(f"{fname} is not defined for complex arrays")
+    shape = tuple(int(s) for s in x.shape)
+    if L_or_tree is None:
+        return Util.maxtransformlevels(x)
+    if isinstance(L_or_tree, (int, np.integer)) and not isinstance(L_or_tree, (bool, np.bool_)):
+        L = int(L_or_tree)
+        if L < 0:
+            raise ArgumentError("L must be positive")
+        if not Util.sufficientpoweroftwo(shape, L):
+            raise ArgumentError("size must have a sufficient power of 2 factor")
+        return L
+    t = np.asarray(L_or_tree)
+    if t.dtype == np.bool_:
+        t = t.view(np.uint8)
+    elif t.dtype != np.uint8:
+        raise TypeError(f"{fname}: a quadtree is a uint8 or bool vector (maketree2)")
+    t = np.ascontiguousarray(t)
+    if not Util.isvalidtree2(shape, t):
+        raise ArgumentError("invalid tree")
+    return t
+
+
+def _wpt2_call(y, x, filt, tree, fw):
+    _check_pair(y, x)
+    if y is x or y.data_ptr() == x.data_ptr():
+        raise ArgumentError("in array is out array")
+    lib = _lib.load()
+    h, st = _context(x.device)
+    q = np.ascontiguousarray(filt.qmf, dtype=np.float64)
+    dims = (C.c_int64 * 2)(int(x.shape[0]), int(x.shape[1]))
+    if isinstance(tree, np.ndarray):
+        rc = lib.wl_wpt2_filter(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), dims, _f64p(q), len(q),
+                                tree.ctypes.data_as(C.POINTER(C.c_uint8)), len(tree), 1 if fw else 0, st)
+    else:
+        rc = lib.wl_wpt2_filter_full(h, _dtype_code(x), C.c_void_p(y.data_ptr()), C.c_void_p(x.data_ptr()), dims, _f64p(q), len(q),
+                                     int(tree), 1 if fw else 0, st)
+    _check(rc, h)
+    return y
+
+
+def _xwpt2(fname, x, wt, L_or_tree, fw, y=None):
+    tree = _wpt2_args(fname, x, wt, L_or_tree)
+    if y is None:
+        x = _prep_in(x, maxdim=2)
+        y = similar(x)
+    elif not isinstance(y, torch.Tensor):
+        raise TypeError("expected a torch tensor resident on the GPU")
+    elif tuple(y.shape) != tuple(x.shape):
+        raise DimensionMismatch("in and out array size must match")
+    return _wpt2_call(y, x, wt, tree, fw)
+
+
+def wpt2(x, wt, L_or_tree=None) -> torch.Tensor:
+    """wpt2(x, wt[, L | tree]): the 2-D wavelet packet transform of an image over a quadtree (maketree2).  An integer
+    (default maxtransformlevels(x)) is the full quadtree of that depth, which is never materialised."""
+    return _xwpt2("wpt2", x, wt, L_or_tree, True)
+
+
+def iwpt2(x, wt, L_or_tree=None) -> torch.Tensor:
+    return _xwpt2("iwpt2", x, wt, L_or_tree, False)
+
+
+def wpt2_(y, x, wt, L_or_tree=None) -> torch.Tensor:
+    """wpt2!(y, x, filter[, L | tree]): into the caller's y (out of place: y is not x)"""
+    return _xwpt2("wpt2", x, wt, L_or_tree, True, y)
+
+
+def iwpt2_(y, x, wt, L_or_tree=None) -> torch.Tensor:
+    return _xwpt2("iwpt2", x, wt, L_or_tree, False, y)
+
+
 # ---- a batch of signals through one packet tree ---------------------------------------------------
 def _xwpt_batch(x, wt, tree_or_L, fw, y, fname, L=None):
     """x: len x B (column-major: unit i = x[:, i]); every column gets the packet transform of the one shared tree, all columns in

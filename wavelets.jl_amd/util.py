@@ -93,6 +93,57 @@ def isvalidtree(x, b) -> bool:
     return True
 
 
+# ---- quadtrees of images (wpt2 / iwpt2; the reference has no 2-D packet tree) ---------
+def _shape2(x_or_shape):
+    shape = tuple(int(s) for s in (x_or_shape.shape if hasattr(x_or_shape, "shape") else x_or_shape))
+    if len(shape) != 2:
+        raise ValueError("a quadtree belongs to a 2-D array")
+    return shape
+
+
+def _quadtreesize(L: int) -> int:
+    """nodes of a quadtree of depth bound L: (4^L - 1) / 3"""
+    return (4 ** int(L) - 1) // 3
+
+
+def maketree2(n0: int, n1: int, L: int = None, kind: str = "full") -> np.ndarray:
+    """The quadtree of an n0 x n1 image as a uint8 vector in breadth-first order: node k has the children 4k + 1 + c,
+    c = ci + 2 cj (ci = 1: the lower half of dimension 0, cj = 1: the right half of dimension 1); (4^L - 1) / 3 nodes.
+    "full": every node splits; "dwt": only child 0 of every depth splits (the Mallat pyramid of dwt(x, wt, L))."""
+    ns = min(maxtransformlevels(int(n0)), maxtransformlevels(int(n1)))
+    if L is None:
+        L = ns
+    L = int(L)
+    assert 0 <= L <= ns
+    b = np.zeros(_quadtreesize(L), dtype=np.uint8)
+    if kind == "full":
+        b[:] = 1
+    elif kind == "dwt":
+        for d in range(L):
+            b[_quadtreesize(d)] = 1
+    else:
+        raise ValueError("uknown symbol")
+    return b
+
+
+def isvalidtree2(x_or_shape, tree) -> bool:
+    """(4^L - 1) / 3 nodes for an L >= 0 with both extents divisible by 2^L, and no set node below a clear one"""
+    n0, n1 = _shape2(x_or_shape)
+    b = np.asarray(tree)
+    if b.ndim != 1:
+        return False
+    L = 0
+    while _quadtreesize(L) < len(b):
+        L += 1
+    if _quadtreesize(L) != len(b) or not sufficientpoweroftwo((n0, n1), L) or min(n0, n1) < 1:
+        return False
+    if len(b) > 1:
+        k = np.arange(1, len(b))
+        if np.any((b[k] != 0) & (b[(k - 1) // 4] == 0)):
+            return False
+    return True
+
+
 # ---- dyadic indexing (dyadic.jl:3-20; 1-based indices / ranges as in the reference) ---------------------
 def dyadicdetailindex(j: int, i: int) -> int:
     return 2 ** j + i
