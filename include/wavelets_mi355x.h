@@ -41,6 +41,12 @@
  *    agrees with the reference to ||y - ref||_2 / ||ref||_2 <= 1e-6 sqrt(L) (Float32),
  *    1e-13 sqrt(L) (Float64) instead of bit for bit.  A host selects it by loading
  *    that file; neither library ever falls back on the other.
+ *    Special values follow the reference too (subnormals are kept, Inf and NaN appear
+ *    where its summation order puts them), with two exemptions: NaN payloads are not
+ *    preserved by the transforms, and the sign of a zero result is unspecified for the
+ *    inverse filter-bank kernels and wl_modwt_mra_batch (they may give -0 where the
+ *    reference's up-sampling loop gives +0; the kernels are listed in DESIGN.md
+ *    section 23).
  *  - There is no CPU fallback: without a gfx950 device every entry point that needs
  *    one returns WL_EHIP / WL_ENODEVICE.
  */
