@@ -483,19 +483,20 @@ def test_long_filter_single_pass_2d_kernel(gpu, W, oracle, wmain, tj):
 
 @pytest.mark.parametrize("dtype,wmain,tp", [(np.float32, 1, 8), (np.float32, 1, 20), (np.float32, 1, 64), (np.float32, 2, 8), (np.float32, 2, 20),
                                             (np.float32, 2, 64), (np.float32, 4, 8), (np.float32, 4, 20), (np.float32, 4, 64),
-                                            (np.float64, 1, 8), (np.float64, 1, 20), (np.float64, 2, 64), (np.float64, 4, 20)])
+                                            (np.float64, 1, 8), (np.float64, 1, 20), (np.float64, 2, 64), (np.float64, 4, 20),
+                                            (np.float32, 1, 40), (np.float32, 2, 40), (np.float32, 4, 40), (np.float64, 2, 40)])
 def test_long_filter_single_pass_2d_inverse_kernel(gpu, W, oracle, dtype, wmain, tp):
     """k_inv2d_lds_long (wl_inv2d_long.hip, round 4): ONE pass per 2-D inverse level -- 12..20 taps in Float32, 8..20 taps in
     Float64, and (enabled here) 8 / 10 taps in Float32 -- LDS exchange of the raw columns incl. the halo pairs that ride on
     wave 0, rings rounded up to a multiple of the request distance D, exit-guarded steps (chunk lengths that are not a multiple
     of the ring), strips of 256 W output rows, every filter length, odd / even depths, non-square blocks, a single strip (the
-    halo wraps onto the strip itself), short last chunks, D = 1 ... 4 -- bit for bit against the oracle; the other tiers give the
-    same bits."""
+    halo wraps onto the strip itself), short last chunks, D = 1 ... 4 (tp = 40: D = 3, the default request distance above 10 taps, with
+    two pairs per lane: the instance of the large default calls) -- bit for bit against the oracle; the other tiers give the same bits."""
     W.set_option("WL_INVLONG_W", wmain)
     W.set_option("WL_INVLONG_TP", tp)
     W.set_option("WL_TILE_INV_LONG", 0)              # (round 5: the small blocks would otherwise take the two-level inverse tiles, own test below)
-    W.set_option("WL_INVLONG_D", {8: 1, 20: 2, 64: 4}[tp])
-    W.set_option("WL_INVLONG_PPL", {8: 2, 20: 1, 64: 0}[tp])       # pairs per lane: forced 2, forced 1 (Float32, W = 1), by size
+    W.set_option("WL_INVLONG_D", {8: 1, 20: 2, 64: 4, 40: 3}[tp])
+    W.set_option("WL_INVLONG_PPL", {8: 2, 20: 1, 64: 0, 40: 2}[tp])       # pairs per lane: forced 2, forced 1 (Float32, W = 1), by size
     W.set_option("WL_INVLONG_WAVES_PER_CU", 0)
     W.set_option("WL_INVLONG2D_MIN_ROWS", 256)
     W.set_option("WL_INVLONG_FMIN", 8)
