@@ -23,23 +23,15 @@
 //
 // Rounding follows the reference exactly: an element whose operands do not wrap is updated as
 // x += (c1*a + c2*b [+ c3*c]) (lift_inbounds!, transforms_lifting.jl:455-483), a wrapped one as
-// x += c1*a; x += c2*b; ... (lift_perboundary!, :437-451); no FMA contraction.
+// x += c1*a; x += c2*b; ... (lift_perboundary!, :437-451); no FMA contraction.  The line tails (reg_line_steps) take the two
+// forms from lift_update (wl_lift_dev.h); the streaming, cascade, short-line, gtile and any-scheme kernels spell them out.
 #include "wl_fast.h"
 #include "wl_lift_shapes.h"
 #include "wl_dev.h"
+#include "wl_lift_dev.h"
 
 
 namespace wl {
-
-__device__ __forceinline__ int l_dpp_next(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xf, 0xf, false); }
-__device__ __forceinline__ int l_dpp_prev(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, false); }
-__device__ __forceinline__ int l_dpp_partner(int v) { return __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false); }   // quad_perm [1,0,3,2]
-__device__ __forceinline__ float l_partner(float v) { return __int_as_float(l_dpp_partner(__float_as_int(v))); }
-__device__ __forceinline__ double l_partner(double v) { return __hiloint2double(l_dpp_partner(__double2hiint(v)), l_dpp_partner(__double2loint(v))); }
-__device__ __forceinline__ float l_next(float v) { return __int_as_float(l_dpp_next(__float_as_int(v))); }
-__device__ __forceinline__ float l_prev(float v) { return __int_as_float(l_dpp_prev(__float_as_int(v))); }
-__device__ __forceinline__ double l_next(double v) { return __hiloint2double(l_dpp_next(__double2hiint(v)), l_dpp_next(__double2loint(v))); }
-__device__ __forceinline__ double l_prev(double v) { return __hiloint2double(l_dpp_prev(__double2hiint(v)), l_dpp_prev(__double2loint(v))); }
 
 template <typename T>
 struct Lift1DArgs {
@@ -53,58 +45,6 @@ struct Lift1DArgs {
     int64_t ntiles;
     LiftCoefs<T> cf;
 };
-
-template <typename T>
-__device__ __forceinline__ void ld8(const T *p, T (&v)[8])
-{
-    constexpr int C = 16 / sizeof(T);
-    typedef T V __attribute__((ext_vector_type(C)));
-#pragma unroll
-    for (int c = 0; c < 8 / C; ++c) {
-        V t = *reinterpret_cast<const V *>(p + c * C);
-#pragma unroll
-        for (int i = 0; i < C; ++i) v[c * C + i] = t[i];
-    }
-}
-template <typename T, int N>
-__device__ __forceinline__ void stN(T *p, const T (&v)[N])
-{
-    constexpr int C = 16 / sizeof(T);
-    typedef T V __attribute__((ext_vector_type(C)));
-#pragma unroll
-    for (int c = 0; c < N / C; ++c) {
-        V t;
-#pragma unroll
-        for (int i = 0; i < C; ++i) t[i] = v[c * C + i];
-        *reinterpret_cast<V *>(p + c * C) = t;
-    }
-}
-
-template <typename T, int N>
-__device__ __forceinline__ void ldv_l(const T *p, T (&v)[N])
-{
-    constexpr int C = ((int)(16 / sizeof(T)) < N) ? (int)(16 / sizeof(T)) : N;
-    typedef T V __attribute__((ext_vector_type(C)));
-#pragma unroll
-    for (int c = 0; c < N / C; ++c) {
-        V t = *reinterpret_cast<const V *>(p + c * C);
-#pragma unroll
-        for (int i = 0; i < C; ++i) v[c * C + i] = t[i];
-    }
-}
-template <typename T, int N>
-__device__ __forceinline__ void stv_l(T *p, const T (&v)[N])
-{
-    constexpr int C = ((int)(16 / sizeof(T)) < N) ? (int)(16 / sizeof(T)) : N;
-    typedef T V __attribute__((ext_vector_type(C)));
-#pragma unroll
-    for (int c = 0; c < N / C; ++c) {
-        V t;
-#pragma unroll
-        for (int i = 0; i < C; ++i) t[i] = v[c * C + i];
-        *reinterpret_cast<V *>(p + c * C) = t;
-    }
-}
 
 template <typename T, int ID, int FW>
 __global__ void __launch_bounds__(256) k_lift1d_stream(Lift1DArgs<T> a)
@@ -124,7 +64,7 @@ __global__ void __launch_bounds__(256) k_lift1d_stream(Lift1DArgs<T> a)
         T s[4], d[4];
         if (FW) {
             T v[8];
-            ld8<T>(a.a + line * a.a_ls + 2 * kw, v);
+            ldv_l<T, 8>(a.a + line * a.a_ls + 2 * kw, v);
 #pragma unroll
             for (int j = 0; j < 4; ++j) { s[j] = v[2 * j]; d[j] = v[2 * j + 1]; }      // Util.split!
         } else {
@@ -201,14 +141,14 @@ __global__ void __launch_bounds__(256) k_lift1d_stream(Lift1DArgs<T> a)
 #pragma unroll
             for (int j = 0; j < 4; ++j) { so[j] = s[j] * a.cf.norm1; dO[j] = d[j] * a.cf.norm2; }     // normalize!
             if (valid) {
-                stN<T, 4>(a.o0 + line * a.o0_ls + k0, so);
-                stN<T, 4>(a.o1 + line * a.o1_ls + k0, dO);
+                stv_l<T, 4>(a.o0 + line * a.o0_ls + k0, so);
+                stv_l<T, 4>(a.o1 + line * a.o1_ls + k0, dO);
             }
         } else {
             T v[8];
 #pragma unroll
             for (int j = 0; j < 4; ++j) { v[2 * j] = s[j]; v[2 * j + 1] = d[j]; }               // Util.merge!
-            if (valid) stN<T, 8>(a.o0 + line * a.o0_ls + 2 * k0, v);
+            if (valid) stv_l<T, 8>(a.o0 + line * a.o0_ls + 2 * k0, v);
         }
     }
 }
@@ -532,18 +472,6 @@ __global__ void __launch_bounds__(1024) k_tail_lift(LiftTailArgs<T> a, LiftSchem
 // boundary of the reference, transforms_lifting.jl:437-451), and the next level's pairs (s[2i], s[2i+1]) are already in the
 // same lane.  Once a lane is down to one pair (64 pairs left) the line is finished with one sample per lane and
 // ds_bpermute gathers (six levels, 32 .. 1 pairs).  No LDS storage, no barrier.
-__device__ __forceinline__ int l_dpp_rol(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x134, 0xf, 0xf, false); }   // lane i <- lane i+1 (mod 64)
-__device__ __forceinline__ int l_dpp_ror(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x13C, 0xf, 0xf, false); }   // lane i <- lane i-1 (mod 64)
-__device__ __forceinline__ float l_rol(float v) { return __int_as_float(l_dpp_rol(__float_as_int(v))); }
-__device__ __forceinline__ float l_ror(float v) { return __int_as_float(l_dpp_ror(__float_as_int(v))); }
-__device__ __forceinline__ double l_rol(double v) { return __hiloint2double(l_dpp_rol(__double2hiint(v)), l_dpp_rol(__double2loint(v))); }
-__device__ __forceinline__ double l_ror(double v) { return __hiloint2double(l_dpp_ror(__double2hiint(v)), l_dpp_ror(__double2loint(v))); }
-__device__ __forceinline__ float l_gather(float v, int srclane) { return __int_as_float(__builtin_amdgcn_ds_bpermute(srclane << 2, __float_as_int(v))); }
-__device__ __forceinline__ double l_gather(double v, int srclane)
-{
-    return __hiloint2double(__builtin_amdgcn_ds_bpermute(srclane << 2, __double2hiint(v)), __builtin_amdgcn_ds_bpermute(srclane << 2, __double2loint(v)));
-}
-
 template <typename T, int PPL>
 __device__ __forceinline__ T lane_operand_rot(const T (&op)[PPL], int off)
 {
@@ -991,23 +919,40 @@ __device__ __forceinline__ void reg_line_steps(T (&s)[H], T (&d)[H], const T (&c
         for (int j = 0; j < H; ++j) {
             const int j0 = j - sh;
             const bool inb = (j0 >= 0) && (j0 + nc - 1 <= H - 1);
-            T x = upd ? d[j] : s[j];
-            if (inb) {
-                T acc = c[k][0] * (upd ? s[((j0 % H) + H) % H] : d[((j0 % H) + H) % H]);
-                if (nc > 1) acc = acc + c[k][1] * (upd ? s[(j0 + 1) % H] : d[(j0 + 1) % H]);
-                if (nc > 2) acc = acc + c[k][2] * (upd ? s[(j0 + 2) % H] : d[(j0 + 2) % H]);
-                x = x + acc;
-            } else {
+            T o[3] = {(T)0, (T)0, (T)0};                            // the wrap is decided at compile time, and so is the form
 #pragma unroll
-                for (int kk = 0; kk < 3; ++kk)
-                    if (kk < nc) {
-                        const int i = (((j0 + kk) % H) + H) % H;
-                        x = x + c[k][kk] * (upd ? s[i] : d[i]);
-                    }
-            }
+            for (int kk = 0; kk < 3; ++kk)
+                if (kk < nc) {
+                    const int i = (((j0 + kk) % H) + H) % H;
+                    o[kk] = upd ? s[i] : d[i];
+                }
+            const T x = lift_update<T>(upd ? d[j] : s[j], c[k], o, nc, inb);
             if (upd) d[j] = x; else s[j] = x;
         }
     }
+}
+// one pass over a line of 2 H samples held in LDS at q with stride st, by the thread that owns it, in place:
+// forward  split -> steps -> normalize  (samples interleaved -> s half, then d half)
+template <typename T, int ID, int H>
+__device__ __forceinline__ void line_pass_fwd(T *q, const int st, const LiftCoefs<T> &cf)
+{
+    T s[H], d[H];
+#pragma unroll
+    for (int k = 0; k < H; ++k) { s[k] = q[(2 * k) * st]; d[k] = q[(2 * k + 1) * st]; }
+    reg_line_steps<T, ID, H>(s, d, cf.c);
+#pragma unroll
+    for (int k = 0; k < H; ++k) { q[k * st] = s[k] * cf.norm1; q[(H + k) * st] = d[k] * cf.norm2; }
+}
+// inverse  normalize -> steps -> merge  (s half, d half -> samples interleaved)
+template <typename T, int ID, int H>
+__device__ __forceinline__ void line_pass_inv(T *q, const int st, const LiftCoefs<T> &cf)
+{
+    T s[H], d[H];
+#pragma unroll
+    for (int k = 0; k < H; ++k) { s[k] = cf.norm1 * q[k * st]; d[k] = cf.norm2 * q[(H + k) * st]; }
+    reg_line_steps<T, ID, H>(s, d, cf.c);
+#pragma unroll
+    for (int k = 0; k < H; ++k) { q[(2 * k) * st] = s[k]; q[(2 * k + 1) * st] = d[k]; }
 }
 __device__ __forceinline__ void reg_tail_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
@@ -1137,23 +1082,11 @@ __device__ __forceinline__ void tail2l_fwd_level(T *P, const LiftTailRegArgs<T> 
 {
     constexpr int H = M / 2, LD = MM + 1;
     if (tid < M) {                                   // rows (dim 2): the line of row tid runs along the columns
-        T s[H], d[H];
-        T *q = P + tid;
-#pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = q[(2 * k) * LD]; d[k] = q[(2 * k + 1) * LD]; }
-        reg_line_steps<T, ID, H>(s, d, a.cf.c);
-#pragma unroll
-        for (int k = 0; k < H; ++k) { q[k * LD] = s[k] * a.cf.norm1; q[(H + k) * LD] = d[k] * a.cf.norm2; }
+        line_pass_fwd<T, ID, H>(P + tid, LD, a.cf);
     }
     tail2l_barrier();
     if (tid < M) {                                   // columns (dim 1)
-        T s[H], d[H];
-        T *q = P + tid * LD;
-#pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = q[2 * k]; d[k] = q[2 * k + 1]; }
-        reg_line_steps<T, ID, H>(s, d, a.cf.c);
-#pragma unroll
-        for (int k = 0; k < H; ++k) { q[k] = s[k] * a.cf.norm1; q[H + k] = d[k] * a.cf.norm2; }
+        line_pass_fwd<T, ID, H>(P + tid * LD, 1, a.cf);
     }
     tail2l_barrier();
     for (int idx = tid; idx < M * M; idx += nthr) {
@@ -1178,23 +1111,11 @@ __device__ __forceinline__ void tail2l_inv_level(T *P, const LiftTailRegArgs<T> 
 {
     constexpr int H = M / 2, LD = MM + 1;
     if (tid < M) {                                   // columns (dim 1) first
-        T s[H], d[H];
-        T *q = P + tid * LD;
-#pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = a.cf.norm1 * q[k]; d[k] = a.cf.norm2 * q[H + k]; }
-        reg_line_steps<T, ID, H>(s, d, a.cf.c);
-#pragma unroll
-        for (int k = 0; k < H; ++k) { q[2 * k] = s[k]; q[2 * k + 1] = d[k]; }
+        line_pass_inv<T, ID, H>(P + tid * LD, 1, a.cf);
     }
     tail2l_barrier();
     if (tid < M) {                                   // rows (dim 2)
-        T s[H], d[H];
-        T *q = P + tid;
-#pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = a.cf.norm1 * q[k * LD]; d[k] = a.cf.norm2 * q[(H + k) * LD]; }
-        reg_line_steps<T, ID, H>(s, d, a.cf.c);
-#pragma unroll
-        for (int k = 0; k < H; ++k) { q[(2 * k) * LD] = s[k]; q[(2 * k + 1) * LD] = d[k]; }
+        line_pass_inv<T, ID, H>(P + tid, LD, a.cf);
     }
     tail2l_barrier();
 }
@@ -1281,35 +1202,17 @@ __device__ __forceinline__ void tail3_fwd_level(T *P, const LiftTail3Args<T> &a,
     const bool act = tid < M * M;
     // ---- planes: lines along dim 3 at (i, j) = (u, v) ----
     if (act) {
-        T s[H], d[H];
-        T *q = P + u + v * L1;
-#pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = q[(2 * k) * L2]; d[k] = q[(2 * k + 1) * L2]; }
-        reg_line_steps<T, ID, H>(s, d, a.cf.c);
-#pragma unroll
-        for (int k = 0; k < H; ++k) { q[k * L2] = s[k] * a.cf.norm1; q[(H + k) * L2] = d[k] * a.cf.norm2; }
+        line_pass_fwd<T, ID, H>(P + u + v * L1, L2, a.cf);
     }
     tail3_barrier();
     // ---- rows: lines along dim 2 at (i, k) = (u, v) ----
     if (act) {
-        T s[H], d[H];
-        T *q = P + u + v * L2;
-#pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = q[(2 * k) * L1]; d[k] = q[(2 * k + 1) * L1]; }
-        reg_line_steps<T, ID, H>(s, d, a.cf.c);
-#pragma unroll
-        for (int k = 0; k < H; ++k) { q[k * L1] = s[k] * a.cf.norm1; q[(H + k) * L1] = d[k] * a.cf.norm2; }
+        line_pass_fwd<T, ID, H>(P + u + v * L2, L1, a.cf);
     }
     tail3_barrier();
     // ---- columns: lines along dim 1 at (j, k) = (u, v) ----
     if (act) {
-        T s[H], d[H];
-        T *q = P + u * L1 + v * L2;
-#pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = q[2 * k]; d[k] = q[2 * k + 1]; }
-        reg_line_steps<T, ID, H>(s, d, a.cf.c);
-#pragma unroll
-        for (int k = 0; k < H; ++k) { q[k] = s[k] * a.cf.norm1; q[H + k] = d[k] * a.cf.norm2; }
+        line_pass_fwd<T, ID, H>(P + u * L1 + v * L2, 1, a.cf);
     }
     tail3_barrier();
     // the seven detail octants are final (the approximation octant too after the last level): lanes along dim 1
@@ -1338,33 +1241,15 @@ __device__ __forceinline__ void tail3_inv_level(T *P, const LiftTail3Args<T> &a,
     const int u = tid % M, v = tid / M;
     const bool act = tid < M * M;
     if (act) {
-        T s[H], d[H];
-        T *q = P + u * L1 + v * L2;
-#pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = a.cf.norm1 * q[k]; d[k] = a.cf.norm2 * q[H + k]; }
-        reg_line_steps<T, ID, H>(s, d, a.cf.c);
-#pragma unroll
-        for (int k = 0; k < H; ++k) { q[2 * k] = s[k]; q[2 * k + 1] = d[k]; }
+        line_pass_inv<T, ID, H>(P + u * L1 + v * L2, 1, a.cf);
     }
     tail3_barrier();
     if (act) {
-        T s[H], d[H];
-        T *q = P + u + v * L2;
-#pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = a.cf.norm1 * q[k * L1]; d[k] = a.cf.norm2 * q[(H + k) * L1]; }
-        reg_line_steps<T, ID, H>(s, d, a.cf.c);
-#pragma unroll
-        for (int k = 0; k < H; ++k) { q[(2 * k) * L1] = s[k]; q[(2 * k + 1) * L1] = d[k]; }
+        line_pass_inv<T, ID, H>(P + u + v * L2, L1, a.cf);
     }
     tail3_barrier();
     if (act) {
-        T s[H], d[H];
-        T *q = P + u + v * L1;
-#pragma unroll
-        for (int k = 0; k < H; ++k) { s[k] = a.cf.norm1 * q[k * L2]; d[k] = a.cf.norm2 * q[(H + k) * L2]; }
-        reg_line_steps<T, ID, H>(s, d, a.cf.c);
-#pragma unroll
-        for (int k = 0; k < H; ++k) { q[(2 * k) * L2] = s[k]; q[(2 * k + 1) * L2] = d[k]; }
+        line_pass_inv<T, ID, H>(P + u + v * L1, L2, a.cf);
     }
     tail3_barrier();
 }

@@ -7,12 +7,12 @@
 // wrap resolved while staging), then each pass gives a thread a short open line segment -- 16 or 8 owned (s, d) pairs plus the
 // cone -- which it runs through split -> steps -> normalize (or normalize -> steps -> merge) in registers as straight-line code;
 // cone pairs are recomputed by the neighbouring segment instead of exchanged, so a pass costs two barriers and no step does.
-// Rounding follows the reference: a pair whose operands do not wrap around the ends of the WHOLE line takes the in-bounds form
-// x += (c1*a + c2*b), the others x += c1*a; x += c2*b (transforms_lifting.jl:437-483); which one depends on the global pair
-// index only (a per-lane select, both forms share their products).
+// Rounding follows the reference (lift_update, wl_lift_dev.h): which summation form a pair takes depends only on whether its
+// operands wrap around the ends of the WHOLE line, i.e. on its global pair index.
 #include "wl_fast.h"
 #include "wl_lift_shapes.h"
 #include "wl_dev.h"
+#include "wl_lift_dev.h"
 
 namespace wl {
 
@@ -63,17 +63,11 @@ __device__ __forceinline__ void seg_line_steps_v(T (&s)[NP], T (&d)[NP], const T
             int jg = kg0 + j;
             if (jg >= half) jg -= half;
             const bool inb = (jg - sh >= 0) && (jg - sh + nc - 1 <= half - 1);
-            const T x = upd ? d[j] : s[j];
-            const T o0 = upd ? s[j0] : d[j0];
-            const T o1 = (nc > 1) ? (upd ? s[(j0 + 1 < NP) ? j0 + 1 : j0] : d[(j0 + 1 < NP) ? j0 + 1 : j0]) : (T)0;
-            const T o2 = (nc > 2) ? (upd ? s[(j0 + 2 < NP) ? j0 + 2 : j0] : d[(j0 + 2 < NP) ? j0 + 2 : j0]) : (T)0;
-            const T m0 = c[k][0] * o0;
-            T acc = m0;
-            T xb = x + m0;
-            if (nc > 1) { const T m1 = c[k][1] * o1; acc = acc + m1; xb = xb + m1; }
-            if (nc > 2) { const T m2 = c[k][2] * o2; acc = acc + m2; xb = xb + m2; }
-            const T xin = x + acc;
-            const T r = FAST ? xin : (inb ? xin : xb);
+            T o[3] = {(T)0, (T)0, (T)0};                          // (j0 + nc - 1 <= NP - 1 by the test above: no clamp needed)
+#pragma unroll
+            for (int kk = 0; kk < 3; ++kk)
+                if (kk < nc) o[kk] = upd ? s[j0 + kk] : d[j0 + kk];
+            const T r = lift_update<T, FAST>(upd ? d[j] : s[j], c[k], o, nc, inb);
             if (upd) d[j] = r; else s[j] = r;
         }
     }
