@@ -6,7 +6,8 @@
 The traced script separates its calls by fills of a marker tensor; the library's kernels (namespace wl) dispatched between
 fill k and fill k + 1 are the launches of call k.  Markdown rows: call, launches, kernels in dispatch order.  --all counts every
 kernel between the fills (the callers around the hot path live outside namespace wl, and a host loop adds torch's own kernels),
-runs of one kernel folded to `name x count`.
+runs of one kernel folded to `name x count`.  --instances keeps each launch's template arguments, grid size and workgroup size
+(`k_fwd2d_tile<float, 8, 2> 4096x1x1/256x1x1`): two builds that dispatch alike give identical tables (tools/dispatch_cases.py).
 """
 import csv
 import glob
@@ -15,7 +16,11 @@ import re
 import sys
 
 
-def main(trace_dir, calls_txt, every=False):
+def _geometry(r):
+    return "x".join(r.get("Grid_Size_" + a, "?") for a in "XYZ") + "/" + "x".join(r.get("Workgroup_Size_" + a, "?") for a in "XYZ")
+
+
+def main(trace_dir, calls_txt, every=False, instances=False):
     files = glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True)
     if not files:
         sys.exit("no *kernel_trace.csv under " + trace_dir)
@@ -23,19 +28,21 @@ def main(trace_dir, calls_txt, every=False):
     for f in files:
         with open(f, newline="") as fh:
             for r in csv.DictReader(fh):
-                rows.append((int(r["Start_Timestamp"]), r["Kernel_Name"]))
+                rows.append((int(r["Start_Timestamp"]), r["Kernel_Name"], _geometry(r)))
     rows.sort()
     labels = [m.group(2) for m in (re.match(r"call (\d+): (.*)", l) for l in open(calls_txt)) if m]
-    fills = [i for i, (_, name) in enumerate(rows) if "FillFunctor" in name]
+    fills = [i for i, (_, name, _g) in enumerate(rows) if "FillFunctor" in name]
     fills = fills[-(len(labels) + 1):]                       # (the marker tensor's own zero fill comes first)
     if len(fills) != len(labels) + 1:
         sys.exit("found %d marker fills for %d calls" % (len(fills), len(labels)))
     print("| call | launches | kernels |")
     print("|---|---|---|")
     for k, label in enumerate(labels):
-        names = [re.sub(r"^void ", "", re.sub(r"\(.*$", "", n.replace("(anonymous namespace)::", ""))) for _, n in rows[fills[k] + 1:fills[k + 1]]
-                 if every or "wl::" in n]
+        mine = [(n, g) for _, n, g in rows[fills[k] + 1:fills[k + 1]] if every or "wl::" in n]
+        names = [re.sub(r"^void ", "", re.sub(r"\(.*$", "", n.replace("(anonymous namespace)::", ""))) for n, _ in mine]
         short = [re.sub(r"<.*$", "", n.split("wl::")[-1]) for n in names]
+        if instances:        # (the parameter list is cut at the first parenthesis: casts inside template arguments do not occur in this library)
+            short = [n.replace("wl::", "") + " " + g for n, (_, g) in zip(names, mine)]
         if every:
             folded = []
             for n in short:
@@ -48,4 +55,4 @@ def main(trace_dir, calls_txt, every=False):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2], "--all" in sys.argv[3:])
+    main(sys.argv[1], sys.argv[2], "--all" in sys.argv[3:], "--instances" in sys.argv[3:])

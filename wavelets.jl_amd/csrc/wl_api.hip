@@ -812,7 +812,6 @@ static int wpt_impl(wl_ctx *ctx, hipStream_t st, T *y, const T *x, const WptCall
     }
     // the packet kernels (k_wpt_fwd_multi / _inv_multi / _tail) move 16-byte vectors straight on x, y and the work buffer: a view that
     // starts 4 or 8 bytes off the grid (buf[1:1+n]) takes the per-depth kernels, which gate on alignment themselves
-    auto al16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     const bool fast_any = (ctx->path == 0) && opt("WL_WPT_FAST", 1) != 0;          // the lifting line kernels check alignment themselves
     // (a batch: every unit base, that is the stride too -- NW is then a multiple of 16 bytes and so is T0's offset in the workspace)
     const bool fast = fast_any && al16(x) && al16(y) && al16(w.T0) && (nunits == 1 || (ustride * sizeof(T)) % 16 == 0);   // the filter-bank packet kernels

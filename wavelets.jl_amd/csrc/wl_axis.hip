@@ -394,7 +394,6 @@ static hipError_t launch_long(hipStream_t st, const Taps<T> &taps, LongArgs<T, F
 }
 
 // ---------------------------------------------------------------------------------------------------
-static inline bool a_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline bool short_ok(int64_t n) { return n >= 16 && n <= 512 && (n % 8) == 0 && (64 % (n / 8)) == 0; }
 
 template <typename T, int F, int FW>
@@ -440,16 +439,6 @@ static hipError_t launch_axis(hipStream_t st, const Taps<T> &taps, const T *src,
     return hipGetLastError();
 }
 
-#define WL_DISPATCH_FA(F_, ...)                              \
-    switch (F_) {                                            \
-    case 2: { constexpr int FF = 2; __VA_ARGS__; } break;    \
-    case 4: { constexpr int FF = 4; __VA_ARGS__; } break;    \
-    case 6: { constexpr int FF = 6; __VA_ARGS__; } break;    \
-    case 8: { constexpr int FF = 8; __VA_ARGS__; } break;    \
-    case 10: { constexpr int FF = 10; __VA_ARGS__; } break;  \
-    default: break;                                          \
-    }
-
 // Which kernel family fast3d_fwd_level takes for this level -- 0: none (not eligible), 1: k_fwd3d_one, 2: k_level3_lds, 3: the
 // single-axis passes.  The level loops of a batch of volumes (wl_batch3d.hip) ask before they launch: tiers 1 and 2 take every
 // volume in one launch.
@@ -467,8 +456,8 @@ int fast3d_fwd_tier(int F, const T *cur, int64_t c1, int64_t c2, const T *y, int
     if (level3_lds_ok<T>(F, n) && cur != y) return 2;
     const int64_t n0 = n[0], n1 = n[1], n2 = n[2];
     if ((F % 2) != 0 || F > 10 || !short_ok(n0) || n1 < 16 || n2 < 16 || (n1 % 16) != 0 || (n2 % 16) != 0 || c1 != n0 ||
-        (c2 % VEC) != 0 || (y1 % VEC) != 0 || (y2 % VEC) != 0 || !a_al16(cur) || !a_al16(y) || !a_al16(T0) || !a_al16(T1) ||
-        (ll && !a_al16(ll)) || n1 > 32767) {
+        (c2 % VEC) != 0 || (y1 % VEC) != 0 || (y2 % VEC) != 0 || !al16(cur) || !al16(y) || !al16(T0) || !al16(T1) ||
+        (ll && !al16(ll)) || n1 > 32767) {
         // not a shape of the axis kernels: the one-pass level from 2^19 elements, the LDS blocks up to 2^20, before the any-extent
         // kernels take it (three passes per level)
         if (fwd3d_one_ok<T>(F, cur, c1, c2, y, y1, y2, ll, n, true)) return 1;
@@ -498,8 +487,8 @@ bool fast3d_fwd_level(hipStream_t st, const Taps<T> &taps, const T *cur, int64_t
     }
     if (tier == 0) return false;
     const int64_t n0 = n[0], n1 = n[1], n2 = n[2], h0 = n0 >> 1, h1 = n1 >> 1, h2 = n2 >> 1;
-    bool ok = false;
-    WL_DISPATCH_FA(F, {
+    return dispatch_taps<2, 4, 6, 8, 10>(F, [&](auto ff) {
+        constexpr int FF = decltype(ff)::value;
         // An option, OFF by default (round 5, measured): the level in SLABS of output plane pairs -- the axis-3 pass of a slab writes
         // 2 * slab planes of T0 and the plane kernel consumes exactly those planes next, in the hope that the intermediate array stays
         // in the Infinity Cache instead of making a round trip through HBM.  512^3 db4 L = 9: whole-box passes 566 us; slabs of 64 / 32 /
@@ -533,8 +522,7 @@ bool fast3d_fwd_level(hipStream_t st, const Taps<T> &taps, const T *cur, int64_t
                         all = all && fwd2d_planes<T>(st, taps, T0 + h2 * P, y + h2 * y2, y1, y2, nullptr, n0, n1, d1 - h2, 0, cu_count, err);
                 }
                 if (!all && *err == hipSuccess) *err = hipErrorInvalidValue;   // (fwd2d_planes accepted this shape for the whole box below before)
-                ok = true;
-                break;
+                return;
             }
         }
         // planes: axis 3 on the (n0*n1) x n2 matrix
@@ -553,9 +541,7 @@ bool fast3d_fwd_level(hipStream_t st, const Taps<T> &taps, const T *cur, int64_t
             s.ll = ll; s.ll2 = h0; s.ll3 = h0 * h1; s.l2 = (int)h1; s.l3 = h2;
             *err = launch_short<T, FF, 1>(st, taps, s, (int)n0, (int)n1, n2);
         }
-        ok = true;
     });
-    return ok;
 }
 
 // (fast3d_inv_tier: the choice of fast3d_inv_level, as fast3d_fwd_tier)
@@ -570,8 +556,8 @@ int fast3d_inv_tier(int F, const T *x, int64_t x1, int64_t x2, const T *llsrc, c
     if (level3_lds_ok<T>(F, n) && x != out && llsrc != out) return 2;
     const int64_t n0 = n[0], n1 = n[1], n2 = n[2], h0 = n0 >> 1;
     if ((F % 2) != 0 || F > 10 || !short_ok(n0) || n1 < 16 || n2 < 16 || (n1 % 16) != 0 || (n2 % 16) != 0 || o1 != n0 ||
-        (o2 % VEC) != 0 || (x1 % VEC) != 0 || (x2 % VEC) != 0 || !a_al16(x) || !a_al16(out) || !a_al16(T0) || !a_al16(T1) ||
-        (llsrc && !a_al16(llsrc)) || n1 > 32767 || (h0 % 4) != 0) {
+        (o2 % VEC) != 0 || (x1 % VEC) != 0 || (x2 % VEC) != 0 || !al16(x) || !al16(out) || !al16(T0) || !al16(T1) ||
+        (llsrc && !al16(llsrc)) || n1 > 32767 || (h0 % 4) != 0) {
         if (inv3d_one_ok<T>(F, x, x1, x2, llsrc, out, o1, o2, n, true)) return 1;
         if (level3_lds_ok<T>(F, n, true) && x != out && llsrc != out) return 2;
         return 0;
@@ -599,8 +585,8 @@ bool fast3d_inv_level(hipStream_t st, const Taps<T> &taps, const T *x, int64_t x
     }
     if (tier == 0) return false;
     const int64_t n0 = n[0], n1 = n[1], n2 = n[2], h0 = n0 >> 1, h1 = n1 >> 1, h2 = n2 >> 1;
-    bool ok = false;
-    WL_DISPATCH_FA(F, {
+    return dispatch_taps<2, 4, 6, 8, 10>(F, [&](auto ff) {
+        constexpr int FF = decltype(ff)::value;
         // columns + rows of every plane in ONE launch when the planes are big enough for the fused 2-D inverse kernel
         bool planes = false;
         if (opt("WL_NO_PLANES", 0) == 0)
@@ -618,21 +604,12 @@ bool fast3d_inv_level(hipStream_t st, const Taps<T> &taps, const T *x, int64_t x
         if (!planes && *err == hipSuccess) *err = launch_axis<T, FF, 0>(st, taps, T0, n0, n0 * n1, T1, n0, n0 * n1, n0, n1, n2, cu_count);
         // planes: axis 3
         if (*err == hipSuccess) *err = launch_axis<T, FF, 0>(st, taps, T1, n0 * n1, 0, out, o2, 0, n0 * n1, n2, 1, cu_count);
-        ok = true;
     });
-    return ok;
 }
 
-#define WL_DISPATCH_FL(F_, ...)                              \
-    switch (F_) {                                            \
-    case 12: { constexpr int FF = 12; __VA_ARGS__; } break;  \
-    case 14: { constexpr int FF = 14; __VA_ARGS__; } break;  \
-    case 16: { constexpr int FF = 16; __VA_ARGS__; } break;  \
-    case 18: { constexpr int FF = 18; __VA_ARGS__; } break;  \
-    case 20: { constexpr int FF = 20; __VA_ARGS__; } break;  \
-    case 24: { constexpr int FF = 24; __VA_ARGS__; } break;  \
-    default: break;                                          \
-    }
+// the lengths of the ring kernels (ring_filter_ok)
+template <typename Fn>
+static bool dispatch_ring_taps(int F, Fn &&fn) { return dispatch_taps<12, 14, 16, 18, 20, 24>(F, fn); }
 
 static bool ring_filter_ok(int F) { return F == 12 || F == 14 || F == 16 || F == 18 || F == 20 || F == 24; }
 bool long_filter_ok(int F) { return ring_filter_ok(F) || vlong_filter_ok(F); }
@@ -650,21 +627,19 @@ bool long_lines_fwd_level(hipStream_t st, const Taps<T> &taps, const T *src, int
 {
     constexpr int VEC = 16 / sizeof(T);
     *err = hipSuccess;
-    if (!long_filter_ok(taps.F) || n < (vlong_filter_ok(taps.F) ? 16 : 512) || (n % 8) != 0 || !a_al16(src) || !a_al16(sdst) || !a_al16(ddst) ||
+    if (!long_filter_ok(taps.F) || n < (vlong_filter_ok(taps.F) ? 16 : 512) || (n % 8) != 0 || !al16(src) || !al16(sdst) || !al16(ddst) ||
         (nlines > 1 && ((src_ls % VEC) != 0 || (s_ls % VEC) != 0 || (d_ls % VEC) != 0)))
         return false;
     if (vlong_only(taps.F) || (vlong_filter_ok(taps.F) && n < 512)) {
         *err = vl_lines_fwd<T>(st, taps, src, src_ls, sdst, s_ls, ddst, d_ls, n, nlines);
         return true;
     }
-    bool ok = false;
-    WL_DISPATCH_FL(taps.F, {
+    return dispatch_ring_taps(taps.F, [&](auto ff) {
+        constexpr int FF = decltype(ff)::value;
         LongArgs<T, FF> a;
         a.a = src; a.a_ls = src_ls; a.b = nullptr; a.b_ls = 0; a.o0 = sdst; a.o0_ls = s_ls; a.o1 = ddst; a.o1_ls = d_ls;
         *err = launch_long<T, FF, 1>(st, taps, a, n, nlines, cu_count);
-        ok = true;
     });
-    return ok;
 }
 template <typename T>
 bool long_lines_inv_level(hipStream_t st, const Taps<T> &taps, const T *ssrc, int64_t s_ls, const T *dsrc, int64_t d_ls,
@@ -672,21 +647,19 @@ bool long_lines_inv_level(hipStream_t st, const Taps<T> &taps, const T *ssrc, in
 {
     constexpr int VEC = 16 / sizeof(T);
     *err = hipSuccess;
-    if (!long_filter_ok(taps.F) || n < (vlong_filter_ok(taps.F) ? 16 : 512) || (n % 8) != 0 || !a_al16(ssrc) || !a_al16(dsrc) || !a_al16(dst) ||
+    if (!long_filter_ok(taps.F) || n < (vlong_filter_ok(taps.F) ? 16 : 512) || (n % 8) != 0 || !al16(ssrc) || !al16(dsrc) || !al16(dst) ||
         (nlines > 1 && ((s_ls % VEC) != 0 || (d_ls % VEC) != 0 || (o_ls % VEC) != 0)))
         return false;
     if (vlong_only(taps.F) || (vlong_filter_ok(taps.F) && n < 512)) {
         *err = vl_lines_inv<T>(st, taps, ssrc, s_ls, dsrc, d_ls, dst, o_ls, n, nlines);
         return true;
     }
-    bool ok = false;
-    WL_DISPATCH_FL(taps.F, {
+    return dispatch_ring_taps(taps.F, [&](auto ff) {
+        constexpr int FF = decltype(ff)::value;
         LongArgs<T, FF> a;
         a.a = ssrc; a.a_ls = s_ls; a.b = dsrc; a.b_ls = d_ls; a.o0 = dst; a.o0_ls = o_ls; a.o1 = nullptr; a.o1_ls = 0;
         *err = launch_long<T, FF, 0>(st, taps, a, n, nlines, cu_count);
-        ok = true;
     });
-    return ok;
 }
 // The strided-axis pass (dim 2 of a matrix of R contiguous rows x C columns) with a long filter.
 template <typename T>
@@ -696,19 +669,17 @@ bool long_axis_level(hipStream_t st, const Taps<T> &taps, int fw, const T *src, 
     constexpr int VEC = 16 / sizeof(T);
     *err = hipSuccess;
     if (!long_filter_ok(taps.F) || (C % (vlong_filter_ok(taps.F) ? 8 : 32)) != 0 || C < (vlong_filter_ok(taps.F) ? 16 : 32) || (R % VEC) != 0 || (lds % VEC) != 0 || (ldd % VEC) != 0 ||
-        !a_al16(src) || !a_al16(dst))
+        !al16(src) || !al16(dst))
         return false;
     if (vlong_only(taps.F) || (vlong_filter_ok(taps.F) && ((C % 32) != 0 || C < 32 || R < 512))) {
         *err = vl_axis<T>(st, taps, fw, src, lds, dst, ldd, R, C, cu_count);
         return true;
     }
-    bool ok = false;
-    WL_DISPATCH_FL(taps.F, {
+    return dispatch_ring_taps(taps.F, [&](auto ff) {
+        constexpr int FF = decltype(ff)::value;
         if (fw) *err = launch_axis<T, FF, 1>(st, taps, src, lds, 0, dst, ldd, 0, R, C, 1, cu_count);
         else *err = launch_axis<T, FF, 0>(st, taps, src, lds, 0, dst, ldd, 0, R, C, 1, cu_count);
-        ok = true;
     });
-    return ok;
 }
 #define WL_INST_LONG(T)                                                                                                          \
     template bool long_lines_fwd_level<T>(hipStream_t, const Taps<T> &, const T *, int64_t, T *, int64_t, T *, int64_t, int64_t, \

@@ -17,15 +17,13 @@ namespace wl {
 
 namespace {
 
-inline bool b_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // the single-volume loops, volume after volume
 template <typename T>
 bool loop_all(int path, int F, int64_t N, int64_t nvol, int64_t xs, int64_t ys, const T *x, const T *y)
 {
     constexpr int VEC = 16 / (int)sizeof(T);
     return opt("WL_BATCH3_LOOP", 0) != 0 || nvol == 1 || path != 0 || (F % 2) != 0 || F > 10 || (xs % VEC) != 0 || (ys % VEC) != 0 ||
-           ((N >> 3) % VEC) != 0 || !b_al16(x) || !b_al16(y);
+           ((N >> 3) % VEC) != 0 || !al16(x) || !al16(y);
 }
 
 inline BoxSpec volume_box(const int64_t dims[3])

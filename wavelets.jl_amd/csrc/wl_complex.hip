@@ -144,8 +144,6 @@ __global__ void __launch_bounds__(CPLX_THREADS) k_cplx_merge(T *__restrict__ z, 
     }
 }
 
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // workgroups per unit: one per 256 lanes of work, no more than keeps about 16 workgroups per CU in flight over all units
 inline unsigned cplx_blocks(int64_t n, int64_t per_lane, int64_t nu, int cu_count)
 {

@@ -2,9 +2,36 @@
 // the ABI layer (wl_api.hip) and by each other.  Every fast kernel must produce results bit-identical to the generic
 // kernels (wl_generic.hip).
 #pragma once
+#include <type_traits>
 #include "wl_internal.h"
 
 namespace wl {
+
+// The tap-count switch of the launchers whose kernels take the filter length as a template argument: calls
+// fn(std::integral_constant<int, Fi>{}) for the listed Fi that equals F and returns whether one did.  Every listed length is
+// instantiated; a length that is not listed declines (the caller's next tier takes the level).
+template <int... Fs, typename Fn>
+inline bool dispatch_taps(int F, Fn &&fn)
+{
+    return ((F == Fs ? (fn(std::integral_constant<int, Fs>{}), true) : false) || ...);
+}
+
+// What the level walks of wl_fwd.hip and wl_inv.hip (FwdWalk, InvWalk) share: where a failed launch reports, and the tap-count
+// switch of a tier -- fn(ff) launches with decltype(ff)::value taps and returns the launch's error.  with_taps: 1 launched, 0 F is
+// not instantiated (the tier declines), WL_EHIP the launch failed.
+struct WalkBase {
+    const int F;
+    int *const hip_err;
+    int fail(hipError_t e) const { if (hip_err) *hip_err = (int)e; return WL_EHIP; }
+    template <typename Fn>
+    int with_taps(Fn &&fn) const
+    {
+        hipError_t e = hipSuccess;
+        if (!dispatch_taps<2, 4, 6, 8, 10>(F, [&](auto ff) { e = fn(ff); })) return 0;
+        return e == hipSuccess ? 1 : fail(e);
+    }
+};
+#define WL_WALK_TRY(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) return fail(e__); } while (0)
 
 // Enqueue all L forward levels of a filter-bank transform.  path: 0 = pick the best kernel
 // per level (streaming kernels for large levels, one LDS-resident kernel for the tail,

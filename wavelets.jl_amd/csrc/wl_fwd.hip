@@ -1050,10 +1050,6 @@ static hipError_t set_max_lds_once(const void *fn, size_t bytes, unsigned char (
     if (e == hipSuccess) { done[dev] = 1; cur[dev] = bytes < 65536 ? 65536 : bytes; }
     return e;
 }
-// tuning / test switches: per-context options (wl_ctx_set_option), see wl_internal.h
-#define env_int(name, dflt) ((int)opt(name, dflt))
-#define env_int_raw(name, dflt) ((int)opt(name, dflt))
-
 template <typename T>
 constexpr int tail_cap() { return sizeof(T) == 4 ? 16384 : 8192; }     // block elements
 template <typename T>
@@ -1071,23 +1067,15 @@ static hipError_t launch_tail(hipStream_t st, const Taps<T> &taps, const T *src,
     const size_t shmem = 2 * (size_t)a.cap * sizeof(T);
     int64_t work = (int64_t)m0 * m1 / 2;
     int threads = work >= 4096 ? 1024 : (work >= 512 ? 256 : 64);
-#define WL_TAIL_LAUNCH(FC_)                                                                                   \
-    do {                                                                                                      \
-        static unsigned char done__[64]; static size_t cur__[64];                                             \
-        hipError_t e = set_max_lds_once(reinterpret_cast<const void *>(&k_tail_fwd<T, FC_>), 160 * 1024, done__, cur__); \
-        if (e != hipSuccess) return e;                                                                        \
-        hipLaunchKernelGGL((k_tail_fwd<T, FC_>), dim3((unsigned)nitems), dim3(threads), shmem, st, a, taps);  \
-    } while (0)
-    switch (taps.F) {
-    case 2: WL_TAIL_LAUNCH(2); break;
-    case 4: WL_TAIL_LAUNCH(4); break;
-    case 6: WL_TAIL_LAUNCH(6); break;
-    case 8: WL_TAIL_LAUNCH(8); break;
-    case 10: WL_TAIL_LAUNCH(10); break;
-    default: WL_TAIL_LAUNCH(0); break;
-    }
-#undef WL_TAIL_LAUNCH
-    return hipGetLastError();
+    hipError_t e = hipSuccess;
+    auto launch = [&](auto fc) {
+        constexpr int FC = decltype(fc)::value;
+        static unsigned char done__[64]; static size_t cur__[64];
+        e = set_max_lds_once(reinterpret_cast<const void *>(&k_tail_fwd<T, FC>), 160 * 1024, done__, cur__);
+        if (e == hipSuccess) hipLaunchKernelGGL((k_tail_fwd<T, FC>), dim3((unsigned)nitems), dim3(threads), shmem, st, a, taps);
+    };
+    if (!dispatch_taps<2, 4, 6, 8, 10>(taps.F, launch)) launch(std::integral_constant<int, 0>{});     // any other length: run-time taps
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 template <typename T, int F, int RPL>
@@ -1100,14 +1088,14 @@ static hipError_t launch_fwd2d_r(hipStream_t st, const Taps<T> &taps, bool lvl1,
     a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.ll = ll; a.ldll = ldll; a.ms = ms; a.ns = ns;
     a.bs_src = bs_src; a.bs_y = bs_y; a.bs_ll = bs_ll; a.nll = nll;
     a.nstrips = (int)((ms + VR - 1) / VR);
-    a.nt = (!lvl1 && env_int("WL_REVERSE", 1)) ? 4 : 0;
-    int TJ = env_int("WL_TJ", 128);
+    a.nt = (!lvl1 && iopt("WL_REVERSE", 1)) ? 4 : 0;
+    int TJ = iopt("WL_TJ", 128);
     // smaller levels: trade chunk length for parallelism (>= ~8 waves per CU while chunks stay >= 32
     // columns, >= 2 per CU down to 16 columns); every chunk length stays a multiple of 16
     auto nwaves = [&](int tj) { return (int64_t)a.nstrips * ((ns + tj - 1) / tj) * nbatch; };
-    const int wpc = env_int("WL_WAVES_PER_CU", 8);
+    const int wpc = iopt("WL_WAVES_PER_CU", 8);
     while (TJ > 32 && (TJ % 32) == 0 && nwaves(TJ) < (int64_t)cu_count * wpc) TJ >>= 1;
-    while (TJ > 16 && (TJ % 32) == 0 && nwaves(TJ) < (int64_t)cu_count * env_int("WL_WAVES_MIN", 8)) TJ >>= 1;
+    while (TJ > 16 && (TJ % 32) == 0 && nwaves(TJ) < (int64_t)cu_count * iopt("WL_WAVES_MIN", 8)) TJ >>= 1;
     a.TJ = TJ;
     a.nchunks = (int)((ns + TJ - 1) / TJ);
     a.tp = shrink<T, F>(taps);
@@ -1135,13 +1123,13 @@ static hipError_t launch_fwd2d_pair(hipStream_t st, const Taps<T> &taps, bool lv
     constexpr int VR = 52 * 4;
     a.src = src; a.lds = lds; a.y = y; a.ldy = ldy; a.ll = ll; a.ldll = ldll; a.ms = ms; a.ns = ns;
     a.nstrips = (int)((ms + VR - 1) / VR);
-    int TJ = env_int("WL_TJ2", 128);
+    int TJ = iopt("WL_TJ2", 128);
     auto nwaves = [&](int tj) { return (int64_t)a.nstrips * ((ns + tj - 1) / tj); };
-    const int wpc = env_int("WL_WAVES_PER_CU", 8);
+    const int wpc = iopt("WL_WAVES_PER_CU", 8);
     while (TJ > 32 && (TJ % 32) == 0 && nwaves(TJ) < (int64_t)cu_count * wpc) TJ >>= 1;
     a.TJ = TJ;
     a.nchunks = (int)((ns + TJ - 1) / TJ);
-    a.rev = (!lvl1 && env_int("WL_REVERSE", 1)) ? 1 : 0;
+    a.rev = (!lvl1 && iopt("WL_REVERSE", 1)) ? 1 : 0;
     a.tp = shrink<T, F>(taps);
     const unsigned nwg = (unsigned)(a.nstrips * a.nchunks);
     if (lvl1) hipLaunchKernelGGL((k_fwd2d_stream2<T, F, 1>), dim3(nwg), dim3(64), 0, st, a);
@@ -1161,7 +1149,7 @@ static hipError_t launch_fwd1d(hipStream_t st, const Taps<T> &taps, bool lvl1, c
     const int64_t cap = (int64_t)cu_count * 8;
     if (gx > cap) gx = cap;
     // gridDim.y is limited to 65535: launch in slabs of lines
-    const int64_t slab = (env_int_raw("WL_SLAB_LINES", 32768) > 0) ? env_int_raw("WL_SLAB_LINES", 32768) : 32768;
+    const int64_t slab = (iopt("WL_SLAB_LINES", 32768) > 0) ? iopt("WL_SLAB_LINES", 32768) : 32768;
     for (int64_t l0 = 0; l0 < nlines; l0 += slab) {
         const int64_t nl = (nlines - l0 < slab) ? (nlines - l0) : slab;
         Fwd1DArgs<T, F> b = a;
@@ -1181,7 +1169,7 @@ static hipError_t launch_fwd1d_multi(hipStream_t st, const Taps<T> &taps, bool l
     a.src = src; a.src_ls = src_ls; a.y = y; a.y_ls = y_ls; a.sdst = sdst; a.s_ls = s_ls; a.n = n; a.NL = NL;
     // tile = 32 KiB of input for long lines; shorter tiles (down to 4 KiB) when there would otherwise be
     // fewer workgroups than CUs -- a workgroup's latency chain (stage, NL levels, barriers) is ~constant
-    a.TS = env_int("WL_TS", 0);
+    a.TS = iopt("WL_TS", 0);
     if (a.TS < 256 || (a.TS % 64) != 0) {
         a.TS = (int)(16384 / sizeof(T));
         // Long lines: shave the tile so that level 1 -- TS / 2 + 2 H1 pairs, 256 threads x (16 / sizeof(T)) pairs per round -- takes
@@ -1191,7 +1179,7 @@ static hipError_t launch_fwd1d_multi(hipStream_t st, const Taps<T> &taps, bool l
         // the power of two (a partial last tile would be most of the work).
         const int H1 = (F - 2) * ((1 << (NL - 1)) - 1);
         const int fit = ((a.TS - 4 * H1) / 64) * 64;
-        if (env_int("WL_TS_FIT", 1) && n >= 8 * (int64_t)a.TS && fit >= a.TS / 2) a.TS = fit;
+        if (iopt("WL_TS_FIT", 1) && n >= 8 * (int64_t)a.TS && fit >= a.TS / 2) a.TS = fit;
     }
     while (a.TS > (int)(4096 / sizeof(T)) && ((n + a.TS - 1) / a.TS) * nlines < 512) a.TS >>= 1;
     a.tp = shrink<T, F>(taps);
@@ -1199,7 +1187,7 @@ static hipError_t launch_fwd1d_multi(hipStream_t st, const Taps<T> &taps, bool l
     const size_t elems = (size_t)((a.TS + 2 * H0 + 7) & ~7) + 16 + (size_t)(a.TS / 2 + 2 * H1 + 8) + 32;   // (+ room for the last groups' windows)
     const size_t shmem = elems * sizeof(T);
     const unsigned ntiles = (unsigned)((n + a.TS - 1) / a.TS);
-    const int64_t slab = (env_int_raw("WL_SLAB_LINES", 32768) > 0) ? env_int_raw("WL_SLAB_LINES", 32768) : 32768;
+    const int64_t slab = (iopt("WL_SLAB_LINES", 32768) > 0) ? iopt("WL_SLAB_LINES", 32768) : 32768;
     for (int64_t l0 = 0; l0 < nlines; l0 += slab) {
         const int64_t nl = (nlines - l0 < slab) ? (nlines - l0) : slab;
         Multi1DArgs<T, F> b = a;
@@ -1236,476 +1224,457 @@ static hipError_t launch_fwd2d_multi(hipStream_t st, const Taps<T> &taps, const 
     return hipGetLastError();
 }
 
-#define WL_DISPATCH_F(F_, ...)                               \
-    switch (F_) {                                            \
-    case 2: { constexpr int FF = 2; __VA_ARGS__; } break;    \
-    case 4: { constexpr int FF = 4; __VA_ARGS__; } break;    \
-    case 6: { constexpr int FF = 6; __VA_ARGS__; } break;    \
-    case 8: { constexpr int FF = 8; __VA_ARGS__; } break;    \
-    case 10: { constexpr int FF = 10; __VA_ARGS__; } break;  \
-    default: break;                                          \
+thread_local SrcView tl_srcview = {0, 0, 0, -1, 0.0, 0.0, nullptr, 0, 0};
+
+// ==========================================================================================
+// The forward level walk.  FwdWalk holds what every tier reads and what the level loop advances.  A tier is a member function that
+// returns the number of levels it enqueued (through took()), 0 when it declines the level -- the next tier of kFwdTiers is tried --
+// or a negative status: WL_EHIP (through fail()), WL_RETRY_GEN, WL_RETRY_NOVIEW, WL_EINVAL_ARG.
+
+template <typename T>
+struct FwdWalk : WalkBase {
+    static constexpr int VEC = 16 / sizeof(T);
+    // the call (lines: a 1-D vector or batched columns)
+    const BoxSpec &b; const Taps<T> &taps; const Work<T> w; hipStream_t st; int cu_count, path, L; T *y;
+    const bool fastF, two_d, lines; const int64_t nlines;
+    // longest line the one-workgroup tail takes.  Batches of many lines: one workgroup per line is only efficient for short lines;
+    // single lines: the latency-optimised tail (wl_tail.hip) takes 4096 samples.  Longer ones get a multi-level pass first.
+    const int64_t line_cap;
+    // the walk: level l (1-based) reads its box n from cur; pp picks the ping-pong buffer its approximation goes to; dominant is
+    // the first tier that ran
+    int l = 1; int64_t n[3] = {0, 0, 0}; const T *cur; Strides3 cur_st; int pp = 0; const char *dominant = nullptr;
+
+    FwdWalk(void *ws, bool ws_gen, int cu_count_, int path_, hipStream_t st_, const BoxSpec &b_, T *y_, const T *x, const Taps<T> &taps_,
+            int L_, int *hip_err_)
+        : WalkBase{taps_.F, hip_err_}, b(b_), taps(taps_), w(carve<T>(ws, b_.dims[0] * b_.dims[1] * b_.dims[2], b_.nt, ws_gen)), st(st_),
+          cu_count(cu_count_), path(path_), L(L_), y(y_), fastF((path_ == 0) && (F % 2 == 0) && (F <= 10)),
+          two_d(b_.nd == 2 && b_.nt == 2), lines(b_.nt == 1 && b_.nd <= 2), nlines(lines ? b_.dims[1] : 1),
+          line_cap((lines && nlines >= 32 && fastF) ? iopt("WL_TAIL_LINES_CAP", 512)
+                                                    : ((lines && fastF && iopt("WL_TAIL2", 1)) ? (int64_t)4096 : (int64_t)tail_cap<T>())),
+          cur(x), cur_st(b_.full) {}
+
+    int levels_left() const { return L - l + 1; }
+    bool last(int NL = 1) const { return l + NL - 1 == L; }       // a launch of NL levels ends the transform
+    T *llbuf() const { return pp ? w.B : w.A; }
+    T *ll_or_null() const { return last() ? (T *)nullptr : llbuf(); }
+    // where a launch of NL levels puts its approximation: y on the last level, else the ping-pong buffer (dense)
+    T *dst(int NL = 1) const { return last(NL) ? y : llbuf(); }
+    int64_t dst_ld(int NL = 1) const { return last(NL) ? b.full.s[1] : (n[0] >> NL); }
+    Strides3 ll_st(int NL = 1) const
+    {
+        const int64_t hn[3] = {n[0] >> NL, b.nt > 1 ? n[1] >> NL : n[1], b.nt > 2 ? n[2] >> NL : n[2]};
+        return dense_strides(hn);
+    }
+    // the 16-byte contract of the vector kernels: contiguous columns, leading dimensions in whole vectors, every base aligned
+    bool vec16() const
+    {
+        return cur_st.s[0] == 1 && (cur_st.s[1] % VEC) == 0 && al16(cur) && (b.full.s[1] % VEC) == 0 && al16(y) && al16(llbuf());
+    }
+    bool vec16_planes() const { return vec16() && (cur_st.s[2] % VEC) == 0 && (b.full.s[2] % VEC) == 0; }
+    // the epilogue of every tier: NL levels are enqueued and the next one reads their approximation from `from`, the ping-pong
+    // buffer they wrote; the next launch writes the other one
+    int took_from(T *from, int NL, const char *name)
+    {
+        if (!dominant) dominant = name;
+        cur = from; cur_st = ll_st(NL); pp = (from == w.A) ? 1 : 0;
+        return NL;
+    }
+    int took(int NL, const char *name) { return took_from(llbuf(), NL, name); }
+
+    // ---- the shifted source view of a translation-invariant batch (SrcView): only the two plane-batch tiers understand it ----
+    bool src_view() const { return l == 1 && tl_srcview.mod > 0; }      // level 1: virtual shifted planes
+    // ... whose launches also threshold the coefficients they store (every level that runs there, once level 1 did)
+    bool src_thresh() const
+    {
+        return tl_srcview.th >= 0 && (src_view() || (l > 1 && tl_srcview.used != 0 && tl_srcview.corner0 == n[0] && tl_srcview.corner1 == n[1]));
+    }
+    int took_view(bool view, bool thr, int NL, const char *name)
+    {
+        if (view) tl_srcview.used = 1;
+        if (thr) { tl_srcview.corner0 = last(NL) ? 0 : (n[0] >> NL); tl_srcview.corner1 = last(NL) ? 0 : (n[1] >> NL); }
+        return took(NL, name);
     }
 
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+    // ---- batch of independent 2-D blocks (box n0 x n1 x B, first two axes transformed: the shifted copies of a translation-invariant
+    //      denoise), planes over blockIdx.y: two levels per launch while the planes are big enough for the fused pair kernel to pay
+    //      (many planes keep the chip full where a single 2048^2 block would not) ----
+    int plane_pair()
+    {
+        if constexpr (sizeof(T) == 4) {
+            if (!(fastF && b.nd == 3 && b.nt == 2 && levels_left() >= 2 && iopt("WL_PAIR_BATCH", 1) != 0 && n[2] >= 2 && n[2] <= 65535 &&
+                  n[0] * n[1] >= (int64_t)iopt("WL_PAIR_BATCH_MIN", 1 << 22) && fwd2d_pair_ok(F, n[0], n[1]) && vec16_planes()))
+                return 0;
+            const bool view = src_view(), thr = src_thresh();
+            WL_WALK_TRY(fwd2d_pair_launch(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], last(2) ? (T *)nullptr : llbuf(), n[0] >> 2, n[0], n[1],
+                                     cu_count, n[2], cur_st.s[2], b.full.s[2], ll_st(2).s[2], view ? tl_srcview.mod : 0,
+                                     view ? tl_srcview.spin0 : 0, thr ? &tl_srcview : nullptr));
+            return took_view(view, thr, 2, "k_fwd2d_pair");
+        }
+        return 0;
+    }
+    // ---- ... else one launch of the LDS-exchange kernel per level ----
+    int plane_lds()
+    {
+        if constexpr (sizeof(T) == 4) {
+            if (!(fastF && b.nd == 3 && b.nt == 2 && fwd2d_lds_ok(F, 1, n[0], n[1]) && n[2] <= 65535 && vec16_planes())) return 0;
+            const bool view = src_view(), thr = src_thresh();
+            WL_WALK_TRY(fwd2d_lds_launch(st, taps, 1, l == 1, cur, cur_st.s[1], y, b.full.s[1], ll_or_null(), n[0] >> 1, n[0], n[1], cu_count, n[2],
+                                    cur_st.s[2], b.full.s[2], ll_st().s[2], (int)n[2], view ? tl_srcview.mod : 0, view ? tl_srcview.spin0 : 0,
+                                    thr ? &tl_srcview : nullptr));
+            return took_view(view, thr, 1, "k_fwd2d_lds");
+        }
+        return 0;
+    }
+    // a virtually shifted source is only valid for the two batch tiers above: anything else would read planes it does not hold
+    int view_guard() { return src_view() ? WL_RETRY_NOVIEW : 0; }
+    // ---- two levels of a block too big for one resident round of the staging tile kernel (2048 rows): tiles without staging ----
+    int tileB()
+    {
+        if constexpr (sizeof(T) == 4) {
+            if (!(fastF && two_d && iopt("WL_TILEB", 1) && levels_left() >= 2 && n[0] <= iopt("WL_TILEB_MAX", 2048) &&
+                  n[1] <= iopt("WL_TILEB_MAX", 2048) && n[0] * n[1] >= (int64_t)iopt("WL_TILEB_MIN", 1 << 21) && vec16() &&
+                  fwd2d_tile_ok(F, 2, n[0], n[1])))
+                return 0;
+            // tall tiles (256 x 64, one workgroup per CU) unless they would leave CUs idle that the 64 x 64 grid fills (blocks of 2^21
+            // elements: 128 tall tiles against 512; 2048 x 1024 two levels 8.0 us on 64 x 64 tiles, 8.7 on tall ones)
+            const int64_t tiles = (n[0] / 64) * (n[1] / 64);
+            const int tall = iopt("WL_TILEB_TALL", 1) != 0 && (n[0] % 256) == 0 && !(tiles / 4 < cu_count && tiles >= cu_count);
+            WL_WALK_TRY(fwd2d_tileB_launch(st, taps, cur, cur_st.s[1], y, b.full.s[1], dst(2), dst_ld(2), (int)n[0], (int)n[1], tall));
+            return took(2, "k_fwd2d_tileB");
+        }
+        return 0;
+    }
+    // ---- tile kernel: 1..3 fused levels of a cache-resident block (wl_tile.hip; Float64: up to 2 levels) ----
+    int tile()
+    {
+        auto al4 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) % (4 * sizeof(T))) == 0; };     // 4-element vectors
+        if (!(fastF && two_d && iopt("WL_TILE", 1) && n[0] <= iopt("WL_TILE_MAX", 1024) && n[1] <= iopt("WL_TILE_MAX", 1024) &&
+              cur_st.s[0] == 1 && (cur_st.s[1] % 4) == 0 && al4(cur) && (b.full.s[1] % 4) == 0 && al4(y) && al4(llbuf())))
+            return 0;
+        int NL = levels_left() > 3 ? 3 : levels_left();
+        const int64_t nmax = n[0] > n[1] ? n[0] : n[1];
+        // three levels per tile launch from 512^2 down (round 5, with the approximation handed over through L2: 2048^2 full depth 34.7 -> 32.2 us,
+        // 512^2 20.1 -> 17.7, 8192^2 -2 %; round 4 measured it 4 % slower and kept two)
+        if (NL == 3 && (nmax > iopt("WL_TILE_NL3_MAX", 512) || sizeof(T) == 8)) NL = 2;
+        while (NL > 1 && !fwd2d_tile_ok(F, NL, n[0], n[1])) --NL;
+        if (!fwd2d_tile_ok(F, NL, n[0], n[1])) return 0;
+        WL_WALK_TRY(fwd2d_tile_launch<T>(st, taps, NL, cur, cur_st.s[1], y, b.full.s[1], dst(NL), dst_ld(NL), (int)n[0], (int)n[1]));
+        return took(NL, "k_fwd2d_tile");
+    }
+    // ---- 12..20 taps, Float32, blocks of 128 .. 1024 rows: two levels per launch through the LDS tile kernel (round 5).  These
+    //      levels ran one streaming launch each (12-13 us apiece, short of workgroups) and the 128^2 level as two line passes:
+    //      8192^2 db6 246 -> 224 us, sym8 286 -> 261, db10 329 -> 303; 1024^2 sym8 full depth 60.5 -> 36.8, 512^2 48.5 -> 29.8.
+    //      Not above 1024 rows (2048^2: four rounds of one 512-thread workgroup per CU: sym8 8192^2 280 us, 4096^2 too: 356).
+    int tile_long()
+    {
+        if constexpr (sizeof(T) == 4) {
+            auto al4 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0; };
+            if (!(path == 0 && F >= 12 && F <= 20 && (F % 2) == 0 && two_d && iopt("WL_TILE_LONG", 1) && n[0] <= iopt("WL_TILE_LONG_MAX", 1024) &&
+                  n[1] <= iopt("WL_TILE_LONG_MAX", 1024) && cur_st.s[0] == 1 && (cur_st.s[1] % 4) == 0 && al4(cur) && (b.full.s[1] % 4) == 0 &&
+                  al4(y) && al4(llbuf()) && b.full.s[0] == 1))
+                return 0;
+            int NL = levels_left() >= 2 ? 2 : 1;
+            while (NL > 1 && !fwd2d_tile_ok(F, NL, n[0], n[1])) --NL;
+            // (a single remaining level of >= 256 rows stays with the streaming kernel below)
+            if (!(fwd2d_tile_ok(F, NL, n[0], n[1]) && (NL == 2 || n[0] < 256))) return 0;
+            WL_WALK_TRY(fwd2d_tile_launch<T>(st, taps, NL, cur, cur_st.s[1], y, b.full.s[1], dst(NL), dst_ld(NL), (int)n[0], (int)n[1]));
+            return took(NL, "k_fwd2d_tile");
+        }
+        return 0;
+    }
+    // ---- 2-D multi-level tiles for the cache-resident levels (two levels per launch) ----
+    int multi2d()
+    {
+        if (!(fastF && F <= 8 && two_d && iopt("WL_NO_MULTI2D", 0) == 0 && n[0] <= iopt("WL_M2D_MAX", 1024) && n[1] <= iopt("WL_M2D_MAX", 1024) &&
+              n[0] >= iopt("WL_M2D_MIN", 128) && n[1] >= iopt("WL_M2D_MIN", 128) && (n[0] % 64) == 0 && (n[1] % 64) == 0 && cur_st.s[0] == 1))
+            return 0;
+        int NL = levels_left();
+        const int nl2max = iopt("WL_M2D_NL", 2);
+        if (NL > nl2max) NL = nl2max;
+        while (NL > 1 && ((n[0] >> NL) < 1 || (n[1] >> NL) < 1)) --NL;
+        const int r = with_taps([&](auto ff) {
+            return launch_fwd2d_multi<T, decltype(ff)::value>(st, taps, cur, cur_st.s[1], y, b.full.s[1], dst(NL), dst_ld(NL), (int)n[0], (int)n[1], NL);
+        });
+        return r > 0 ? took(NL, "k_fwd2d_multi") : r;
+    }
+    // ---- 3-D boxes of <= 4096 elements: every remaining level in one workgroup (wl_tail.hip) ----
+    int tail3()
+    {
+        const int NL = levels_left();
+        if (!(path == 0 && b.nd == 3 && b.nt == 3 && iopt("WL_TAIL3", 1) && b.full.s[0] == 1 && cur_st.s[0] == 1 &&
+              tail3_ok<T>(F, n[0], n[1], n[2], NL)))
+            return 0;
+        WL_WALK_TRY(launch_tail3<T>(st, taps, 1, cur, cur_st.s[1], cur_st.s[2], y, b.full.s[1], b.full.s[2], (int)n[0], (int)n[1], (int)n[2], NL));
+        return took(NL, "k_tail3");
+    }
+    // ---- LDS-resident tail: finishes every remaining level in one launch ----
+    int tail()
+    {
+        if (!(path == 0 && (two_d || lines) && b.full.s[0] == 1)) return 0;
+        const int NL = levels_left();
+        const int64_t blk = two_d ? n[0] * n[1] : n[0];
+        // filters beyond 24 taps: one workgroup is slow at 2 F multiply-adds per sample -- the chip-wide line / axis
+        // kernels of wl_vlong.hip take every level down to 16 samples per dimension first
+        // ... except 12..20 taps on power-of-two blocks of <= 4096 elements: the LDS-resident tail is instantiated for them
+        const bool long_tail = F >= 12 && iopt("WL_LONG_TAIL", 1) && tail2_ok<T>(F, two_d ? 2 : 1, n[0], two_d ? n[1] : 1, NL, 20);
+        const int64_t vl_cap = long_tail ? (int64_t)4096
+                               : ((vlong_filter_ok(F) && iopt("WL_NO_LONGF", 0) == 0) ? (two_d ? 64 : 16) : ((int64_t)1 << 40));
+        if (!(blk <= (two_d ? (int64_t)tail_cap<T>() : line_cap) && blk <= vl_cap && n[0] < (1 << 20) && (!two_d || n[1] <= 256))) return 0;
+        // power-of-two blocks / lines of <= 16 KiB: the latency-optimised tail (wl_tail.hip)
+        const bool t2 = iopt("WL_TAIL2", 1) && tail2_ok<T>(F, two_d ? 2 : 1, n[0], two_d ? n[1] : 1, NL, 20);
+        const auto launch = t2 ? launch_tail2<T> : launch_tail<T>;
+        if (two_d) WL_WALK_TRY(launch(st, taps, cur, cur_st.s[1], y, b.full.s[1], 0, 0, 1, (int)n[0], (int)n[1], 2, NL));
+        else WL_WALK_TRY(launch(st, taps, cur, 0, y, 0, cur_st.s[1], b.full.s[1], (int)nlines, (int)n[0], 1, 1, NL));   // one workgroup per line
+        return took(NL, t2 ? "k_tail2_fwd" : "k_tail_fwd");
+    }
+    // ---- 1-D multi-level tile kernel: up to 4 levels per pass over HBM ----
+    int multi1d()
+    {
+        if (!(fastF && lines && iopt("WL_NO_MULTI", 0) == 0 && n[0] > line_cap && (n[0] % (8 * VEC)) == 0 && cur_st.s[0] == 1 && al16(cur) &&
+              al16(y) && (nlines == 1 || ((cur_st.s[1] % VEC) == 0 && (b.full.s[1] % VEC) == 0))))
+            return 0;
+        int NL = levels_left();
+        // big stages are bandwidth-bound: 4 levels keep the halo (F-2)(2^NL - 1) small; small stages are launch-latency
+        // bound: up to 8 levels per launch saves whole launches (1-D db2 2^20 f64: 23.8 -> 17.3 us with 6, 15.9 with 8)
+        int nl_auto = 4;
+        if (n[0] * nlines < ((int64_t)1 << 22)) {
+            // levels left before the one-workgroup tail can take the line: split them evenly over the fewest launches
+            int lg_n = 0, lg_cap = 0;
+            while (((int64_t)2 << lg_n) <= n[0]) ++lg_n;
+            while (((int64_t)2 << lg_cap) <= line_cap) ++lg_cap;
+            int r = lg_n - lg_cap;
+            if (r > levels_left()) r = levels_left();
+            if (r < 1) r = 1;
+            // (up to 8 levels per launch: the halo (F-2)(2^NL - 1) is then a multiple of the tile, but these lines are a few MiB
+            //  in L2 and a launch saved is ~1 us net -- r04: 2^20 db4 19.0 -> 18.0 us, L = 8: 12.4 -> 11.3)
+            int per = iopt("WL_NL_SMALL_MAX", 8);
+            if (per < 1) per = 1;
+            if (per > 8) per = 8;
+            const int stages = (r + per - 1) / per;
+            nl_auto = (r + stages - 1) / stages;
+        }
+        const int nlmax = iopt("WL_NLMAX", nl_auto);
+        if (NL > nlmax) NL = nlmax;
+        while (NL > 1 && (n[0] % ((int64_t)(1 << NL) * 4 * VEC)) != 0) --NL;   // alignment of every level's stores
+        // after NL levels the approximation has n >> NL samples per line
+        const int r = with_taps([&](auto ff) {
+            return launch_fwd1d_multi<T, decltype(ff)::value>(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], dst(NL), dst_ld(NL), n[0], nlines, NL);
+        });
+        return r > 0 ? took(NL, "k_fwd1d_multi") : r;
+    }
+    // ---- LDS-exchange streaming kernel: one or two fused 2-D levels (f32, wl_fwd2d.hip) ----
+    int lds_f32()
+    {
+        if constexpr (sizeof(T) == 4) {
+            if (!(fastF && two_d && iopt("WL_LDS2D", 1) && n[0] >= iopt("WL_LDS2D_MIN_ROWS", 256) && vec16())) return 0;
+            int nlev = 0;
+            if (levels_left() >= 2 && iopt("WL_FUSE2", 1) && fwd2d_lds_ok(F, 2, n[0], n[1]) &&
+                n[0] * n[1] >= (int64_t)opt("WL_LDS_PAIR_MIN", (long long)1 << 24))
+                nlev = 2;
+            else if (fwd2d_lds_ok(F, 1, n[0], n[1]))
+                nlev = 1;
+            // ... and FOUR on request (WL_FUSE4 = 1) when the two levels after the pair would be the tiles of k_fwd2d_tileB: the same tiles run
+            //     inside the pair's launch, each as soon as the pair workgroups it reads from have published their columns.  Built and
+            //     measured in round 6 (profiles/r06_c3_timeline.md): the tile work does hide under the pair (the tiles end 5-7 us after
+            //     the last pair workgroup instead of 19-20), but the pair is HBM-bound and its own end slips by as much -- 8192^2 L = 13
+            //     within +-1 us of the two-launch chain in five interleaved A/B runs.  Off by default: no gain to pay for in-launch hand-over.
+            if (nlev == 2 && levels_left() >= 4 && opt("WL_FUSE4", 0) != 0 && tl_sync != nullptr && iopt("WL_TILEB", 1) &&
+                (n[0] >> 2) <= iopt("WL_TILEB_MAX", 2048) && (n[1] >> 2) <= iopt("WL_TILEB_MAX", 2048) &&
+                (n[0] >> 2) * (n[1] >> 2) >= (int64_t)iopt("WL_TILEB_MIN", 1 << 21) && fwd2d_pair_tile_ok(F, n[0], n[1], cu_count)) {
+                T *ll4buf = pp ? w.A : w.B;
+                // the tiles write the level-(l+3) approximation while the pair workgroups still read `cur`: after a non-fused
+                // pair (l > 1) the other ping-pong buffer IS cur -- then the two-level pair below runs instead (the last four
+                // levels write it into y, not into ll4buf)
+                const uintptr_t c_lo = (uintptr_t)cur, c_hi = (uintptr_t)(cur + cur_st.s[1] * (n[1] - 1) + n[0]);
+                const uintptr_t q_lo = (uintptr_t)ll4buf, q_hi = (uintptr_t)(ll4buf + (n[0] >> 4) * (n[1] >> 4));
+                if (al16(ll4buf) && (last(4) || q_hi <= c_lo || c_hi <= q_lo)) {
+                    WL_WALK_TRY(fwd2d_pair_tile_launch(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], llbuf(), n[0] >> 2,
+                                                  last(4) ? (T *)nullptr : ll4buf, n[0] >> 4, n[0], n[1], cu_count, tl_sync));
+                    // four levels, and the next one reads ll4buf, the OTHER ping-pong buffer (pp stays as it is)
+                    return took_from(ll4buf, 4, "k_fwd2d_pair_tile");
+                }
+            }
+            if (!nlev) return 0;
+            WL_WALK_TRY(fwd2d_lds_launch(st, taps, nlev, l == 1, cur, cur_st.s[1], y, b.full.s[1], dst(nlev), dst_ld(nlev), n[0], n[1], cu_count));
+            return took(nlev, (nlev == 2) ? "k_fwd2d_pair" : "k_fwd2d_lds");
+        }
+        return 0;
+    }
+    // ---- Float64: the LDS-exchange level kernel with two rows per lane (wl_fwd2d64.hip) ----
+    int lds_f64()
+    {
+        if constexpr (sizeof(T) == 8) {
+            if (!(fastF && two_d && iopt("WL_LDS2D", 1) && n[0] >= iopt("WL_LDS2D_MIN_ROWS", 256) && vec16() && fwd2d_lds64_ok(F, n[0], n[1])))
+                return 0;
+            // two levels per launch from 2^22 elements upwards (the Float64 pair kernel, wl_pair2d64.hip)
+            if (levels_left() >= 2 && iopt("WL_FUSE2", 1) && fwd2d_pair64_ok(F, n[0], n[1]) &&
+                n[0] * n[1] >= (int64_t)opt("WL_LDS_PAIR_MIN64", (long long)1 << 23)) {
+                WL_WALK_TRY(fwd2d_pair64_launch(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], dst(2), dst_ld(2), n[0], n[1], cu_count));
+                return took(2, "k_fwd2d_pair64");
+            }
+            WL_WALK_TRY(fwd2d_lds64_launch(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], dst(), dst_ld(), n[0], n[1], cu_count));
+            return took(1, "k_fwd2d_lds64");
+        }
+        return 0;
+    }
+    // ---- streaming 2-D, two levels fused (f32) ----
+    int stream2()
+    {
+        if constexpr (sizeof(T) == 4) {
+            if (!(fastF && F <= 8 && two_d && iopt("WL_FUSE2", 1) && levels_left() >= 2 && n[0] >= 512 && (n[0] % 16) == 0 &&
+                  n[0] * n[1] >= (int64_t)iopt("WL_FUSE2_MIN", 1 << 24) && n[1] >= 64 && (n[1] % 32) == 0 && vec16()))
+                return 0;
+            const int r = with_taps([&](auto ff) {
+                return launch_fwd2d_pair<T, decltype(ff)::value>(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], dst(2), dst_ld(2), n[0], n[1], cu_count);
+            });
+            return r > 0 ? took(2, "k_fwd2d_stream2") : r;
+        }
+        return 0;
+    }
+    // ---- streaming 2-D level ----
+    int stream2d()
+    {
+        if (!(fastF && two_d && n[0] >= 64 * VEC && (n[0] % 8) == 0 && n[1] >= 16 && (n[1] % 16) == 0 && vec16())) return 0;
+        const int r = with_taps([&](auto ff) {
+            return launch_fwd2d<T, decltype(ff)::value>(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], ll_or_null(), n[0] >> 1, n[0], n[1], cu_count);
+        });
+        return r > 0 ? took(1, "k_fwd2d_stream") : r;
+    }
+    // ---- streaming 1-D level (vector, or every column of a matrix) ----
+    int stream1d()
+    {
+        if (!(fastF && lines && n[0] >= 512 && (n[0] % 8) == 0 && cur_st.s[0] == 1 && al16(cur) && al16(y) && al16(llbuf()) &&
+              (nlines == 1 || ((cur_st.s[1] % VEC) == 0 && (b.full.s[1] % VEC) == 0))))
+            return 0;
+        const int r = with_taps([&](auto ff) {
+            return launch_fwd1d<T, decltype(ff)::value>(st, taps, l == 1, cur, cur_st.s[1], dst(), dst_ld(), y + (n[0] >> 1), b.full.s[1], n[0], nlines,
+                                                        cu_count);
+        });
+        return r > 0 ? took(1, "k_fwd1d_stream") : r;
+    }
+    // ---- 12..20 taps, Float32, blocks whose rows tile into strips of 256: one pass per level (wl_fwd2d_long.hip) ----
+    int lds_long()
+    {
+        if constexpr (sizeof(T) == 4) {
+            if (!(path == 0 && two_d && iopt("WL_LONG2D", 1) && n[0] >= iopt("WL_LONG2D_MIN_ROWS", 256) && b.full.s[0] == 1 &&
+                  fwd2d_long_ok(F, n[0], n[1]) && vec16()))
+                return 0;
+            WL_WALK_TRY(fwd2d_long_launch(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], dst(), dst_ld(), n[0], n[1], cu_count));
+            return took(1, "k_fwd2d_lds_long");
+        }
+        return 0;
+    }
+    // ---- long filters (12..24 taps): line kernel with multi-lane halo, 2-D as axis pass + line pass (wl_axis.hip) ----
+    int long_filters()
+    {
+        if (!(path == 0 && long_filter_ok(F) && iopt("WL_NO_LONGF", 0) == 0 && b.full.s[0] == 1 && cur_st.s[0] == 1)) return 0;
+        hipError_t e = hipSuccess;
+        bool done = false;
+        const int64_t h0 = n[0] >> 1, h1 = n[1] >> 1, ldy = b.full.s[1];
+        if (lines) {
+            done = long_lines_fwd_level<T>(st, taps, cur, cur_st.s[1], dst(), dst_ld(), y + h0, ldy, n[0], nlines, cu_count, &e);
+            WL_WALK_TRY(e);
+        } else if (two_d && long_shape2d_ok(F, n[0], n[1]) && (ldy % VEC) == 0 && (cur_st.s[1] % VEC) == 0 && al16(cur) && al16(y) &&
+                   al16(llbuf())) {
+            // rows (dim 2) into T0 = [s-columns | d-columns], then the columns of T0 as lines with the LL quadrant routed on
+            if (!w.T0) return WL_RETRY_GEN;
+            done = long_axis_level<T>(st, taps, 1, cur, cur_st.s[1], w.T0, n[0], n[0], n[1], cu_count, &e);
+            WL_WALK_TRY(e);
+            if (done) {
+                bool ok = long_lines_fwd_level<T>(st, taps, w.T0, n[0], dst(), dst_ld(), y + h0, ldy, n[0], h1, cu_count, &e);
+                WL_WALK_TRY(e);
+                ok = ok && long_lines_fwd_level<T>(st, taps, w.T0 + h1 * n[0], n[0], y + h1 * ldy, ldy, y + h1 * ldy + h0, ldy, n[0], h1,
+                                                   cu_count, &e);
+                WL_WALK_TRY(e);
+                if (!ok) return WL_EINVAL_ARG;      // (eligibility is identical for the three launches)
+            }
+        }
+        return done ? took(1, (vlong_only(F) || n[0] < 512) ? "k_vl_lines" : "k_long_lines") : 0;
+    }
+    // ---- 3-D level: one pass, LDS blocks, or three single-axis streaming passes (fast3d_fwd_tier, wl_axis.hip) ----
+    int fast3d()
+    {
+        if (!(fastF && b.nd == 3 && b.nt == 3 && iopt("WL_NO_FAST3D", 0) == 0 && cur_st.s[0] == 1 && b.full.s[0] == 1)) return 0;
+        hipError_t e3 = hipSuccess;
+        const char *k3 = "k_fwd_axis_stream";
+        if (!w.T0) return WL_RETRY_GEN;
+        const bool done = fast3d_fwd_level<T>(st, taps, cur, cur_st.s[1], cur_st.s[2], y, b.full.s[1], b.full.s[2], ll_or_null(), n, w.T0, w.T1,
+                                              cu_count, &e3, &k3);
+        WL_WALK_TRY(e3);
+        return done ? took(1, k3) : 0;
+    }
+    // ---- 2-D level of any even extents, F <= 10: one LDS-tile launch instead of two generic passes (wl_gtile.hip) ----
+    int gtile()
+    {
+        if (!(fastF && two_d && path == 0 && iopt("WL_GTILE", 1) && b.full.s[0] == 1 && cur_st.s[0] == 1 && gtile_ok(F, n[0], n[1]))) return 0;
+        WL_WALK_TRY(gtile_launch<T>(st, taps, 1, cur, cur_st.s[1], y, b.full.s[1], ll_or_null(), n[0] >> 1, (int)n[0], (int)n[1]));
+        return took(1, "k_fwd2d_gtile");
+    }
+    // ---- generic level (any rank / size / filter): one pass per axis, never declines ----
+    int generic()
+    {
+        if (b.nt > 1 && !w.T0) return WL_RETRY_GEN;
+        const Extent3 ext = {{n[0], n[1], n[2]}}, lo = low_corner(b, n);
+        const Strides3 box_st = dense_strides(n);
+        const T *in = cur;
+        Strides3 in_st = cur_st;
+        const char *name = nullptr;
+        for (int a = b.nt - 1, tog = 0; a >= 0; --a, tog ^= 1) {
+            // F <= 10: four pairs per thread from a register window, compile-time taps (wl_anyaxis.hip); else one output per thread
+            const bool any = path == 0 && iopt("WL_ANYAXIS", 1) && any_axis_ok(F, ext, a);
+            T *out = (a == 0) ? y : (tog ? w.T1 : w.T0), *ll = (a == 0) ? ll_or_null() : (T *)nullptr;
+            const Strides3 out_st = (a == 0) ? b.full : box_st, l_st = (a == 0) ? ll_st() : box_st;
+            if (any) WL_WALK_TRY(any_axis_pass<T>(st, taps, 1, in, in_st, out, out_st, ll, l_st, ext, a, lo));
+            else WL_WALK_TRY(generic_fwd_filter_pass<T>(st, taps, in, in_st, out, out_st, ll, l_st, ext, a, lo));
+            in = out; in_st = out_st;
+            name = any ? "k_fwd_any" : "k_generic_fwd_filter";
+        }
+        return took(1, name);
+    }
+};
 
-thread_local SrcView tl_srcview = {0, 0, 0, -1, 0.0, 0.0, nullptr, 0, 0};
+// The priority order: for every level the first tier that does not decline takes it.
+template <typename T>
+static constexpr int (FwdWalk<T>::*kFwdTiers[])() = {
+    &FwdWalk<T>::plane_pair,     // batch of planes, Float32, >= WL_PAIR_BATCH_MIN elements each: two levels (k_fwd2d_pair; WL_PAIR_BATCH)
+    &FwdWalk<T>::plane_lds,      // batch of planes, Float32: one level per launch (k_fwd2d_lds)
+    &FwdWalk<T>::view_guard,     // WL_RETRY_NOVIEW: a shifted source view that neither tier above took
+    &FwdWalk<T>::tileB,          // 2-D Float32, <= 2048 rows and >= 2^21 elements: two levels without staging (k_fwd2d_tileB; WL_TILEB)
+    &FwdWalk<T>::tile,           // 2-D <= 1024 rows: 1..3 levels per launch (k_fwd2d_tile; WL_TILE)
+    &FwdWalk<T>::tile_long,      // 2-D Float32, 12..20 taps, <= 1024 rows: two levels per launch (k_fwd2d_tile; WL_TILE_LONG)
+    &FwdWalk<T>::multi2d,        // 2-D F <= 8, 128..1024 rows in multiples of 64: two levels per launch (k_fwd2d_multi; WL_NO_MULTI2D)
+    &FwdWalk<T>::tail3,          // 3-D box of <= 4096 elements: all remaining levels (k_tail3; WL_TAIL3)
+    &FwdWalk<T>::tail,           // small 2-D block / short lines: all remaining levels (k_tail2_fwd, k_tail_fwd; WL_TAIL2, WL_LONG_TAIL)
+    &FwdWalk<T>::multi1d,        // lines longer than the tail takes: up to 8 levels per launch (k_fwd1d_multi; WL_NO_MULTI)
+    &FwdWalk<T>::lds_f32,        // 2-D Float32 >= 256 rows: 1, 2 or 4 levels (k_fwd2d_lds, _pair, _pair_tile; WL_LDS2D, WL_FUSE2, WL_FUSE4)
+    &FwdWalk<T>::lds_f64,        // 2-D Float64 >= 256 rows: one or two levels (k_fwd2d_lds64, k_fwd2d_pair64; WL_LDS2D, WL_FUSE2)
+    &FwdWalk<T>::stream2,        // 2-D Float32 F <= 8, >= 2^24 elements: two levels (k_fwd2d_stream2; WL_FUSE2)
+    &FwdWalk<T>::stream2d,       // 2-D level, rows in multiples of 8 (k_fwd2d_stream)
+    &FwdWalk<T>::stream1d,       // lines of >= 512 samples (k_fwd1d_stream)
+    &FwdWalk<T>::lds_long,       // 2-D Float32, 12..20 taps, rows in strips of 256 (k_fwd2d_lds_long; WL_LONG2D)
+    &FwdWalk<T>::long_filters,   // 12..24 and Battle taps: lines, 2-D as axis pass + line passes (k_long_lines, k_vl_lines; WL_NO_LONGF)
+    &FwdWalk<T>::fast3d,         // 3-D level (k_fwd3d_one, k_level3_lds, k_fwd_axis_stream; WL_NO_FAST3D)
+    &FwdWalk<T>::gtile,          // 2-D level of any even extents (k_fwd2d_gtile; WL_GTILE)
+    &FwdWalk<T>::generic,        // anything: one pass per axis (k_fwd_any, k_generic_fwd_filter; WL_ANYAXIS)
+};
 
 template <typename T>
 int filter_fwd_levels(void *ws, bool ws_gen, int cu_count, int path, hipStream_t st, const BoxSpec &b,
                       T *y, const T *x, const Taps<T> &taps, int L, const char **kernel_name, int *hip_err)
 {
-#define WL_TRY(expr)                                                  \
-    do {                                                              \
-        hipError_t e__ = (expr);                                      \
-        if (e__ != hipSuccess) { if (hip_err) *hip_err = (int)e__; return WL_EHIP; } \
-    } while (0)
-    const int64_t N = b.dims[0] * b.dims[1] * b.dims[2];
-    Work<T> w = carve<T>(ws, N, b.nt, ws_gen);
-    constexpr int VEC = 16 / sizeof(T);
-    const int F = taps.F;
-    const bool fastF = (path == 0) && (F % 2 == 0) && (F <= 10);
-    const bool two_d = (b.nd == 2 && b.nt == 2);
-    const bool lines = (b.nt == 1 && b.nd <= 2);          // 1-D vector or batched columns
-    const int64_t nlines = lines ? b.dims[1] : 1;
-    const char *dominant = nullptr;
-
-    const T *cur = x;
-    Strides3 cur_st = b.full;
-    int pp = 0;
-    int lstep = 1;
-    for (int l = 1; l <= L; l += lstep) {
-        lstep = 1;
-        int64_t n[3];
-        level_box(b, l, n);
-        Extent3 ext = {{n[0], n[1], n[2]}};
-        Extent3 lo = low_corner(b, n);
-        const bool last = (l == L);
-        T *llbuf = pp ? w.B : w.A;
-        int64_t hn[3] = {lo.n[0], lo.n[1], lo.n[2]};
-        Strides3 ll_st = dense_strides(hn);
-        Strides3 box_st = dense_strides(n);
-
-        // ---- batch of independent 2-D blocks (box n0 x n1 x B, first two axes transformed: the shifted copies of a
-        //      translation-invariant denoise): one launch of the LDS-exchange kernel per level, planes over blockIdx.y ----
-        // ... two levels per launch while the planes are big enough for the fused pair kernel to pay (many planes keep the chip full
-        //     where a single 2048^2 block would not)
-        if constexpr (sizeof(T) == 4) {
-            if (fastF && b.nd == 3 && b.nt == 2 && (L - l + 1) >= 2 && env_int("WL_PAIR_BATCH", 1) != 0 && n[2] >= 2 && n[2] <= 65535 &&
-                n[0] * n[1] >= (int64_t)env_int_raw("WL_PAIR_BATCH_MIN", 1 << 22) && fwd2d_pair_ok(F, n[0], n[1]) && cur_st.s[0] == 1 &&
-                (cur_st.s[1] % VEC) == 0 && (cur_st.s[2] % VEC) == 0 && aligned16(cur) && (b.full.s[1] % VEC) == 0 &&
-                (b.full.s[2] % VEC) == 0 && aligned16(y) && aligned16(llbuf)) {
-                const bool view = (l == 1 && tl_srcview.mod > 0);
-                const bool thr = tl_srcview.th >= 0 && (view || (l > 1 && tl_srcview.used != 0 && tl_srcview.corner0 == n[0] && tl_srcview.corner1 == n[1]));
-                const bool lastp = (l + 1 == L);
-                int64_t hn2[3] = {n[0] >> 2, n[1] >> 2, n[2]};
-                Strides3 ll2_st = dense_strides(hn2);
-                WL_TRY(fwd2d_pair_launch(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], lastp ? (T *)nullptr : llbuf, hn2[0], n[0], n[1],
-                                         cu_count, n[2], cur_st.s[2], b.full.s[2], ll2_st.s[2], view ? tl_srcview.mod : 0,
-                                         view ? tl_srcview.spin0 : 0, thr ? &tl_srcview : nullptr));
-                if (view) tl_srcview.used = 1;
-                if (thr) { tl_srcview.corner0 = lastp ? 0 : hn2[0]; tl_srcview.corner1 = lastp ? 0 : hn2[1]; }
-                if (!dominant) dominant = "k_fwd2d_pair";
-                lstep = 2;
-                cur = llbuf; cur_st = ll2_st; pp ^= 1;
-                continue;
-            }
-        }
-        if constexpr (sizeof(T) == 4) {
-            if (fastF && b.nd == 3 && b.nt == 2 && fwd2d_lds_ok(F, 1, n[0], n[1]) && n[2] <= 65535 && cur_st.s[0] == 1 &&
-                (cur_st.s[1] % VEC) == 0 && (cur_st.s[2] % VEC) == 0 && aligned16(cur) && (b.full.s[1] % VEC) == 0 &&
-                (b.full.s[2] % VEC) == 0 && aligned16(y) && aligned16(llbuf)) {
-                const bool view = (l == 1 && tl_srcview.mod > 0);      // level 1 of a translation-invariant batch: virtual shifted planes
-                // ... whose launches also threshold the coefficients they store (every level that runs here, once level 1 did)
-                const bool thr = tl_srcview.th >= 0 && (view || (l > 1 && tl_srcview.used != 0 && tl_srcview.corner0 == n[0] && tl_srcview.corner1 == n[1]));
-                WL_TRY(fwd2d_lds_launch(st, taps, 1, l == 1, cur, cur_st.s[1], y, b.full.s[1], last ? (T *)nullptr : llbuf, hn[0],
-                                        n[0], n[1], cu_count, n[2], cur_st.s[2], b.full.s[2], ll_st.s[2], (int)n[2],
-                                        view ? tl_srcview.mod : 0, view ? tl_srcview.spin0 : 0, thr ? &tl_srcview : nullptr));
-                if (thr) { tl_srcview.corner0 = last ? 0 : hn[0]; tl_srcview.corner1 = last ? 0 : hn[1]; }
-                if (view) tl_srcview.used = 1;
-                if (!dominant) dominant = "k_fwd2d_lds";
-                cur = llbuf; cur_st = ll_st; pp ^= 1;
-                continue;
-            }
-        }
-        // a virtually shifted source is only valid for the two batch tiers above: anything else would read planes it does not hold
-        if (l == 1 && tl_srcview.mod > 0) return WL_RETRY_NOVIEW;
-        // ---- two levels of a block too big for one resident round of the staging tile kernel (2048 rows): tiles without staging ----
-        if constexpr (sizeof(T) == 4) {
-            if (fastF && two_d && env_int("WL_TILEB", 1) && (L - l + 1) >= 2 && n[0] <= env_int("WL_TILEB_MAX", 2048) &&
-                n[1] <= env_int("WL_TILEB_MAX", 2048) && n[0] * n[1] >= (int64_t)env_int_raw("WL_TILEB_MIN", 1 << 21) && cur_st.s[0] == 1 &&
-                (cur_st.s[1] % 4) == 0 && aligned16(cur) && (b.full.s[1] % 4) == 0 && aligned16(y) && aligned16(llbuf) &&
-                fwd2d_tile_ok(F, 2, n[0], n[1])) {
-                const bool lastt = (l + 1 == L);
-                T *lld = lastt ? y : llbuf;
-                const int64_t ldd = lastt ? b.full.s[1] : (n[0] >> 2);
-                // tall tiles (256 x 64, one workgroup per CU) unless they would leave CUs idle that the 64 x 64 grid fills (blocks of 2^21
-                // elements: 128 tall tiles against 512; 2048 x 1024 two levels 8.0 us on 64 x 64 tiles, 8.7 on tall ones)
-                const int64_t tiles = (n[0] / 64) * (n[1] / 64);
-                const int tall = env_int("WL_TILEB_TALL", 1) != 0 && (n[0] % 256) == 0 && !(tiles / 4 < cu_count && tiles >= cu_count);
-                WL_TRY(fwd2d_tileB_launch(st, taps, cur, cur_st.s[1], y, b.full.s[1], lld, ldd, (int)n[0], (int)n[1], tall));
-                if (!dominant) dominant = "k_fwd2d_tileB";
-                lstep = 2;
-                int64_t hn2[3] = {n[0] >> 2, n[1] >> 2, n[2]};
-                cur = llbuf; cur_st = dense_strides(hn2); pp ^= 1;
-                continue;
-            }
-        }
-        // ---- tile kernel: 1..3 fused levels of a cache-resident block (wl_tile.hip; Float64: up to 2 levels) ----
-        {
-            auto al4 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) % (4 * sizeof(T))) == 0; };     // 4-element vectors
-            if (fastF && two_d && env_int("WL_TILE", 1) && n[0] <= env_int("WL_TILE_MAX", 1024) && n[1] <= env_int("WL_TILE_MAX", 1024) &&
-                cur_st.s[0] == 1 && (cur_st.s[1] % 4) == 0 && al4(cur) && (b.full.s[1] % 4) == 0 && al4(y) && al4(llbuf)) {
-                int NL = L - l + 1;
-                if (NL > 3) NL = 3;
-                const int64_t nmax = n[0] > n[1] ? n[0] : n[1];
-                // three levels per tile launch from 512^2 down (round 5, with the approximation handed over through L2: 2048^2 full depth 34.7 -> 32.2 us,
-                // 512^2 20.1 -> 17.7, 8192^2 -2 %; round 4 measured it 4 % slower and kept two)
-                if (NL == 3 && (nmax > env_int("WL_TILE_NL3_MAX", 512) || sizeof(T) == 8)) NL = 2;
-                while (NL > 1 && !fwd2d_tile_ok(F, NL, n[0], n[1])) --NL;
-                if (fwd2d_tile_ok(F, NL, n[0], n[1])) {
-                    const bool lastt = (l + NL - 1 == L);
-                    T *lld = lastt ? y : llbuf;
-                    const int64_t ldd = lastt ? b.full.s[1] : (n[0] >> NL);
-                    WL_TRY(fwd2d_tile_launch<T>(st, taps, NL, cur, cur_st.s[1], y, b.full.s[1], lld, ldd, (int)n[0], (int)n[1]));
-                    if (!dominant) dominant = "k_fwd2d_tile";
-                    lstep = NL;
-                    int64_t hn2[3] = {n[0] >> NL, n[1] >> NL, n[2]};
-                    cur = llbuf; cur_st = dense_strides(hn2); pp ^= 1;
-                    continue;
-                }
-            }
-        }
-        // ---- 12..20 taps, Float32, blocks of 128 .. 1024 rows: two levels per launch through the LDS tile kernel (round 5).  These
-        //      levels ran one streaming launch each (12-13 us apiece, short of workgroups) and the 128^2 level as two line passes:
-        //      8192^2 db6 246 -> 224 us, sym8 286 -> 261, db10 329 -> 303; 1024^2 sym8 full depth 60.5 -> 36.8, 512^2 48.5 -> 29.8.
-        //      Not above 1024 rows (2048^2: four rounds of one 512-thread workgroup per CU: sym8 8192^2 280 us, 4096^2 too: 356).
-        if constexpr (sizeof(T) == 4) {
-            auto al4 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0; };
-            if (path == 0 && F >= 12 && F <= 20 && (F % 2) == 0 && two_d && env_int("WL_TILE_LONG", 1) && n[0] <= env_int("WL_TILE_LONG_MAX", 1024) &&
-                n[1] <= env_int("WL_TILE_LONG_MAX", 1024) && cur_st.s[0] == 1 && (cur_st.s[1] % 4) == 0 && al4(cur) && (b.full.s[1] % 4) == 0 && al4(y) &&
-                al4(llbuf) && b.full.s[0] == 1) {
-                int NL = (L - l + 1) >= 2 ? 2 : 1;
-                while (NL > 1 && !fwd2d_tile_ok(F, NL, n[0], n[1])) --NL;
-                // (a single remaining level of >= 256 rows stays with the streaming kernel below)
-                if (fwd2d_tile_ok(F, NL, n[0], n[1]) && (NL == 2 || n[0] < 256)) {
-                    const bool lastt = (l + NL - 1 == L);
-                    T *lld = lastt ? y : llbuf;
-                    const int64_t ldd = lastt ? b.full.s[1] : (n[0] >> NL);
-                    WL_TRY(fwd2d_tile_launch<T>(st, taps, NL, cur, cur_st.s[1], y, b.full.s[1], lld, ldd, (int)n[0], (int)n[1]));
-                    if (!dominant) dominant = "k_fwd2d_tile";
-                    lstep = NL;
-                    int64_t hn2[3] = {n[0] >> NL, n[1] >> NL, n[2]};
-                    cur = llbuf; cur_st = dense_strides(hn2); pp ^= 1;
-                    continue;
-                }
-            }
-        }
-        // ---- 2-D multi-level tiles for the cache-resident levels (two levels per launch) ----
-        if (fastF && F <= 8 && two_d && env_int("WL_NO_MULTI2D", 0) == 0 && n[0] <= env_int("WL_M2D_MAX", 1024) &&
-            n[1] <= env_int("WL_M2D_MAX", 1024) && n[0] >= env_int("WL_M2D_MIN", 128) && n[1] >= env_int("WL_M2D_MIN", 128) && (n[0] % 64) == 0 && (n[1] % 64) == 0 &&
-            cur_st.s[0] == 1) {
-            int NL = (L - l + 1);
-            const int nl2max = env_int("WL_M2D_NL", 2);
-            if (NL > nl2max) NL = nl2max;
-            while (NL > 1 && ((n[0] >> NL) < 1 || (n[1] >> NL) < 1)) --NL;
-            const bool lastm = (l + NL - 1 == L);
-            T *lld = lastm ? y : llbuf;
-            const int64_t ldd = lastm ? b.full.s[1] : (n[0] >> NL);
-            bool ok = false;
-            WL_DISPATCH_F(F, WL_TRY((launch_fwd2d_multi<T, FF>(st, taps, cur, cur_st.s[1], y, b.full.s[1], lld, ldd,
-                                                               (int)n[0], (int)n[1], NL)));
-                          ok = true);
-            if (ok) {
-                if (!dominant) dominant = "k_fwd2d_multi";
-                lstep = NL;
-                int64_t hn2[3] = {n[0] >> NL, n[1] >> NL, n[2]};
-                cur = llbuf; cur_st = dense_strides(hn2); pp ^= 1;
-                continue;
-            }
-        }
-        // ---- 3-D boxes of <= 4096 elements: every remaining level in one workgroup (wl_tail.hip) ----
-        if (path == 0 && b.nd == 3 && b.nt == 3 && env_int("WL_TAIL3", 1) && b.full.s[0] == 1 && cur_st.s[0] == 1 &&
-            tail3_ok<T>(F, n[0], n[1], n[2], L - l + 1)) {
-            WL_TRY(launch_tail3<T>(st, taps, 1, cur, cur_st.s[1], cur_st.s[2], y, b.full.s[1], b.full.s[2], (int)n[0], (int)n[1], (int)n[2],
-                                   L - l + 1));
-            if (!dominant) dominant = "k_tail3";
-            break;
-        }
-        // ---- LDS-resident tail: finishes every remaining level in one launch ----
-        // (batches of many lines: one workgroup per line is only efficient for short lines -- longer ones take
-        //  another pass of the multi-level tile kernel first)
-        // single lines: the latency-optimised tail (wl_tail.hip) takes 4096 samples; longer lines get another multi-level pass first
-        const int64_t line_cap = (lines && nlines >= 32 && fastF) ? env_int("WL_TAIL_LINES_CAP", 512)
-                                 : ((lines && fastF && env_int("WL_TAIL2", 1)) ? (int64_t)4096 : (int64_t)tail_cap<T>());
-        if (path == 0 && (two_d || lines) && b.full.s[0] == 1) {
-            const int64_t blk = two_d ? n[0] * n[1] : n[0];
-            // filters beyond 24 taps: one workgroup is slow at 2 F multiply-adds per sample -- the chip-wide line / axis
-            // kernels of wl_vlong.hip take every level down to 16 samples per dimension first
-            // ... except 12..20 taps on power-of-two blocks of <= 4096 elements: the LDS-resident tail is instantiated for them
-            const bool long_tail = F >= 12 && env_int("WL_LONG_TAIL", 1) && tail2_ok<T>(F, two_d ? 2 : 1, n[0], two_d ? n[1] : 1, L - l + 1, 20);
-            const int64_t vl_cap = long_tail ? (int64_t)4096
-                                   : ((vlong_filter_ok(F) && env_int("WL_NO_LONGF", 0) == 0) ? (two_d ? 64 : 16) : ((int64_t)1 << 40));
-            if (blk <= (two_d ? (int64_t)tail_cap<T>() : line_cap) && blk <= vl_cap && n[0] < (1 << 20) && (!two_d || n[1] <= 256)) {
-                // power-of-two blocks / lines of <= 16 KiB: the latency-optimised tail (wl_tail.hip)
-                const bool t2 = env_int("WL_TAIL2", 1) && tail2_ok<T>(F, two_d ? 2 : 1, n[0], two_d ? n[1] : 1, L - l + 1, 20);
-                if (two_d) {
-                    if (t2) WL_TRY(launch_tail2<T>(st, taps, cur, cur_st.s[1], y, b.full.s[1], 0, 0, 1, (int)n[0], (int)n[1], 2, L - l + 1));
-                    else WL_TRY(launch_tail<T>(st, taps, cur, cur_st.s[1], y, b.full.s[1], 0, 0, 1, (int)n[0], (int)n[1], 2, L - l + 1));
-                } else {   // one workgroup per line
-                    if (t2) WL_TRY(launch_tail2<T>(st, taps, cur, 0, y, 0, cur_st.s[1], b.full.s[1], (int)nlines, (int)n[0], 1, 1, L - l + 1));
-                    else WL_TRY(launch_tail<T>(st, taps, cur, 0, y, 0, cur_st.s[1], b.full.s[1], (int)nlines, (int)n[0], 1, 1, L - l + 1));
-                }
-                if (!dominant) dominant = t2 ? "k_tail2_fwd" : "k_tail_fwd";
-                break;
-            }
-        }
-        bool done = false;
-        // ---- 1-D multi-level tile kernel: up to 4 levels per pass over HBM ----
-        if (fastF && lines && env_int("WL_NO_MULTI", 0) == 0 && n[0] > line_cap && (n[0] % (8 * VEC)) == 0 &&
-            cur_st.s[0] == 1 && aligned16(cur) && aligned16(y) &&
-            (nlines == 1 || ((cur_st.s[1] % VEC) == 0 && (b.full.s[1] % VEC) == 0))) {
-            int NL = L - l + 1;
-            // big stages are bandwidth-bound: 4 levels keep the halo (F-2)(2^NL - 1) small; small stages are launch-latency
-            // bound: up to 8 levels per launch saves whole launches (1-D db2 2^20 f64: 23.8 -> 17.3 us with 6, 15.9 with 8)
-            int nl_auto = 4;
-            if (n[0] * nlines < ((int64_t)1 << 22)) {
-                // levels left before the one-workgroup tail can take the line: split them evenly over the fewest launches
-                int lg_n = 0, lg_cap = 0;
-                while (((int64_t)2 << lg_n) <= n[0]) ++lg_n;
-                while (((int64_t)2 << lg_cap) <= line_cap) ++lg_cap;
-                int r = lg_n - lg_cap;
-                if (r > L - l + 1) r = L - l + 1;
-                if (r < 1) r = 1;
-                // (up to 8 levels per launch: the halo (F-2)(2^NL - 1) is then a multiple of the tile, but these lines are a few MiB
-                //  in L2 and a launch saved is ~1 us net -- r04: 2^20 db4 19.0 -> 18.0 us, L = 8: 12.4 -> 11.3)
-                int per = env_int("WL_NL_SMALL_MAX", 8);
-                if (per < 1) per = 1;
-                if (per > 8) per = 8;
-                const int stages = (r + per - 1) / per;
-                nl_auto = (r + stages - 1) / stages;
-            }
-            const int nlmax = env_int("WL_NLMAX", nl_auto);
-            if (NL > nlmax) NL = nlmax;
-            while (NL > 1 && (n[0] % ((int64_t)(1 << NL) * 4 * VEC)) != 0) --NL;   // alignment of every level's stores
-            const bool lastm = (l + NL - 1 == L);
-            // after NL levels the approximation has n >> NL samples per line
-            T *sd = lastm ? y : llbuf;
-            const int64_t sls = lastm ? b.full.s[1] : (n[0] >> NL);
-            WL_DISPATCH_F(F, WL_TRY((launch_fwd1d_multi<T, FF>(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], sd, sls,
-                                                               n[0], nlines, NL)));
-                          done = true);
-            if (done) {
-                if (!dominant) dominant = "k_fwd1d_multi";
-                lstep = NL;
-                int64_t hn2[3] = {n[0] >> NL, n[1], n[2]};
-                cur = llbuf; cur_st = dense_strides(hn2); pp ^= 1;
-                continue;
-            }
-        }
-        // ---- LDS-exchange streaming kernel: one or two fused 2-D levels (f32, wl_fwd2d.hip) ----
-        if constexpr (sizeof(T) == 4) {
-            if (fastF && two_d && env_int("WL_LDS2D", 1) && n[0] >= env_int("WL_LDS2D_MIN_ROWS", 256) && cur_st.s[0] == 1 &&
-                (cur_st.s[1] % VEC) == 0 && aligned16(cur) && (b.full.s[1] % VEC) == 0 && aligned16(y) && aligned16(llbuf)) {
-                int nlev = 0;
-                if ((L - l + 1) >= 2 && env_int("WL_FUSE2", 1) && fwd2d_lds_ok(F, 2, n[0], n[1]) &&
-                    n[0] * n[1] >= (int64_t)opt("WL_LDS_PAIR_MIN", (long long)1 << 24))
-                    nlev = 2;
-                else if (fwd2d_lds_ok(F, 1, n[0], n[1]))
-                    nlev = 1;
-                // ... and FOUR on request (WL_FUSE4 = 1) when the two levels after the pair would be the tiles of k_fwd2d_tileB: the same tiles run
-                //     inside the pair's launch, each as soon as the pair workgroups it reads from have published their columns.  Built and
-                //     measured in round 6 (profiles/r06_c3_timeline.md): the tile work does hide under the pair (the tiles end 5-7 us after
-                //     the last pair workgroup instead of 19-20), but the pair is HBM-bound and its own end slips by as much -- 8192^2 L = 13
-                //     within +-1 us of the two-launch chain in five interleaved A/B runs.  Off by default: no gain to pay for in-launch hand-over.
-                if (nlev == 2 && (L - l + 1) >= 4 && opt("WL_FUSE4", 0) != 0 && tl_sync != nullptr && env_int("WL_TILEB", 1) &&
-                    (n[0] >> 2) <= env_int("WL_TILEB_MAX", 2048) && (n[1] >> 2) <= env_int("WL_TILEB_MAX", 2048) &&
-                    (n[0] >> 2) * (n[1] >> 2) >= (int64_t)env_int_raw("WL_TILEB_MIN", 1 << 21) && fwd2d_pair_tile_ok(F, n[0], n[1], cu_count)) {
-                    const bool last4 = (l + 3 == L);
-                    T *ll2buf = llbuf, *ll4buf = pp ? w.A : w.B;
-                    // the tiles write the level-(l+3) approximation while the pair workgroups still read `cur`: after a non-fused
-                    // pair (l > 1) the other ping-pong buffer IS cur -- then the two-level pair below runs instead (the last four
-                    // levels write it into y, not into ll4buf)
-                    const uintptr_t c_lo = (uintptr_t)cur, c_hi = (uintptr_t)(cur + cur_st.s[1] * (n[1] - 1) + n[0]);
-                    const uintptr_t q_lo = (uintptr_t)ll4buf, q_hi = (uintptr_t)(ll4buf + (n[0] >> 4) * (n[1] >> 4));
-                    if (aligned16(ll4buf) && (last4 || q_hi <= c_lo || c_hi <= q_lo)) {
-                        WL_TRY(fwd2d_pair_tile_launch(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], ll2buf, n[0] >> 2, last4 ? (T *)nullptr : ll4buf,
-                                                      n[0] >> 4, n[0], n[1], cu_count, tl_sync));
-                        if (!dominant) dominant = "k_fwd2d_pair_tile";
-                        lstep = 4;
-                        int64_t hn4[3] = {n[0] >> 4, n[1] >> 4, n[2]};
-                        cur = ll4buf; cur_st = dense_strides(hn4);
-                        continue;
-                    }
-                }
-                if (nlev) {
-                    const bool lastp = (l + nlev - 1 == L);
-                    T *lld = lastp ? y : llbuf;
-                    const int64_t ldd = lastp ? b.full.s[1] : (n[0] >> nlev);
-                    WL_TRY(fwd2d_lds_launch(st, taps, nlev, l == 1, cur, cur_st.s[1], y, b.full.s[1], lld, ldd, n[0], n[1], cu_count));
-                    if (!dominant) dominant = (nlev == 2) ? "k_fwd2d_pair" : "k_fwd2d_lds";
-                    lstep = nlev;
-                    int64_t hn2[3] = {n[0] >> nlev, n[1] >> nlev, n[2]};
-                    cur = llbuf; cur_st = dense_strides(hn2); pp ^= 1;
-                    continue;
-                }
-            }
-        }
-        // ---- Float64: the LDS-exchange level kernel with two rows per lane (wl_fwd2d64.hip) ----
-        if constexpr (sizeof(T) == 8) {
-            if (fastF && two_d && env_int("WL_LDS2D", 1) && n[0] >= env_int("WL_LDS2D_MIN_ROWS", 256) && cur_st.s[0] == 1 &&
-                (cur_st.s[1] % VEC) == 0 && aligned16(cur) && (b.full.s[1] % VEC) == 0 && aligned16(y) && aligned16(llbuf) &&
-                fwd2d_lds64_ok(F, n[0], n[1])) {
-                // two levels per launch from 2^22 elements upwards (the Float64 pair kernel, wl_pair2d64.hip)
-                if ((L - l + 1) >= 2 && env_int("WL_FUSE2", 1) && fwd2d_pair64_ok(F, n[0], n[1]) &&
-                    n[0] * n[1] >= (int64_t)opt("WL_LDS_PAIR_MIN64", (long long)1 << 23)) {
-                    const bool lastp = (l + 1 == L);
-                    T *lld2 = lastp ? y : llbuf;
-                    const int64_t ldd2 = lastp ? b.full.s[1] : (n[0] >> 2);
-                    WL_TRY(fwd2d_pair64_launch(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], lld2, ldd2, n[0], n[1], cu_count));
-                    if (!dominant) dominant = "k_fwd2d_pair64";
-                    lstep = 2;
-                    int64_t hn4[3] = {n[0] >> 2, n[1] >> 2, n[2]};
-                    cur = llbuf; cur_st = dense_strides(hn4); pp ^= 1;
-                    continue;
-                }
-                T *lld = last ? y : llbuf;
-                const int64_t ldd = last ? b.full.s[1] : (n[0] >> 1);
-                WL_TRY(fwd2d_lds64_launch(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], lld, ldd, n[0], n[1], cu_count));
-                if (!dominant) dominant = "k_fwd2d_lds64";
-                lstep = 1;
-                int64_t hn2[3] = {n[0] >> 1, n[1] >> 1, n[2]};
-                cur = llbuf; cur_st = dense_strides(hn2); pp ^= 1;
-                continue;
-            }
-        }
-        // ---- streaming 2-D, two levels fused (f32) ----
-        if constexpr (sizeof(T) == 4) {
-            if (fastF && F <= 8 && two_d && env_int("WL_FUSE2", 1) && (L - l + 1) >= 2 && n[0] >= 512 && (n[0] % 16) == 0 &&
-                n[0] * n[1] >= (int64_t)env_int_raw("WL_FUSE2_MIN", 1 << 24) &&
-                n[1] >= 64 && (n[1] % 32) == 0 && cur_st.s[0] == 1 && (cur_st.s[1] % VEC) == 0 && aligned16(cur) &&
-                (b.full.s[1] % VEC) == 0 && aligned16(y) && aligned16(llbuf)) {
-                const bool lastp = (l + 1 == L);
-                T *lld = lastp ? y : llbuf;
-                const int64_t ldd = lastp ? b.full.s[1] : (n[0] >> 2);
-                bool ok = false;
-                WL_DISPATCH_F(F, WL_TRY((launch_fwd2d_pair<T, FF>(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], lld, ldd,
-                                                                  n[0], n[1], cu_count)));
-                              ok = true);
-                if (ok) {
-                    if (!dominant) dominant = "k_fwd2d_stream2";
-                    lstep = 2;
-                    int64_t hn2[3] = {n[0] >> 2, n[1] >> 2, n[2]};
-                    cur = llbuf; cur_st = dense_strides(hn2); pp ^= 1;
-                    continue;
-                }
-            }
-        }
-        // ---- streaming 2-D level ----
-        if (fastF && two_d && n[0] >= 64 * VEC && (n[0] % 8) == 0 && n[1] >= 16 && (n[1] % 16) == 0 &&
-            cur_st.s[0] == 1 && (cur_st.s[1] % VEC) == 0 && aligned16(cur) &&
-            (b.full.s[1] % VEC) == 0 && aligned16(y) && aligned16(llbuf)) {
-            WL_DISPATCH_F(F, WL_TRY((launch_fwd2d<T, FF>(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1],
-                                                         last ? (T *)nullptr : llbuf, ll_st.s[1], n[0], n[1], cu_count)));
-                          done = true);
-            if (done && !dominant) dominant = "k_fwd2d_stream";
-        }
-        // ---- streaming 1-D level (vector, or every column of a matrix) ----
-        if (!done && fastF && lines && n[0] >= 512 && (n[0] % 8) == 0 && cur_st.s[0] == 1 && aligned16(cur) &&
-            aligned16(y) && aligned16(llbuf) && (nlines == 1 || ((cur_st.s[1] % VEC) == 0 && (b.full.s[1] % VEC) == 0)) &&
-            true) {
-            T *sd = last ? y : llbuf;
-            int64_t sls = last ? b.full.s[1] : ll_st.s[1];
-            WL_DISPATCH_F(F, WL_TRY((launch_fwd1d<T, FF>(st, taps, l == 1, cur, cur_st.s[1], sd, sls, y + (n[0] >> 1),
-                                                         b.full.s[1], n[0], nlines, cu_count)));
-                          done = true);
-            if (done && !dominant) dominant = "k_fwd1d_stream";
-        }
-        // ---- 12..20 taps, Float32, blocks whose rows tile into strips of 256: one pass per level (wl_fwd2d_long.hip) ----
-        if constexpr (sizeof(T) == 4) {
-            if (!done && path == 0 && two_d && env_int("WL_LONG2D", 1) && n[0] >= env_int("WL_LONG2D_MIN_ROWS", 256) && b.full.s[0] == 1 &&
-                cur_st.s[0] == 1 && fwd2d_long_ok(F, n[0], n[1]) && (cur_st.s[1] % VEC) == 0 && aligned16(cur) && (b.full.s[1] % VEC) == 0 &&
-                aligned16(y) && aligned16(llbuf)) {
-                T *lld = last ? y : llbuf;
-                const int64_t ldd = last ? b.full.s[1] : (n[0] >> 1);
-                WL_TRY(fwd2d_long_launch(st, taps, l == 1, cur, cur_st.s[1], y, b.full.s[1], lld, ldd, n[0], n[1], cu_count));
-                if (!dominant) dominant = "k_fwd2d_lds_long";
-                lstep = 1;
-                int64_t hn2[3] = {n[0] >> 1, n[1] >> 1, n[2]};
-                cur = llbuf; cur_st = dense_strides(hn2); pp ^= 1;
-                continue;
-            }
-        }
-        // ---- long filters (12..24 taps): line kernel with multi-lane halo, 2-D as axis pass + line pass (wl_axis.hip) ----
-        if (!done && path == 0 && long_filter_ok(F) && env_int("WL_NO_LONGF", 0) == 0 && b.full.s[0] == 1 && cur_st.s[0] == 1) {
-            hipError_t e = hipSuccess;
-            const int64_t h0 = n[0] >> 1, h1 = n[1] >> 1, ldy = b.full.s[1];
-            if (lines) {
-                T *sd = last ? y : llbuf;
-                const int64_t sls = last ? ldy : ll_st.s[1];
-                done = long_lines_fwd_level<T>(st, taps, cur, cur_st.s[1], sd, sls, y + h0, ldy, n[0], nlines, cu_count, &e);
-                WL_TRY(e);
-            } else if (two_d && long_shape2d_ok(F, n[0], n[1]) && (ldy % VEC) == 0 &&
-                       (cur_st.s[1] % VEC) == 0 && aligned16(cur) && aligned16(y) && aligned16(llbuf)) {
-                // rows (dim 2) into T0 = [s-columns | d-columns], then the columns of T0 as lines with the LL quadrant routed on
-                if (!w.T0) return WL_RETRY_GEN;
-                done = long_axis_level<T>(st, taps, 1, cur, cur_st.s[1], w.T0, n[0], n[0], n[1], cu_count, &e);
-                WL_TRY(e);
-                if (done) {
-                    T *lld = last ? y : llbuf;
-                    const int64_t ldd = last ? ldy : h0;
-                    bool ok = long_lines_fwd_level<T>(st, taps, w.T0, n[0], lld, ldd, y + h0, ldy, n[0], h1, cu_count, &e);
-                    WL_TRY(e);
-                    ok = ok && long_lines_fwd_level<T>(st, taps, w.T0 + h1 * n[0], n[0], y + h1 * ldy, ldy, y + h1 * ldy + h0, ldy, n[0], h1,
-                                                       cu_count, &e);
-                    WL_TRY(e);
-                    if (!ok) return WL_EINVAL_ARG;      // (eligibility is identical for the three launches)
-                }
-            }
-            if (done && !dominant) dominant = (vlong_only(F) || n[0] < 512) ? "k_vl_lines" : "k_long_lines";
-        }
-        // ---- 3-D level from three single-axis streaming passes (wl_axis.hip) ----
-        if (!done && fastF && b.nd == 3 && b.nt == 3 && env_int("WL_NO_FAST3D", 0) == 0 && cur_st.s[0] == 1 && b.full.s[0] == 1) {
-            hipError_t e3 = hipSuccess;
-            const char *k3 = "k_fwd_axis_stream";
-            if (!w.T0) return WL_RETRY_GEN;
-            done = fast3d_fwd_level<T>(st, taps, cur, cur_st.s[1], cur_st.s[2], y, b.full.s[1], b.full.s[2],
-                                       last ? (T *)nullptr : llbuf, n, w.T0, w.T1, cu_count, &e3, &k3);
-            WL_TRY(e3);
-            if (done && !dominant) dominant = k3;
-        }
-        // ---- 2-D level of any even extents, F <= 10: one LDS-tile launch instead of two generic passes (wl_gtile.hip) ----
-        if (!done && fastF && two_d && path == 0 && env_int("WL_GTILE", 1) && b.full.s[0] == 1 && cur_st.s[0] == 1 && gtile_ok(F, n[0], n[1])) {
-            WL_TRY(gtile_launch<T>(st, taps, 1, cur, cur_st.s[1], y, b.full.s[1], last ? (T *)nullptr : llbuf, ll_st.s[1], (int)n[0], (int)n[1]));
-            if (!dominant) dominant = "k_fwd2d_gtile";
-            done = true;
-        }
-        // ---- generic level (any rank / size / filter) ----
-        if (!done) {
-            if (b.nt > 1 && !w.T0) return WL_RETRY_GEN;
-            const T *in = cur;
-            Strides3 in_st = cur_st;
-            int tog = 0;
-            for (int a = b.nt - 1; a >= 0; --a) {
-                // F <= 10: four pairs per thread from a register window, compile-time taps (wl_anyaxis.hip); else one output per thread
-                const bool any = path == 0 && env_int("WL_ANYAXIS", 1) && any_axis_ok(F, ext, a);
-                if (a != 0) {
-                    T *out = tog ? w.T1 : w.T0;
-                    if (any) WL_TRY(any_axis_pass<T>(st, taps, 1, in, in_st, out, box_st, (T *)nullptr, box_st, ext, a, lo));
-                    else WL_TRY(generic_fwd_filter_pass<T>(st, taps, in, in_st, out, box_st, (T *)nullptr, box_st, ext, a, lo));
-                    in = out; in_st = box_st; tog ^= 1;
-                } else {
-                    if (any) WL_TRY(any_axis_pass<T>(st, taps, 1, in, in_st, y, b.full, last ? (T *)nullptr : llbuf, ll_st, ext, a, lo));
-                    else WL_TRY(generic_fwd_filter_pass<T>(st, taps, in, in_st, y, b.full, last ? (T *)nullptr : llbuf, ll_st, ext, a, lo));
-                    if (!dominant) dominant = any ? "k_fwd_any" : "k_generic_fwd_filter";
-                }
-            }
-        }
-        cur = llbuf; cur_st = ll_st; pp ^= 1;
+    FwdWalk<T> s(ws, ws_gen, cu_count, path, st, b, y, x, taps, L, hip_err);
+    while (s.l <= L) {
+        level_box(b, s.l, s.n);
+        int r = 0;
+        for (auto tier : kFwdTiers<T>)
+            if ((r = (s.*tier)()) != 0) break;
+        if (r < 0) return r;
+        s.l += r;
     }
-    if (kernel_name) *kernel_name = dominant ? dominant : "none";
+    if (kernel_name) *kernel_name = s.dominant ? s.dominant : "none";
     return WL_OK;
-#undef WL_TRY
 }
+
 
 // One forward level of `nlines` independent lines with the streaming kernel (used by the packet
 // transform for fully split depths).  Returns false when the shape/filter is not eligible.
@@ -1716,13 +1685,12 @@ bool fast_lines_fwd_level(hipStream_t st, const Taps<T> &taps, const T *src, int
     constexpr int VEC = 16 / sizeof(T);
     const int F = taps.F;
     *err = hipSuccess;
-    if ((F % 2) != 0 || F > 10 || n < 512 || (n % 8) != 0 || !aligned16(src) || !aligned16(sdst) ||
-        !aligned16(ddst) || (src_ls % VEC) != 0 || (s_ls % VEC) != 0 || (d_ls % VEC) != 0)
+    if ((F % 2) != 0 || F > 10 || n < 512 || (n % 8) != 0 || !al16(src) || !al16(sdst) ||
+        !al16(ddst) || (src_ls % VEC) != 0 || (s_ls % VEC) != 0 || (d_ls % VEC) != 0)
         return false;
-    bool done = false;
-    WL_DISPATCH_F(F, *err = launch_fwd1d<T, FF>(st, taps, false, src, src_ls, sdst, s_ls, ddst, d_ls, n, nlines, cu_count);
-                  done = true);
-    return done;
+    return dispatch_taps<2, 4, 6, 8, 10>(F, [&](auto ff) {
+        *err = launch_fwd1d<T, decltype(ff)::value>(st, taps, false, src, src_ls, sdst, s_ls, ddst, d_ls, n, nlines, cu_count);
+    });
 }
 template bool fast_lines_fwd_level<float>(hipStream_t, const Taps<float> &, const float *, int64_t, float *, int64_t, float *,
                                           int64_t, int64_t, int64_t, int, hipError_t *);
@@ -1740,7 +1708,7 @@ bool fwd2d_planes(hipStream_t st, const Taps<T> &taps, const T *src, T *y, int64
     const int F = taps.F;
     *err = hipSuccess;
     if ((F % 2) != 0 || F > 10 || n0 < 64 * VEC || (n0 % 8) != 0 || n1 < 16 || (n1 % 16) != 0 || (y1 % VEC) != 0 || (y2 % VEC) != 0 ||
-        !aligned16(src) || !aligned16(y) || (ll && !aligned16(ll)) || nplanes > 65535)
+        !al16(src) || !al16(y) || (ll && !al16(ll)) || nplanes > 65535)
         return false;
     if constexpr (sizeof(T) == 4) {
         // Float32 planes of >= 256 rows: the LDS-exchange level kernel, batched over blockIdx.y (wl_fwd2d.hip)
@@ -1750,11 +1718,10 @@ bool fwd2d_planes(hipStream_t st, const Taps<T> &taps, const T *src, T *y, int64
             return true;
         }
     }
-    bool ok = false;
-    WL_DISPATCH_F(F, *err = launch_fwd2d_r<T, FF, VEC>(st, taps, false, src, n0, y, y1, ll, n0 >> 1, n0, n1, cu_count, nplanes, n0 * n1, y2,
-                                                        (n0 >> 1) * (n1 >> 1), nll);
-                  ok = true);
-    return ok;
+    return dispatch_taps<2, 4, 6, 8, 10>(F, [&](auto ff) {
+        *err = launch_fwd2d_r<T, decltype(ff)::value, VEC>(st, taps, false, src, n0, y, y1, ll, n0 >> 1, n0, n1, cu_count, nplanes, n0 * n1, y2,
+                                                           (n0 >> 1) * (n1 >> 1), nll);
+    });
 }
 template bool fwd2d_planes<float>(hipStream_t, const Taps<float> &, const float *, float *, int64_t, int64_t, float *, int64_t, int64_t,
                                   int64_t, int, int, hipError_t *);

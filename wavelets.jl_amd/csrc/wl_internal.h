@@ -50,6 +50,9 @@ inline long long opt(const char *name, long long dflt)
             if (strcmp(o->key[i], name) == 0) return o->val[i];
     return dflt;
 }
+inline int iopt(const char *name, int dflt) { return (int)opt(name, dflt); }
+// the vector paths move 16 bytes per lane
+inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <typename T>
 struct Taps {

@@ -499,35 +499,25 @@ static hipError_t launch_tail_inv(hipStream_t st, const Taps<T> &taps, const T *
     }
     const int64_t work = (int64_t)n0 * n1;
     const int threads = work >= 4096 ? 1024 : (work >= 512 ? 256 : 64);
-#define WL_TI(FC_)                                                                                             \
-    do {                                                                                                       \
-        static unsigned char attr_set[64] = {0};                                                               \
-        int dev = 0;                                                                                           \
-        (void)hipGetDevice(&dev);                                                                              \
-        dev &= 63;                                                                                             \
-        if (!attr_set[dev]) {                                                                                  \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tail_inv<T, FC_>),            \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);        \
-            if (e != hipSuccess) return e;                                                                     \
-            attr_set[dev] = 1;                                                                                 \
-        }                                                                                                      \
-        hipLaunchKernelGGL((k_tail_inv<T, FC_>), dim3((unsigned)nitems), dim3(threads), shmem, st, a, taps);   \
-    } while (0)
-    switch (taps.F) {
-    case 2: WL_TI(2); break;
-    case 4: WL_TI(4); break;
-    case 6: WL_TI(6); break;
-    case 8: WL_TI(8); break;
-    case 10: WL_TI(10); break;
-    default: WL_TI(0); break;
-    }
-#undef WL_TI
-    return hipGetLastError();
+    hipError_t e = hipSuccess;
+    auto launch = [&](auto fc) {
+        constexpr int FC = decltype(fc)::value;
+        static unsigned char attr_set[64] = {0};
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        dev &= 63;
+        if (!attr_set[dev]) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tail_inv<T, FC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e != hipSuccess) return;
+            attr_set[dev] = 1;
+        }
+        hipLaunchKernelGGL((k_tail_inv<T, FC>), dim3((unsigned)nitems), dim3(threads), shmem, st, a, taps);
+    };
+    if (!dispatch_taps<2, 4, 6, 8, 10>(taps.F, launch)) launch(std::integral_constant<int, 0>{});     // any other length: run-time taps
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------------
-static inline int i_env(const char *name, int dflt) { return (int)opt(name, dflt); }   // per-context options
-static inline bool i_al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <typename T, int F>
 static hipError_t launch_inv1d(hipStream_t st, const Taps<T> &taps, const T *ssrc, int64_t s_ls, const T *dsrc, int64_t d_ls,
@@ -540,7 +530,7 @@ static hipError_t launch_inv1d(hipStream_t st, const Taps<T> &taps, const T *ssr
     int64_t gx = (a.ntiles + 3) / 4;
     const int64_t cap = (int64_t)cu_count * 8;
     if (gx > cap) gx = cap;
-    const int64_t slab = (i_env("WL_SLAB_LINES", 32768) > 0) ? i_env("WL_SLAB_LINES", 32768) : 32768;
+    const int64_t slab = (iopt("WL_SLAB_LINES", 32768) > 0) ? iopt("WL_SLAB_LINES", 32768) : 32768;
     for (int64_t l0 = 0; l0 < nlines; l0 += slab) {      // gridDim.y <= 65535
         const int64_t nl = (nlines - l0 < slab) ? (nlines - l0) : slab;
         Inv1DArgs<T, F> b = a;
@@ -629,7 +619,7 @@ static hipError_t launch_inv1d2(hipStream_t st, const Taps<T> &taps, const T *s2
     int64_t gx = (a.ntiles + 3) / 4;
     const int64_t cap = (int64_t)cu_count * 8;
     if (gx > cap) gx = cap;
-    const int64_t slab = (i_env("WL_SLAB_LINES", 32768) > 0) ? i_env("WL_SLAB_LINES", 32768) : 32768;
+    const int64_t slab = (iopt("WL_SLAB_LINES", 32768) > 0) ? iopt("WL_SLAB_LINES", 32768) : 32768;
     for (int64_t l0 = 0; l0 < nlines; l0 += slab) {      // gridDim.y <= 65535
         const int64_t nl = (nlines - l0 < slab) ? (nlines - l0) : slab;
         Inv1D2Args<T, F> b = a;
@@ -800,9 +790,9 @@ static hipError_t launch_inv2d(hipStream_t st, const Taps<T> &taps, const T *x, 
     a.bs_x = bs_x; a.bs_ll = bs_ll; a.bs_dst = bs_dst; a.nll = nll;
     const int64_t h0 = n0 >> 1, h1 = n1 >> 1;
     a.nstrips = (int)((h0 + VP - 1) / VP);
-    int TP = i_env("WL_INV2D_TP", 64);
+    int TP = iopt("WL_INV2D_TP", 64);
     if (TP < 8 || (TP % 8) != 0) TP = 64;                 // (a test knob must not be able to divide by zero)
-    const int64_t wpc = (i_env("WL_INV2D_WAVES", 16) > 0) ? i_env("WL_INV2D_WAVES", 16) : 16;
+    const int64_t wpc = (iopt("WL_INV2D_WAVES", 16) > 0) ? iopt("WL_INV2D_WAVES", 16) : 16;
     while (TP > 8 && (int64_t)a.nstrips * ((h1 + TP - 1) / TP) * nbatch < (int64_t)cu_count * wpc) TP >>= 1;
     a.TP = TP;
     a.nchunks = (int)((h1 + TP - 1) / TP);
@@ -1017,13 +1007,13 @@ static hipError_t launch_inv2d_pair_f(hipStream_t st, const Taps<float> &taps, c
     a.x = x; a.ldx = ldx; a.ll = ll; a.ldl = ldl; a.dst = dst; a.ldd = ldd; a.n0 = n0; a.n1 = n1;
     const int64_t h0 = n0 >> 1, h1 = n1 >> 1;
     a.nstrips = (int)((h0 + 2 * VP - 1) / (2 * VP));
-    int TP = i_env("WL_INVPAIR_TP", 64);
+    int TP = iopt("WL_INVPAIR_TP", 64);
     if (TP < 8 || (TP % 8) != 0) TP = 64;
     while (TP > 16 && (int64_t)a.nstrips * ((h1 + TP - 1) / TP) < (int64_t)cu_count * 4) TP >>= 1;
     a.TP = TP;
     a.nchunks = (int)((h1 + TP - 1) / TP);
     a.tp = shrink_i<float, F>(taps);
-    a.prio = i_env("WL_INVPAIR_PRIO", 2);
+    a.prio = iopt("WL_INVPAIR_PRIO", 2);
     // four waves per SIMD: the 8-tap instance spills 18 VGPRs for it and is still far ahead of three waves without spills
     // (8192^2 db4, both levels: 126 us against 175) -- like the single-level kernel this one is latency-bound per wave
     constexpr int MW = (F <= 8) ? 4 : 2;
@@ -1031,332 +1021,339 @@ static hipError_t launch_inv2d_pair_f(hipStream_t st, const Taps<float> &taps, c
     return hipGetLastError();
 }
 
-static hipError_t launch_inv2d_pair(hipStream_t st, const Taps<float> &taps, const float *x, int64_t ldx, const float *ll, int64_t ldl,
-                                    float *dst, int64_t ldd, int64_t n0, int64_t n1, int cu_count)
-{
-    switch (taps.F) {
-    case 2: return launch_inv2d_pair_f<2>(st, taps, x, ldx, ll, ldl, dst, ldd, n0, n1, cu_count);
-    case 4: return launch_inv2d_pair_f<4>(st, taps, x, ldx, ll, ldl, dst, ldd, n0, n1, cu_count);
-    case 6: return launch_inv2d_pair_f<6>(st, taps, x, ldx, ll, ldl, dst, ldd, n0, n1, cu_count);
-    case 8: return launch_inv2d_pair_f<8>(st, taps, x, ldx, ll, ldl, dst, ldd, n0, n1, cu_count);
-    case 10: return launch_inv2d_pair_f<10>(st, taps, x, ldx, ll, ldl, dst, ldd, n0, n1, cu_count);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-#define WL_DISPATCH_FI(F_, ...)                              \
-    switch (F_) {                                            \
-    case 2: { constexpr int FF = 2; __VA_ARGS__; } break;    \
-    case 4: { constexpr int FF = 4; __VA_ARGS__; } break;    \
-    case 6: { constexpr int FF = 6; __VA_ARGS__; } break;    \
-    case 8: { constexpr int FF = 8; __VA_ARGS__; } break;    \
-    case 10: { constexpr int FF = 10; __VA_ARGS__; } break;  \
-    default: break;                                          \
-    }
+// ==========================================================================================
+// The inverse level walk, deepest level first.  InvWalk holds what every tier reads and what the level loop advances.  A tier is a
+// member function that returns the number of levels it enqueued (through took(): 1, or 2 for levels l and l - 1), 0 when it
+// declines the level -- the next tier of kInvTiers is tried -- or a negative status: WL_EHIP (through fail()), WL_RETRY_GEN,
+// WL_EINVAL_ARG.  The two tails run before the loop and return the level it starts at.
 
 template <typename T>
-int filter_inv_levels(void *ws, bool ws_gen, int cu_count, int path, hipStream_t st, const BoxSpec &b,
-                      T *y, const T *x, const Taps<T> &taps, int L, const char **kernel_name, int *hip_err)
-{
-#define WL_TRYI(expr)                                                  \
-    do {                                                               \
-        hipError_t e__ = (expr);                                       \
-        if (e__ != hipSuccess) { if (hip_err) *hip_err = (int)e__; return WL_EHIP; } \
-    } while (0)
-    const int64_t N = b.dims[0] * b.dims[1] * b.dims[2];
-    Work<T> w = carve<T>(ws, N, b.nt, ws_gen);
-    constexpr int VEC = 16 / sizeof(T);
-    const int F = taps.F;
-    const bool fastF = (path == 0) && (F % 2 == 0) && (F <= 10) && i_env("WL_NO_INVFAST", 0) == 0;
-    const bool two_d = (b.nd == 2 && b.nt == 2);
-    const bool lines = (b.nt == 1 && b.nd <= 2);
-    const int64_t nlines = lines ? b.dims[1] : 1;
-    const char *dominant = nullptr;
+struct InvWalk : WalkBase {
+    static constexpr int VEC = 16 / sizeof(T);
+    // the call
+    const BoxSpec &b; const Taps<T> &taps; const Work<T> w; hipStream_t st; int cu_count, path, L; T *y; const T *x;
+    const bool fastF, two_d, lines; const int64_t nlines;
+    // the walk: level l writes its box n to res; its approximation is llsrc, the reconstruction of the deeper level (dense), or
+    // nullptr: take it from x; pp picks the ping-pong buffer of a level that does not write y; dominant is the last tier that ran
+    // (the generic passes: only when nothing else did)
+    int l; int64_t n[3] = {0, 0, 0}; T *res = nullptr; Strides3 res_st = {{0, 0, 0}};
+    const T *llsrc = nullptr; Strides3 llsrc_st = {{0, 0, 0}}; int pp = 0; const char *dominant = nullptr;
 
-    int pp = 0;
-    const T *llsrc = nullptr;              // reconstruction of the deeper level (dense), nullptr: take it from x
-    Strides3 llsrc_st = {{0, 0, 0}};
-    int l_start = L;
+    InvWalk(void *ws, bool ws_gen, int cu_count_, int path_, hipStream_t st_, const BoxSpec &b_, T *y_, const T *x_, const Taps<T> &taps_,
+            int L_, int *hip_err_)
+        : WalkBase{taps_.F, hip_err_}, b(b_), taps(taps_), w(carve<T>(ws, b_.dims[0] * b_.dims[1] * b_.dims[2], b_.nt, ws_gen)), st(st_),
+          cu_count(cu_count_), path(path_), L(L_), y(y_), x(x_),
+          fastF((path_ == 0) && (F % 2 == 0) && (F <= 10) && iopt("WL_NO_INVFAST", 0) == 0), two_d(b_.nd == 2 && b_.nt == 2),
+          lines(b_.nt == 1 && b_.nd <= 2), nlines(lines ? b_.dims[1] : 1), l(L_) {}
+
+    // where level lv is written: y at level 1, else the ping-pong buffer (dense)
+    T *out(int lv) const { return lv == 1 ? y : (pp ? w.B : w.A); }
+    void enter() { level_box(b, l, n); res = out(l); res_st = (l == 1) ? b.full : dense_strides(n); }
+    // a launch that takes level l - 1 as well writes that level's box
+    struct Shallower { int64_t n[3]; T *res; int64_t ld; };
+    Shallower shallower() const
+    {
+        Shallower s;
+        level_box(b, l - 1, s.n);
+        s.res = out(l - 1); s.ld = (l - 1 == 1) ? b.full.s[1] : s.n[0];
+        return s;
+    }
+    // the approximation of level l and its leading dimension
+    const T *ss() const { return llsrc ? llsrc : x; }
+    int64_t sls() const { return llsrc ? llsrc_st.s[1] : b.full.s[1]; }
+    bool ll_ok(int mod) const { return !llsrc || (al16(llsrc) && (llsrc_st.s[1] % mod) == 0); }
+    // the 16-byte contract of the vector kernels: leading dimensions in whole vectors, every base aligned
+    bool vec16(int ll_mod = 2) const { return (b.full.s[1] % VEC) == 0 && (res_st.s[1] % VEC) == 0 && al16(x) && al16(res) && ll_ok(ll_mod); }
+    // the epilogue of every tier: levels l .. l - NL + 1 are enqueued, the next one takes its approximation from the last of them
+    int took(int NL, const char *name)
+    {
+        int64_t no[3];
+        level_box(b, l - NL + 1, no);
+        dominant = name;
+        llsrc = out(l - NL + 1); llsrc_st = dense_strides(no); pp ^= 1;
+        return NL;
+    }
+
     // ---- LDS tail: the deepest levels whose output fits one workgroup's LDS ----
-    if (path == 0 && i_env("WL_NO_INVTAIL", 0) == 0 && (two_d || lines) && b.full.s[0] == 1) {
+    int tail()
+    {
+        if (!(path == 0 && iopt("WL_NO_INVTAIL", 0) == 0 && (two_d || lines) && b.full.s[0] == 1)) return l;
         int l_lo = L + 1;
+        int64_t nq[3];
         for (int q = L; q >= 1; --q) {
-            int64_t nq[3];
             level_box(b, q, nq);
             const int64_t blk = two_d ? nq[0] * nq[1] : nq[0];
             const bool fits = two_d ? (((nq[0] | 1) * nq[1]) <= inv_tail_cap<T>() + 256 && nq[1] <= 256)
                                     : (2 * nq[0] <= 2 * (int64_t)inv_tail_cap<T>());
             // 12 ... 20 taps on power-of-two blocks of <= 4096 elements / lines: the LDS-resident tail is instantiated for them (as in
             // the forward direction); other long-filter shapes leave the tail at 64 / 16 samples, the chip-wide kernels take the rest
-            const bool long_tail = F >= 12 && i_env("WL_LONG_TAIL", 1) != 0 && i_env("WL_TAIL2", 1) != 0 &&
+            const bool long_tail = F >= 12 && iopt("WL_LONG_TAIL", 1) != 0 && iopt("WL_TAIL2", 1) != 0 &&
                                    (two_d ? tail2_inv_ok<T>(F, 2, nq[0], nq[1], L - q + 1, y, 0) : tail2_inv_ok<T>(F, 1, nq[0], 1, L - q + 1, y, b.full.s[1]));
             const int64_t vl_cap = long_tail ? (int64_t)4096
-                                   : ((vlong_filter_ok(taps.F) && i_env("WL_NO_LONGF", 0) == 0) ? (two_d ? 64 : 16) : ((int64_t)1 << 40));
-            if (blk <= (int64_t)i_env("WL_INVTAIL_MAX", 4096) && blk <= vl_cap && blk <= inv_tail_cap<T>() && fits && nq[0] < (1 << 20)) l_lo = q; else break;
+                                   : ((vlong_filter_ok(taps.F) && iopt("WL_NO_LONGF", 0) == 0) ? (two_d ? 64 : 16) : ((int64_t)1 << 40));
+            if (blk <= (int64_t)iopt("WL_INVTAIL_MAX", 4096) && blk <= vl_cap && blk <= inv_tail_cap<T>() && fits && nq[0] < (1 << 20)) l_lo = q; else break;
         }
-        if (l_lo <= L) {
-            int64_t nq[3];
-            level_box(b, l_lo, nq);
-            const bool to_y = (l_lo == 1);
-            T *res = to_y ? y : (pp ? w.B : w.A);
-            Strides3 res_st = to_y ? b.full : dense_strides(nq);
-            // power-of-two blocks / lines of <= 16 KiB with a <= 10-tap filter: the latency-optimised tail (wl_tail.hip)
-            const bool t2 = i_env("WL_TAIL2", 1) != 0 &&
-                            (two_d ? tail2_inv_ok<T>(F, 2, nq[0], nq[1], L - l_lo + 1, res, 0)
-                                   : tail2_inv_ok<T>(F, 1, nq[0], 1, L - l_lo + 1, res, res_st.s[1]));
-            if (two_d) {
-                if (t2) WL_TRYI(launch_tail2_inv<T>(st, taps, x, b.full.s[1], 0, res, res_st.s[1], 0, 1, (int)nq[0], (int)nq[1], 2, L - l_lo + 1));
-                else WL_TRYI(launch_tail_inv<T>(st, taps, x, b.full.s[1], 0, res, res_st.s[1], 0, 1, (int)nq[0], (int)nq[1], 2, L - l_lo + 1));
-            } else {
-                if (t2) WL_TRYI(launch_tail2_inv<T>(st, taps, x, 0, b.full.s[1], res, 0, res_st.s[1], (int)nlines, (int)nq[0], 1, 1, L - l_lo + 1));
-                else WL_TRYI(launch_tail_inv<T>(st, taps, x, 0, b.full.s[1], res, 0, res_st.s[1], (int)nlines, (int)nq[0], 1, 1, L - l_lo + 1));
-            }
-            dominant = t2 ? "k_tail2_inv" : "k_tail_inv";
-            llsrc = res; llsrc_st = dense_strides(nq); pp ^= 1;
-            l_start = l_lo - 1;
-        }
+        if (l_lo > L) return l;
+        level_box(b, l_lo, nq);
+        const int NL = L - l_lo + 1;
+        T *r = out(l_lo);
+        const Strides3 r_st = (l_lo == 1) ? b.full : dense_strides(nq);
+        // power-of-two blocks / lines of <= 16 KiB with a <= 10-tap filter: the latency-optimised tail (wl_tail.hip)
+        const bool t2 = iopt("WL_TAIL2", 1) != 0 &&
+                        (two_d ? tail2_inv_ok<T>(F, 2, nq[0], nq[1], NL, r, 0) : tail2_inv_ok<T>(F, 1, nq[0], 1, NL, r, r_st.s[1]));
+        const auto launch = t2 ? launch_tail2_inv<T> : launch_tail_inv<T>;
+        if (two_d) WL_WALK_TRY(launch(st, taps, x, b.full.s[1], 0, r, r_st.s[1], 0, 1, (int)nq[0], (int)nq[1], 2, NL));
+        else WL_WALK_TRY(launch(st, taps, x, 0, b.full.s[1], r, 0, r_st.s[1], (int)nlines, (int)nq[0], 1, 1, NL));
+        return l - took(NL, t2 ? "k_tail2_inv" : "k_tail_inv");
     }
     // ---- 3-D: the deepest levels whose output is a power-of-two box of <= 4096 elements, one workgroup (wl_tail.hip) ----
-    if (path == 0 && b.nd == 3 && b.nt == 3 && i_env("WL_TAIL3", 1) != 0 && b.full.s[0] == 1 && l_start == L) {
+    int tail3()
+    {
+        if (!(path == 0 && b.nd == 3 && b.nt == 3 && iopt("WL_TAIL3", 1) != 0 && b.full.s[0] == 1 && l == L)) return l;
         int l_lo = L + 1;
+        int64_t nq[3];
         for (int q = L; q >= 1; --q) {
-            int64_t nq[3];
             level_box(b, q, nq);
             if (tail3_ok<T>(F, nq[0], nq[1], nq[2], L - q + 1)) l_lo = q; else break;
         }
-        if (l_lo <= L) {
-            int64_t nq[3];
-            level_box(b, l_lo, nq);
-            const bool to_y = (l_lo == 1);
-            T *res = to_y ? y : (pp ? w.B : w.A);
-            Strides3 res_st = to_y ? b.full : dense_strides(nq);
-            WL_TRYI(launch_tail3<T>(st, taps, 0, x, b.full.s[1], b.full.s[2], res, res_st.s[1], res_st.s[2], (int)nq[0], (int)nq[1], (int)nq[2],
-                                    L - l_lo + 1));
-            dominant = "k_tail3";
-            llsrc = res; llsrc_st = dense_strides(nq); pp ^= 1;
-            l_start = l_lo - 1;
-        }
+        if (l_lo > L) return l;
+        level_box(b, l_lo, nq);
+        T *r = out(l_lo);
+        const Strides3 r_st = (l_lo == 1) ? b.full : dense_strides(nq);
+        WL_WALK_TRY(launch_tail3<T>(st, taps, 0, x, b.full.s[1], b.full.s[2], r, r_st.s[1], r_st.s[2], (int)nq[0], (int)nq[1], (int)nq[2], L - l_lo + 1));
+        return l - took(L - l_lo + 1, "k_tail3");
     }
-    for (int l = l_start; l >= 1; --l) {
-        int64_t n[3];
-        level_box(b, l, n);
-        Extent3 ext = {{n[0], n[1], n[2]}};
-        Extent3 lo = low_corner(b, n);
-        Strides3 box_st = dense_strides(n);
-        T *res = (l == 1) ? y : (pp ? w.B : w.A);
-        Strides3 res_st = (l == 1) ? b.full : box_st;
-        bool done = false;
-        // the LDS-exchange level kernel (wl_inv2d_long.hip: which filter lengths per element type), output rows a multiple of 256
-        auto try_lds_long = [&]() -> hipError_t {
-            if (!done && path == 0 && two_d && i_env("WL_INVLONG2D", 1) != 0 && n[0] >= i_env("WL_INVLONG2D_MIN_ROWS", 256) && b.full.s[0] == 1 &&
-                inv2d_long_ok(F, n[0], n[1], (int)sizeof(T)) && (b.full.s[1] % VEC) == 0 && (res_st.s[1] % VEC) == 0 && i_al16(x) && i_al16(res) &&
-                (!llsrc || (i_al16(llsrc) && (llsrc_st.s[1] % 2) == 0))) {
-                hipError_t e = inv2d_long_launch<T>(st, taps, x, b.full.s[1], llsrc, llsrc ? llsrc_st.s[1] : 0, res, res_st.s[1], n[0], n[1], cu_count);
-                if (e != hipSuccess) return e;
-                dominant = "k_inv2d_lds_long";
-                done = true;
-            }
-            return hipSuccess;
-        };
-        // 8 / 10 taps: ahead of the streaming kernels where it is enabled for them (WL_INVLONG_FMIN / _FMIN64) and the block is large
-        if (F <= 10 && n[0] * n[1] >= (int64_t)i_env("WL_INVLONG_SHORT_MIN", 1 << 22) &&
-            !(sizeof(T) == 4 && F <= 8 && l >= 2 && (l % 2) == 0)) WL_TRYI(try_lds_long());
 
-        // ---- big 2-D blocks: levels l and l-1 in one launch, the level-l reconstruction handed over through an LDS column ring ----
+    // ---- the LDS-exchange level kernel (wl_inv2d_long.hip: which filter lengths per element type), output rows a multiple of 256 ----
+    int lds_long()
+    {
+        if (!(path == 0 && two_d && iopt("WL_INVLONG2D", 1) != 0 && n[0] >= iopt("WL_INVLONG2D_MIN_ROWS", 256) && b.full.s[0] == 1 &&
+              inv2d_long_ok(F, n[0], n[1], (int)sizeof(T)) && vec16()))
+            return 0;
+        WL_WALK_TRY(inv2d_long_launch<T>(st, taps, x, b.full.s[1], llsrc, llsrc ? llsrc_st.s[1] : 0, res, res_st.s[1], n[0], n[1], cu_count));
+        return took(1, "k_inv2d_lds_long");
+    }
+    // 8 / 10 taps: ahead of the streaming kernels where it is enabled for them (WL_INVLONG_FMIN / _FMIN64) and the block is large --
+    // but not where the Float32 pair below may take levels l and l - 1
+    int lds_long_short()
+    {
+        const bool pair_level = sizeof(T) == 4 && F <= 8 && l >= 2 && (l % 2) == 0;
+        return (F <= 10 && n[0] * n[1] >= (int64_t)iopt("WL_INVLONG_SHORT_MIN", 1 << 22) && !pair_level) ? lds_long() : 0;
+    }
+    // 12..20 taps: the whole 2-D level in one pass
+    int lds_long_12() { return F >= 12 ? lds_long() : 0; }
+    // ---- big 2-D blocks: levels l and l-1 in one launch, the level-l reconstruction handed over through an LDS column ring ----
+    int pair()
+    {
         if constexpr (sizeof(T) == 4) {
             // (l even: the pairs end at level 1, so the two biggest levels share a launch)
-            if (!done && fastF && two_d && l >= 2 && (l % 2) == 0 && i_env("WL_INV_PAIR", 1) != 0 && b.full.s[0] == 1 && (b.full.s[1] % VEC) == 0 && i_al16(x) &&
-                (!llsrc || (i_al16(llsrc) && (llsrc_st.s[1] % 2) == 0))) {
-                int64_t n1[3];
-                level_box(b, l - 1, n1);                    // output extents of the shallower level
-                T *res1 = (l - 1 == 1) ? y : (pp ? w.B : w.A);
-                const int64_t r_ld = (l - 1 == 1) ? b.full.s[1] : n1[0];
-                if (n1[0] == 2 * n[0] && n1[1] == 2 * n[1] && n1[0] * n1[1] >= (int64_t)i_env("WL_INV_PAIR_MIN", 1 << 24) &&
-                    inv2d_pair_ok(F, n1[0], n1[1]) && (r_ld % VEC) == 0 && i_al16(res1)) {
-                    WL_TRYI(launch_inv2d_pair(st, taps, x, b.full.s[1], llsrc, llsrc_st.s[1], res1, r_ld, n1[0], n1[1], cu_count));
-                    dominant = "k_inv2d_pair";
-                    llsrc = res1; llsrc_st = dense_strides(n1); pp ^= 1;
-                    --l;                                     // two levels consumed
-                    continue;
-                }
-            }
+            if (!(fastF && two_d && l >= 2 && (l % 2) == 0 && iopt("WL_INV_PAIR", 1) != 0 && b.full.s[0] == 1 && (b.full.s[1] % VEC) == 0 &&
+                  al16(x) && ll_ok(2)))
+                return 0;
+            const Shallower s1 = shallower();
+            if (!(s1.n[0] == 2 * n[0] && s1.n[1] == 2 * n[1] && s1.n[0] * s1.n[1] >= (int64_t)iopt("WL_INV_PAIR_MIN", 1 << 24) &&
+                  inv2d_pair_ok(F, s1.n[0], s1.n[1]) && (s1.ld % VEC) == 0 && al16(s1.res)))
+                return 0;
+            const int r = with_taps([&](auto ff) {
+                return launch_inv2d_pair_f<decltype(ff)::value>(st, taps, x, b.full.s[1], llsrc, llsrc_st.s[1], s1.res, s1.ld, s1.n[0], s1.n[1], cu_count);
+            });
+            return r > 0 ? took(2, "k_inv2d_pair") : r;
         }
-        // ---- small 2-D blocks: two levels (l and l-1) per launch, LDS tiles (wl_tile.hip) ----
-        // (round 5: 12..20 taps as well -- these levels ran one streaming launch each and the 128^2 level as two line passes)
-        if (!done && (fastF || (F >= 12 && F <= 20 && (F % 2) == 0 && i_env("WL_TILE_INV_LONG", 1) != 0)) && two_d && path == 0 && l >= 2 &&
-            i_env("WL_TILE_INV", 1) != 0 && b.full.s[0] == 1) {
-            int64_t n1[3];
-            level_box(b, l - 1, n1);                        // output extents of the shallower level
-            if (inv2d_tile2_ok<T>(F, n1[0], n1[1]) && n1[0] <= i_env("WL_TILE_INV_MAX", 1024) && n1[1] <= i_env("WL_TILE_INV_MAX", 1024)) {
-                T *res1 = (l - 1 == 1) ? y : (pp ? w.B : w.A);
-                const int64_t r_ld = (l - 1 == 1) ? b.full.s[1] : n1[0];
-                const T *ss = llsrc ? llsrc : x;
-                const int64_t sls = llsrc ? llsrc_st.s[1] : b.full.s[1];
-                WL_TRYI(inv2d_tile2_launch<T>(st, taps, x, b.full.s[1], ss, sls, res1, r_ld, (int)n1[0], (int)n1[1]));
-                dominant = "k_inv2d_tile2";
-                llsrc = res1; llsrc_st = dense_strides(n1); pp ^= 1;
-                --l;                                         // two levels consumed
-                continue;
-            }
-        }
-        // ---- lines: two levels (l and l-1) per launch ----
-        if (fastF && lines && l >= 2 && i_env("WL_NO_INV1D2", 0) == 0 && n[0] >= 512 && (n[0] % 8) == 0 && b.full.s[0] == 1 &&
-            i_al16(x) && i_al16(y) && (nlines == 1 || ((b.full.s[1] % VEC) == 0 && (!llsrc || (llsrc_st.s[1] % VEC) == 0)))) {
-            int64_t n1[3];
-            level_box(b, l - 1, n1);                        // output extents of the shallower level: n1[0] = 2 n[0]
-            T *res1 = (l - 1 == 1) ? y : (pp ? w.B : w.A);
-            const int64_t r_ls = (l - 1 == 1) ? b.full.s[1] : n1[0];
-            const T *ss = llsrc ? llsrc : x;
-            const int64_t sls = llsrc ? llsrc_st.s[1] : b.full.s[1];
-            if (i_al16(ss) && i_al16(res1)) {
-                WL_DISPATCH_FI(F, WL_TRYI((launch_inv1d2<T, FF>(st, taps, ss, sls, x + (n[0] >> 1), b.full.s[1], x + n[0], b.full.s[1],
-                                                                res1, r_ls, n1[0], nlines, cu_count)));
-                               done = true);
-            }
-            if (done) {
-                dominant = "k_inv1d_stream2";
-                llsrc = res1; llsrc_st = dense_strides(n1); pp ^= 1;
-                --l;                                         // two levels consumed
-                continue;
-            }
-        }
-        if (fastF && lines && n[0] >= 512 && (n[0] % 8) == 0 && b.full.s[0] == 1 && i_al16(x) && i_al16(y) &&
-            (nlines == 1 || (b.full.s[1] % VEC) == 0)) {
-            const T *ss = llsrc ? llsrc : x;
-            const int64_t sls = llsrc ? llsrc_st.s[1] : b.full.s[1];
-            WL_DISPATCH_FI(F, WL_TRYI((launch_inv1d<T, FF>(st, taps, ss, sls, x + (n[0] >> 1), b.full.s[1], res, res_st.s[1],
-                                                           n[0], nlines, cu_count)));
-                           done = true);
-            if (done) dominant = "k_inv1d_stream";
-        }
-        // ---- fused 2-D level: one pass over HBM ----
-        if (!done && fastF && two_d && i_env("WL_NO_INV2D", 0) == 0 && n[0] >= 128 && (n[0] % 8) == 0 && n[1] >= 16 &&
-            (n[1] % 8) == 0 && (F < 10 || (n[1] % 16) == 0) && b.full.s[0] == 1 && (b.full.s[1] % VEC) == 0 && (res_st.s[1] % VEC) == 0 && i_al16(x) && i_al16(res) &&
-            (!llsrc || (i_al16(llsrc) && (llsrc_st.s[1] % 2) == 0))) {
-            // pairs per lane: 2 (8-byte loads / 16-byte stores for f32) from 256 rows, 1 below; 4 is a tuning option for f32
-            int ppl = i_env("WL_INV2D_PPL", 2);
-            if (n[0] < 256) ppl = 1;
-            else if (n[0] < 512 || sizeof(T) != 4 || ppl != 4) ppl = 2;
-            if (ppl == 4) {
-                if constexpr (sizeof(T) == 4) {
-                    WL_DISPATCH_FI(F, WL_TRYI((launch_inv2d<T, FF, 4>(st, taps, x, b.full.s[1], llsrc, llsrc_st.s[1], res, res_st.s[1],
-                                                                       n[0], n[1], cu_count)));
-                                    done = true);
-                }
-            } else if (ppl == 2) {
-                WL_DISPATCH_FI(F, WL_TRYI((launch_inv2d<T, FF, 2>(st, taps, x, b.full.s[1], llsrc, llsrc_st.s[1], res, res_st.s[1],
-                                                                   n[0], n[1], cu_count)));
-                                done = true);
-            } else {
-                WL_DISPATCH_FI(F, WL_TRYI((launch_inv2d<T, FF, 1>(st, taps, x, b.full.s[1], llsrc, llsrc_st.s[1], res, res_st.s[1],
-                                                                   n[0], n[1], cu_count)));
-                                done = true);
-            }
-            if (done) dominant = "k_inv2d_stream";
-        }
-        if (!done && fastF && two_d && n[0] >= 512 && (n[0] % 8) == 0 && n[1] >= 32 && (n[1] % 16) == 0 &&
-            b.full.s[0] == 1 && (b.full.s[1] % VEC) == 0 && i_al16(x) && i_al16(y)) {
-            // dim-1 pass: every column is a line of length n0: s = rows [0,h0), d = rows [h0,n0)
-            const int64_t h0 = n[0] >> 1, h1 = n[1] >> 1;
-            if (!w.T0) return WL_RETRY_GEN;
-            T *tmp = w.T0;                         // n0 x n1 dense
-            bool ok = true;
-            if (llsrc) {
-                // columns [0,h1): approximation from the deeper reconstruction; columns [h1,n1): from x
-                WL_DISPATCH_FI(F, WL_TRYI((launch_inv1d<T, FF>(st, taps, llsrc, llsrc_st.s[1], x + h0, b.full.s[1], tmp, n[0],
-                                                               n[0], h1, cu_count)));
-                               WL_TRYI((launch_inv1d<T, FF>(st, taps, x + h1 * b.full.s[1], b.full.s[1], x + h1 * b.full.s[1] + h0,
-                                                            b.full.s[1], tmp + h1 * n[0], n[0], n[0], h1, cu_count))));
-            } else {
-                WL_DISPATCH_FI(F, WL_TRYI((launch_inv1d<T, FF>(st, taps, x, b.full.s[1], x + h0, b.full.s[1], tmp, n[0], n[0], n[1],
-                                                               cu_count))));
-            }
-            // dim-2 pass
-            WL_DISPATCH_FI(F, WL_TRYI((launch_inv_dim2<T, FF>(st, taps, tmp, n[0], res, res_st.s[1], n[0], n[1], cu_count))));
-            (void)ok;
-            done = true;
-            dominant = "k_inv_dim2_stream";
-        }
-        // ---- batch of independent 2-D blocks (box n0 x n1 x B, first two axes transformed): the fused inverse level
-        //      kernel with the planes over blockIdx.y ----
-        if (!done && path == 0 && (fastF || (F >= 12 && F <= 20)) && b.nd == 3 && b.nt == 2 && b.full.s[0] == 1 && (l == 1 || res_st.s[1] == n[0])) {
-            hipError_t e = hipSuccess;
-            const char *kn = nullptr;
-            done = inv2d_planes<T>(st, taps, x, b.full.s[1], b.full.s[2], llsrc, res, n[0], n[1], n[2], llsrc ? (int)n[2] : 0, cu_count, &e, &kn,
-                                   res_st.s[2]);      // (l == 1: y's own plane stride, the caller's image_stride; deeper levels: dense)
-            WL_TRYI(e);
-            if (done) dominant = kn;
-        }
-        // ---- 12..20 taps, output rows a multiple of 256: the whole 2-D level in one pass (wl_inv2d_long.hip) ----
-        if (!done && F >= 12) WL_TRYI(try_lds_long());
-        // ---- long filters (12..24 taps) ----
-        if (!done && path == 0 && long_filter_ok(F) && i_env("WL_NO_LONGF", 0) == 0 && b.full.s[0] == 1) {
-            hipError_t e = hipSuccess;
-            const int64_t h0 = n[0] >> 1, h1 = n[1] >> 1, ldx = b.full.s[1];
-            if (lines) {
-                const T *ss = llsrc ? llsrc : x;
-                const int64_t sls = llsrc ? llsrc_st.s[1] : ldx;
-                done = long_lines_inv_level<T>(st, taps, ss, sls, x + h0, ldx, res, res_st.s[1], n[0], nlines, cu_count, &e);
-                WL_TRYI(e);
-            } else if (two_d && long_shape2d_ok(F, n[0], n[1]) && (ldx % VEC) == 0 &&
-                       (res_st.s[1] % VEC) == 0 && i_al16(x) && i_al16(res) && (!llsrc || (i_al16(llsrc) && (llsrc_st.s[1] % VEC) == 0))) {
-                // columns (dim 1) into T0, the approximation quadrant from the deeper reconstruction; then rows (dim 2)
-                const T *ss = llsrc ? llsrc : x;
-                const int64_t sls = llsrc ? llsrc_st.s[1] : ldx;
-                if (!w.T0) return WL_RETRY_GEN;
-                done = long_lines_inv_level<T>(st, taps, ss, sls, x + h0, ldx, w.T0, n[0], n[0], h1, cu_count, &e);
-                WL_TRYI(e);
-                if (done) {
-                    bool ok = long_lines_inv_level<T>(st, taps, x + h1 * ldx, ldx, x + h1 * ldx + h0, ldx, w.T0 + h1 * n[0], n[0], n[0], h1,
-                                                      cu_count, &e);
-                    WL_TRYI(e);
-                    ok = ok && long_axis_level<T>(st, taps, 0, w.T0, n[0], res, res_st.s[1], n[0], n[1], cu_count, &e);
-                    WL_TRYI(e);
-                    if (!ok) return WL_EINVAL_ARG;
-                }
-            }
-            if (done) dominant = (vlong_only(F) || n[0] < 512) ? "k_vl_lines" : "k_long_lines";
-        }
-        if (!done && fastF && b.nd == 3 && b.nt == 3 && i_env("WL_NO_FAST3D", 0) == 0 && b.full.s[0] == 1 && res_st.s[0] == 1) {
-            hipError_t e3 = hipSuccess;
-            if (!w.T0) return WL_RETRY_GEN;
-            const char *k3 = "k_inv_axis_stream";
-            done = fast3d_inv_level<T>(st, taps, x, b.full.s[1], b.full.s[2], llsrc, res, res_st.s[1], res_st.s[2], n,
-                                       w.T0, w.T1, cu_count, &e3, &k3);
-            WL_TRYI(e3);
-            if (done) dominant = k3;
-        }
-        // ---- 2-D level of any even extents, F <= 10: one LDS-tile launch instead of two generic passes (wl_gtile.hip) ----
-        if (!done && fastF && two_d && path == 0 && i_env("WL_GTILE", 1) && b.full.s[0] == 1 && res_st.s[0] == 1 && gtile_ok(F, n[0], n[1])) {
-            WL_TRYI(gtile_launch<T>(st, taps, 0, x, b.full.s[1], res, res_st.s[1], const_cast<T *>(llsrc), llsrc ? llsrc_st.s[1] : 0, (int)n[0],
-                                    (int)n[1]));
-            dominant = "k_inv2d_gtile";
-            done = true;
-        }
-        if (!done) {
-            if (b.nt > 1 && !w.T0) return WL_RETRY_GEN;
-            const T *in = x;
-            Strides3 in_st = b.full;
-            int tog = 0;
-            for (int a = 0; a < b.nt; ++a) {
-                const bool firstp = (a == 0), lastp = (a == b.nt - 1);
-                T *out; Strides3 out_st;
-                if (lastp) { out = res; out_st = res_st; }
-                else { out = tog ? w.T1 : w.T0; out_st = box_st; tog ^= 1; }
-                const bool any = path == 0 && i_env("WL_ANYAXIS", 1) && any_axis_ok(F, ext, a);
-                if (any)
-                    WL_TRYI(any_axis_pass<T>(st, taps, 0, in, in_st, out, out_st, firstp ? const_cast<T *>(llsrc) : (T *)nullptr, llsrc_st, ext, a, lo));
-                else
-                    WL_TRYI(generic_inv_filter_pass<T>(st, taps, in, in_st, firstp ? llsrc : (const T *)nullptr, llsrc_st, out, out_st, ext, a, lo));
-                in = out; in_st = out_st;
-                if (lastp && !dominant) dominant = any ? "k_inv_any" : "k_generic_inv_filter";
-            }
-        }
-        llsrc = res; llsrc_st = box_st; pp ^= 1;
+        return 0;
     }
-    if (kernel_name) *kernel_name = dominant ? dominant : "none";
+    // ---- small 2-D blocks: two levels (l and l-1) per launch, LDS tiles (wl_tile.hip) ----
+    // (round 5: 12..20 taps as well -- these levels ran one streaming launch each and the 128^2 level as two line passes)
+    int tile2()
+    {
+        if (!((fastF || (F >= 12 && F <= 20 && (F % 2) == 0 && iopt("WL_TILE_INV_LONG", 1) != 0)) && two_d && path == 0 && l >= 2 &&
+              iopt("WL_TILE_INV", 1) != 0 && b.full.s[0] == 1))
+            return 0;
+        const Shallower s1 = shallower();
+        if (!(inv2d_tile2_ok<T>(F, s1.n[0], s1.n[1]) && s1.n[0] <= iopt("WL_TILE_INV_MAX", 1024) && s1.n[1] <= iopt("WL_TILE_INV_MAX", 1024))) return 0;
+        WL_WALK_TRY(inv2d_tile2_launch<T>(st, taps, x, b.full.s[1], ss(), sls(), s1.res, s1.ld, (int)s1.n[0], (int)s1.n[1]));
+        return took(2, "k_inv2d_tile2");
+    }
+    // ---- lines: two levels (l and l-1) per launch ----
+    int lines2()
+    {
+        if (!(fastF && lines && l >= 2 && iopt("WL_NO_INV1D2", 0) == 0 && n[0] >= 512 && (n[0] % 8) == 0 && b.full.s[0] == 1 && al16(x) &&
+              al16(y) && (nlines == 1 || ((b.full.s[1] % VEC) == 0 && (!llsrc || (llsrc_st.s[1] % VEC) == 0)))))
+            return 0;
+        const Shallower s1 = shallower();                // s1.n[0] = 2 n[0]
+        if (!(al16(ss()) && al16(s1.res))) return 0;
+        const int r = with_taps([&](auto ff) {
+            return launch_inv1d2<T, decltype(ff)::value>(st, taps, ss(), sls(), x + (n[0] >> 1), b.full.s[1], x + n[0], b.full.s[1], s1.res, s1.ld,
+                                                         s1.n[0], nlines, cu_count);
+        });
+        return r > 0 ? took(2, "k_inv1d_stream2") : r;
+    }
+    // ---- lines: one level per launch ----
+    int lines1()
+    {
+        if (!(fastF && lines && n[0] >= 512 && (n[0] % 8) == 0 && b.full.s[0] == 1 && al16(x) && al16(y) && (nlines == 1 || (b.full.s[1] % VEC) == 0)))
+            return 0;
+        const int r = with_taps([&](auto ff) {
+            return launch_inv1d<T, decltype(ff)::value>(st, taps, ss(), sls(), x + (n[0] >> 1), b.full.s[1], res, res_st.s[1], n[0], nlines, cu_count);
+        });
+        return r > 0 ? took(1, "k_inv1d_stream") : r;
+    }
+    // ---- fused 2-D level: one pass over HBM ----
+    int stream2d()
+    {
+        if (!(fastF && two_d && iopt("WL_NO_INV2D", 0) == 0 && n[0] >= 128 && (n[0] % 8) == 0 && n[1] >= 16 && (n[1] % 8) == 0 &&
+              (F < 10 || (n[1] % 16) == 0) && b.full.s[0] == 1 && vec16()))
+            return 0;
+        // pairs per lane: 2 (8-byte loads / 16-byte stores for f32) from 256 rows, 1 below; 4 is a tuning option for f32
+        int ppl = iopt("WL_INV2D_PPL", 2);
+        if (n[0] < 256) ppl = 1;
+        else if (n[0] < 512 || sizeof(T) != 4 || ppl != 4) ppl = 2;
+        const int r = with_taps([&](auto ff) {
+            constexpr int FF = decltype(ff)::value;
+            if constexpr (sizeof(T) == 4)
+                if (ppl == 4) return launch_inv2d<T, FF, 4>(st, taps, x, b.full.s[1], llsrc, llsrc_st.s[1], res, res_st.s[1], n[0], n[1], cu_count);
+            if (ppl == 2) return launch_inv2d<T, FF, 2>(st, taps, x, b.full.s[1], llsrc, llsrc_st.s[1], res, res_st.s[1], n[0], n[1], cu_count);
+            return launch_inv2d<T, FF, 1>(st, taps, x, b.full.s[1], llsrc, llsrc_st.s[1], res, res_st.s[1], n[0], n[1], cu_count);
+        });
+        return r > 0 ? took(1, "k_inv2d_stream") : r;
+    }
+    // ---- 2-D level as a line pass into T0 and a dim-2 pass ----
+    int dim2()
+    {
+        if (!(fastF && two_d && n[0] >= 512 && (n[0] % 8) == 0 && n[1] >= 32 && (n[1] % 16) == 0 && b.full.s[0] == 1 && (b.full.s[1] % VEC) == 0 &&
+              al16(x) && al16(y)))
+            return 0;
+        // dim-1 pass: every column is a line of length n0: s = rows [0,h0), d = rows [h0,n0)
+        const int64_t h0 = n[0] >> 1, h1 = n[1] >> 1, ldx = b.full.s[1];
+        if (!w.T0) return WL_RETRY_GEN;
+        T *tmp = w.T0;                         // n0 x n1 dense
+        const int r = with_taps([&](auto ff) {
+            constexpr int FF = decltype(ff)::value;
+            // columns [0,h1): approximation from the deeper reconstruction when there is one; columns [h1,n1): from x
+            hipError_t e = launch_inv1d<T, FF>(st, taps, ss(), sls(), x + h0, ldx, tmp, n[0], n[0], llsrc ? h1 : n[1], cu_count);
+            if (e == hipSuccess && llsrc)
+                e = launch_inv1d<T, FF>(st, taps, x + h1 * ldx, ldx, x + h1 * ldx + h0, ldx, tmp + h1 * n[0], n[0], n[0], h1, cu_count);
+            // dim-2 pass
+            return e != hipSuccess ? e : launch_inv_dim2<T, FF>(st, taps, tmp, n[0], res, res_st.s[1], n[0], n[1], cu_count);
+        });
+        return r > 0 ? took(1, "k_inv_dim2_stream") : r;
+    }
+    // ---- batch of independent 2-D blocks (box n0 x n1 x B, first two axes transformed): the fused inverse level
+    //      kernel with the planes over blockIdx.y ----
+    int planes()
+    {
+        if (!(path == 0 && (fastF || (F >= 12 && F <= 20)) && b.nd == 3 && b.nt == 2 && b.full.s[0] == 1 && (l == 1 || res_st.s[1] == n[0]))) return 0;
+        hipError_t e = hipSuccess;
+        const char *kn = nullptr;
+        const bool done = inv2d_planes<T>(st, taps, x, b.full.s[1], b.full.s[2], llsrc, res, n[0], n[1], n[2], llsrc ? (int)n[2] : 0, cu_count,
+                                          &e, &kn, res_st.s[2]);      // (l == 1: y's own plane stride, the caller's image_stride; deeper levels: dense)
+        WL_WALK_TRY(e);
+        return done ? took(1, kn) : 0;
+    }
+    // ---- long filters (12..24 taps) ----
+    int long_filters()
+    {
+        if (!(path == 0 && long_filter_ok(F) && iopt("WL_NO_LONGF", 0) == 0 && b.full.s[0] == 1)) return 0;
+        hipError_t e = hipSuccess;
+        bool done = false;
+        const int64_t h0 = n[0] >> 1, h1 = n[1] >> 1, ldx = b.full.s[1];
+        if (lines) {
+            done = long_lines_inv_level<T>(st, taps, ss(), sls(), x + h0, ldx, res, res_st.s[1], n[0], nlines, cu_count, &e);
+            WL_WALK_TRY(e);
+        } else if (two_d && long_shape2d_ok(F, n[0], n[1]) && vec16(VEC)) {
+            // columns (dim 1) into T0, the approximation quadrant from the deeper reconstruction; then rows (dim 2)
+            if (!w.T0) return WL_RETRY_GEN;
+            done = long_lines_inv_level<T>(st, taps, ss(), sls(), x + h0, ldx, w.T0, n[0], n[0], h1, cu_count, &e);
+            WL_WALK_TRY(e);
+            if (done) {
+                bool ok = long_lines_inv_level<T>(st, taps, x + h1 * ldx, ldx, x + h1 * ldx + h0, ldx, w.T0 + h1 * n[0], n[0], n[0], h1, cu_count, &e);
+                WL_WALK_TRY(e);
+                ok = ok && long_axis_level<T>(st, taps, 0, w.T0, n[0], res, res_st.s[1], n[0], n[1], cu_count, &e);
+                WL_WALK_TRY(e);
+                if (!ok) return WL_EINVAL_ARG;
+            }
+        }
+        return done ? took(1, (vlong_only(F) || n[0] < 512) ? "k_vl_lines" : "k_long_lines") : 0;
+    }
+    // ---- 3-D level: one pass, LDS blocks, or three single-axis streaming passes (fast3d_inv_tier, wl_axis.hip) ----
+    int fast3d()
+    {
+        if (!(fastF && b.nd == 3 && b.nt == 3 && iopt("WL_NO_FAST3D", 0) == 0 && b.full.s[0] == 1 && res_st.s[0] == 1)) return 0;
+        hipError_t e3 = hipSuccess;
+        if (!w.T0) return WL_RETRY_GEN;
+        const char *k3 = "k_inv_axis_stream";
+        const bool done = fast3d_inv_level<T>(st, taps, x, b.full.s[1], b.full.s[2], llsrc, res, res_st.s[1], res_st.s[2], n, w.T0, w.T1, cu_count,
+                                              &e3, &k3);
+        WL_WALK_TRY(e3);
+        return done ? took(1, k3) : 0;
+    }
+    // ---- 2-D level of any even extents, F <= 10: one LDS-tile launch instead of two generic passes (wl_gtile.hip) ----
+    int gtile()
+    {
+        if (!(fastF && two_d && path == 0 && iopt("WL_GTILE", 1) && b.full.s[0] == 1 && res_st.s[0] == 1 && gtile_ok(F, n[0], n[1]))) return 0;
+        WL_WALK_TRY(gtile_launch<T>(st, taps, 0, x, b.full.s[1], res, res_st.s[1], const_cast<T *>(llsrc), llsrc ? llsrc_st.s[1] : 0, (int)n[0], (int)n[1]));
+        return took(1, "k_inv2d_gtile");
+    }
+    // ---- generic level (any rank / size / filter): one pass per axis, never declines ----
+    int generic()
+    {
+        if (b.nt > 1 && !w.T0) return WL_RETRY_GEN;
+        const Extent3 ext = {{n[0], n[1], n[2]}}, lo = low_corner(b, n);
+        const Strides3 box_st = dense_strides(n);
+        const T *in = x;
+        Strides3 in_st = b.full;
+        bool any = false;
+        for (int a = 0; a < b.nt; ++a) {
+            const bool lastp = (a == b.nt - 1);
+            T *out = lastp ? res : ((a & 1) ? w.T1 : w.T0), *ll = (a == 0) ? const_cast<T *>(llsrc) : (T *)nullptr;
+            const Strides3 out_st = lastp ? res_st : box_st;
+            any = path == 0 && iopt("WL_ANYAXIS", 1) && any_axis_ok(F, ext, a);
+            if (any) WL_WALK_TRY(any_axis_pass<T>(st, taps, 0, in, in_st, out, out_st, ll, llsrc_st, ext, a, lo));
+            else WL_WALK_TRY(generic_inv_filter_pass<T>(st, taps, in, in_st, ll, llsrc_st, out, out_st, ext, a, lo));
+            in = out; in_st = out_st;
+        }
+        return took(1, dominant ? dominant : (any ? "k_inv_any" : "k_generic_inv_filter"));
+    }
+};
+
+// The priority order: for every level the first tier that does not decline takes it.
+template <typename T>
+static constexpr int (InvWalk<T>::*kInvTiers[])() = {
+    &InvWalk<T>::lds_long_short,   // 2-D, F <= 10, >= WL_INVLONG_SHORT_MIN elements, not a level the pair may take (k_inv2d_lds_long; WL_INVLONG2D)
+    &InvWalk<T>::pair,             // 2-D Float32, even l, >= 2^24 output elements: levels l and l - 1 (k_inv2d_pair; WL_INV_PAIR)
+    &InvWalk<T>::tile2,            // 2-D, output <= 1024 rows, 2..20 taps: levels l and l - 1 (k_inv2d_tile2; WL_TILE_INV, WL_TILE_INV_LONG)
+    &InvWalk<T>::lines2,           // lines of >= 512 samples: levels l and l - 1 (k_inv1d_stream2; WL_NO_INV1D2)
+    &InvWalk<T>::lines1,           // lines of >= 512 samples (k_inv1d_stream)
+    &InvWalk<T>::stream2d,         // 2-D level of >= 128 rows in one pass (k_inv2d_stream; WL_NO_INV2D, WL_INV2D_PPL)
+    &InvWalk<T>::dim2,             // 2-D level of >= 512 rows in two passes through T0 (k_inv1d_stream + k_inv_dim2_stream)
+    &InvWalk<T>::planes,           // batch of planes (inv2d_planes: k_inv2d_lds_long, k_inv2d_stream)
+    &InvWalk<T>::lds_long_12,      // 2-D, 12..20 taps, rows in strips of 256 (k_inv2d_lds_long; WL_INVLONG2D)
+    &InvWalk<T>::long_filters,     // 12..24 and Battle taps: lines, 2-D as line passes + axis pass (k_long_lines, k_vl_lines; WL_NO_LONGF)
+    &InvWalk<T>::fast3d,           // 3-D level (k_inv3d_one, k_level3_lds, k_inv_axis_stream; WL_NO_FAST3D)
+    &InvWalk<T>::gtile,            // 2-D level of any even extents (k_inv2d_gtile; WL_GTILE)
+    &InvWalk<T>::generic,          // anything: one pass per axis (k_inv_any, k_generic_inv_filter; WL_ANYAXIS)
+};
+
+template <typename T>
+int filter_inv_levels(void *ws, bool ws_gen, int cu_count, int path, hipStream_t st, const BoxSpec &b,
+                      T *y, const T *x, const Taps<T> &taps, int L, const char **kernel_name, int *hip_err)
+{
+    InvWalk<T> s(ws, ws_gen, cu_count, path, st, b, y, x, taps, L, hip_err);
+    // the deepest levels in one workgroup: k_tail(2)_inv, else (3-D) k_tail3
+    for (auto pre : {&InvWalk<T>::tail, &InvWalk<T>::tail3}) {
+        const int l_start = (s.*pre)();
+        if (l_start < 0) return l_start;
+        s.l = l_start;
+    }
+    while (s.l >= 1) {
+        s.enter();
+        int r = 0;
+        for (auto tier : kInvTiers<T>)
+            if ((r = (s.*tier)()) != 0) break;
+        if (r < 0) return r;
+        s.l -= r;
+    }
+    if (kernel_name) *kernel_name = s.dominant ? s.dominant : "none";
     return WL_OK;
-#undef WL_TRYI
 }
 
 template <typename T>
@@ -1366,13 +1363,12 @@ bool fast_lines_inv_level(hipStream_t st, const Taps<T> &taps, const T *ssrc, in
     constexpr int VEC = 16 / sizeof(T);
     const int F = taps.F;
     *err = hipSuccess;
-    if ((F % 2) != 0 || F > 10 || n < 512 || (n % 8) != 0 || !i_al16(ssrc) || !i_al16(dsrc) ||
-        !i_al16(dst) || (s_ls % VEC) != 0 || (d_ls % VEC) != 0 || (o_ls % VEC) != 0)
+    if ((F % 2) != 0 || F > 10 || n < 512 || (n % 8) != 0 || !al16(ssrc) || !al16(dsrc) ||
+        !al16(dst) || (s_ls % VEC) != 0 || (d_ls % VEC) != 0 || (o_ls % VEC) != 0)
         return false;
-    bool done = false;
-    WL_DISPATCH_FI(F, *err = launch_inv1d<T, FF>(st, taps, ssrc, s_ls, dsrc, d_ls, dst, o_ls, n, nlines, cu_count);
-                   done = true);
-    return done;
+    return dispatch_taps<2, 4, 6, 8, 10>(F, [&](auto ff) {
+        *err = launch_inv1d<T, decltype(ff)::value>(st, taps, ssrc, s_ls, dsrc, d_ls, dst, o_ls, n, nlines, cu_count);
+    });
 }
 template bool fast_lines_inv_level<float>(hipStream_t, const Taps<float> &, const float *, int64_t, const float *, int64_t,
                                           float *, int64_t, int64_t, int64_t, int, hipError_t *);
@@ -1391,11 +1387,11 @@ bool inv2d_planes(hipStream_t st, const Taps<T> &taps, const T *x, int64_t x1, i
     const int F = taps.F;
     *err = hipSuccess;
     if ((F % 2) != 0 || F > 20 || n0 < 256 || (n0 % 8) != 0 || n1 < 16 || (n1 % 16) != 0 || (x1 % VEC) != 0 || (x2 % VEC) != 0 ||
-        (dst_ps % VEC) != 0 || !i_al16(x) || !i_al16(dst) || (ll && !i_al16(ll)) || nplanes > 65535)
+        (dst_ps % VEC) != 0 || !al16(x) || !al16(dst) || (ll && !al16(ll)) || nplanes > 65535)
         return false;
     // the LDS-exchange level kernel (wl_inv2d_long.hip) where it is enabled for this filter length and the batch is large
-    if (i_env("WL_INVLONG2D", 1) != 0 && inv2d_long_ok(F, n0, n1, (int)sizeof(T)) && n0 >= i_env("WL_INVLONG2D_MIN_ROWS", 256) &&
-        (F >= 12 || n0 * n1 * nplanes >= (int64_t)i_env("WL_INVLONG_SHORT_MIN", 1 << 22))) {
+    if (iopt("WL_INVLONG2D", 1) != 0 && inv2d_long_ok(F, n0, n1, (int)sizeof(T)) && n0 >= iopt("WL_INVLONG2D_MIN_ROWS", 256) &&
+        (F >= 12 || n0 * n1 * nplanes >= (int64_t)iopt("WL_INVLONG_SHORT_MIN", 1 << 22))) {
         const InvLongBatch bt = {nplanes, x2, (n0 >> 1) * (n1 >> 1), dst_ps, ll ? nll : 0};
         *err = inv2d_long_launch<T>(st, taps, x, x1, ll, n0 >> 1, dst, n0, n0, n1, cu_count, bt);
         if (kernel) *kernel = "k_inv2d_lds_long";
@@ -1403,11 +1399,10 @@ bool inv2d_planes(hipStream_t st, const Taps<T> &taps, const T *x, int64_t x1, i
     }
     if (F > 10) return false;
     if (kernel) *kernel = "k_inv2d_stream";
-    bool ok = false;
-    WL_DISPATCH_FI(F, *err = launch_inv2d<T, FF, 2>(st, taps, x, x1, ll, n0 >> 1, dst, n0, n0, n1, cu_count, nplanes, x2,
-                                                     (n0 >> 1) * (n1 >> 1), dst_ps, nll);
-                   ok = true);
-    return ok;
+    return dispatch_taps<2, 4, 6, 8, 10>(F, [&](auto ff) {
+        *err = launch_inv2d<T, decltype(ff)::value, 2>(st, taps, x, x1, ll, n0 >> 1, dst, n0, n0, n1, cu_count, nplanes, x2,
+                                                       (n0 >> 1) * (n1 >> 1), dst_ps, nll);
+    });
 }
 template bool inv2d_planes<float>(hipStream_t, const Taps<float> &, const float *, int64_t, int64_t, const float *, float *, int64_t,
                                   int64_t, int64_t, int, int, hipError_t *, const char **, int64_t);

@@ -128,7 +128,6 @@ inline int match_shape(const LiftScheme<T> &sc)
 
 // ---- launch helpers ---------------------------------------------------------------------------------------------------------
 inline int l_env(const char *name, int dflt) { return (int)opt(name, dflt); }   // per-context options
-inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // a failed call / launch inside a *_fast function: its HIP error goes to the function's *hip_err and WL_EHIP comes back
 #define WL_E(expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { if (hip_err) *hip_err = (int)e__; return WL_EHIP; } } while (0)

@@ -449,19 +449,8 @@ static hipError_t launch_vl_lines(hipStream_t st, const Taps<T> &taps, VlLineArg
 }
 
 // ---------------------------------------------------------------------------------------------------
-#define WL_DISPATCH_FV(F_, ...)                              \
-    switch (F_) {                                            \
-    case 12: { constexpr int FF = 12; __VA_ARGS__; } break;  \
-    case 14: { constexpr int FF = 14; __VA_ARGS__; } break;  \
-    case 16: { constexpr int FF = 16; __VA_ARGS__; } break;  \
-    case 18: { constexpr int FF = 18; __VA_ARGS__; } break;  \
-    case 20: { constexpr int FF = 20; __VA_ARGS__; } break;  \
-    case 24: { constexpr int FF = 24; __VA_ARGS__; } break;  \
-    case 23: { constexpr int FF = 23; __VA_ARGS__; } break;  \
-    case 41: { constexpr int FF = 41; __VA_ARGS__; } break;  \
-    case 59: { constexpr int FF = 59; __VA_ARGS__; } break;  \
-    default: break;                                          \
-    }
+template <typename Fn>
+static bool dispatch_vl_taps(int F, Fn &&fn) { return dispatch_taps<12, 14, 16, 18, 20, 24, 23, 41, 59>(F, fn); }
 
 // instantiated lengths: the Battle-Lemarie filters (no other fast path), and the 12..24-tap families for the levels that
 // are too small for their ring kernels (wl_axis.hip: lines >= 512, axis lengths in multiples of 32)
@@ -474,7 +463,8 @@ hipError_t vl_lines_fwd(hipStream_t st, const Taps<T> &taps, const T *src, int64
                         int64_t d_ls, int64_t n, int64_t nlines)
 {
     hipError_t e = hipErrorInvalidValue;
-    WL_DISPATCH_FV(taps.F, {
+    dispatch_vl_taps(taps.F, [&](auto ff) {
+        constexpr int FF = decltype(ff)::value;
         VlLineArgs<T, FF> a;
         a.a = src; a.a_ls = src_ls; a.b = nullptr; a.b_ls = 0; a.o0 = sdst; a.o0_ls = s_ls; a.o1 = ddst; a.o1_ls = d_ls;
         e = launch_vl_lines<T, FF, 1>(st, taps, a, n, nlines);
@@ -486,7 +476,8 @@ hipError_t vl_lines_inv(hipStream_t st, const Taps<T> &taps, const T *ssrc, int6
                         int64_t o_ls, int64_t n, int64_t nlines)
 {
     hipError_t e = hipErrorInvalidValue;
-    WL_DISPATCH_FV(taps.F, {
+    dispatch_vl_taps(taps.F, [&](auto ff) {
+        constexpr int FF = decltype(ff)::value;
         VlLineArgs<T, FF> a;
         a.a = ssrc; a.a_ls = s_ls; a.b = dsrc; a.b_ls = d_ls; a.o0 = dst; a.o0_ls = o_ls; a.o1 = nullptr; a.o1_ls = 0;
         e = launch_vl_lines<T, FF, 0>(st, taps, a, n, nlines);
@@ -498,7 +489,8 @@ hipError_t vl_axis(hipStream_t st, const Taps<T> &taps, int fw, const T *src, in
                    int cu_count)
 {
     hipError_t e = hipErrorInvalidValue;
-    WL_DISPATCH_FV(taps.F, {
+    dispatch_vl_taps(taps.F, [&](auto ff) {
+        constexpr int FF = decltype(ff)::value;
         if (fw) e = launch_vl_axis<T, FF, 1>(st, taps, src, lds, dst, ldd, R, C, cu_count);
         else e = launch_vl_axis<T, FF, 0>(st, taps, src, lds, dst, ldd, R, C, cu_count);
     });
